@@ -31,6 +31,11 @@ Prints ONE JSON line on rank 0.
                         hipMemcpyAsync per band, colour/depth on two copy streams, double-buffered framebuffer)
   extra.swr_render_ms   the full drop-in call (upload 120 MB + draw + gather, host pointers in, pixels out)
   cpu_baseline          (rank 0, N = 1 only) the CPU oracle — the C restatement of Renderer.swift's loop
+
+--dump-outputs DIR: the images the last timed frame of the headline pass left in the framebuffer (what swr_read_depth /
+swr_read_color hand a caller) are written as DIR/<name>.npy, finite float32, at most 64 MB in all (the depth clear value +inf
+goes into a class map beside the depth image: frame_outputs); the inputs are fixed by the arguments, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -48,6 +53,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_COPY_CEILING_GBS = 6290.0  # measured float4-copy ceiling (same guide)
 # VALU issue peak: 256 CUs x 4 SIMDs, one wave64 VALU instruction per 2 cycles per SIMD, 2.4 GHz (same guide)
 VALU_PEAK_WAVE_INSTS_PER_S = 256 * 4 * 2.4e9 / 2
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: all files of one run together, .npy headers included
+DUMP_SAMPLE_SEED = 0x5EED_D0   # --dump-outputs: the element sample of outputs over the budget
 
 
 def shard_rows(swr, height: int, world: int, rank: int):
@@ -78,6 +85,40 @@ def csrc_digest():
         with open(f, "rb") as fh:
             h.update(os.path.basename(f).encode() + b"\0" + fh.read())
     return h.hexdigest()[:16]
+
+
+def frame_outputs(ctx, flags, no_color_flag, r0, r1):
+    """The last drawn frame as its caller receives it, rows r0..r1 (this process's band), as finite float32 arrays:
+      depth            the depth image, 0 where the value is not finite (pixels no fragment reached keep the clear value +inf)
+      depth_nonfinite  per pixel 0 = finite, 1 = +inf, 2 = -inf, 3 = NaN: with `depth` the image is recovered exactly
+      color            unless the frame is depth-only: the RGBA colour image, channels 0..255"""
+    d = ctx.read_depth()[r0:r1]
+    cls = np.select([np.isposinf(d), np.isneginf(d), np.isnan(d)], [1, 2, 3], 0).astype(np.float32)
+    out = {"depth": np.where(cls == 0, d, np.float32(0)), "depth_nonfinite": cls}
+    if not flags & no_color_flag:
+        out["color"] = ctx.read_color()[r0:r1].astype(np.float32)
+    return out
+
+
+def dump_outputs(outputs, out_dir, budget_bytes, suffix=""):
+    """out_dir/<name><suffix>.npy per output.  Over the budget, each output is cut to a fixed, seeded sample of its flattened
+    elements (ascending element order, the same share of every output; outputs of one size share one sample, so depth and
+    depth_nonfinite stay paired), so the files of two runs line up element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 4 for a in outputs.values())
+    budget_bytes -= 4096 * len(outputs)                       # room for the .npy headers
+    written = {}
+    for name, a in sorted(outputs.items()):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        assert np.isfinite(a).all(), f"{name}: non-finite values"
+        if total > budget_bytes:
+            keep = a.size * budget_bytes // total
+            pick = np.random.default_rng([DUMP_SAMPLE_SEED, a.size]).choice(a.size, keep, replace=False, shuffle=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        path = os.path.join(out_dir, f"{name}{suffix}.npy")
+        np.save(path, a)
+        written[os.path.basename(path)] = list(a.shape)
+    return {"dir": out_dir, "files": written, "sampled": total > budget_bytes}
 
 
 def cpu_baseline(scene, budget_s: float = 15.0):
@@ -131,7 +172,11 @@ def main():
     ap.add_argument("--color", action="store_true", help="headline = colour+depth instead of depth-only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the images of the last timed frame to DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -246,6 +291,8 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     mpix = W * H * args.steps / dt / 1e6
     frames_before_headline = args.steps + args.warmup
+    # read back now (every later pass draws other frames into the framebuffer); the files are written at the end
+    outputs = frame_outputs(ctx, flags, S.FLAG_NO_COLOR, r0, r1) if args.dump_outputs else None
 
     # one frame alone: enqueue -> host sees it finished (no other frame in flight)
     lat = []
@@ -472,6 +519,10 @@ def main():
         out["vs_cpu_baseline"] = {"ratio": round(out["value"] / out["cpu_baseline"]["value"], 1),
                                   "note": "value / cpu_baseline.value (1 host core, C port of Renderer.swift): reported baseline, not target"}
     ctx.close()
+    if outputs is not None:
+        # under a launcher every rank writes its own band (<name>_rank<k>.npy); the bands share the budget
+        out["dumped_outputs"] = dump_outputs(outputs, args.dump_outputs, DUMP_BUDGET_BYTES // world,
+                                             f"_rank{rank}" if world > 1 else "")
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -266,7 +266,7 @@ def test_bin_overflow_is_repaired_or_reported(swr, oracle, bins):
         same(None, d, None, rc_d, "overflow inside a group")
 
 
-def test_product_library_has_no_ablation_switch(swr, oracle):
+def test_product_library_has_no_ablation_switch(swr, oracle, tmp_path):
     """SWR_DEBUG_VARIANT selected timing-only k_raster instantiations with invalid results; the
     product library no longer contains them (only `make ablation` builds them, into another .so)."""
     code = (
@@ -275,8 +275,7 @@ def test_product_library_has_no_ablation_switch(swr, oracle):
         "with swr_amd.Context() as ctx:\n"
         "    c, d = ctx.render(s.vertices, s.indices, s.transform, 640, 360, 1)\n"
         "np.save(r'%s', d)\n")
-    out = os.path.join(ROOT, "gpurun_out", "variant4_depth.npy") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) \
-        else "/tmp/variant4_depth.npy"
+    out = str(tmp_path / "variant4_depth.npy")
     r = subprocess.run([sys.executable, "-c", code % out], env={**os.environ, "SWR_DEBUG_VARIANT": "4"}, cwd=ROOT,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
