@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SWR_ABI_VERSION 5
+#define SWR_ABI_VERSION 6
 
 /* ---- status codes (the reference has no error channel: it fatalError()s / try!s,
  *      Renderer.swift:26,209,239,497; GpuRenderer.swift:20-31,37-38) ------------------ */
@@ -64,7 +64,7 @@ enum {
                                       (:158-161), bgra8Unorm store (round to nearest), ROIs whose min-x or
                                       min-y is 0 skipped (GpuRenderer.swift:122-124); IEEE arithmetic (the
                                       reference's MTL_FAST_MATH build is not bit-reproducible) */
-    SWR_FLAG_REAL_LINES = 1u << 3  /* OPT-IN, .line primitives only.  Default (flag clear) = the reference as written:
+    SWR_FLAG_REAL_LINES = 1u << 3, /* OPT-IN, .line primitives only.  Default (flag clear) = the reference as written:
                                       draw(line:colorBuffer:depthBuffer:) has an empty body (Renderer.swift:289-293), a
                                       .line pass only clears.  With the flag every 2-index primitive is drawn with the
                                       reference's own DDA (draw(line:with:in:), Renderer.swift:405-419) between its two
@@ -74,7 +74,35 @@ enum {
                                       not plotted), in the colour of the FIRST vertex, later primitives overwrite
                                       earlier ones, no z-test, depth stays +inf.  Lines longer than 2^20 steps or with a
                                       non-finite endpoint are skipped (the reference would trap / never finish) */
+    SWR_FLAG_LOAD = 1u << 4        /* LOAD ACTION (ABI 6; Metal's MTLLoadActionLoad): the frame is Renderer.render(renderPass:) WITHOUT the
+                                      clear of Renderer.swift:205-206 — the same loop continues from the image already there (see
+                                      "Load frames" below) */
 };
+
+/* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
+ * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
+ * continues from the image already there.
+ *   z-test (SWR_FLAG_DEPTH_TEST; always under SWR_FLAG_METAL_RULES): a fragment is kept iff d < depth[x,y], depth[x,y] starting at
+ *     the loaded value — strict '<', so on an equal depth the image that was there wins (first drawn wins, across frames).  A loaded
+ *     NaN or -inf is never replaced; -0 and +0 compare equal (neither replaces the other); denormals compare exactly.
+ *   painter's order (no z-test): covered pixels are overwritten, the others keep the loaded colour; the depth image stays exactly
+ *     as loaded.
+ *   SWR_FLAG_NO_COLOR: colour is neither read nor written (the band's colour image after such a frame is unspecified, as before);
+ *     depth is loaded.  .vertices and real lines behave as above; a .line frame without SWR_FLAG_REAL_LINES leaves the image as it is.
+ * Composition: the image of scene A drawn with M_A, then scene B drawn with M_B as a load frame, is bit for bit the clear frame of
+ * A || B drawn with the identity, every vertex pre-transformed by its own matrix (Vertex.apply order, float32, no FMA), B's indices
+ * offset by A's vertex count; chains of any length alike.
+ * The starting image:
+ *   resident path (swr_draw / swr_draw_primitives): the band's image of the last frame drawn on the context;
+ *   right after swr_target_set: the cleared image (colour 0, depth +inf) — a load frame there IS the clear frame;
+ *   swr_target_write: the images it wrote;
+ *   swr_render: pass->color / pass->depth are the starting image (swr_target_write + the draw); with scene_id the scene is still
+ *     cached, the images never are.
+ * Bin overflow: a load frame never builds silently on an overflowed frame.  A frame whose bins overflowed is rastered empty; if it
+ *   is the last frame it is redrawn from the SAME starting image.  A load frame whose starting image is such an empty frame (or a
+ *   load frame built on one, any number of frames back) counts as dropped: reported with SWR_ERR_FRAME_DROPPED when it was
+ *   presented or when it is the last frame of the burst (whose image the next load frame or swr_read_* would see), and every later
+ *   load frame on top of it is reported too, until a clear frame, swr_target_set or swr_target_write replaces the image. */
 
 /* ---- Vertex (Renderer.swift:154-157): two SIMD3<Float>, each padded to 16 B --------- */
 typedef struct swr_vertex {
@@ -283,6 +311,12 @@ int swr_draw(swr_context* ctx, const float transform[16], uint32_t flags);
  * (the reference's draw(line:) is an empty stub, Renderer.swift:289-293). */
 int swr_draw_primitives(swr_context* ctx, const float transform[16], uint32_t flags, int32_t primitive_type);
 int swr_sync(swr_context* ctx);
+/* The band's current image (what the next SWR_FLAG_LOAD frame starts from) := rows [row_begin,row_end) of the caller's full-size
+ * images, per band (a multi-device context: every band its own rows, like swr_present in the other direction).  Everything drawn
+ * before is completed and checked first (like swr_sync; its error is returned and nothing is written).  Either pointer may be
+ * NULL: that image stays as it is (the cleared one right after swr_target_set).  Page-locked sources go straight to the device,
+ * others are staged.  (ABI 6) */
+int swr_target_write(swr_context* ctx, const void* color_full_image, const float* depth_full_image);
 
 /* ---- host-visible frames: the gather ("final image gathered with pinned hipMemcpyAsync") -------------------
  * The reference's images live in CPU/GPU-shared MTLBuffers (App.swift:59-60,80-101) and are complete on return

@@ -15,6 +15,7 @@ FLAG_DEPTH_TEST = 1
 FLAG_NO_COLOR = 2
 FLAG_METAL_RULES = 4
 FLAG_REAL_LINES = 8      # .line primitives: the reference's DDA (Renderer.swift:405-419) instead of its empty stub (:289-293)
+FLAG_LOAD = 16           # load action (ABI 6): the frame starts from the image already there instead of the clear (include/swr.h)
 
 # every symbol include/swr.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -24,7 +25,7 @@ ABI_SYMBOLS = [
     "swr_band_rows", "swr_scene_attributes", "swr_material_set", "swr_texture_upload",
     "swr_timing_sample", "swr_context_bands", "swr_context_band_info", "swr_host_alloc", "swr_host_free",
     "swr_host_register", "swr_host_unregister", "swr_present", "swr_present_wait", "swr_device_count",
-    "swr_render_timings", "swr_debug_fault", "swr_debug_set",
+    "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -168,6 +169,8 @@ def load_library():
         if not os.environ.get("SWR_LIBRARY"):      # only an older A/B build loaded by tools/ may lack the ABI 4 entry points
             raise
     L.swr_present.argtypes = [vp, vp, vp]
+    L.swr_target_write.argtypes = [vp, vp, vp]
+    L.swr_target_write.restype = ctypes.c_int
     L.swr_present_wait.argtypes = [vp]
     for name in ("swr_context_bands", "swr_context_band_info", "swr_host_register", "swr_host_unregister", "swr_present",
                  "swr_present_wait"):
@@ -339,6 +342,22 @@ class Context:
     def sync(self):
         self._check(self._L.swr_sync(self._h))
 
+    def target_write(self, color=None, depth=None):
+        """swr_target_write: the band's current image (what the next FLAG_LOAD frame starts from) := the rows of these full-size
+        images (uint8 (height, width, 4) BGRA / float32 (height, width); a HostImage too); None keeps that image."""
+        def ptr(a, dtype):
+            if a is None:
+                return None, None
+            arr = a.array if hasattr(a, "array") else a
+            if not (isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.flags.c_contiguous):
+                arr = np.ascontiguousarray(arr, dtype=dtype)
+            if arr.size != self.width * self.height * (4 if dtype == np.uint8 else 1):
+                raise ValueError("target_write: the image must have the target's full size")
+            return arr.ctypes.data, arr
+        cp, keep_c = ptr(color, np.uint8)
+        dp, keep_d = ptr(depth, np.float32)
+        self._check(self._L.swr_target_write(self._h, cp, dp))
+
     def bands(self):
         """[(device, row_begin, row_end)] of every band of the context."""
         out = []
@@ -444,6 +463,8 @@ class Context:
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 8)
         i = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
         m = np.ascontiguousarray(transform, dtype=np.float32).reshape(16)
+        if (flags & FLAG_LOAD) and (depth is None or (color is None and not (flags & FLAG_NO_COLOR))):
+            raise ValueError("render with FLAG_LOAD: color / depth are the starting image and must be given")
         if color is None and not (flags & FLAG_NO_COLOR):
             color = np.full((height, width, 4), 0xCD, dtype=np.uint8)
         if depth is None:

@@ -188,6 +188,12 @@ struct swr_context {
     hipEvent_t frame_done[NFB] = {};     // raster stream -> copy streams, per framebuffer
     hipEvent_t copy_done[NFB][2] = {};   // [fb][image]: the raster into fb waits for these
     bool copy_recorded[NFB][2] = {};
+    // ---- load frames (SWR_FLAG_LOAD): a frame that starts from the band's current image instead of the clear
+    bool src_clear = true;              // the current image is the cleared one (swr_target_set): a load frame is then a clear frame
+    int load_src = 0;                   // the framebuffer the last frame loaded from (its overflow redraw reads it again)
+    hipEvent_t src_ready = nullptr;     // frame lanes: the source frame's raster, waited for by the load frame's raster
+    hipEvent_t read_done[NFB] = {};     // frame lanes: the raster of the load frame that read framebuffer fb; writers of fb wait for it
+    bool read_recorded[NFB] = {};
     // pinned staging for destinations that are not page-locked (two 8 MiB chunks per image, D2H / memcpy pipelined)
     static constexpr size_t STAGE_BYTES = 8u << 20;
     void* stage[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
@@ -266,6 +272,8 @@ struct swr_context {
     uint32_t* h_pairs = nullptr;
     uint32_t* h_pairs_dev = nullptr;
     bool frame_presented[PAIR_RING] = {};   // was frame f copied to the host (swr_present)?  Only then can an overflow be seen
+    bool frame_load[PAIR_RING] = {};        // did frame f start from the image of frame f - 1 (a load frame)?
+    bool src_bad = false;                   // the image of frame frames_checked - 1 is wrong: an overflow left it empty, or it loaded one
     uint32_t* h_misc = nullptr;
     // Depth-only z-tested frames: 32-bit depth keys (k_raster_depth) until the scene shows that too many of its tiles have
     // to be rastered again with the 64-bit keys (depths that are not > +0: a 2-D scene at z = 0, geometry in front of the
@@ -497,6 +505,7 @@ int sync_streams(swr_context* c) {
             if (!rc && ls) rc = wait_stream(c, ls, "frame lane");
     if (rc) return sticky(c) ? sticky(c) : rc;
     c->synced_upto = c->posted;      // NOT frame_no: enqueue_frame may sync after it has numbered the frame it is about to post
+    for (bool& r : c->read_recorded) r = false;     // every load frame's read of its source has completed: nothing to wait for
     return SWR_OK;
 }
 
@@ -631,6 +640,9 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
     f.biglist = (uint4*)sl.biglist.p;
     f.color = (uint8_t*)c->color[c->fb_cur].p;
     f.depth = (float*)c->depth[c->fb_cur].p;
+    const bool load = (flags & SWR_FLAG_LOAD) != 0;
+    f.src_color = load ? (const uint8_t*)c->color[c->load_src].p : nullptr;
+    f.src_depth = load ? (const float*)c->depth[c->load_src].p : nullptr;
     f.tg = c->tg;
     memcpy(f.m, m, sizeof f.m);
     f.flags = flags;
@@ -660,6 +672,8 @@ void harvest(swr_context* c) {
 int wait_for_copies_of(swr_context* c, int fb, hipStream_t s) {
     for (int img = 0; img < 2; img++)
         if (c->copy_recorded[fb][img]) HIP_TRY(c, hipStreamWaitEvent(s, c->copy_done[fb][img], 0));
+    // ... nor a load frame of another lane still reading it as its source
+    if (c->read_recorded[fb]) HIP_TRY(c, hipStreamWaitEvent(s, c->read_done[fb], 0));
     return SWR_OK;
 }
 
@@ -686,6 +700,7 @@ int enqueue_frame(swr_context* c) {
         int rc = flush_raster(c, c->frame_no);
         if (rc) return rc;
         fill_word(c, c->frame_no) = 0;
+        c->frame_load[c->frame_no % swr_context::PAIR_RING] = false;     // (no pixels: nothing it could load wrongly)
         pair_word(c, c->frame_no++) = 0;
         c->posted = c->frame_no;
         c->bin_enqueued.store(c->frame_no); c->ras_enqueued.store(c->frame_no);
@@ -700,8 +715,13 @@ int enqueue_frame(swr_context* c) {
         DeviceFrame f = make_frame(c, 0, frame, c->last_m, c->last_flags);
         pair_word(c, frame) = 0;
         fill_word(c, frame) = 0;
+        c->frame_load[frame % swr_context::PAIR_RING] = (c->last_flags & SWR_FLAG_LOAD) != 0;
         if ((rc = wait_for_copies_of(c, c->fb_cur, c->stream))) return rc;
         launch_points_or_lines(f, c->last_prim, c->stream);
+        if ((c->last_flags & SWR_FLAG_LOAD) && lane_mode(c)) {
+            HIP_TRY(c, hipEventRecord(c->read_done[c->load_src], c->stream));
+            c->read_recorded[c->load_src] = true;
+        }
         HIP_TRY(c, hipGetLastError());
         c->posted = c->frame_no;
         c->bin_enqueued.store(c->frame_no); c->ras_enqueued.store(c->frame_no);
@@ -712,6 +732,8 @@ int enqueue_frame(swr_context* c) {
     }
     const uint64_t frame = c->frame_no++;
     c->frame_presented[frame % swr_context::PAIR_RING] = false;
+    const bool load = (c->last_flags & SWR_FLAG_LOAD) != 0;
+    c->frame_load[frame % swr_context::PAIR_RING] = load;
     const int si = (int)(frame % swr_context::NSLOT);
     c->last_slot = si;
     DeviceFrame f = make_frame(c, si, frame, c->last_m, c->last_flags);
@@ -816,6 +838,11 @@ int enqueue_frame(swr_context* c) {
         }
         int rc = wait_for_copies_of(c, c->fb_cur, S);
         if (rc) return fail_frame(rc);
+        // a load frame: its raster starts after the raster of the frame it loads (the previous one, on another lane); its binning
+        // still overlaps that raster
+        const bool src_wait = load && c->last_stream && c->last_stream != S;
+        if (src_wait && hipEventRecord(c->src_ready, c->last_stream) != hipSuccess)
+            return fail_frame(fatal(c, SWR_ERR_HIP, "frame %llu: recording the source frame's completion failed", (unsigned long long)frame));
         auto enq = [&]() -> int {
             if (zero_tables) HIP_TRY(c, hipMemsetAsync(c->slot[si].tilebuf.p, 0, zero_bytes, S));
             if (fill_memset) HIP_TRY(c, hipMemsetAsync(f.fill, 0, (size_t)(CNT_WORDS + tiles_of(f.tg)) * 4, S));
@@ -832,9 +859,14 @@ int enqueue_frame(swr_context* c) {
                 launch_fill(f, S, nullptr);
             }
             if (!f.skip_sort) launch_sort_bins(f, S, nullptr);
+            if (src_wait) HIP_TRY(c, hipStreamWaitEvent(S, c->src_ready, 0));
             if (ev) HIP_TRY(c, hipEventRecord(ev[3], S));
             launch_raster(f, S, nullptr);
             if (ev) HIP_TRY(c, hipEventRecord(ev[4], S));
+            if (load) {
+                HIP_TRY(c, hipEventRecord(c->read_done[c->load_src], S));
+                c->read_recorded[c->load_src] = true;
+            }
             if (frame % (uint64_t)swr_context::PACE_EVERY == 0) {
                 const int k = (int)((frame / (uint64_t)swr_context::PACE_EVERY) % 4);
                 HIP_TRY(c, hipEventRecord(c->pace_ev[k], S));
@@ -1248,6 +1280,7 @@ int single_target_set(swr_context* c, int64_t width, int64_t height, int64_t row
     int rc = check_target_args(c, width, height, row_begin, row_end);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
+    c->src_clear = true;        // the band images are the cleared ones again (what the next load frame starts from)
     if (c->has_target && c->tg.width == width && c->tg.height == height && c->tg.row_begin == row_begin && c->tg.row_end == row_end)
         return SWR_OK;          // the same target again (swr_render every frame): nothing to resize, nothing to wait for
     if ((rc = check_frames(c)) || (rc = sync_copies(c))) return rc;      // (an overflowed frame presented just before is repaired / reported first)
@@ -1263,6 +1296,7 @@ int single_target_set(swr_context* c, int64_t width, int64_t height, int64_t row
         if ((rc = ensure(c, c->color[fb], px * 4))) return rc;
         if ((rc = ensure(c, c->depth[fb], px * 4))) return rc;
         c->copy_recorded[fb][0] = c->copy_recorded[fb][1] = false;
+        c->read_recorded[fb] = false;
     }
     c->fb_cur = c->fb_last = 0;
     for (auto& sl : c->slot)
@@ -1282,7 +1316,7 @@ int check_draw_args(swr_context* c, uint32_t flags, int32_t primitive_type) {
     if (primitive_type != SWR_PRIMITIVE_TRIANGLE && primitive_type != SWR_PRIMITIVE_LINE &&
         primitive_type != SWR_PRIMITIVE_VERTICES)
         return fail(c, SWR_ERR_UNSUPPORTED, "unknown primitive type %d", primitive_type);
-    if (flags & ~(uint32_t)(SWR_FLAG_DEPTH_TEST | SWR_FLAG_NO_COLOR | SWR_FLAG_METAL_RULES | SWR_FLAG_REAL_LINES))
+    if (flags & ~(uint32_t)(SWR_FLAG_DEPTH_TEST | SWR_FLAG_NO_COLOR | SWR_FLAG_METAL_RULES | SWR_FLAG_REAL_LINES | SWR_FLAG_LOAD))
         return fail(c, SWR_ERR_BAD_ARG, "unknown flag bits 0x%x", flags);
     if ((flags & SWR_FLAG_REAL_LINES) && primitive_type != SWR_PRIMITIVE_LINE)
         return fail(c, SWR_ERR_BAD_ARG, "SWR_FLAG_REAL_LINES only applies to .line primitives");
@@ -1313,6 +1347,16 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
         if ((rc = check_frames(c))) return rc;
     }
     memcpy(c->last_m, transform, sizeof c->last_m);
+    if (flags & SWR_FLAG_LOAD) {
+        if (c->src_clear) {
+            flags &= ~(uint32_t)SWR_FLAG_LOAD;      // loading the cleared image IS the clear frame
+        } else {
+            // the frame reads the last frame's buffer and writes another one (the pipelined paths reuse a buffer when nothing copies it)
+            c->load_src = c->fb_last;
+            if (c->fb_cur == c->load_src) c->fb_cur = (c->load_src + 1) % swr_context::NFB;
+        }
+    }
+    c->src_clear = false;
     c->last_flags = flags;
     c->last_prim = primitive_type;
     return enqueue_frame(c);
@@ -1386,16 +1430,21 @@ int check_frames(swr_context* c) {
         const uint32_t pairs = used(L);
         uint32_t need = pairs;
         uint32_t total_pairs = pair_word(c, L);               // (for the switch to exact bins)
+        bool bad_prev = c->src_bad;                            // the image of frame f - 1 is wrong
         for (uint64_t f = c->frames_checked; f < L; f++) {
             const uint32_t pf = used(f);
             if (pf > limit()) { need = std::max(need, pf); total_pairs = std::max(total_pairs, pair_word(c, f)); }
-            // an earlier frame that overflowed was rastered empty: that matters only if it was copied to the host
-            if (pf > limit() && c->frame_presented[f % swr_context::PAIR_RING]) {
+            // an earlier frame that overflowed was rastered empty — and a load frame built on such an image is as wrong: that matters
+            // only if it was copied to the host
+            const bool bad = pf > limit() || (c->frame_load[f % swr_context::PAIR_RING] && bad_prev);
+            if (bad && c->frame_presented[f % swr_context::PAIR_RING]) {
                 if (!dropped || pf > dropped_pairs) { dropped_frame = f; dropped_pairs = pf; }
                 dropped = true;
             }
+            bad_prev = bad;
         }
         c->frames_checked = L;
+        c->src_bad = bad_prev;
         const uint32_t old_limit = limit();
         if (need > old_limit) {
             if ((rc = sync_copies(c))) return rc;
@@ -1419,8 +1468,20 @@ int check_frames(swr_context* c) {
                 if ((rc = ensure_capacity(c, (uint32_t)want))) return rc;
             }
         }
+        if (c->frame_load[L % swr_context::PAIR_RING] && c->src_bad) {
+            // the last frame loaded a wrong image: a redraw cannot repair it — reported (whether it was copied or not: it is what the
+            // next load frame, swr_present or swr_read_* would see), and so is every load frame built on it until an image is replaced
+            c->draw_pending = false;
+            c->present_pending = false;
+            c->frames_checked = c->frame_no;
+            harvest(c);
+            return fail(c, SWR_ERR_FRAME_DROPPED, "frame %llu is a load frame whose starting image was rastered empty by a bin overflow "
+                        "(the bins have been grown) — redraw the chain from a clear frame, swr_target_set or swr_target_write",
+                        (unsigned long long)L);
+        }
         if (pairs <= old_limit) {
             c->draw_pending = false;
+            c->src_bad = false;
             c->present_pending = false;        // the last frame is verified: a later repair must not copy into a stale destination
             c->frames_checked = c->frame_no;
             c->last.tile_pairs = pair_word(c, L);
@@ -1435,6 +1496,37 @@ int check_frames(swr_context* c) {
         if (was_presented && (rc = enqueue_present(c, c->present_color, c->present_depth))) return rc;
     }
     return fail(c, SWR_ERR_HIP, "pair list kept overflowing");
+}
+
+// swr_target_write: rows [row_begin, row_end) of the caller's images become the band's current image (what the next load frame
+// starts from).  Everything drawn before is finished and checked first; NULL keeps that image (the cleared one after swr_target_set).
+int single_target_write(swr_context* c, const void* color_full, const float* depth_full) {
+    if (const int f = sticky(c)) return f;
+    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_target_write needs swr_target_set first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = check_frames(c)) || (rc = sync_copies(c))) return rc;
+    const size_t px = (size_t)c->tg.width * (size_t)(c->tg.row_end - c->tg.row_begin);
+    const int fb = c->fb_last;
+    if (px) {
+        const size_t off = (size_t)c->tg.row_begin * (size_t)c->tg.width;
+        // (pageable sources are staged by the runtime; page-locked ones go straight over the link)
+        if (c->src_clear && (!color_full || !depth_full)) {
+            // an image not given keeps the cleared state: the clear of a .line pass (the reference's empty stub), Renderer.swift:205-206
+            DeviceFrame f{};
+            f.color = (uint8_t*)c->color[fb].p;
+            f.depth = (float*)c->depth[fb].p;
+            f.tg = c->tg;
+            launch_points_or_lines(f, SWR_PRIMITIVE_LINE, c->stream);
+            HIP_TRY(c, hipGetLastError());
+        }
+        if (color_full) HIP_TRY(c, hipMemcpyAsync(c->color[fb].p, (const uint32_t*)color_full + off, px * 4, hipMemcpyHostToDevice, c->stream));
+        if (depth_full) HIP_TRY(c, hipMemcpyAsync(c->depth[fb].p, depth_full + off, px * 4, hipMemcpyHostToDevice, c->stream));
+        if ((rc = wait_stream(c, c->stream, "image upload"))) return sticky(c) ? sticky(c) : rc;
+    }
+    c->src_clear = false;
+    c->src_bad = false;
+    return SWR_OK;
 }
 
 int single_sync(swr_context* c) {
@@ -1515,7 +1607,9 @@ void destroy_single(swr_context* c) {
     for (int i = 0; i < swr_context::NFB; i++) {
         if (c->frame_done[i]) hipEventDestroy(c->frame_done[i]);
         for (int j = 0; j < 2; j++) if (c->copy_done[i][j]) hipEventDestroy(c->copy_done[i][j]);
+        if (c->read_done[i]) hipEventDestroy(c->read_done[i]);
     }
+    if (c->src_ready) hipEventDestroy(c->src_ready);
     for (int i = 0; i < 2; i++) {
         for (int j = 0; j < 2; j++) {
             if (c->stage[i][j]) hipHostFree(c->stage[i][j]);
@@ -1583,7 +1677,9 @@ int create_single(int dev, swr_context** out, int helpers, uint32_t wait_budget_
         for (int i = 0; i < swr_context::NFB; i++) {
             hipEventCreateWithFlags(&c->frame_done[i], hipEventDisableTiming);
             for (int j = 0; j < 2; j++) hipEventCreateWithFlags(&c->copy_done[i][j], hipEventDisableTiming);
+            hipEventCreateWithFlags(&c->read_done[i], hipEventDisableTiming);
         }
+        hipEventCreateWithFlags(&c->src_ready, hipEventDisableTiming);
         // frame lanes (swr_context::lane_stream): one stream per working set.  SWR_LANES=0: the two-stream pipeline of rounds 1-3
         {
             const char* ln = getenv("SWR_LANES");
@@ -1643,7 +1739,7 @@ void sub_band(int64_t row_begin, int64_t row_end, int n, int k, int64_t* r0, int
 extern "C" {
 
 int swr_abi_version(void) { return SWR_ABI_VERSION; }
-const char* swr_version(void) { return "swr-hip gfx950 0.4 (tile 64x32, wave64 LDS visibility keys: 32-bit depth keys + winner table, span ring, one-launch binning, frame lanes, multi-device bands)"; }
+const char* swr_version(void) { return "swr-hip gfx950 0.5 (tile 64x32, wave64 LDS visibility keys: 32-bit depth keys + winner table, span ring, one-launch binning, frame lanes, multi-device bands, load action)"; }
 int swr_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
@@ -1790,6 +1886,15 @@ int swr_draw_primitives(swr_context* c, const float transform[16], uint32_t flag
 
 int swr_draw(swr_context* c, const float transform[16], uint32_t flags) {
     return swr_draw_primitives(c, transform, flags, SWR_PRIMITIVE_TRIANGLE);
+}
+
+int swr_target_write(swr_context* c, const void* color_full, const float* depth_full) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    if (is_group(c)) {
+        if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_target_write needs swr_target_set first");
+        return group_run(c, [=](swr_context* k) { return single_target_write(k, color_full, depth_full); });
+    }
+    return single_target_write(c, color_full, depth_full);
 }
 
 int swr_sync(swr_context* c) {
@@ -1991,6 +2096,9 @@ int swr_render(swr_context* c, const swr_render_pass* p) {
     // the pass carries its own fragment stage: NULL material = the reference's passthrough
     if ((rc = swr_material_set(c, p->material))) return rc;
     if ((rc = swr_target_set(c, p->width, p->height, 0, p->height))) return rc;
+    // a load frame: the caller's images are its starting image (inputs now, never cached)
+    if ((p->flags & SWR_FLAG_LOAD) &&
+        (rc = swr_target_write(c, (p->flags & SWR_FLAG_NO_COLOR) ? nullptr : p->color, p->depth))) return rc;
     const swr_context* kf = c->kids.empty() ? c : c->kids[0];
     const uint64_t frames0 = kf->frame_no;
     if ((rc = swr_draw_primitives(c, p->transform, p->flags, p->primitive_type))) return rc;

@@ -111,6 +111,8 @@ struct DeviceFrame {
     uint32_t capacity;
     uint8_t* color;
     float* depth;
+    const uint8_t* src_color;      // load frames (SWR_FLAG_LOAD): the framebuffer the frame starts from (never color / depth)
+    const float* src_depth;
     Target tg;
     float m[16];                   // column-major transform
     uint32_t flags;                // SWR_FLAG_*

@@ -1120,6 +1120,8 @@ struct RasterArgs {
     int vs_log;         // 2^vs_log workgroups per tile, each owning TILE_H >> vs_log of its rows (small grids, see launch_raster)
     uint32_t* redo_dev; // k_raster_depth: tiles (one in REDO_SAMPLE) that had to be rastered again with 64-bit keys, since the last launch
     uint32_t* host_redo;    // ... handed to the host's pinned word by the next launch (the host then switches the scene to the 64-bit kernel)
+    const uint8_t* src_color;   // load frames (SWR_FLAG_LOAD): the image the frame starts from, band-local like color / depth and never
+    const float* src_depth;     // the same buffers (read-only for the frame)
 };
 constexpr int REDO_SAMPLE = 8;
 
@@ -1176,6 +1178,15 @@ __device__ __forceinline__ bool k32_undecided(float k) {
 }
 
 constexpr unsigned long long KEY_EMPTY = ~0ull;
+// Load frames (SWR_FLAG_LOAD), z-tested: a pixel starts with the key of the depth already there, low word 0 — every fragment of a load
+// frame carries its primitive word + 1, so on an equal depth the loaded image wins (strict '<', the first drawn keeps the pixel) and
+// the resolve knows a low word of 0 as "no fragment of this frame".  A loaded NaN gets the key 0 (no fragment's depth orders below
+// it: never replaced), a loaded -0 the key of +0 (equal under '<'); the resolve stores the loaded bits themselves, not a decode.
+__device__ __forceinline__ unsigned long long loaded_key(float d) {
+    const uint32_t u = __float_as_uint(d) & 0x7FFFFFFFu;
+    if (u > 0x7F800000u) return 0ull;
+    return (unsigned long long)orderable_depth(u ? d : 0.0f) << 32;
+}
 // A pixel has a winner iff the high word of its key is below the orderable image of +inf: the z-mode dense step
 // stores NaN / +inf depths as +inf keys instead of testing every fragment (they lose against any real depth and
 // are never resolved); painter's-mode keys have a zero high word; KEY_EMPTY has all ones.
@@ -1355,7 +1366,9 @@ constexpr int VAR_ALLCOOP = 20;
 #endif
 // K32: 32-bit depth keys (RasterLds32).  Returns true (workgroup-uniform) when the tile has to be rastered again with the
 // 64-bit keys — only a K32 instance ever does.
-template <bool ZTEST, int VAR, bool METAL, bool EXT, bool COLOR, bool PLAIN = false, bool K32 = false>
+// LOAD: a load frame (SWR_FLAG_LOAD): the tile starts from the image in a.src_color / a.src_depth instead of the clear, pixels without a
+// fragment of this frame keep it (painter's order: the depth image is the loaded one everywhere).
+template <bool ZTEST, int VAR, bool METAL, bool EXT, bool COLOR, bool PLAIN = false, bool K32 = false, bool LOAD = false>
 __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::conditional<K32, RasterLds32, RasterLds64>::type& L) {
     static_assert(!METAL || ZTEST, "the Metal rules always z-test");
     static_assert(!EXT || COLOR, "the extended fragment stage only exists for colour frames");
@@ -1489,7 +1502,41 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
     }
 
     // clear fused into the LDS init (Renderer.clear :205-206, :232-236)
-    if constexpr (K32) {
+    bool load_nan = false;      // (LOAD, 32-bit keys) a loaded NaN: ds_min_f32 would let any fragment replace it — the 64-bit path decides
+    if constexpr (LOAD && ZTEST) {
+        // a load frame: the depth already there (pixels outside the band / image stay empty: never resolved).  The 32-bit keys take
+        // four pixels per 16-B read; the 64-bit ones one pixel per lane and step (256 consecutive pixels: coalesced), not unrolled —
+        // the init must not raise the register peak the raster loop sets (Metal rules: 88 -> 90 unrolled)
+        if constexpr (K32) {
+            if (tid == 0) L.redo = 0u;
+            for (int i = tid; i < TILE_W * TILE_H / 4; i += RASTER_THREADS) {
+                const int ly = (i * 4) / TILE_W, lx = (i * 4) % TILE_W;
+                const int y = Y0 + ly, x = X0 + lx;
+                float d4[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
+                if (y <= Y1 && x <= X1) {
+                    const float* sp = a.src_depth + (size_t)(y - a.tg.row_begin) * (size_t)a.tg.width + (size_t)x;
+                    if ((a.tg.width & 3) == 0 && x + 3 <= X1) {
+                        const float4 v = *reinterpret_cast<const float4*>(sp);
+                        d4[0] = v.x; d4[1] = v.y; d4[2] = v.z; d4[3] = v.w;
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; k++) if (x + k <= X1) d4[k] = sp[k];
+                    }
+                }
+                reinterpret_cast<float4*>(L.keys)[i] = make_float4(d4[0], d4[1], d4[2], d4[3]);
+#pragma unroll
+                for (int k = 0; k < 4; k++) load_nan = load_nan || d4[k] != d4[k];
+            }
+        } else {
+            if constexpr (WTAB_OK) { if (tid < WTAB_WORDS) L.winners[tid] = make_uint2(0u, 0u); }
+#pragma unroll 1
+            for (int i = tid; i < TILE_W * TILE_H; i += RASTER_THREADS) {
+                const int y = Y0 + i / TILE_W, x = X0 + i % TILE_W;
+                keys[i] = (y <= Y1 && x <= X1) ? loaded_key(a.src_depth[(size_t)(y - a.tg.row_begin) * (size_t)a.tg.width + (size_t)x])
+                                               : KEY_EMPTY;
+            }
+        }
+    } else if constexpr (K32) {
         if (tid == 0) L.redo = 0u;
         for (int i = tid; i < TILE_W * TILE_H / 4; i += RASTER_THREADS)
             reinterpret_cast<float4*>(L.keys)[i] = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);   // (:206)
@@ -1498,6 +1545,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
         if constexpr (WTAB_OK) { if (tid < WTAB_WORDS) L.winners[tid] = make_uint2(0u, 0u); }
     }
     __syncthreads();
+    if constexpr (K32 && LOAD) { if (load_nan) L.redo = 1u; }     // (after the barrier that follows tid 0's reset; read after the raster's)
     if constexpr (K32) {
         if (insort) {                                                   // (workgroup-uniform)
             uint32_t s_pos[SORT_PER];
@@ -1566,6 +1614,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
             // visibility keys order by the ORIGINAL primitive index (Renderer.swift:222,258)
             if (a.reordered) t.prim = __float_as_uint(q1.w) >> GEOM_ORIG_SHIFT;
             if (WTAB_OK && wtab) t.prim = (t.prim << WTAB_LOCAL_BITS) | e;     // ... and the position in the bin below it (winner table)
+            if (LOAD && ZTEST) t.prim += 1u;                                    // (low word 0 = the loaded image: loaded_key)
             ya = max(t.ch.s0y, Yw0);
             // Metal rules: the samples of the ROI's last row lie at max-y + 0.5, half a pixel below every vertex: never
             // inside (the float evaluation of :144-153 errs by ~2^-8 px at most for GEOM_SMALL extents), so it is not walked
@@ -2068,8 +2117,9 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const unsigned long long key = keys[p + k];
-                    const uint32_t low = ZTEST ? (uint32_t)key : 0xFFFFFFFFu - (uint32_t)key;
-                    pos[g][k] = (uint32_t)(key >> 32) < KEY_LIVE_BELOW ? (low & ((1u << WTAB_LOCAL_BITS) - 1u)) : 0xFFFFu;
+                    const uint32_t low = ZTEST ? (uint32_t)key - (LOAD ? 1u : 0u) : 0xFFFFFFFFu - (uint32_t)key;
+                    const bool live = (uint32_t)(key >> 32) < KEY_LIVE_BELOW && !(LOAD && ZTEST && (uint32_t)key == 0u);
+                    pos[g][k] = live ? (low & ((1u << WTAB_LOCAL_BITS) - 1u)) : 0xFFFFu;
                 }
                 *reinterpret_cast<uint2*>(pix + p) = make_uint2(pos[g][0] | (pos[g][1] << 16), pos[g][2] | (pos[g][3] << 16));
             }
@@ -2183,16 +2233,45 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                     uint32_t cpix[4];
                     float dpix[4];
                     uint32_t stored = 0u;              // (rounds) which of the four pixels this round stores
+                    const size_t at = (size_t)(y - a.tg.row_begin) * (size_t)W + (size_t)x;   // App.swift:351-360
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
                         cpix[k] = 0u;                  // Pixel(0,0,0,0) (:205)
                         dpix[k] = INFINITY;            // (:206)
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
                         if (x + k > X1) continue;
                         if (ps[k] == 0xFFFFu) { if (base == 0u) stored |= 1u << k; continue; }
                         const uint32_t rid = rid_of(ps[k]) - base;
                         if (rid < (uint32_t)WTAB_RCAP) { shade(rid, x + k, y, cpix[k], dpix[k]); stored |= 1u << k; }
                     }
-                    const size_t at = (size_t)(y - a.tg.row_begin) * (size_t)W + (size_t)x;   // App.swift:351-360
+                    if constexpr (LOAD) {
+                        // a load frame: pixels without a winner keep the loaded image (painter's order: its depth everywhere).  Read
+                        // after the shades, so that nothing of it is live across them (the register peak is there).
+                        if (ps[0] == 0xFFFFu || ps[1] == 0xFFFFu || ps[2] == 0xFFFFu || ps[3] == 0xFFFFu || !ZTEST) {
+                            uint32_t sc[4] = {0u, 0u, 0u, 0u};
+                            float sd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                            if (vec_ok && x + 3 <= X1) {
+                                const uint4 c4 = *reinterpret_cast<const uint4*>(a.src_color + at * 4);
+                                const float4 d4 = *reinterpret_cast<const float4*>(a.src_depth + at);
+                                sc[0] = c4.x; sc[1] = c4.y; sc[2] = c4.z; sc[3] = c4.w;
+                                sd[0] = d4.x; sd[1] = d4.y; sd[2] = d4.z; sd[3] = d4.w;
+                            } else {
+#pragma unroll
+                                for (int k = 0; k < 4; k++) {
+                                    if (x + k > X1) continue;
+                                    sc[k] = reinterpret_cast<const uint32_t*>(a.src_color)[at + k];
+                                    sd[k] = a.src_depth[at + k];
+                                }
+                            }
+#pragma unroll
+                            for (int k = 0; k < 4; k++) {
+                                if (ps[k] == 0xFFFFu) cpix[k] = sc[k];
+                                if (ps[k] == 0xFFFFu || !ZTEST) dpix[k] = sd[k];
+                            }
+                        }
+                    }
                     if (one_round && vec_ok && x + 3 <= X1) {
                         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                         typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -2226,8 +2305,9 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
         for (int g = 0; g < 8; g++) {
             const int p = (tid + (g >> 2) * RASTER_THREADS) * 4 + (g & 3);
             const unsigned long long key = keys[p];
-            const uint32_t prim = ZTEST ? (uint32_t)key : 0xFFFFFFFFu - (uint32_t)key;
-            sl[g] = (uint32_t)(key >> 32) < KEY_LIVE_BELOW ? a.inv[prim] : 0u;
+            const uint32_t prim = ZTEST ? (uint32_t)key - (LOAD ? 1u : 0u) : 0xFFFFFFFFu - (uint32_t)key;
+            const bool live = (uint32_t)(key >> 32) < KEY_LIVE_BELOW && !(LOAD && ZTEST && (uint32_t)key == 0u);
+            sl[g] = live ? a.inv[prim] : 0u;
         }
 #pragma unroll
         for (int g = 0; g < 8; g++) slots[(tid + (g >> 2) * RASTER_THREADS) * 4 + (g & 3)] = sl[g];
@@ -2242,13 +2322,18 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
             const int y = Y0 + ly, x = X0 + lx;
             if (y < Yp0 || y > Yp1 || x > X1) continue;
             float d4[4];
+            const size_t at = (size_t)(y - a.tg.row_begin) * (size_t)W + (size_t)x;   // App.swift:351-360
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const uint32_t hi = (uint32_t)(keys[ly * TILE_W + lx + k] >> 32);
+                const unsigned long long key = keys[ly * TILE_W + lx + k];
+                const uint32_t hi = (uint32_t)(key >> 32);
                 d4[k] = depth_from_orderable(min(hi, KEY_LIVE_BELOW));
-                zero_seen = zero_seen || (d4[k] == 0.0f);
+                if (LOAD && (hi >= KEY_LIVE_BELOW || (uint32_t)key == 0u)) {
+                    if (x + k <= X1) d4[k] = a.src_depth[at + k];      // no fragment of this frame: the loaded bits
+                } else {
+                    zero_seen = zero_seen || (d4[k] == 0.0f);
+                }
             }
-            const size_t at = (size_t)(y - a.tg.row_begin) * (size_t)W + (size_t)x;   // App.swift:351-360
             if (vec_ok && x + 3 <= X1) {
                 typedef float f32x4 __attribute__((ext_vector_type(4)));
                 f32x4 dv = {d4[0], d4[1], d4[2], d4[3]};
@@ -2278,6 +2363,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
         // neighbouring pixels usually share the winning primitive: its record, T() and vertex
         // colours are fetched / computed once per run of equal primitives
         uint32_t cached_prim[NG], slot[NG];
+        uint32_t lmask[NG];          // (LOAD) pixels of the group without a fragment of this frame
         float4 q2[NG], q3[NG], ca[NG], cb[NG], cc[NG], na[NG], nb[NG], nc[NG];
         int4 g0[NG];
         float cfx[NG], cfy[NG];
@@ -2289,6 +2375,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
             y[g] = Y0 + ly[g]; x[g] = X0 + lx[g];
             on[g] = !(y[g] < Yp0 || y[g] > Yp1 || x[g] > X1);
             cached_prim[g] = 0xFFFFFFFFu; slot[g] = 0u;
+            lmask[g] = 0u;
             q2[g] = q3[g] = ca[g] = cb[g] = cc[g] = na[g] = nb[g] = nc[g] = make_float4(0, 0, 0, 0);
             g0[g] = make_int4(0, 0, 0, 0);
             cfx[g] = cfy[g] = 0.0f;
@@ -2307,9 +2394,10 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
             for (int g = 0; g < NG; g++) {
                 const unsigned long long key = keys[ly[g] * TILE_W + lx[g] + k];
                 const uint32_t hi = (uint32_t)(key >> 32);
-                const bool live = on[g] && hi < KEY_LIVE_BELOW && x[g] + k <= X1;
-                prim[g] = ZTEST ? (uint32_t)key : 0xFFFFFFFFu - (uint32_t)key;
+                const bool live = on[g] && hi < KEY_LIVE_BELOW && x[g] + k <= X1 && !(LOAD && ZTEST && (uint32_t)key == 0u);
+                prim[g] = ZTEST ? (uint32_t)key - (LOAD ? 1u : 0u) : 0xFFFFFFFFu - (uint32_t)key;
                 d[g] = INFINITY;           // (:206)
+                if (LOAD && !COLD && !live) lmask[g] |= 1u << k;     // a load frame: no fragment of this frame (the store below)
                 need_rec[g] = live && want_color;
                 if (ZTEST && live) {
                     d[g] = depth_from_orderable(hi);
@@ -2403,6 +2491,12 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                 if constexpr (COLD) {
                     if (on[g] && x[g] + k <= X1) {
                         const size_t at1 = (size_t)(y[g] - a.tg.row_begin) * (size_t)W + (size_t)(x[g] + k);
+                        if (LOAD && !need_rec[g]) {     // (colour frames: need_rec = a fragment of this frame won the pixel)
+                            c = reinterpret_cast<const uint32_t*>(a.src_color)[at1];
+                            d[g] = a.src_depth[at1];
+                        } else if (LOAD && !ZTEST) {
+                            d[g] = a.src_depth[at1];
+                        }
                         reinterpret_cast<uint32_t*>(a.color)[at1] = c;
                         a.depth[at1] = d[g];
                     }
@@ -2416,6 +2510,17 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
         for (int g = 0; g < NG; g++) {
             if (COLD || !on[g]) continue;
             const size_t at = (size_t)(y[g] - a.tg.row_begin) * (size_t)W + (size_t)x[g];   // App.swift:351-360
+            if (LOAD && (lmask[g] != 0u || !ZTEST)) {
+                // a load frame: the pixels without a fragment of this frame keep the loaded image (painter's order: the loaded depth
+                // everywhere)
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    if (x[g] + k > X1) continue;
+                    const bool ld = (lmask[g] >> k) & 1u;
+                    if (want_color && ld) cpix[g][k] = reinterpret_cast<const uint32_t*>(a.src_color)[at + k];
+                    if (ld || !ZTEST) dpix[g][k] = a.src_depth[at + k];
+                }
+            }
             if (vec_ok && x[g] + 3 <= X1) {
                 // streaming stores: nothing on the GPU reads the framebuffer again, and 33 MB of dirty lines left in the
                 // L2s would be written back at the end of the kernel, in front of the next one
@@ -2442,28 +2547,34 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
 // The kernels proper: the reference's fragment stage — colour and depth-only frames (SWR_FLAG_NO_COLOR) as separate kernels, so
 // that each has its own register allocation (tools/vgprs.sh: 86 depth-only, 87 colour, 88 Metal rules; the budget of 88 above) —
 // and the extended one.  PLAIN = the colour kernels of scenes with more than 2^20 primitives (no winner table: raster_tile).
-template <bool ZTEST, int VAR = 0, bool METAL = false, bool COLOR = false, bool PLAIN = false>
+// LOAD = the load frames' twin of each kernel (SWR_FLAG_LOAD), same register budget.
+template <bool ZTEST, int VAR = 0, bool METAL = false, bool COLOR = false, bool PLAIN = false, bool LOAD = false>
 __global__ __launch_bounds__(RASTER_THREADS, SWR_RASTER_MIN_WAVES) __attribute__((amdgpu_num_vgpr(SWR_RASTER_VGPRS)))
 void k_raster(RasterArgs a) {
     __shared__ RasterLds64 L;
-    raster_tile<ZTEST, VAR, METAL, false, COLOR, PLAIN>(a, L);
+    raster_tile<ZTEST, VAR, METAL, false, COLOR, PLAIN, false, LOAD>(a, L);
 }
-template <bool ZTEST, bool METAL = false, bool PLAIN = false>
+template <bool ZTEST, bool METAL = false, bool PLAIN = false, bool LOAD = false>
 __global__ __launch_bounds__(RASTER_THREADS, PLAIN ? 4 : SWR_RASTER_MIN_WAVES_EXT)
 void k_raster_ext(RasterArgs a) {
     __shared__ RasterLds64 L;
-    raster_tile<ZTEST, 0, METAL, true, true, PLAIN>(a, L);
+    raster_tile<ZTEST, 0, METAL, true, true, PLAIN, false, LOAD>(a, L);
 }
 // Depth-only z-tested frames under the CPU rules: 32-bit keys first; the rare tile whose result they cannot vouch for (a
 // zero, whose sign is the first-drawn winner's) is rastered again, by the same workgroup, with the 64-bit keys.  One LDS block for both.
+// (Load frames: a loaded +-0 shows up as a zero of the result like any other — the same redo; a loaded NaN, which ds_min_f32 would
+// replace, sends its tile there from the LDS init.)
+template <bool LOAD = false>
 __global__ __launch_bounds__(RASTER_THREADS, SWR_RASTER_MIN_WAVES) __attribute__((amdgpu_num_vgpr(SWR_RASTER_VGPRS)))
 void k_raster_depth(RasterArgs a) {
     constexpr size_t BYTES = sizeof(RasterLds64) > sizeof(RasterLds32) ? sizeof(RasterLds64) : sizeof(RasterLds32);
     __shared__ __attribute__((aligned(16))) unsigned char raw[BYTES];
     if (blockIdx.x == 0 && threadIdx.x == 0) *a.host_redo = atomicExch(a.redo_dev, 0u);     // what the launches before this one counted
-    if (raster_tile<true, 0, false, false, false, false, true>(a, *reinterpret_cast<RasterLds32*>(raw))) {
-        if (threadIdx.x == 0 && blockIdx.x % REDO_SAMPLE == 0) atomicAdd(a.redo_dev, 1u);
-        raster_tile<true, VAR_ALLCOOP, false, false, false, false, false>(a, *reinterpret_cast<RasterLds64*>(raw));
+    if (raster_tile<true, 0, false, false, false, false, true, LOAD>(a, *reinterpret_cast<RasterLds32*>(raw))) {
+        // (load frames are not counted: a starting image full of NaN or zeros says nothing about the scene, and the count decides
+        // whether the scene's clear frames stay on the 32-bit keys)
+        if (!LOAD && threadIdx.x == 0 && blockIdx.x % REDO_SAMPLE == 0) atomicAdd(a.redo_dev, 1u);
+        raster_tile<true, VAR_ALLCOOP, false, false, false, false, false, LOAD>(a, *reinterpret_cast<RasterLds64*>(raw));
     }
 }
 
@@ -2474,12 +2585,16 @@ void k_raster_depth(RasterArgs a) {
 // index order, no z.  "Later overwrites" = the highest index wins, so an atomicMax of (index + 1)
 // per pixel reproduces the serial loop; the band's depth buffer doubles as that u32 scratch and is
 // reset to +inf by the resolve (the reference leaves depth at its cleared value).
+// LOAD (SWR_FLAG_LOAD): the frame writes another framebuffer than the one it starts from, so the scratch is still the destination's
+// depth buffer; the resolve takes the loaded colour where no point / line landed and the loaded depth everywhere, and the clear
+// becomes a copy of the loaded image.
+template <bool LOAD = false>
 __global__ void k_clear_band(uint32_t* __restrict__ color, uint32_t* __restrict__ depth_bits, int64_t n,
-                             uint32_t depth_value) {
+                             uint32_t depth_value, const uint32_t* __restrict__ src_color, const uint32_t* __restrict__ src_depth) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (color) color[i] = 0u;                       // Pixel(0,0,0,0) (:205)
-        depth_bits[i] = depth_value;
+        if (color) color[i] = LOAD ? src_color[i] : 0u;                          // Pixel(0,0,0,0) (:205)
+        depth_bits[i] = (LOAD && src_depth) ? src_depth[i] : depth_value;
     }
 }
 
@@ -2534,12 +2649,14 @@ __global__ void k_lines(const swr_vertex* __restrict__ vtx, const int64_t* __res
     }
 }
 
+template <bool LOAD = false>
 __global__ void k_points_resolve(const swr_vertex* __restrict__ vtx, const int64_t* __restrict__ idx,
-                                 uint32_t* __restrict__ color, uint32_t* __restrict__ depth_bits, int64_t n) {
+                                 uint32_t* __restrict__ color, uint32_t* __restrict__ depth_bits, int64_t n,
+                                 const uint32_t* __restrict__ src_color, const uint32_t* __restrict__ src_depth) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint32_t o = depth_bits[i];
-        uint32_t c = 0u;
+        uint32_t c = LOAD ? src_color[i] : 0u;
         if (o) {
             const float4 v = reinterpret_cast<const float4*>(vtx)[2 * idx[o - 1] + 1];
             VertexOut vin;
@@ -2553,7 +2670,7 @@ __global__ void k_points_resolve(const swr_vertex* __restrict__ vtx, const int64
             c = qb | (qg << 8) | (qr << 16) | (qa << 24);
         }
         color[i] = c;
-        depth_bits[i] = 0x7F800000u;                                          // +inf (:206)
+        depth_bits[i] = LOAD ? src_depth[i] : 0x7F800000u;                    // +inf (:206)
     }
 }
 
@@ -2568,9 +2685,18 @@ void launch_points_or_lines(const DeviceFrame& f, int primitive_type, hipStream_
     const bool points = primitive_type == SWR_PRIMITIVE_VERTICES && want_color && f.index_count >= 3;
     const bool lines = primitive_type == SWR_PRIMITIVE_LINE && (f.flags & SWR_FLAG_REAL_LINES) && want_color && f.index_count >= 2;
     // .line (as written: an empty stub) and colour-less passes only clear; .vertices and real lines first zero the order
-    // scratch (= depth bits)
-    hipLaunchKernelGGL(k_clear_band, dim3(blocks), dim3(256), 0, s, want_color ? (uint32_t*)f.color : nullptr,
-                       (uint32_t*)f.depth, n, (points || lines) ? 0u : 0x7F800000u);
+    // scratch (= depth bits).  Load frames: the clear is a copy of the loaded image (only the depth scratch is zeroed for points / lines).
+    const bool load = (f.flags & SWR_FLAG_LOAD) != 0;
+    const uint32_t* sc = (const uint32_t*)f.src_color;
+    const uint32_t* sd = (const uint32_t*)f.src_depth;
+    if (!load)
+        hipLaunchKernelGGL(k_clear_band<false>, dim3(blocks), dim3(256), 0, s, want_color ? (uint32_t*)f.color : nullptr,
+                           (uint32_t*)f.depth, n, (points || lines) ? 0u : 0x7F800000u, nullptr, nullptr);
+    else if (points || lines)
+        hipLaunchKernelGGL(k_clear_band<true>, dim3(blocks), dim3(256), 0, s, nullptr, (uint32_t*)f.depth, n, 0u, nullptr, nullptr);
+    else if (f.color != f.src_color || f.depth != f.src_depth)
+        hipLaunchKernelGGL(k_clear_band<true>, dim3(blocks), dim3(256), 0, s, want_color ? (uint32_t*)f.color : nullptr,
+                           (uint32_t*)f.depth, n, 0x7F800000u, sc, sd);
     if (!points && !lines) return;
     const int64_t ni = f.index_count;
     float4x4 m;
@@ -2582,8 +2708,12 @@ void launch_points_or_lines(const DeviceFrame& f, int primitive_type, hipStream_
     else
         hipLaunchKernelGGL(k_points, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, s, f.vertices, f.indices, ni, m, f.tg,
                            (uint32_t*)f.depth);
-    hipLaunchKernelGGL(k_points_resolve, dim3(blocks), dim3(256), 0, s, f.vertices, f.indices, (uint32_t*)f.color,
-                       (uint32_t*)f.depth, n);
+    if (load)
+        hipLaunchKernelGGL(k_points_resolve<true>, dim3(blocks), dim3(256), 0, s, f.vertices, f.indices, (uint32_t*)f.color,
+                           (uint32_t*)f.depth, n, sc, sd);
+    else
+        hipLaunchKernelGGL(k_points_resolve<false>, dim3(blocks), dim3(256), 0, s, f.vertices, f.indices, (uint32_t*)f.color,
+                           (uint32_t*)f.depth, n, nullptr, nullptr);
 }
 
 void launch_validate_indices(const int64_t* indices, int64_t count, int64_t vertex_count,
@@ -2763,7 +2893,8 @@ bool frame_uses_k32(const DeviceFrame& f) {
     return f.k32 && (f.flags & SWR_FLAG_DEPTH_TEST) && (f.flags & SWR_FLAG_NO_COLOR) && !(f.flags & SWR_FLAG_METAL_RULES);
 }
 
-bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
+template <bool LOAD>
+static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     RasterArgs a;
     a.geo = f.geo; a.geo_full = f.geo_full; a.tri_rgb = f.tri_rgb;
     a.inv = f.inv; a.reordered = f.reordered;
@@ -2783,7 +2914,10 @@ bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     a.host_pairs = f.host_counters; a.host_fill = f.host_fill; a.host_max = f.host_max;
     a.redo_dev = f.redo_dev; a.host_redo = f.host_redo;
     a.insort = f.insort;
-    a.pack_local = f.ntri <= (1ll << WTAB_PRIM_BITS) ? 1 : 0;
+    a.src_color = LOAD ? f.src_color : nullptr;
+    a.src_depth = LOAD ? f.src_depth : nullptr;
+    // (a load frame's z-tested keys carry the packed word + 1: the last primitive of a scene of exactly 2^20 would wrap)
+    a.pack_local = f.ntri < (1ll << WTAB_PRIM_BITS) + (LOAD ? 0 : 1) ? 1 : 0;
     const bool plain = !a.pack_local;      // more than 2^20 primitives: the colour kernels without the winner table
     const unsigned ntiles = (unsigned)(f.tg.tiles_x * f.tg.tiles_y);
     if (ntiles == 0) return false;
@@ -2798,20 +2932,20 @@ bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     const unsigned tiles = ntiles << a.vs_log;
     const bool ext = f.material.shader != SWR_SHADER_PASSTHROUGH && a.color != nullptr;
     if (f.flags & SWR_FLAG_METAL_RULES) {
-        if (ext && plain) SWR_LAUNCH(stop, (k_raster_ext<true, true, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (ext) SWR_LAUNCH(stop, (k_raster_ext<true, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, true, true, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, true, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else SWR_LAUNCH(stop, (k_raster<true, 0, true, false>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        if (ext && plain) SWR_LAUNCH(stop, (k_raster_ext<true, true, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (ext) SWR_LAUNCH(stop, (k_raster_ext<true, true, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, true, true, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, true, true, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else SWR_LAUNCH(stop, (k_raster<true, 0, true, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
         return stop != nullptr;
     }
     if (ext) {
         if (f.flags & SWR_FLAG_DEPTH_TEST) {
-            if (plain) SWR_LAUNCH(stop, (k_raster_ext<true, false, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-            else SWR_LAUNCH(stop, (k_raster_ext<true, false>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+            if (plain) SWR_LAUNCH(stop, (k_raster_ext<true, false, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+            else SWR_LAUNCH(stop, (k_raster_ext<true, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
         } else {
-            if (plain) SWR_LAUNCH(stop, (k_raster_ext<false, false, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-            else SWR_LAUNCH(stop, (k_raster_ext<false, false>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+            if (plain) SWR_LAUNCH(stop, (k_raster_ext<false, false, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+            else SWR_LAUNCH(stop, (k_raster_ext<false, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
         }
         return stop != nullptr;
     }
@@ -2819,7 +2953,7 @@ bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     // timing-only ablations of k_raster<ztest> (results invalid): compiled only into lib/libswr_hip_ablation.so
     // (`make ablation`, used by tools/variants.sh); the product library has neither the kernels nor the switch
     static const int variant = getenv("SWR_DEBUG_VARIANT") ? atoi(getenv("SWR_DEBUG_VARIANT")) : 0;
-    if ((f.flags & SWR_FLAG_DEPTH_TEST) && variant > 0 && !a.color) {
+    if (!LOAD && (f.flags & SWR_FLAG_DEPTH_TEST) && variant > 0 && !a.color) {
         switch (variant) {
 #define SWR_V(N) case N: hipLaunchKernelGGL((k_raster<true, N>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a); return false;
             SWR_V(1) SWR_V(2) SWR_V(3) SWR_V(4) SWR_V(5) SWR_V(8) SWR_V(9) SWR_V(10) SWR_V(11)
@@ -2829,16 +2963,20 @@ bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     }
 #endif
     if (f.flags & SWR_FLAG_DEPTH_TEST) {
-        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, false, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (frame_uses_k32(f)) SWR_LAUNCH(stop, k_raster_depth, dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else SWR_LAUNCH(stop, (k_raster<true, 0, false, false>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (frame_uses_k32(f)) SWR_LAUNCH(stop, k_raster_depth<LOAD>, dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else SWR_LAUNCH(stop, (k_raster<true, 0, false, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
     } else {
-        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<false, 0, false, true, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color) SWR_LAUNCH(stop, (k_raster<false, 0, false, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else SWR_LAUNCH(stop, (k_raster<false, 0, false, false>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<false, 0, false, true, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (a.color) SWR_LAUNCH(stop, (k_raster<false, 0, false, true, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else SWR_LAUNCH(stop, (k_raster<false, 0, false, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
     }
     return stop != nullptr;
+}
+
+bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
+    return (f.flags & SWR_FLAG_LOAD) ? launch_raster_t<true>(f, s, stop) : launch_raster_t<false>(f, s, stop);
 }
 
 }  // namespace swr

@@ -124,8 +124,12 @@ struct Material {
     const Image<Pixel>* texture = nullptr;     // texturedPhong only; caller-owned b,g,r,a texels
 };
 
+// A render pass's load action (Metal's MTLLoadAction; include/swr.h SWR_FLAG_LOAD): clear = the reference's render(renderPass:)
+// (Renderer.swift:205-206 clear first); load = the pass draws on top of what colorBuffer / depthBuffer already hold.
+enum class LoadAction { clear, load };
+
 // Renderer.swift:191-200 (+ the optional extended fragment stage: empty attributes / passthrough material
-// = the reference's RenderPass exactly)
+// = the reference's RenderPass exactly; + the load action, clear by default = the reference)
 struct RenderPass {
     ColorImage colorBuffer;
     DepthImage depthBuffer;
@@ -135,6 +139,7 @@ struct RenderPass {
     matrix_float4x4 transform = matrix_float4x4::identity();
     std::vector<VertexAttributes> attributes = {};
     Material material = {};
+    LoadAction loadAction = LoadAction::clear;
 };
 
 namespace detail {
@@ -165,7 +170,7 @@ public:
         rp.indices = p.indices.data();
         rp.index_count = (int64_t)p.indices.size();
         rp.primitive_type = (int32_t)p.primitiveType;
-        rp.flags = flags;
+        rp.flags = flags | (p.loadAction == LoadAction::load ? (uint32_t)SWR_FLAG_LOAD : 0u);
         for (int c = 0; c < 4; c++)
             for (int r = 0; r < 4; r++) rp.transform[4 * c + r] = p.transform.columns[c][r];
         swr_material mat{};
