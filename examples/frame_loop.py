@@ -6,7 +6,10 @@ Every frame the app builds `projection * Transform(scale 2, rotation(time), tran
 and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident on the MI355X
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
-    python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test]
+    python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
+
+--objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
+per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
 
 The demo mesh is a UV sphere standing in for ModelIO's `MDLMesh(sphereWithExtent: 0.4, segments: 13x13,
 inwardNormals: true)` (App.swift:124) with colour = |normal| (App.swift:133).  `--obj` loads a
@@ -210,9 +213,25 @@ def write_ppm(path: str, bgra: np.ndarray):
         f.write(np.ascontiguousarray(bgra[..., [2, 1, 0]]).tobytes())
 
 
+def object_transforms(time: float, n: int):
+    """The app's matrix for n copies of the mesh: copy j spins with its own phase and sits at its own place on an
+    ceil(sqrt(n))-wide grid (a screen-space offset applied after the projection: x' = x + dx * w)."""
+    g = max(1, math.ceil(math.sqrt(n)))
+    out = []
+    for j in range(n):
+        m = S.app_transform(time + 0.37 * j, scale=2.0 / g).reshape(4, 4).copy()     # rows = columns (column-major)
+        dx = (2.0 * (j % g) + 1.0) / g - 1.0
+        dy = 1.0 - (2.0 * (j // g) + 1.0) / g
+        m[:, 0] += np.float32(dx) * m[:, 3]
+        m[:, 1] += np.float32(dy) * m[:, 3]
+        out.append(np.ascontiguousarray(m.reshape(16), dtype=np.float32))
+    return out
+
+
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
-        time0: float = 0.0):
-    """Returns the list of (colour, depth) frames; writes PPMs when `out` is given."""
+        time0: float = 0.0, objects: int = 1):
+    """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
+    mesh, one draw list per frame (the third element of every result is then the list of matrices)."""
     vertices, indices = load_mesh(obj) if obj else sphere_mesh()
     flags = S.FLAG_DEPTH_TEST if depth_test else 0
     results = []
@@ -221,8 +240,12 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
         ctx.target_set(size, size)                      # MetalView.Coordinator.width/height, App.swift:52-53
         time = time0
         for k in range(frames):
-            m = S.app_transform(time)                   # App.swift:169-183
-            ctx.draw(m, flags)                          # renderer.render(renderPass:), App.swift:185
+            if objects > 1:
+                m = object_transforms(time, objects)
+                ctx.draw_list([(0, indices.size, mj) for mj in m], flags)    # all copies in one frame
+            else:
+                m = S.app_transform(time)               # App.swift:169-183
+                ctx.draw(m, flags)                      # renderer.render(renderPass:), App.swift:185
             color, depth = ctx.read_color(), ctx.read_depth()
             results.append((color, depth, m))
             if out:
@@ -279,11 +302,12 @@ if __name__ == "__main__":
     ap.add_argument("--depth-test", action="store_true")
     ap.add_argument("--stream", action="store_true", help="asynchronous presents into two page-locked image sets")
     ap.add_argument("--gpus", type=int, default=1, help="bands / GPUs of the one context (with --stream)")
+    ap.add_argument("--objects", type=int, default=1, help="copies of the mesh, each with its own matrix: one draw list per frame")
     a = ap.parse_args()
     if a.stream:
         res = run_streamed(a.frames, a.size, a.ply or a.obj, a.depth_test, device_count=a.gpus)
         print(f"{a.frames} frames streamed, coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
-    _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test)
+    _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
-    print(f"{a.frames} frames, {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")
+    print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

@@ -318,6 +318,33 @@ int swr_sync(swr_context* ctx);
  * others are staged.  (ABI 6) */
 int swr_target_write(swr_context* ctx, const void* color_full_image, const float* depth_full_image);
 
+/* ---- Draw lists: several draws with their own transforms in one frame — DESIGN.md §12 ----------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6): nothing existing changes.  The presence of the swr_draw_list symbol is the feature test.
+ * One draw item = a range of the uploaded index array drawn with its own transform. */
+typedef struct swr_draw_item {
+    int64_t first_index;   /* into the uploaded index array; multiple of 3 */
+    int64_t index_count;   /* multiple of 3; 0 = an empty draw */
+    float   transform[16]; /* column-major, exactly as swr_draw's */
+} swr_draw_item;           /* 80 bytes */
+#define SWR_DRAW_LIST_MAX 4096
+/* One frame of `item_count` draws.  The frame is Renderer.render(renderPass:) over the concatenation of the items: item k contributes
+ * the triangles indices[first_index_k, first_index_k + index_count_k), each transformed by transform_k; the primitive order is item
+ * order first, then index order inside an item.  So under painter's order a later item covers an earlier one, and under the z-test
+ * (strict '<') the earlier item wins a tie.  The image is bit for bit the clear frame (the load frame under SWR_FLAG_LOAD) of the
+ * pre-transformed concatenation drawn with the identity, and bit for bit the chain of item_count frames of one item each, the first
+ * a clear frame and the others SWR_FLAG_LOAD frames.
+ *   Ranges may overlap, repeat and come in any order: one range drawn K times with K matrices is instancing.  item_count == 0 is a
+ *     frame without triangles (it clears, or keeps the image under SWR_FLAG_LOAD).
+ *   flags apply to the whole frame (SWR_FLAG_DEPTH_TEST, SWR_FLAG_NO_COLOR, SWR_FLAG_METAL_RULES, SWR_FLAG_LOAD); material, vertex
+ *     attributes and texture are the context's, as for swr_draw.  Triangles only.
+ *   Asynchronous like swr_draw; the list is copied, the caller may overwrite it as soon as the call returns.  A multi-device context
+ *     draws the list on every band.  swr_timings.triangles counts the list's total; swr_present / swr_read_* / SWR_ERR_FRAME_DROPPED
+ *     behave as for any other frame.
+ * Errors: SWR_ERR_INDEX_COUNT — a first_index or index_count that is not a multiple of 3;  SWR_ERR_BAD_ARG — a range outside the
+ *   uploaded index array, items == NULL with item_count > 0, item_count < 0;  SWR_ERR_UNSUPPORTED — item_count > SWR_DRAW_LIST_MAX,
+ *   or 2^24 triangles or more in the list;  SWR_ERR_NO_SCENE — no scene or no target. */
+int swr_draw_list(swr_context* ctx, const swr_draw_item* items, int32_t item_count, uint32_t flags);
+
 /* ---- host-visible frames: the gather ("final image gathered with pinned hipMemcpyAsync") -------------------
  * The reference's images live in CPU/GPU-shared MTLBuffers (App.swift:59-60,80-101) and are complete on return
  * of render (scheduleAndWait, Metal+Extensions.swift:57-67).  Here every band is copied device -> host into its

@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "swr_band_rows", "swr_scene_attributes", "swr_material_set", "swr_texture_upload",
     "swr_timing_sample", "swr_context_bands", "swr_context_band_info", "swr_host_alloc", "swr_host_free",
     "swr_host_register", "swr_host_unregister", "swr_present", "swr_present_wait", "swr_device_count",
-    "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write",
+    "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -84,6 +84,17 @@ class RenderTimes(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 FAULT_NONE, FAULT_LOST_EVENT, FAULT_ENQUEUE = 0, 1, 2
+
+
+class DrawItem(ctypes.Structure):
+    """swr_draw_item: indices [first_index, first_index + index_count) drawn with `transform` (16 floats, as Context.draw's)."""
+    _fields_ = [("first_index", ctypes.c_int64), ("index_count", ctypes.c_int64), ("transform", ctypes.c_float * 16)]
+
+
+DRAW_LIST_MAX = 4096
+
+# structured-array form of a draw list (Context.draw_list accepts it as is)
+DRAW_ITEM_DTYPE = np.dtype([("first_index", np.int64), ("index_count", np.int64), ("transform", np.float32, (16,))])
 
 
 class Timings(ctypes.Structure):
@@ -169,6 +180,12 @@ def load_library():
         if not os.environ.get("SWR_LIBRARY"):      # only an older A/B build loaded by tools/ may lack the ABI 4 entry points
             raise
     L.swr_present.argtypes = [vp, vp, vp]
+    try:
+        L.swr_draw_list.argtypes = [vp, vp, i32, u32]
+        L.swr_draw_list.restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
     L.swr_target_write.argtypes = [vp, vp, vp]
     L.swr_target_write.restype = ctypes.c_int
     L.swr_present_wait.argtypes = [vp]
@@ -338,6 +355,26 @@ class Context:
         rc = self._L.swr_draw_primitives(self._h, self._m_ptr, flags, primitive_type)
         if rc:
             self._check(rc)
+
+    @staticmethod
+    def draw_items(items) -> np.ndarray:
+        """A draw list as the structured array swr_draw_list reads (DRAW_ITEM_DTYPE, 80 bytes per item): from such an array
+        itself, or from (first_index, index_count, transform) tuples."""
+        if isinstance(items, np.ndarray) and items.dtype == DRAW_ITEM_DTYPE:
+            return np.ascontiguousarray(items)
+        items = list(items)
+        a = np.zeros(len(items), dtype=DRAW_ITEM_DTYPE)
+        for k, (first, count, transform) in enumerate(items):
+            a[k]["first_index"] = first
+            a[k]["index_count"] = count
+            a[k]["transform"] = np.asarray(transform, dtype=np.float32).reshape(16)
+        return a
+
+    def draw_list(self, items, flags: int = 0):
+        """swr_draw_list: one frame of several draws, each an index range with its own transform (include/swr.h).  `items`:
+        (first_index, index_count, transform) tuples or a DRAW_ITEM_DTYPE array.  The list is copied by the call."""
+        a = self.draw_items(items)
+        self._check(self._L.swr_draw_list(self._h, a.ctypes.data if a.size else None, a.size, flags))
 
     def sync(self):
         self._check(self._L.swr_sync(self._h))

@@ -25,6 +25,8 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <iterator>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -224,6 +226,14 @@ struct swr_context {
         DevBuf tilebuf;        // [CNT_WORDS counters][tiles tile_count][tiles+1 tile_start][tiles cursor]
         hipEvent_t bin_done = nullptr, ras_done = nullptr;
         uint64_t ras_event_frame = ~0ull;   // the frame whose k_raster this slot's ras_done tracks (none yet)
+        // draw-list frames: the item table (pinned staging -> device, on the frame's own stream, before its binning)
+        // and the frame's per-slot colours / attributes / original-index table (k_list_gather)
+        DevBuf items, lrgb, lnrm, linv;
+        ListItem* items_host = nullptr;     // pinned; rewritten only after items_copied (its last copy) has completed
+        size_t items_cap = 0;
+        hipEvent_t items_copied = nullptr;
+        bool items_recorded = false;
+        uint64_t items_frame = 0;           // the frame whose copy items_copied follows
     } slot[NSLOT];
     hipStream_t bin_stream = nullptr;   // the stream binning is enqueued on (== stream when pipelining is off)
     hipStream_t bin_stream_own = nullptr;
@@ -310,6 +320,17 @@ struct swr_context {
     uint64_t posted = 0;                        // frames whose binning share has been handed to the helper (or run inline)
     static constexpr int RAS_RING = 64;          // frames whose raster share may be waiting for ras_worker; swr_draw blocks beyond that
     struct RasJob { DeviceFrame f; hipEvent_t ev3 = nullptr, ev4 = nullptr; int si = 0; bool sort_here = false; int fb = 0; bool paced = false; } ras_job[RAS_RING];
+    // ---- draw lists (swr_draw_list)
+    bool stream_sorted = false;         // the stream is Morton-sorted: a list's ranges must be runs of slots (cut the stream at them)
+    std::vector<uint32_t> cuts;         // primitive indices the stream is cut at now (sorted; empty: one segment, as uploaded)
+    DevBuf cuts_dev;
+    std::vector<ListItem> list;         // the items of the last draw-list frame (its redo after an overflow needs them again)
+    int64_t list_tris = 0;              // its total
+    int64_t list_units = 0;             // its k_bin work units
+    bool list_affine = false;
+    bool list_identity = false;         // frame slot == stream slot and order number == original index for every item
+    bool last_list = false;             // the last frame was a draw list
+    int64_t list_plan_max = 0;          // largest binning size (work units * 64) of a list since the upload (fixed-bin limits)
     // last draw (for the overflow redo and for swr_render)
     float last_m[16]{};
     uint32_t last_flags = 0;
@@ -649,6 +670,82 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
     return f;
 }
 
+// ---- draw-list frames ----------------------------------------------------------------------------------------------
+// The frame of the last draw list: V = the list's total primitives, binned by k_bin<.., LIST> over (item, stream group) work units
+// (fixed-stride bins) or by k_list_setup + k_scan + k_fill (exact-size bins).  Unless every item's frame slots are its stream slots,
+// the raster reads the frame's own copies of the per-slot tables (k_list_gather).
+void make_list_frame(swr_context* c, int si, DeviceFrame& f) {
+    swr_context::Slot& sl = c->slot[si];
+    f.ntri = c->list_tris;
+    f.items = (const ListItem*)sl.items.p;
+    f.nitems = (int32_t)c->list.size();
+    f.units = c->list_units;
+    f.list_affine = c->list_affine ? 1 : 0;
+    const int tiles = tiles_of(c->tg);
+    f.fixed_bins = (c->fixed_mode && f.ntri > 0) ? 1 : 0;
+    if (f.fixed_bins) {
+        f.plan = plan_binning(f.units * 64, tiles, false);
+        if (c->synced_upto == c->posted)     // (an idle context: twice the workgroups, as make_frame)
+            f.plan.G = (int)std::max<int64_t>(1, std::min<int64_t>(SWR_TUNE_IDLE_BIN_G, std::max<int64_t>(f.plan.G, (f.units + 7) / 8)));
+    } else {
+        f.plan = plan_binning(f.ntri, tiles, true);
+    }
+    if (!c->list_identity && f.ntri > 0) {
+        f.reordered = 1;                    // keys carry order numbers; inv maps them to frame slots
+        f.inv = (const uint32_t*)sl.linv.p;
+        f.gather.rgb = (const float4*)c->tri_rgb.p; f.gather.nrm = (const float4*)c->tri_nrm.p;
+        f.gather.inv_out = (uint32_t*)sl.linv.p;
+        // (sized by swr_draw_list for the flags and material of the list; a material set after it is not the list's)
+        const size_t need = (size_t)f.ntri * 48;
+        if (!(f.flags & SWR_FLAG_NO_COLOR) && sl.lrgb.bytes >= need) {
+            f.tri_rgb = f.gather.rgb_out = (float4*)sl.lrgb.p;
+            if (c->material.shader != SWR_SHADER_PASSTHROUGH && sl.lnrm.bytes >= need) f.tri_nrm = f.gather.nrm_out = (float4*)sl.lnrm.p;
+        }
+    }
+}
+
+// What the binning share of a draw-list frame enqueues in front of its binning, on the frame's stream (captured by value: in the
+// two-stream pipeline a helper thread enqueues it later).
+struct ListPrep {
+    bool on = false;
+    void* dev = nullptr; const void* host = nullptr; size_t bytes = 0;
+    hipEvent_t copied = nullptr;
+};
+
+// The item table into the slot's pinned staging.  The staging is rewritten only once the copy that last read it has completed: in the
+// two-stream pipeline that copy is enqueued by the binning helper, so its binning share has to be on the stream first.
+int stage_list(swr_context* c, int si, uint64_t frame, ListPrep& lp) {
+    swr_context::Slot& sl = c->slot[si];
+    int rc;
+    if (!sl.items_copied) HIP_TRY(c, hipEventCreateWithFlags(&sl.items_copied, hipEventDisableTiming));
+    if (sl.items_recorded && sl.items_frame < frame) {      // (a frame number posted again after a failed post: it never copied)
+        if (!lane_mode(c) && (rc = wait_counter(c, c->bin_enqueued, sl.items_frame, "the binning share of an earlier draw list"))) return rc;
+        if ((rc = poll_event(c, sl.items_copied, "the copy of an earlier frame's draw list", sl.items_frame))) return rc;
+        sl.items_recorded = false;
+    }
+    const size_t n = c->list.size();
+    if (sl.items_cap < n) {
+        if (sl.items_host) { HIP_TRY(c, hipHostFree(sl.items_host)); sl.items_host = nullptr; sl.items_cap = 0; }
+        const size_t want = std::max<size_t>(64, n);
+        HIP_TRY(c, hipHostMalloc((void**)&sl.items_host, want * sizeof(ListItem), hipHostMallocDefault));
+        sl.items_cap = want;
+    }
+    if (n) memcpy(sl.items_host, c->list.data(), n * sizeof(ListItem));
+    sl.items_recorded = true;
+    sl.items_frame = frame;
+    lp.on = true;
+    lp.dev = sl.items.p; lp.host = sl.items_host; lp.bytes = n * sizeof(ListItem);
+    lp.copied = sl.items_copied;
+    return SWR_OK;
+}
+
+int enqueue_list_prep(swr_context* c, const ListPrep& lp, hipStream_t s) {
+    if (!lp.on) return SWR_OK;
+    if (lp.bytes) HIP_TRY(c, hipMemcpyAsync(lp.dev, lp.host, lp.bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipEventRecord(lp.copied, s));
+    return SWR_OK;
+}
+
 // read the events of every completed-but-unread frame (caller has synchronised the stream)
 void harvest(swr_context* c) {
     for (; c->harvested < c->seq; c->harvested++) {
@@ -737,6 +834,12 @@ int enqueue_frame(swr_context* c) {
     const int si = (int)(frame % swr_context::NSLOT);
     c->last_slot = si;
     DeviceFrame f = make_frame(c, si, frame, c->last_m, c->last_flags);
+    ListPrep lp;
+    if (c->last_list) {
+        make_list_frame(c, si, f);
+        const int rc = stage_list(c, si, frame, lp);
+        if (rc) { c->frame_no = frame; return rc; }
+    }
     hipEvent_t* ev = nullptr;
     if (c->timing >= 2 || (c->timing == 1 && (c->frame_no % (uint64_t)c->timing_every) == 0)) {
         if (c->seq - c->harvested >= (uint64_t)swr_context::RING) {   // ring full: drain it
@@ -846,6 +949,7 @@ int enqueue_frame(swr_context* c) {
         auto enq = [&]() -> int {
             if (zero_tables) HIP_TRY(c, hipMemsetAsync(c->slot[si].tilebuf.p, 0, zero_bytes, S));
             if (fill_memset) HIP_TRY(c, hipMemsetAsync(f.fill, 0, (size_t)(CNT_WORDS + tiles_of(f.tg)) * 4, S));
+            { const int rl = enqueue_list_prep(c, lp, S); if (rl) return rl; }
             if (e0) HIP_TRY(c, hipEventRecord(e0, S));
             if (f.fixed_bins) {
                 launch_bin(f, S, nullptr);
@@ -893,7 +997,7 @@ int enqueue_frame(swr_context* c) {
     // helpers or the caller's own thread?  (idle context: every earlier frame is complete)
     const bool streaming = sb != sr && (c->bin_worker || c->ras_worker) && !(c->inline_idle && c->synced_upto == c->posted);
     const bool paced = streaming && c->ras_worker != nullptr;      // cross-stream order by host polls instead of event waits
-    auto bin_share = [c, f, si, sb, sr, frame, zero_tables, zero_bytes, e0, e1, e2, sort_on_raster_stream, slot_wait, paced, fill_memset]() -> int {
+    auto bin_share = [c, f, si, sb, sr, frame, zero_tables, zero_bytes, e0, e1, e2, sort_on_raster_stream, slot_wait, paced, fill_memset, lp]() -> int {
         swr_context::Slot& sl = c->slot[si];
         if (slot_wait) {
             // the first event-carrying raster at or after that frame (RAS_EVERY); its event must have been bound /
@@ -911,6 +1015,7 @@ int enqueue_frame(swr_context* c) {
         // tile table (counts, starts, counters) is simply zeroed.
         if (zero_tables) HIP_TRY(c, hipMemsetAsync(sl.tilebuf.p, 0, zero_bytes, sb));
         if (fill_memset) HIP_TRY(c, hipMemsetAsync(f.fill, 0, (size_t)(CNT_WORDS + tiles_of(f.tg)) * 4, sb));
+        { const int rl = enqueue_list_prep(c, lp, sb); if (rl) return rl; }
         if (e0) HIP_TRY(c, hipEventRecord(e0, sb));
         // bin_done = the completion of the chain's last kernel itself (bound at launch) where there is one
         hipEvent_t stop = (sb != sr && c->bind_events) ? sl.bin_done : nullptr;
@@ -1110,6 +1215,9 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     c->has_scene = false;
     c->has_attrs = false;
     c->draw_pending = false;
+    c->last_list = false;
+    c->cuts.clear();                 // a new stream is one segment
+    c->list_plan_max = 0;
     c->present_pending = false;
     int rc;
     if ((rc = ensure(c, c->vertices, (size_t)vertex_count * sizeof(swr_vertex)))) return rc;
@@ -1179,6 +1287,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
         HIP_TRY(c, hipEventRecord(c->up_chunk_ev, side));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->up_chunk_ev, 0));
         c->reordered = true;                                          // (identity order; the original index travels in GeomRec.flags)
+        c->stream_sorted = false;
     } else {
         if (index_count)
             HIP_TRY(c, hipMemcpyAsync(c->indices.p, indices, (size_t)index_count * 8, hipMemcpyHostToDevice, c->stream));
@@ -1188,6 +1297,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, launch_build_stream(b, c->stream));
         c->reordered = ntri > 0 && ntri < SORT_MAX_TRIS && sort_mode != -1;   // original index travels in GeomRec.flags
+        c->stream_sorted = reorder;
     }
     HIP_TRY(c, hipMemcpyAsync(c->h_misc, c->slot[0].tilebuf.p, CNT_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->up_ev[2], c->stream));
@@ -1359,6 +1469,185 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
     c->src_clear = false;
     c->last_flags = flags;
     c->last_prim = primitive_type;
+    c->last_list = false;
+    return enqueue_frame(c);
+}
+
+// ---- swr_draw_list ----------------------------------------------------------------------------------------------
+// The argument checks of a list against a scene of `ni` indices (ready: a scene and a target are there); *tris = the list's total.
+int check_list_args(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags, bool ready, int64_t ni, int64_t* tris) {
+    int rc = check_draw_args(c, flags, SWR_PRIMITIVE_TRIANGLE);
+    if (rc) return rc;
+    if (n < 0) return fail(c, SWR_ERR_BAD_ARG, "swr_draw_list: item_count %d", (int)n);
+    if (n > SWR_DRAW_LIST_MAX) return fail(c, SWR_ERR_UNSUPPORTED, "swr_draw_list: %d items (at most %d)", (int)n, SWR_DRAW_LIST_MAX);
+    if (n > 0 && !items) return fail(c, SWR_ERR_BAD_ARG, "swr_draw_list: items is NULL");
+    for (int32_t k = 0; k < n; k++)
+        if (items[k].first_index % 3 != 0 || items[k].index_count % 3 != 0)
+            return fail(c, SWR_ERR_INDEX_COUNT, "swr_draw_list: item %d: first_index %lld / index_count %lld not a multiple of 3", (int)k,
+                        (long long)items[k].first_index, (long long)items[k].index_count);
+    if (!ready) return fail(c, SWR_ERR_NO_SCENE, "swr_draw_list needs swr_scene_upload and swr_target_set first");
+    int64_t total = 0;
+    for (int32_t k = 0; k < n; k++) {
+        const int64_t a = items[k].first_index, cnt = items[k].index_count;
+        if (a < 0 || cnt < 0 || a > ni || cnt > ni - a)
+            return fail(c, SWR_ERR_BAD_ARG, "swr_draw_list: item %d: indices [%lld, %lld + %lld) outside the %lld uploaded", (int)k,
+                        (long long)a, (long long)a, (long long)cnt, (long long)ni);
+        total += cnt / 3;
+        if (total >= SORT_MAX_TRIS)
+            return fail(c, SWR_ERR_UNSUPPORTED, "swr_draw_list: 2^24 triangles or more in one list (the width of the order number)");
+    }
+    *tris = total;
+    return SWR_OK;
+}
+
+// Rebuild the stream cut at `cuts` (every stream idle): sorted by (segment, Morton code), so that every segment is a run of slots.
+int restream(swr_context* c, const std::vector<uint32_t>& cuts) {
+    int rc;
+    const int64_t ntri = c->ni / 3;
+    if ((rc = ensure(c, c->cuts_dev, std::max<size_t>(1, cuts.size()) * 4))) return rc;
+    if (!cuts.empty()) HIP_TRY(c, hipMemcpyAsync(c->cuts_dev.p, cuts.data(), cuts.size() * 4, hipMemcpyHostToDevice, c->stream));
+    StreamBuild b{};
+    b.vertices = (const swr_vertex*)c->vertices.p; b.nv = c->nv;
+    b.indices = (const int64_t*)c->indices.p; b.ntri = ntri;
+    b.sort = true;
+    b.scratch = (uint32_t*)c->stream_scratch.p;
+    b.sort_temp = c->sort_temp.p; b.sort_temp_bytes = c->sort_temp.bytes;
+    b.tri_xyz = (float4*)c->tri_xyz.p; b.tri_rgb = (float4*)c->tri_rgb.p;
+    b.inv = (uint32_t*)c->inv.p; b.box64 = (float4*)c->box64.p;
+    b.cuts = (const uint32_t*)c->cuts_dev.p; b.ncuts = (int)cuts.size();
+    HIP_TRY(c, launch_build_stream(b, c->stream));
+    if (c->has_attrs)
+        launch_gather_attrs((const swr_vertex_attr*)c->attrs.p, c->nv, (const int64_t*)c->indices.p, ntri,
+                            (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = wait_stream(c, c->stream, "stream rebuild (draw list)"))) return sticky(c) ? sticky(c) : rc;
+    c->cuts = cuts;
+    return SWR_OK;
+}
+
+int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags) {
+    if (const int f = sticky(c)) return f;
+    int64_t tris = 0;
+    int rc = check_list_args(c, items, n, flags, c->has_scene && c->has_target, c->ni, &tris);
+    if (rc) return rc;
+    if (!(flags & SWR_FLAG_NO_COLOR) && c->material.shader != SWR_SHADER_PASSTHROUGH) {
+        if (!c->has_attrs)
+            return fail(c, SWR_ERR_BAD_ARG, "the material needs vertex attributes (swr_scene_attributes)");
+        if (c->material.shader == SWR_SHADER_TEXTURED_PHONG && c->tex_w <= 0)
+            return fail(c, SWR_ERR_BAD_ARG, "the material needs a texture (swr_texture_upload)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->frame_no - c->frames_checked >= (uint64_t)swr_context::PAIR_RING - 2) {
+        if ((rc = check_frames(c))) return rc;
+    }
+    // the items, resolved: primitive ranges, frame bases, work units
+    std::vector<ListItem> list((size_t)n);
+    std::vector<uint32_t> need;             // the cuts the stream needs
+    const int64_t ntri = c->ni / 3;
+    int64_t vbase = 0, units = 0;
+    bool affine = true, identity = true;
+    for (int32_t k = 0; k < n; k++) {
+        ListItem& it = list[(size_t)k];
+        it.first = (uint32_t)(items[k].first_index / 3);
+        it.count = (uint32_t)(items[k].index_count / 3);
+        it.vbase = (uint32_t)vbase;
+        it.ubase = (uint32_t)units;
+        memcpy(it.m, items[k].transform, sizeof it.m);
+        if (it.count) {
+            units += (int64_t)((it.first + it.count - 1) >> 6) - (int64_t)(it.first >> 6) + 1;
+            affine = affine && it.m[3] == 0.0f && it.m[7] == 0.0f && it.m[11] == 0.0f && it.m[15] == 1.0f;
+            identity = identity && it.first == it.vbase;
+            if (it.first > 0) need.push_back(it.first);
+            if ((int64_t)it.first + it.count < ntri) need.push_back(it.first + it.count);
+        }
+        vbase += it.count;
+    }
+    // A Morton-sorted stream scatters an index range over the whole stream: cut it at every range boundary first (once per new set
+    // of boundaries — the cuts made for earlier lists stay while they are few)
+    if (c->stream_sorted && !need.empty()) {
+        std::sort(need.begin(), need.end());
+        need.erase(std::unique(need.begin(), need.end()), need.end());
+        if (!std::includes(c->cuts.begin(), c->cuts.end(), need.begin(), need.end())) {
+            std::vector<uint32_t> cuts;
+            std::set_union(c->cuts.begin(), c->cuts.end(), need.begin(), need.end(), std::back_inserter(cuts));
+            if (cuts.size() > (size_t)2 * SWR_DRAW_LIST_MAX) cuts = need;
+            if ((rc = check_frames(c))) return rc;           // (every stream idle; an overflowed last frame redrawn on the old stream)
+            if ((rc = restream(c, cuts))) return rc;
+        }
+    }
+    // per-slot buffers for V frame slots (grown with every stream idle)
+    {
+        const size_t V = (size_t)std::max<int64_t>(tris, 1);
+        const bool color = !(flags & SWR_FLAG_NO_COLOR);
+        const bool ext = color && c->material.shader != SWR_SHADER_PASSTHROUGH;
+        auto small = [&](const swr_context::Slot& sl) {
+            return sl.geo.bytes < V * sizeof(GeomRec) || sl.geo_full.bytes < V * sizeof(GeomFull) || sl.ranges.bytes < V * sizeof(uint2) ||
+                   sl.items.bytes < std::max<size_t>(1, (size_t)n) * sizeof(ListItem) ||
+                   (!identity && (sl.linv.bytes < V * 4 || (color && sl.lrgb.bytes < V * 48) || (ext && sl.lnrm.bytes < V * 48)));
+        };
+        bool grow = false;
+        for (auto& sl : c->slot) grow = grow || small(sl);
+        if (grow) {
+            if ((rc = sync_streams(c))) return rc;
+            for (auto& sl : c->slot) {
+                if ((rc = ensure(c, sl.geo, V * sizeof(GeomRec)))) return rc;
+                if ((rc = ensure(c, sl.geo_full, V * sizeof(GeomFull)))) return rc;
+                if ((rc = ensure(c, sl.ranges, V * sizeof(uint2)))) return rc;
+                if ((rc = ensure(c, sl.items, std::max<size_t>(1, (size_t)n) * sizeof(ListItem)))) return rc;
+                if (!identity) {
+                    if ((rc = ensure(c, sl.linv, V * 4))) return rc;
+                    if (color && (rc = ensure(c, sl.lrgb, V * 48))) return rc;
+                    if (ext && (rc = ensure(c, sl.lnrm, V * 48))) return rc;
+                }
+            }
+        }
+    }
+    // fixed-stride bins: k_bin<.., LIST> must be able to hold the list's work (a workgroup's share of the units below the cursor
+    // limit); a list beyond that moves the context to the exact-size bins, as a scene that needs more than a region would
+    // The first guess of the bins, as size_bins makes it for a scene, by the list's V: they only grow (with every stream idle)
+    const int tiles = tiles_of(c->tg);
+    if (c->fixed_mode && tris > 0) {
+        const uint32_t cmax = fixed_cap_max(units * 64, tiles);
+        if (cmax < c->cap_tile) {
+            if ((rc = sync_streams(c))) return rc;
+            c->fixed_mode = false;
+            c->fixed_allowed = false;
+        } else {
+            uint64_t want = std::max<uint64_t>(std::max<uint64_t>(64, (uint64_t)(6 * tris / tiles)), (uint64_t)std::min<int64_t>(tris, 1024));
+            // (capped for the scene's own frames too: a region survives into them, and their cursors must stay below 2^16)
+            want = std::min<uint64_t>((want + 63) & ~63ull, fixed_cap_max(std::max<int64_t>(ntri, units * 64), tiles));
+            if (want > c->cap_tile) {
+                if ((rc = sync_streams(c))) return rc;
+                if ((rc = ensure_bins(c, (size_t)tiles * want))) return rc;
+                c->cap_tile = (uint32_t)want;
+            }
+        }
+    }
+    if (!c->fixed_mode && tris > 0) {
+        const uint32_t want = (uint32_t)std::min<uint64_t>((uint64_t)tris * 2 + 65536, 0xFFFFFFF0ull);
+        if (want > c->capacity) {
+            if ((rc = sync_streams(c))) return rc;
+            if ((rc = ensure_capacity(c, want))) return rc;
+        }
+    }
+    c->list_plan_max = std::max<int64_t>(c->list_plan_max, units * 64);
+    c->list.swap(list);
+    c->list_tris = tris;
+    c->list_units = units;
+    c->list_affine = affine;
+    c->list_identity = identity;
+    if (flags & SWR_FLAG_LOAD) {
+        if (c->src_clear) {
+            flags &= ~(uint32_t)SWR_FLAG_LOAD;
+        } else {
+            c->load_src = c->fb_last;
+            if (c->fb_cur == c->load_src) c->fb_cur = (c->load_src + 1) % swr_context::NFB;
+        }
+    }
+    c->src_clear = false;
+    c->last_flags = flags;
+    c->last_prim = SWR_PRIMITIVE_TRIANGLE;
+    c->last_list = true;
     return enqueue_frame(c);
 }
 
@@ -1449,7 +1738,7 @@ int check_frames(swr_context* c) {
         if (need > old_limit) {
             if ((rc = sync_copies(c))) return rc;
             if (c->fixed_mode) {
-                const uint32_t cmax = fixed_cap_max(c->ni / 3, tiles_of(c->tg));
+                const uint32_t cmax = fixed_cap_max(std::max<int64_t>(c->ni / 3, c->list_plan_max), tiles_of(c->tg));
                 if (need > cmax) {
                     // a tile needs more than a fixed region can hold: exact-size bins (four binning kernels) from here on
                     c->fixed_mode = false;
@@ -1486,7 +1775,7 @@ int check_frames(swr_context* c) {
             c->frames_checked = c->frame_no;
             c->last.tile_pairs = pair_word(c, L);
             c->last.tiles = tiles_of(c->tg);
-            c->last.triangles = c->ni / 3;
+            c->last.triangles = c->last_list ? c->list_tris : c->ni / 3;
             return finish();
         }
         // the last frame overflowed: redraw it into the same framebuffer, copy it again
@@ -1590,7 +1879,7 @@ void destroy_single(swr_context* c) {
                 (unsigned long long)c->hp_frames, c->hp_t[0] / c->hp_frames, c->hp_t[1] / c->hp_frames, c->hp_t[2] / c->hp_frames,
                 c->hp_t[3] / c->hp_frames, c->hp_t[4] / c->hp_frames, c->hp_t[5] / c->hp_frames);
     DevBuf* bufs[] = {&c->redo_cnt, &c->vertices, &c->indices, &c->tri_rgb, &c->tri_xyz, &c->inv, &c->box64, &c->stream_scratch, &c->sort_temp,
-                      &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes};
+                      &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev};
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
@@ -1599,8 +1888,11 @@ void destroy_single(swr_context* c) {
     for (hipStream_t ls : c->lane_stream) if (ls) hipStreamDestroy(ls);
     for (hipEvent_t e : c->pace_ev) if (e) hipEventDestroy(e);
     for (auto& sl : c->slot) {
-        DevBuf* sb[] = {&sl.geo, &sl.geo_full, &sl.ranges, &sl.bins, &sl.bin_matrix, &sl.live, &sl.tilebuf, &sl.biglist};
+        DevBuf* sb[] = {&sl.geo, &sl.geo_full, &sl.ranges, &sl.bins, &sl.bin_matrix, &sl.live, &sl.tilebuf, &sl.biglist,
+                        &sl.items, &sl.lrgb, &sl.lnrm, &sl.linv};
         for (DevBuf* b : sb) if (b->p) hipFree(b->p);
+        if (sl.items_host) hipHostFree(sl.items_host);
+        if (sl.items_copied) hipEventDestroy(sl.items_copied);
         if (sl.bin_done) hipEventDestroy(sl.bin_done);
         if (sl.ras_done) hipEventDestroy(sl.ras_done);
     }
@@ -1886,6 +2178,19 @@ int swr_draw_primitives(swr_context* c, const float transform[16], uint32_t flag
 
 int swr_draw(swr_context* c, const float transform[16], uint32_t flags) {
     return swr_draw_primitives(c, transform, flags, SWR_PRIMITIVE_TRIANGLE);
+}
+
+int swr_draw_list(swr_context* c, const swr_draw_item* items, int32_t item_count, uint32_t flags) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    if (!is_group(c)) return single_draw_list(c, items, item_count, flags);
+    // the group checks what it can see (every band holds the same scene); the bands draw their own copy of the list
+    int64_t tris = 0;
+    const swr_context* k0 = c->kids[0];
+    int rc = check_list_args(c, items, item_count, flags, k0->has_scene && c->group_has_target, k0->ni, &tris);
+    if (rc) return rc;
+    auto list = std::make_shared<std::vector<swr_draw_item>>(items, items + item_count);
+    group_post(c, [=](swr_context* k) { return single_draw_list(k, list->data(), item_count, flags); });
+    return SWR_OK;
 }
 
 int swr_target_write(swr_context* c, const void* color_full, const float* depth_full) {

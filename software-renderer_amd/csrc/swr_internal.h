@@ -52,6 +52,18 @@ struct Target {
 // device-side frame counters (one 32-bit word each)
 enum { CNT_PAIRS = 0, CNT_OVERFLOW = 1, CNT_BAD_INDEX = 2, CNT_WORDS = 8 };
 
+// One item of a draw-list frame on the device (swr_draw_item, resolved by the host).  Item k draws the scene primitives
+// [first, first + count) — in a segmented stream (swr_upload.hip) also the stream slots [first, first + count) — into the frame slots
+// [vbase, vbase + count); its k_bin work units are [ubase, ubase + groups of 64 stream slots it touches).  The order number of
+// primitive o of the item (GeomRec.flags, the visibility keys) is vbase + o - first.
+struct ListItem {
+    uint32_t first, count, vbase, ubase;
+    float m[16];                   // column-major, as swr_draw's
+};
+static_assert(sizeof(ListItem) == 80, "ListItem must be 80 bytes");
+constexpr int LIST_ITEM_BITS = 12;  // k_bin<.., LIST> packs (item, group of the item) into 32 bits: item < SWR_DRAW_LIST_MAX = 2^12
+static_assert(SWR_DRAW_LIST_MAX <= (1 << LIST_ITEM_BITS), "item ids must fit the packed work unit");
+
 // Geometry of the LDS binning path (see plan_binning in swr_kernels.hip).
 struct BinPlan {
     bool use_lds;
@@ -116,6 +128,14 @@ struct DeviceFrame {
     Target tg;
     float m[16];                   // column-major transform
     uint32_t flags;                // SWR_FLAG_*
+    // draw-list frames (swr_draw_list): NULL for every other frame.  ntri is then the list's total V; geo / geo_full /
+    // ranges / bins hold FRAME slots, and tri_rgb / tri_nrm / inv the frame's own per-slot copies (k_list_gather).
+    const ListItem* items;         // [nitems] on the device
+    int32_t nitems;
+    int64_t units;                 // (item, 64-slot stream group) work units of k_bin<.., LIST>
+    int32_t list_affine;           // every item's transform has the last row (0, 0, 0, 1): k_bin<.., AFF, LIST>
+    // inv_out != NULL: the binning launch first gathers the frame's own per-slot tables (k_list_gather) from the scene's
+    struct { const float4* rgb; const float4* nrm; float4* rgb_out; float4* nrm_out; uint32_t* inv_out; } gather;
 };
 
 void launch_validate_indices(const int64_t* indices, int64_t count, int64_t vertex_count,
@@ -130,6 +150,8 @@ struct StreamBuild {
     uint32_t* scratch;             // 4 * ntri + 8 words
     void* sort_temp; size_t sort_temp_bytes;
     float4* tri_xyz; float4* tri_rgb; uint32_t* inv; float4* box64;
+    const uint32_t* cuts;          // draw lists: [ncuts] sorted primitive indices the stream is cut at (sorted by (segment, Morton code))
+    int ncuts;
 };
 size_t stream_sort_temp_bytes(int64_t ntri);
 hipError_t launch_build_stream(const StreamBuild& b, hipStream_t s);

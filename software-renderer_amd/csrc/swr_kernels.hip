@@ -283,8 +283,11 @@ __device__ __forceinline__ void decode_vertices(const GeomFull* __restrict__ ful
 // (AFF = the transform's last row is (0, 0, 0, 1) — identity, orthographic, any affine map: w is then exactly 1 for every
 // finite vertex (0*x + 0*y + 0*z + 1, :160) and x / 1 = x (:162), so the nine IEEE divisions per triangle are skipped; a
 // non-finite vertex makes sx / sy non-finite either way and the triangle is skipped either way.  Chosen by the host, k_bin only.)
-template <bool MT, bool AFF = false>
-__device__ __forceinline__ uint2 setup_triangle_r(const SetupArgs& a, int64_t p, const float4& xa, const float4& xb, const float4& xc);
+// (LIST = a draw-list frame: the item's transform *mk instead of a.m, and the order number lorig instead of the original index in
+// the GeomRec flags; p is the frame slot)
+template <bool MT, bool AFF = false, bool LIST = false>
+__device__ __forceinline__ uint2 setup_triangle_r(const SetupArgs& a, int64_t p, const float4& xa, const float4& xb, const float4& xc,
+                                                  const float4x4* mk = nullptr, uint32_t lorig = 0u);
 __device__ __forceinline__ uint2 setup_triangle(const SetupArgs& a, int64_t p, const float4& xa, const float4& xb, const float4& xc) {
     return a.metal ? setup_triangle_r<true>(a, p, xa, xb, xc) : setup_triangle_r<false>(a, p, xa, xb, xc);
 }
@@ -293,10 +296,12 @@ __device__ __forceinline__ uint2 setup_triangle(const SetupArgs& a, int64_t p) {
     return setup_triangle(a, p, a.tri_xyz[3 * p + 0], a.tri_xyz[3 * p + 1], a.tri_xyz[3 * p + 2]);
 }
 // ... with the corners already loaded (k_setup_hist fetches those of its next group while it works on this one)
-template <bool MT, bool AFF>
-__device__ __forceinline__ uint2 setup_triangle_r(const SetupArgs& a, int64_t p, const float4& xa, const float4& xb, const float4& xc) {
+template <bool MT, bool AFF, bool LIST>
+__device__ __forceinline__ uint2 setup_triangle_r(const SetupArgs& a, int64_t p, const float4& xa, const float4& xb, const float4& xc,
+                                                  const float4x4* mk, uint32_t lorig) {
     uint2 range = make_uint2(RANGE_NONE_X, 0u);
-    const uint32_t orig = a.reordered ? __float_as_uint(xa.w) : 0u;
+    const uint32_t orig = LIST ? lorig : (a.reordered ? __float_as_uint(xa.w) : 0u);
+    const float4x4& M = LIST ? *mk : a.m;
     // vertex colours are passed through by vertex_shader untouched (Shaders.metal:53) and are only
     // consumed by the resolve, which fetches them for the winning primitive through idx32 / rgb
     const float4 ca = make_float4(0, 0, 0, 0), cb = ca, cc = ca;
@@ -310,7 +315,7 @@ __device__ __forceinline__ uint2 setup_triangle_r(const SetupArgs& a, int64_t p,
         for (int k = 0; k < 3; k++) {
             // Vertex.apply(transform:) (:159-163) through the vertex_shader hook
             VertexOut vo = vertex_shader(make_float3(xs[k].x, xs[k].y, xs[k].z),
-                                         make_float3(cs[k].x, cs[k].y, cs[k].z), a.m);
+                                         make_float3(cs[k].x, cs[k].y, cs[k].z), M);
             const float nx = AFF ? vo.pos.x : vo.pos.x / vo.pos.w;
             const float ny = AFF ? vo.pos.y : vo.pos.y / vo.pos.w;
             const float nz = AFF ? vo.pos.z : vo.pos.z / vo.pos.w;
@@ -493,12 +498,12 @@ __device__ __forceinline__ int wave_incl_add(int v);
 // by less than one pixel) + a bound on the rounding error of the per-vertex transform (Σ|m_ij·c_j| terms at
 // 2^-20 relative, propagated through the divide) + 2^-18 of the coordinate itself.  NaN anywhere (a
 // non-finite vertex poisons its box) makes every comparison false: not culled.  Wave-uniform.
-__device__ __forceinline__ bool group_culled(const SetupArgs& a, int64_t g) {
+__device__ __forceinline__ bool group_culled_m(const SetupArgs& a, int64_t g, const float4x4& M) {
     const float4 lo = a.box64[2 * g], hi = a.box64[2 * g + 1];
     const float fw = (float)a.tg.width, fh = (float)a.tg.height;
     // error scale of one transformed coordinate: Σ_j |m_ij| * max|c_j| + |m_i3|
     const float ax = fmaxf(fabsf(lo.x), fabsf(hi.x)), ay = fmaxf(fabsf(lo.y), fabsf(hi.y)), az = fmaxf(fabsf(lo.z), fabsf(hi.z));
-    const float4 c0 = a.m.columns[0], c1 = a.m.columns[1], c2 = a.m.columns[2], c3 = a.m.columns[3];
+    const float4 c0 = M.columns[0], c1 = M.columns[1], c2 = M.columns[2], c3 = M.columns[3];
     const float d = 9.5367431640625e-07f;   // 2^-20
     const float ex = d * (fabsf(c0.x) * ax + fabsf(c1.x) * ay + fabsf(c2.x) * az + fabsf(c3.x));
     const float ey = d * (fabsf(c0.y) * ax + fabsf(c1.y) * ay + fabsf(c2.y) * az + fabsf(c3.y));
@@ -530,6 +535,7 @@ __device__ __forceinline__ bool group_culled(const SetupArgs& a, int64_t g) {
     return sx1 + margin < 0.0f || sx0 - margin >= fw || sy1 + margin < (float)a.tg.row_begin ||
            sy0 - margin >= (float)a.tg.row_end;
 }
+__device__ __forceinline__ bool group_culled(const SetupArgs& a, int64_t g) { return group_culled_m(a, g, a.m); }
 
 // Workgroup g owns the contiguous chunk [g*chunk, (g+1)*chunk) of the primitives in BOTH walks.
 // k_setup_hist: per-workgroup tile histogram in LDS (ds_add), written as row g of the matrix
@@ -751,6 +757,40 @@ __global__ __launch_bounds__(BT) void k_fill_lds(const uint2* __restrict__ range
 // rotate by three, so the array zeroed here was last read by a raster that finished before this kernel could start).
 // A tile that receives more than cap entries overflows: the frame's largest fill goes to the host, which grows cap and
 // redraws (or falls back to the exact-size path above when a tile needs more than FIXED_CAP_MAX entries).
+// ---- draw-list frames ------------------------------------------------------------------------------------------
+// The item of frame slot v (UNITS: of k_bin work unit v): the last item whose vbase (ubase) is <= v.  Empty items share their base
+// with the next item and are passed over; item 0 starts at 0.  (A binary search over <= SWR_DRAW_LIST_MAX items.)
+template <bool UNITS>
+__device__ __forceinline__ int list_find(const ListItem* __restrict__ items, int n, uint32_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const uint32_t key = UNITS ? items[mid].ubase : items[mid].vbase;
+        if (key <= v) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+__device__ __forceinline__ float4x4 list_matrix(const ListItem* __restrict__ items, int k) {
+    const float4* c = reinterpret_cast<const float4*>(items[k].m);
+    float4x4 m;
+    m.columns[0] = c[0]; m.columns[1] = c[1]; m.columns[2] = c[2]; m.columns[3] = c[3];
+    return m;
+}
+// A k_bin work unit as its workgroup's list holds it: item k in the low LIST_ITEM_BITS, the item's group index above.  Lane `lane`
+// of the wave that walks it owns stream slot s (valid inside the item's range), which is frame slot f; obias turns the original index
+// of the slot (corner 0's w) into the order number.  The item is wave-uniform: its fields and matrix are scalar loads.
+struct ListUnit { int64_t s; uint32_t f, obias; int k; bool valid; };
+__device__ __forceinline__ ListUnit list_unit(const ListItem* __restrict__ items, uint32_t ent, int lane) {
+    ListUnit u;
+    u.k = __builtin_amdgcn_readfirstlane((int)(ent & ((1u << LIST_ITEM_BITS) - 1u)));
+    const uint32_t first = items[u.k].first, cnt = items[u.k].count, vbase = items[u.k].vbase;
+    u.s = ((int64_t)(first >> 6) + (int64_t)(ent >> LIST_ITEM_BITS)) * 64 + lane;
+    u.valid = u.s >= (int64_t)first && u.s < (int64_t)first + cnt;
+    u.f = vbase + (uint32_t)(u.s - (int64_t)first);
+    u.obias = vbase - first;
+    return u;
+}
+
 struct BinArgs {
     SetupArgs a;
     uint32_t* fill;         // [CNT_WORDS counters][ntiles] of this frame (zero on entry)
@@ -762,6 +802,9 @@ struct BinArgs {
     int tag_class;
     uint4* biglist;         // [BIGLIST_CAP] (slot, ranges.x, ranges.y, -) of the frame's deferred triangles
     int defer_ok;           // this frame's k_sort_bins will run
+    const ListItem* items;  // draw-list frames (k_bin<.., LIST>): the items, and the (item, stream group) work units
+    int nitems;
+    int64_t units;
 };
 constexpr uint32_t FIXED_CAP_MAX = 61440u;   // cursor halves stay below 2^16: cap + primitives owned by one workgroup < 65536
 enum { CNT_MAXFILL = 3, CNT_BIGLIST = 4, CNT_BIGSEEN = 5 };
@@ -777,7 +820,10 @@ __device__ __forceinline__ int tiles_of_box(const PixBox& b) {
     return b.x0 <= b.x1 ? (b.x1 / TILE_W - b.x0 / TILE_W + 1) * (b.y1 / TILE_H - b.y0 / TILE_H + 1) : 0;
 }
 
-template <int BT, bool MT, bool DEFER, bool AFF = false>
+// LIST: a draw-list frame.  The work units are (item, 64-slot stream group) pairs instead of stream groups — spread over the workgroups
+// the same way — and the lanes of a unit outside the item's slot range are idle.  Everything the frame writes (geo, ranges, bins, the
+// deferred list) is indexed by frame slot; the cull projects the group's box with the item's matrix.
+template <int BT, bool MT, bool DEFER, bool AFF = false, bool LIST = false>
 // Register budget of the plain kernel: 56 VGPRs (tools/vgprs.sh) — with 58 the pipelined cfg4 frame measured 4 % slower (one of its waves has
 // to fit beside five raster waves of 88); neither launch bounds nor amdgpu_waves_per_eu make this hipcc keep it, the source does.
 __global__ __launch_bounds__(BT) void k_bin(BinArgs b) {
@@ -798,23 +844,73 @@ __global__ __launch_bounds__(BT) void k_bin(BinArgs b) {
     }
     __syncthreads();
     {
-        const int64_t groups = (a.ntri + 63) >> 6;
+        const int64_t groups = LIST ? b.units : (a.ntri + 63) >> 6;
         for (int i0 = t & ~63; i0 < per; i0 += BT) {                 // wave-uniform trip count
             const int i = i0 + lane;
             const int64_t g = (int64_t)i * gridDim.x + blockIdx.x;
-            const bool keep = i < per && g < groups && !(a.cull && group_culled(a, g));
+            bool keep;
+            uint32_t ent = (uint32_t)g;
+            if constexpr (LIST) {
+                keep = i < per && g < groups;
+                if (keep) {
+                    const int k = list_find<true>(b.items, b.nitems, (uint32_t)g);
+                    const uint32_t gi = (uint32_t)g - b.items[k].ubase;
+                    ent = (uint32_t)k | (gi << LIST_ITEM_BITS);
+                    keep = !(a.cull && group_culled_m(a, (int64_t)(b.items[k].first >> 6) + gi, list_matrix(b.items, k)));
+                }
+            } else {
+                keep = i < per && g < groups && !(a.cull && group_culled(a, g));
+            }
             const unsigned long long mask = __ballot(keep);
             uint32_t base = 0u;
             if (lane == 0 && mask) base = atomicAdd(&nlive_s, (uint32_t)__popcll(mask));
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            if (keep) mylist[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)g;
+            if (keep) mylist[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = ent;
         }
     }
     __syncthreads();
     const uint32_t nlive = nlive_s;
     const int tiles_x = a.tg.tiles_x;
     // ---- 2: setup + histogram (the 48 B per lane of the NEXT group in flight while this one is transformed)
-    {
+    if constexpr (LIST) {
+        float4 nxa = make_float4(0, 0, 0, 0), nxb = nxa, nxc = nxa;
+        {
+            const uint32_t j0 = t >> 6;
+            if (j0 < nlive) {
+                const ListUnit u = list_unit(b.items, mylist[j0], lane);
+                if (u.valid) { nxa = a.tri_xyz[3 * u.s + 0]; nxb = a.tri_xyz[3 * u.s + 1]; nxc = a.tri_xyz[3 * u.s + 2]; }
+            }
+        }
+        for (uint32_t j = t >> 6; j < nlive; j += BT / 64) {
+            const ListUnit u = list_unit(b.items, mylist[j], lane);
+            const float4 xa = nxa, xb = nxb, xc = nxc;
+            {
+                const uint32_t jn = j + BT / 64;
+                if (jn < nlive) {
+                    const ListUnit un = list_unit(b.items, mylist[jn], lane);
+                    if (un.valid) { nxa = a.tri_xyz[3 * un.s + 0]; nxb = a.tri_xyz[3 * un.s + 1]; nxc = a.tri_xyz[3 * un.s + 2]; }
+                }
+            }
+            uint2 r = make_uint2(RANGE_NONE_X, 0u);
+            if (u.valid) {
+                const float4x4 mk = list_matrix(b.items, u.k);
+                r = setup_triangle_r<MT, AFF, true>(a, u.f, xa, xb, xc, &mk, __float_as_uint(xa.w) + u.obias);
+                if (DEFER && tiles_of_box(unpack_box(r)) > BIN_BIG_TILES) {
+                    const uint32_t e = atomicAdd(&b.fill[CNT_BIGLIST], 1u);
+                    if (e < BIGLIST_CAP) {
+                        b.biglist[e] = make_uint4(u.f, r.x, r.y, 0u);
+                        atomicAdd(&bigp_s, (uint32_t)tiles_of_box(unpack_box(r)));
+                        r = make_uint2(RANGE_NONE_X, 0u);
+                    }
+                }
+                a.ranges[u.f] = r;
+            }
+            for_each_tile(unpack_box(r), u.f, [&](const PixBox&, uint32_t, int tx, int ty) {
+                const int tile = ty * tiles_x + tx;
+                atomicAdd(&hist[tile >> 1], 1u << ((tile & 1) << 4));
+            });
+        }
+    } else {
         float4 nxa = make_float4(0, 0, 0, 0), nxb = nxa, nxc = nxa;
         {
             const uint32_t j0 = t >> 6;
@@ -908,7 +1004,13 @@ __global__ __launch_bounds__(BT) void k_bin(BinArgs b) {
 #pragma unroll
         for (int k = 0; k < FB; k++) {
             const uint32_t j = j0 + (uint32_t)k * (BT / 64);
-            pp[k] = j < nlive ? ((int64_t)mylist[j] << 6) + lane : a.ntri;
+            if constexpr (LIST) {          // (frame slots)
+                ListUnit u{};
+                if (j < nlive) u = list_unit(b.items, mylist[j], lane);
+                pp[k] = u.valid ? (int64_t)u.f : a.ntri;
+            } else {
+                pp[k] = j < nlive ? ((int64_t)mylist[j] << 6) + lane : a.ntri;
+            }
             rr[k] = pp[k] < a.ntri ? a.ranges[pp[k]] : make_uint2(RANGE_NONE_X, 0u);
         }
 #pragma unroll
@@ -942,6 +1044,53 @@ __global__ __launch_bounds__(256) void k_setup_bin(SetupArgs a) {
     for (int ty = b.y0 / TILE_H; ty <= b.y1 / TILE_H; ty++)
         for (int tx = b.x0 / TILE_W; tx <= b.x1 / TILE_W; tx++)
             atomicAdd(&a.tile_count[ty * a.tg.tiles_x + tx], 1u);
+}
+
+// ... of a draw-list frame: one thread per FRAME slot f (a.ntri = the list's total), its item by a binary search over the items'
+// frame bases.  Feeds the exact-size bins (k_scan, k_fill), which work on frame slots unchanged.
+__global__ __launch_bounds__(256) void k_list_setup(SetupArgs a, const ListItem* __restrict__ items, int nitems) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= a.ntri) return;
+    const int k = list_find<false>(items, nitems, (uint32_t)f);
+    const uint32_t first = items[k].first, vbase = items[k].vbase;
+    const int64_t s = (int64_t)first + (f - (int64_t)vbase);
+    const float4x4 mk = list_matrix(items, k);
+    const float4 xa = a.tri_xyz[3 * s + 0], xb = a.tri_xyz[3 * s + 1], xc = a.tri_xyz[3 * s + 2];
+    const uint32_t ord = __float_as_uint(xa.w) + (vbase - first);
+    const uint2 r = a.metal ? setup_triangle_r<true, false, true>(a, f, xa, xb, xc, &mk, ord)
+                            : setup_triangle_r<false, false, true>(a, f, xa, xb, xc, &mk, ord);
+    a.ranges[f] = r;
+    const PixBox b = unpack_box(r);
+    if (b.x0 > b.x1) return;
+    for (int ty = b.y0 / TILE_H; ty <= b.y1 / TILE_H; ty++)
+        for (int tx = b.x0 / TILE_W; tx <= b.x1 / TILE_W; tx++)
+            atomicAdd(&a.tile_count[ty * a.tg.tiles_x + tx], 1u);
+}
+
+// The raster and the resolve read a primitive's colours (tri_rgb), attributes (tri_nrm) and, from a key's order number, its slot
+// (inv) by the slot its bin entry holds.  A draw-list frame's entries are frame slots: this kernel gives the frame its own copies of
+// those tables, indexed by frame slot (inv: by order number), so every raster kernel runs unchanged.  rgb_out / nrm_out NULL: not
+// needed by this frame (depth-only; no extended fragment stage).
+__global__ __launch_bounds__(256) void k_list_gather(const ListItem* __restrict__ items, int nitems, int64_t nslots,
+                                                     const float4* __restrict__ tri_xyz, const float4* __restrict__ rgb,
+                                                     const float4* __restrict__ nrm, float4* __restrict__ rgb_out,
+                                                     float4* __restrict__ nrm_out, uint32_t* __restrict__ inv_out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < nslots; f += stride) {
+        const int k = list_find<false>(items, nitems, (uint32_t)f);
+        const uint32_t first = items[k].first, vbase = items[k].vbase;
+        const int64_t s = (int64_t)first + (f - (int64_t)vbase);
+        const uint32_t ord = __float_as_uint(tri_xyz[3 * s].w) + (vbase - first);
+        if (ord < (uint64_t)nslots) inv_out[ord] = (uint32_t)f;     // (always, in a stream cut at the items' ranges)
+        if (rgb_out) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) rgb_out[3 * f + c] = rgb[3 * s + c];
+        }
+        if (nrm_out) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) nrm_out[3 * f + c] = nrm[3 * s + c];
+        }
+    }
 }
 
 // Second walk over the triangles' tile rectangles; a returning atomic on the tile's cursor
@@ -2777,6 +2926,11 @@ hipError_t prepare_device() {
     SWR_BIN_ATTR(false, false, false) SWR_BIN_ATTR(true, false, false) SWR_BIN_ATTR(false, true, false) SWR_BIN_ATTR(true, true, false)
     SWR_BIN_ATTR(false, false, true) SWR_BIN_ATTR(true, false, true) SWR_BIN_ATTR(false, true, true) SWR_BIN_ATTR(true, true, true)
 #undef SWR_BIN_ATTR
+#define SWR_BIN_ATTR(MT, DF, AF) \
+    if ((e = hipFuncSetAttribute((const void*)k_bin<256, MT, DF, AF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    SWR_BIN_ATTR(false, false, false) SWR_BIN_ATTR(true, false, false) SWR_BIN_ATTR(false, true, false) SWR_BIN_ATTR(true, true, false)
+    SWR_BIN_ATTR(false, false, true) SWR_BIN_ATTR(true, false, true) SWR_BIN_ATTR(false, true, true) SWR_BIN_ATTR(true, true, true)
+#undef SWR_BIN_ATTR
     return hipFuncSetAttribute((const void*)k_fill_lds<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
@@ -2794,8 +2948,10 @@ hipError_t prepare_device() {
 // itself got faster, 97 -> 93 us: profiles/r02/hist16_ab.txt.  Only k_setup_hist keeps the small histogram.)
 static bool bin_h16(int per) { return SWR_TUNE_HIST16 && (int64_t)per * 64 < 65536; }
 
+static void launch_list_gather(const DeviceFrame& f, hipStream_t s);
 void launch_setup_bin(const DeviceFrame& f, hipStream_t s) {
     if (f.ntri <= 0) return;
+    launch_list_gather(f, s);
     const SetupArgs a = make_setup_args(f);
     const int ntiles = f.tg.tiles_x * f.tg.tiles_y;
     if (f.plan.use_lds) {
@@ -2806,10 +2962,21 @@ void launch_setup_bin(const DeviceFrame& f, hipStream_t s) {
         else hipLaunchKernelGGL((k_setup_hist<256, false>), dim3(f.plan.G), dim3(256), lds, s, a, f.bin_matrix, f.live, per, ntiles);
         hipLaunchKernelGGL(k_colscan, dim3((ntiles + 15) / 16), dim3(256), 0, s, f.bin_matrix, f.plan.G, ntiles,
                            f.tile_count);
+    } else if (f.items) {
+        const unsigned blocks = (unsigned)((f.ntri + 255) / 256);
+        hipLaunchKernelGGL(k_list_setup, dim3(blocks), dim3(256), 0, s, a, f.items, (int)f.nitems);
     } else {
         const unsigned blocks = (unsigned)((f.ntri + 255) / 256);
         hipLaunchKernelGGL(k_setup_bin, dim3(blocks), dim3(256), 0, s, a);
     }
+}
+
+// a draw-list frame's own per-slot tables, in front of its binning (DeviceFrame::gather)
+static void launch_list_gather(const DeviceFrame& f, hipStream_t s) {
+    if (f.ntri <= 0 || !f.items || !f.gather.inv_out) return;
+    const unsigned blocks = (unsigned)std::min<int64_t>(2048, (f.ntri + 255) / 256);
+    hipLaunchKernelGGL(k_list_gather, dim3(blocks), dim3(256), 0, s, f.items, (int)f.nitems, f.ntri, f.tri_xyz, f.gather.rgb,
+                       f.gather.nrm, f.gather.rgb_out, f.gather.nrm_out, f.gather.inv_out);
 }
 
 // Can the frame be binned by the single-launch k_bin (fixed-stride bins), and how large may a tile region be?  Needs the
@@ -2828,18 +2995,33 @@ uint32_t fixed_cap_max(int64_t ntri, int ntiles) {
 }
 
 bool launch_bin(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
+    launch_list_gather(f, s);
     BinArgs b;
     b.a = make_setup_args(f);
     b.fill = f.fill; b.fill_next = f.fill_next; b.bins = f.bins; b.cap = f.cap_tile;
     b.ntiles = f.tg.tiles_x * f.tg.tiles_y;
     b.per = live_groups_per_workgroup(f.ntri, f.plan.G);
     b.tag_class = f.ntri < (1ll << CLASS_SHIFT) ? 1 : 0;
+    b.items = f.items; b.nitems = f.nitems; b.units = f.units;
+    if (f.items) b.per = (int)((f.units + f.plan.G - 1) / f.plan.G);
     // the deferring kernel (three registers more: it would not fit beside five raster waves) only for frames
     // whose predecessor reported triangles for the list, and whose k_sort_bins runs
     b.biglist = f.biglist; b.defer_ok = (f.biglist && f.defer_big && !f.skip_sort) ? 1 : 0;
     const size_t lds = (size_t)((b.ntiles + 1) / 2) * 4 + (size_t)(b.per + 1) * 4 + 2 * (256 / 64) * 4 + 4;
     // the transform's last row is (0, 0, 0, 1): w == 1 for every finite vertex, no perspective divide (setup_triangle_r<.., AFF>)
-    const bool aff = f.m[3] == 0.0f && f.m[7] == 0.0f && f.m[11] == 0.0f && f.m[15] == 1.0f;
+    const bool aff = f.items ? f.list_affine != 0 : f.m[3] == 0.0f && f.m[7] == 0.0f && f.m[11] == 0.0f && f.m[15] == 1.0f;
+    if (f.items) {
+#define SWR_BIN_GOL(MT, DF, AF) SWR_LAUNCH(stop, (k_bin<256, MT, DF, AF, true>), dim3(f.plan.G), dim3(256), (uint32_t)lds, s, b)
+        if (aff) {
+            if (b.defer_ok) { if (b.a.metal) SWR_BIN_GOL(true, true, true); else SWR_BIN_GOL(false, true, true); }
+            else { if (b.a.metal) SWR_BIN_GOL(true, false, true); else SWR_BIN_GOL(false, false, true); }
+        } else {
+            if (b.defer_ok) { if (b.a.metal) SWR_BIN_GOL(true, true, false); else SWR_BIN_GOL(false, true, false); }
+            else { if (b.a.metal) SWR_BIN_GOL(true, false, false); else SWR_BIN_GOL(false, false, false); }
+        }
+#undef SWR_BIN_GOL
+        return stop != nullptr;
+    }
 #define SWR_BIN_GO2(MT, DF, AF) SWR_LAUNCH(stop, (k_bin<256, MT, DF, AF>), dim3(f.plan.G), dim3(256), (uint32_t)lds, s, b)
     if (aff) {
         if (b.defer_ok) { if (b.a.metal) SWR_BIN_GO2(true, true, true); else SWR_BIN_GO2(false, true, true); }

@@ -113,6 +113,22 @@ __global__ void k_morton(const swr_vertex* __restrict__ vtx, int64_t nv, const i
 
 // slot s <- original primitive perm[s]
 // (perm == NULL: identity order, slots [s0, ntri) only — the one-shot upload's chunks)
+// Draw lists: the segment of primitive ids[i] — the number of cuts at or below it — as the key of a second, stable
+// sort of the Morton-sorted ids.  Every segment is then a contiguous run of slots, in Morton order inside.
+__global__ void k_segment_keys(const uint32_t* __restrict__ ids, int64_t ntri, const uint32_t* __restrict__ cuts, int ncuts,
+                               uint32_t* __restrict__ keys) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ntri; i += stride) {
+        const uint32_t o = ids[i];
+        int lo = 0, hi = ncuts;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (cuts[mid] <= o) lo = mid + 1; else hi = mid;
+        }
+        keys[i] = (uint32_t)lo;
+    }
+}
+
 __global__ void k_gather_stream(const swr_vertex* __restrict__ v, int64_t nv, const int64_t* __restrict__ idx,
                                 int64_t s0, int64_t ntri, const uint32_t* __restrict__ perm, float4* __restrict__ tri_xyz,
                                 float4* __restrict__ tri_rgb, uint32_t* __restrict__ inv) {
@@ -197,7 +213,10 @@ size_t stream_sort_temp_bytes(int64_t ntri) {
     size_t bytes = 0;
     hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)ntri, 0, 30, (hipStream_t)0);
-    return bytes;
+    size_t seg = 0;     // (the segment pass of a draw-list rebuild: at most 14 key bits)
+    hipcub::DeviceRadixSort::SortPairs(nullptr, seg, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                       (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)ntri, 0, 14, (hipStream_t)0);
+    return std::max(bytes, seg);
 }
 
 // scratch: 4 arrays of ntri uint32 (codes in/out, ids in/out) followed by 8 words of bounds.
@@ -219,6 +238,16 @@ hipError_t launch_build_stream(const StreamBuild& b, hipStream_t s) {
                                                           (int)b.ntri, 0, 30, s);
         if (e != hipSuccess) return e;
         perm = ids_out;
+        if (b.cuts && b.ncuts > 0) {
+            // a second pass by segment; the radix sort is stable, so the Morton order inside every segment stays
+            hipLaunchKernelGGL(k_segment_keys, dim3(2048), dim3(256), 0, s, ids_out, b.ntri, b.cuts, b.ncuts, codes_in);
+            int bits = 1;
+            while ((1ll << bits) <= (int64_t)b.ncuts) bits++;
+            bytes = b.sort_temp_bytes;
+            e = hipcub::DeviceRadixSort::SortPairs(b.sort_temp, bytes, codes_in, codes_out, ids_out, ids_in, (int)b.ntri, 0, bits, s);
+            if (e != hipSuccess) return e;
+            perm = ids_in;
+        }
     }
     hipLaunchKernelGGL(k_gather_stream, dim3(2048), dim3(256), 0, s, b.vertices, b.nv, b.indices, (int64_t)0, b.ntri, perm,
                        b.tri_xyz, b.tri_rgb, b.inv);

@@ -142,6 +142,14 @@ struct RenderPass {
     LoadAction loadAction = LoadAction::clear;
 };
 
+// One draw of a draw list (swr_draw_item, include/swr.h): indices [firstIndex, firstIndex + indexCount) of the resident scene
+// drawn with their own transform — several meshes or draw calls of one render pass, or instances of one mesh, in one frame.
+struct DrawItem {
+    int64_t firstIndex = 0;             // multiple of 3
+    int64_t indexCount = 0;             // multiple of 3
+    matrix_float4x4 transform = matrix_float4x4::identity();
+};
+
 namespace detail {
 class Context {
 public:
@@ -194,6 +202,19 @@ public:
             }
         }
         int rc = swr_render(ctx_, &rp);
+        if (rc) throw RenderError(rc, swr_last_error(ctx_));
+    }
+    // One frame of several draws (swr_draw_list) on the scene and target the last render() with a sceneId left resident; the
+    // image is the context's, as after that render() (its colour / depth buffers are not written).
+    void drawList(const std::vector<DrawItem>& items, uint32_t flags) {
+        std::vector<swr_draw_item> list(items.size());
+        for (size_t k = 0; k < items.size(); k++) {
+            list[k].first_index = items[k].firstIndex;
+            list[k].index_count = items[k].indexCount;
+            for (int c = 0; c < 4; c++)
+                for (int r = 0; r < 4; r++) list[k].transform[4 * c + r] = items[k].transform.columns[c][r];
+        }
+        int rc = swr_draw_list(ctx_, list.data(), (int32_t)list.size(), flags);
         if (rc) throw RenderError(rc, swr_last_error(ctx_));
     }
 private:
