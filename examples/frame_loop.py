@@ -10,6 +10,8 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
+--pick X,Y also writes every frame's ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy of the mesh and which of its
+triangles are visible at pixel (X, Y): mouse picking (use it with --objects N).
 
 The demo mesh is a UV sphere standing in for ModelIO's `MDLMesh(sphereWithExtent: 0.4, segments: 13x13,
 inwardNormals: true)` (App.swift:124) with colour = |normal| (App.swift:133).  `--obj` loads a
@@ -229,11 +231,12 @@ def object_transforms(time: float, n: int):
 
 
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
-        time0: float = 0.0, objects: int = 1):
+        time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
-    mesh, one draw list per frame (the third element of every result is then the list of matrices)."""
+    mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
+    frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel."""
     vertices, indices = load_mesh(obj) if obj else sphere_mesh()
-    flags = S.FLAG_DEPTH_TEST if depth_test else 0
+    flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | (swr_amd.binding.FLAG_PRIMITIVE_IDS if pick else 0)
     results = []
     with swr_amd.Context() as ctx:
         ctx.scene_upload(vertices, indices)            # RenderPass.vertices / .indices, App.swift:163
@@ -242,11 +245,22 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
         for k in range(frames):
             if objects > 1:
                 m = object_transforms(time, objects)
-                ctx.draw_list([(0, indices.size, mj) for mj in m], flags)    # all copies in one frame
+                items = [(0, indices.size, mj) for mj in m]
+                ctx.draw_list(items, flags)             # all copies in one frame
             else:
                 m = S.app_transform(time)               # App.swift:169-183
+                items = [(0, indices.size, m)]
                 ctx.draw(m, flags)                      # renderer.render(renderPass:), App.swift:185
             color, depth = ctx.read_color(), ctx.read_depth()
+            if pick:
+                # mouse picking: the ID under the pixel, mapped to (copy, triangle of the mesh) over the list's item bases
+                x, y = pick
+                ids = ctx.read_ids()
+                obj_k, tri = swr_amd.binding.list_ids_to_items(ids[y:y + 1, x:x + 1], items)
+                if obj_k[0, 0] < 0:
+                    print(f"frame {k}: pixel ({x}, {y}): nothing")
+                else:
+                    print(f"frame {k}: pixel ({x}, {y}): copy {obj_k[0, 0]}, triangle {tri[0, 0]}, depth {depth[y, x]:.6g}")
             results.append((color, depth, m))
             if out:
                 os.makedirs(out, exist_ok=True)
@@ -303,11 +317,13 @@ if __name__ == "__main__":
     ap.add_argument("--stream", action="store_true", help="asynchronous presents into two page-locked image sets")
     ap.add_argument("--gpus", type=int, default=1, help="bands / GPUs of the one context (with --stream)")
     ap.add_argument("--objects", type=int, default=1, help="copies of the mesh, each with its own matrix: one draw list per frame")
+    ap.add_argument("--pick", default=None, help="X,Y: print the copy and the triangle under that pixel every frame (primitive IDs)")
     a = ap.parse_args()
     if a.stream:
         res = run_streamed(a.frames, a.size, a.ply or a.obj, a.depth_test, device_count=a.gpus)
         print(f"{a.frames} frames streamed, coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
-    _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects)
+    pick = tuple(int(t) for t in a.pick.split(",")) if a.pick else None
+    _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

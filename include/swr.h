@@ -74,10 +74,30 @@ enum {
                                       not plotted), in the colour of the FIRST vertex, later primitives overwrite
                                       earlier ones, no z-test, depth stays +inf.  Lines longer than 2^20 steps or with a
                                       non-finite endpoint are skipped (the reference would trap / never finish) */
-    SWR_FLAG_LOAD = 1u << 4        /* LOAD ACTION (ABI 6; Metal's MTLLoadActionLoad): the frame is Renderer.render(renderPass:) WITHOUT the
+    SWR_FLAG_LOAD = 1u << 4,       /* LOAD ACTION (ABI 6; Metal's MTLLoadActionLoad): the frame is Renderer.render(renderPass:) WITHOUT the
                                       clear of Renderer.swift:205-206 — the same loop continues from the image already there (see
                                       "Load frames" below) */
+    SWR_FLAG_PRIMITIVE_IDS = 1u << 5 /* the frame also writes an ID image: which triangle is visible at every pixel (Metal: a second
+                                      colour attachment written with [[primitive_id]]); read it with swr_read_ids (see "Primitive
+                                      IDs" below) */
 };
+
+/* ---- Primitive IDs (SWR_FLAG_PRIMITIVE_IDS) — DESIGN.md §13 --------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6): the presence of the swr_read_ids symbol is the feature test.
+ * A frame drawn with the flag also writes one uint32_t per pixel, band-local and laid out like the depth image.
+ *   The ID of a pixel is the order number of the primitive whose fragment the frame keeps there — the winner whose colour and depth
+ *     the frame stores, under painter's order, the z-test and the Metal rules alike, with every fragment shader:
+ *     swr_draw, swr_draw_primitives(SWR_PRIMITIVE_TRIANGLE), swr_render: the triangle index p (indices[3p .. 3p+2]);
+ *     swr_draw_list: the triangle's position in the concatenation of the items — item k's j-th triangle is vbase_k + j, vbase_k the
+ *       sum of index_count / 3 of the items before it.
+ *   SWR_ID_NONE marks a pixel where the frame keeps no fragment: nothing covers it, its only fragments have a NaN or +inf depth
+ *     under the z-test, or (SWR_FLAG_LOAD) the loaded image wins there.  IDs never come from earlier frames.
+ *   Triangles only: .vertices and .line frames with the flag fail with SWR_ERR_UNSUPPORTED.
+ *   The colour and depth images of a frame are bit for bit the same with and without the flag.
+ * swr_read_ids(ctx, dst): like swr_read_depth — completes everything, then copies rows [row_begin, row_end) of each band into the
+ *   caller's full-size image (width * height words).  SWR_ERR_BAD_ARG when the last frame was drawn without the flag, or when
+ *   swr_target_set / swr_target_write has been called since.  An overflowed last frame is redrawn with its flags, IDs included. */
+#define SWR_ID_NONE 0xFFFFFFFFu
 
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
@@ -373,6 +393,7 @@ int swr_present(swr_context* ctx, void* color_full_image, float* depth_full_imag
 int swr_present_wait(swr_context* ctx);
 int swr_read_color(swr_context* ctx, void* dst_full_image);
 int swr_read_depth(swr_context* ctx, float* dst_full_image);
+int swr_read_ids(swr_context* ctx, uint32_t* dst_full_image);   /* SWR_FLAG_PRIMITIVE_IDS frames (see "Primitive IDs" above) */
 
 /* Timing instrumentation: hipEvents on the context stream.  level 0 = off, 1 = two events around
  * the dominant kernel (k_raster) only, 2 = around every stage (each event costs a few us of

@@ -16,6 +16,8 @@ FLAG_NO_COLOR = 2
 FLAG_METAL_RULES = 4
 FLAG_REAL_LINES = 8      # .line primitives: the reference's DDA (Renderer.swift:405-419) instead of its empty stub (:289-293)
 FLAG_LOAD = 16           # load action (ABI 6): the frame starts from the image already there instead of the clear (include/swr.h)
+FLAG_PRIMITIVE_IDS = 32  # the frame also writes an ID image: which triangle is visible at every pixel (Context.read_ids)
+ID_NONE = 0xFFFFFFFF     # SWR_ID_NONE: a pixel where the frame keeps no fragment
 
 # every symbol include/swr.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -25,7 +27,7 @@ ABI_SYMBOLS = [
     "swr_band_rows", "swr_scene_attributes", "swr_material_set", "swr_texture_upload",
     "swr_timing_sample", "swr_context_bands", "swr_context_band_info", "swr_host_alloc", "swr_host_free",
     "swr_host_register", "swr_host_unregister", "swr_present", "swr_present_wait", "swr_device_count",
-    "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list",
+    "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list", "swr_read_ids",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -183,6 +185,12 @@ def load_library():
     try:
         L.swr_draw_list.argtypes = [vp, vp, i32, u32]
         L.swr_draw_list.restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
+    try:
+        L.swr_read_ids.argtypes = [vp, vp]
+        L.swr_read_ids.restype = ctypes.c_int
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
             raise
@@ -467,6 +475,15 @@ class Context:
         self._check(self._L.swr_read_depth(self._h, out.ctypes.data))
         return out
 
+    def read_ids(self, out: np.ndarray | None = None) -> np.ndarray:
+        """swr_read_ids: the ID image of the last frame, drawn with FLAG_PRIMITIVE_IDS — (height, width) uint32, the triangle (draw
+        lists: the position in the concatenation of the items) visible at every pixel, ID_NONE where the frame kept no fragment."""
+        if out is None:
+            out = np.zeros((self.height, self.width), dtype=np.uint32)
+        assert out.flags.c_contiguous and out.nbytes == self.width * self.height * 4
+        self._check(self._L.swr_read_ids(self._h, out.ctypes.data))
+        return out
+
     def timing_enable(self, level=2):
         """0/False off, 1 = events around k_raster only, 2/True = around every stage."""
         level = 2 if level is True else (0 if level is False else int(level))
@@ -526,6 +543,7 @@ class Context:
                 t = np.ascontiguousarray(shading.texture, dtype=np.uint8)
                 rp.texture, rp.tex_width, rp.tex_height = t.ctypes.data, t.shape[1], t.shape[0]
         self._check(self._L.swr_render(self._h, ctypes.byref(rp)))
+        self.width, self.height, self.row_begin, self.row_end = width, height, 0, height     # (swr_render sets the target: read_ids)
         return color, depth
 
 
@@ -534,3 +552,25 @@ def render(scene, extra_flags: int = 0, device: int = -1):
     with Context(device) as ctx:
         return ctx.render(scene.vertices, scene.indices, scene.transform, scene.width, scene.height,
                           scene.flags | extra_flags, shading=scene.shading)
+
+
+def list_ids_to_items(ids: np.ndarray, items) -> tuple[np.ndarray, np.ndarray]:
+    """Map the ID image of a draw-list frame (Context.read_ids after Context.draw_list) to (item, triangle-in-item) arrays of the
+    same shape: item k's j-th triangle has the ID vbase_k + j, vbase_k = the sum of index_count / 3 of the items before it (a
+    search over the vbases).  Pixels with ID_NONE get -1 in both.  `items`: what was passed to draw_list."""
+    a = Context.draw_items(items)
+    counts = (a["index_count"] // 3).astype(np.int64)
+    vbase = np.concatenate([[0], np.cumsum(counts)[:-1]]) if counts.size else np.zeros(0, np.int64)
+    ids = np.asarray(ids)
+    live = ids != ID_NONE
+    v = ids.astype(np.int64)
+    # the last item whose vbase is <= the ID and that has triangles (empty items share their vbase with the next one)
+    nonempty = np.nonzero(counts > 0)[0]
+    k = np.full(ids.shape, -1, dtype=np.int64)
+    j = np.full(ids.shape, -1, dtype=np.int64)
+    if nonempty.size:
+        pos = np.searchsorted(vbase[nonempty], v[live], side="right") - 1
+        kk = nonempty[np.clip(pos, 0, None)]
+        k[live] = kk
+        j[live] = v[live] - vbase[kk]
+    return k, j

@@ -183,6 +183,10 @@ struct swr_context {
     static constexpr int NFB = NSLOT;
     static_assert(NFB >= 2, "double-buffered at least");
     DevBuf color[NFB], depth[NFB];
+    // SWR_FLAG_PRIMITIVE_IDS: the ID image of each framebuffer, sized by the first ID frame on a target (a context
+    // that never asks pays no memory); ids_valid = the last frame wrote one (cleared by swr_target_set / swr_target_write)
+    DevBuf ids[NFB];
+    bool ids_valid = false;
     int fb_cur = 0;                     // the next swr_draw renders into this buffer
     int fb_last = 0;                    // the buffer of the last swr_draw (what swr_present / swr_read_* copy)
     hipStream_t last_stream = nullptr;  // the stream that carries the last frame's raster (swr_present records frame_done behind it)
@@ -623,7 +627,8 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
     f.defer_big = 0;
     f.redo_dev = (uint32_t*)c->redo_cnt.p;
     f.host_redo = c->h_pairs_dev + 2 * swr_context::PAIR_RING + 1;
-    f.k32 = (c->k32_ok && c->dbg_k32 && f.redo_dev) ? 1 : 0;
+    // (ID frames take the 64-bit keys, whose key carries the winner: they neither use nor move the scene's 32-bit-key state)
+    f.k32 = (c->k32_ok && c->dbg_k32 && f.redo_dev && !(flags & SWR_FLAG_PRIMITIVE_IDS)) ? 1 : 0;
     f.tile_count = tb + CNT_WORDS;
     f.tile_start = tb + CNT_WORDS + tiles_of(c->tg);
     f.tile_cursor = tb + CNT_WORDS + 2 * tiles_of(c->tg) + 1;
@@ -664,6 +669,7 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
     const bool load = (flags & SWR_FLAG_LOAD) != 0;
     f.src_color = load ? (const uint8_t*)c->color[c->load_src].p : nullptr;
     f.src_depth = load ? (const float*)c->depth[c->load_src].p : nullptr;
+    f.ids = (flags & SWR_FLAG_PRIMITIVE_IDS) ? (uint32_t*)c->ids[c->fb_cur].p : nullptr;
     f.tg = c->tg;
     memcpy(f.m, m, sizeof f.m);
     f.flags = flags;
@@ -1168,7 +1174,8 @@ int copy_band(swr_context* c, int fb, int img, void* dst_full, uint64_t frame) {
     const size_t bytes = (size_t)(c->tg.row_end - c->tg.row_begin) * row;
     if (!bytes) return SWR_OK;
     uint8_t* dst = (uint8_t*)dst_full + (size_t)c->tg.row_begin * row;
-    const uint8_t* src = (const uint8_t*)(img == 0 ? c->color[fb].p : c->depth[fb].p);
+    const uint8_t* src = (const uint8_t*)(img == 0 ? c->color[fb].p : img == 1 ? c->depth[fb].p : c->ids[fb].p);
+    if (img == 2) img = 1;      // the ID image (swr_read_ids) goes on the depth image's copy stream, through its staging
     hipStream_t s = c->copy_stream[img];
     HIP_TRY(c, hipStreamWaitEvent(s, c->frame_done[fb], 0));
     if (is_pinned(dst)) {
@@ -1391,6 +1398,7 @@ int single_target_set(swr_context* c, int64_t width, int64_t height, int64_t row
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->src_clear = true;        // the band images are the cleared ones again (what the next load frame starts from)
+    c->ids_valid = false;       // (and no frame on them has written IDs)
     if (c->has_target && c->tg.width == width && c->tg.height == height && c->tg.row_begin == row_begin && c->tg.row_end == row_end)
         return SWR_OK;          // the same target again (swr_render every frame): nothing to resize, nothing to wait for
     if ((rc = check_frames(c)) || (rc = sync_copies(c))) return rc;      // (an overflowed frame presented just before is repaired / reported first)
@@ -1426,10 +1434,25 @@ int check_draw_args(swr_context* c, uint32_t flags, int32_t primitive_type) {
     if (primitive_type != SWR_PRIMITIVE_TRIANGLE && primitive_type != SWR_PRIMITIVE_LINE &&
         primitive_type != SWR_PRIMITIVE_VERTICES)
         return fail(c, SWR_ERR_UNSUPPORTED, "unknown primitive type %d", primitive_type);
-    if (flags & ~(uint32_t)(SWR_FLAG_DEPTH_TEST | SWR_FLAG_NO_COLOR | SWR_FLAG_METAL_RULES | SWR_FLAG_REAL_LINES | SWR_FLAG_LOAD))
+    if (flags & ~(uint32_t)(SWR_FLAG_DEPTH_TEST | SWR_FLAG_NO_COLOR | SWR_FLAG_METAL_RULES | SWR_FLAG_REAL_LINES | SWR_FLAG_LOAD |
+                            SWR_FLAG_PRIMITIVE_IDS))
         return fail(c, SWR_ERR_BAD_ARG, "unknown flag bits 0x%x", flags);
     if ((flags & SWR_FLAG_REAL_LINES) && primitive_type != SWR_PRIMITIVE_LINE)
         return fail(c, SWR_ERR_BAD_ARG, "SWR_FLAG_REAL_LINES only applies to .line primitives");
+    if ((flags & SWR_FLAG_PRIMITIVE_IDS) && primitive_type != SWR_PRIMITIVE_TRIANGLE)
+        return fail(c, SWR_ERR_UNSUPPORTED, "SWR_FLAG_PRIMITIVE_IDS: triangles only");
+    return SWR_OK;
+}
+
+// An ID frame (SWR_FLAG_PRIMITIVE_IDS) needs the ID image of every framebuffer at the target's size: allocated by the first one on a
+// target (swr_target_set waits for the frames before a resize, so no frame in flight uses a buffer that grows here)
+int ensure_ids(swr_context* c, uint32_t flags) {
+    if (!(flags & SWR_FLAG_PRIMITIVE_IDS)) return SWR_OK;
+    const size_t bytes = (size_t)c->tg.width * (size_t)(c->tg.row_end - c->tg.row_begin) * 4;
+    for (DevBuf& b : c->ids) {
+        const int rc = ensure(c, b, bytes);
+        if (rc) return rc;
+    }
     return SWR_OK;
 }
 
@@ -1456,6 +1479,7 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
         // the new transform replaces the one a redo of the last frame would need)
         if ((rc = check_frames(c))) return rc;
     }
+    if ((rc = ensure_ids(c, flags))) return rc;
     memcpy(c->last_m, transform, sizeof c->last_m);
     if (flags & SWR_FLAG_LOAD) {
         if (c->src_clear) {
@@ -1468,6 +1492,7 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
     }
     c->src_clear = false;
     c->last_flags = flags;
+    c->ids_valid = (flags & SWR_FLAG_PRIMITIVE_IDS) != 0;
     c->last_prim = primitive_type;
     c->last_list = false;
     return enqueue_frame(c);
@@ -1540,6 +1565,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
     if (c->frame_no - c->frames_checked >= (uint64_t)swr_context::PAIR_RING - 2) {
         if ((rc = check_frames(c))) return rc;
     }
+    if ((rc = ensure_ids(c, flags))) return rc;
     // the items, resolved: primitive ranges, frame bases, work units
     std::vector<ListItem> list((size_t)n);
     std::vector<uint32_t> need;             // the cuts the stream needs
@@ -1646,6 +1672,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
     }
     c->src_clear = false;
     c->last_flags = flags;
+    c->ids_valid = (flags & SWR_FLAG_PRIMITIVE_IDS) != 0;
     c->last_prim = SWR_PRIMITIVE_TRIANGLE;
     c->last_list = true;
     return enqueue_frame(c);
@@ -1815,6 +1842,7 @@ int single_target_write(swr_context* c, const void* color_full, const float* dep
     }
     c->src_clear = false;
     c->src_bad = false;
+    c->ids_valid = false;       // the image is the caller's now: no frame's IDs describe it
     return SWR_OK;
 }
 
@@ -1834,16 +1862,20 @@ int single_present_wait(swr_context* c) {
     return SWR_OK;
 }
 
+// img: 0 colour, 1 depth, 2 the ID image (swr_read_ids)
 int single_read(swr_context* c, int img, void* dst) {
     if (const int f = sticky(c)) return f;
     if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_* needs swr_target_set first");
+    if (img == 2 && !c->ids_valid)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_read_ids: the last frame was drawn without SWR_FLAG_PRIMITIVE_IDS, or swr_target_set / "
+                    "swr_target_write came after it");
     int rc = single_sync(c);
     if (rc) return rc;
     if (tiles_of(c->tg) == 0) return SWR_OK;
     const int fb = c->fb_last;
     HIP_TRY(c, hipEventRecord(c->frame_done[fb], c->stream));
     if ((rc = copy_band(c, fb, img, dst, c->frame_no ? c->frame_no - 1 : 0))) return rc;
-    if ((rc = wait_stream(c, c->copy_stream[img], "copy stream"))) return sticky(c) ? sticky(c) : rc;
+    if ((rc = wait_stream(c, c->copy_stream[img == 2 ? 1 : img], "copy stream"))) return sticky(c) ? sticky(c) : rc;
     return SWR_OK;
 }
 
@@ -1883,6 +1915,7 @@ void destroy_single(swr_context* c) {
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
+    for (DevBuf& b : c->ids) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->fillbuf) if (b.p) hipFree(b.p);
     for (auto& lf : c->lanefill) for (DevBuf& b : lf) if (b.p) hipFree(b.p);
     for (hipStream_t ls : c->lane_stream) if (ls) hipStreamDestroy(ls);
@@ -2232,6 +2265,12 @@ int swr_read_depth(swr_context* c, float* dst) {
     if (!c || !dst) return SWR_ERR_BAD_ARG;
     if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_read(k, 1, dst); });
     return single_read(c, 1, dst);
+}
+
+int swr_read_ids(swr_context* c, uint32_t* dst) {
+    if (!c || !dst) return SWR_ERR_BAD_ARG;
+    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_read(k, 2, dst); });
+    return single_read(c, 2, dst);
 }
 
 // ---- page-locked host images ---------------------------------------------------------------------------------------

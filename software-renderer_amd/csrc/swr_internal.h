@@ -125,6 +125,7 @@ struct DeviceFrame {
     float* depth;
     const uint8_t* src_color;      // load frames (SWR_FLAG_LOAD): the framebuffer the frame starts from (never color / depth)
     const float* src_depth;
+    uint32_t* ids;                 // SWR_FLAG_PRIMITIVE_IDS frames: the ID image, band-local like depth (else NULL)
     Target tg;
     float m[16];                   // column-major transform
     uint32_t flags;                // SWR_FLAG_*

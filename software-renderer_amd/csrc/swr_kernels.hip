@@ -1271,6 +1271,7 @@ struct RasterArgs {
     uint32_t* host_redo;    // ... handed to the host's pinned word by the next launch (the host then switches the scene to the 64-bit kernel)
     const uint8_t* src_color;   // load frames (SWR_FLAG_LOAD): the image the frame starts from, band-local like color / depth and never
     const float* src_depth;     // the same buffers (read-only for the frame)
+    uint32_t* ids;              // SWR_FLAG_PRIMITIVE_IDS: the frame's ID image, band-local like depth (IDS instances only)
 };
 constexpr int REDO_SAMPLE = 8;
 
@@ -1340,6 +1341,28 @@ __device__ __forceinline__ unsigned long long loaded_key(float d) {
 // stores NaN / +inf depths as +inf keys instead of testing every fragment (they lose against any real depth and
 // are never resolved); painter's-mode keys have a zero high word; KEY_EMPTY has all ones.
 constexpr uint32_t KEY_LIVE_BELOW = 0xFF800000u;
+
+// SWR_FLAG_PRIMITIVE_IDS: the ID of a pixel is the order number in its key's low word — the original primitive
+// index, the draw list's order number — undone from the forms the keys carry it in: +1 in z-tested load frames, ~ under painter's
+// order, << WTAB_LOCAL_BITS (shift) in the winner table.  A pixel without a winner of this frame (empty, only NaN / +inf depths, or
+// the loaded image kept in a load frame) is SWR_ID_NONE.
+template <bool ZTEST, bool LOAD>
+__device__ __forceinline__ uint32_t key_id(unsigned long long key, int shift = 0) {
+    const uint32_t lo = (uint32_t)key;
+    const bool live = (uint32_t)(key >> 32) < KEY_LIVE_BELOW && !(LOAD && ZTEST && lo == 0u);
+    const uint32_t w = ZTEST ? lo - (LOAD ? 1u : 0u) : 0xFFFFFFFFu - lo;
+    return live ? w >> shift : (uint32_t)SWR_ID_NONE;
+}
+// the IDs of one 4-pixel group at band-local element `at`: one streaming 16-B store, or pixel by pixel at a ragged right edge
+__device__ __forceinline__ void store_ids4(uint32_t* ids, size_t at, bool vec, int x, int X1, const uint32_t (&id)[4]) {
+    if (vec && x + 3 <= X1) {
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 v = {id[0], id[1], id[2], id[3]};
+        __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(ids + at));
+    } else {
+        for (int k = 0; k < 4 && x + k <= X1; k++) ids[at + k] = id[k];
+    }
+}
 
 // Per-lane triangle state for the span walk.
 struct TriState {
@@ -1517,11 +1540,13 @@ constexpr int VAR_ALLCOOP = 20;
 // 64-bit keys — only a K32 instance ever does.
 // LOAD: a load frame (SWR_FLAG_LOAD): the tile starts from the image in a.src_color / a.src_depth instead of the clear, pixels without a
 // fragment of this frame keep it (painter's order: the depth image is the loaded one everywhere).
-template <bool ZTEST, int VAR, bool METAL, bool EXT, bool COLOR, bool PLAIN = false, bool K32 = false, bool LOAD = false>
+// IDS: the frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) to a.ids, next to the depth; 64-bit keys only.
+template <bool ZTEST, int VAR, bool METAL, bool EXT, bool COLOR, bool PLAIN = false, bool K32 = false, bool LOAD = false, bool IDS = false>
 __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::conditional<K32, RasterLds32, RasterLds64>::type& L) {
     static_assert(!METAL || ZTEST, "the Metal rules always z-test");
     static_assert(!EXT || COLOR, "the extended fragment stage only exists for colour frames");
     static_assert(!K32 || (ZTEST && !COLOR && !METAL), "32-bit keys: depth-only z-tested frames under the CPU rules");
+    static_assert(!IDS || (!K32 && VAR == 0), "primitive IDs need the winner in the key: 64-bit keys, the product kernels");
 #ifndef SWR_UNIT
 #define SWR_UNIT 4
 #endif
@@ -2271,6 +2296,16 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                     pos[g][k] = live ? (low & ((1u << WTAB_LOCAL_BITS) - 1u)) : 0xFFFFu;
                 }
                 *reinterpret_cast<uint2*>(pix + p) = make_uint2(pos[g][0] | (pos[g][1] << 16), pos[g][2] | (pos[g][3] << 16));
+                if constexpr (IDS) {
+                    // the IDs leave now, while the keys are still there (the records overwrite them): the same pixels as pass 3's
+                    const int y = Y0 + p / TILE_W, x = X0 + p % TILE_W;
+                    if (y >= Yp0 && y <= Yp1 && x <= X1) {
+                        uint32_t id[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) id[k] = key_id<ZTEST, LOAD>(keys[p + k], WTAB_LOCAL_BITS);
+                        store_ids4(a.ids, (size_t)(y - a.tg.row_begin) * (size_t)W + (size_t)x, vec_ok, x, X1, id);
+                    }
+                }
             }
             __syncthreads();
             uint32_t nrec = m;
@@ -2490,6 +2525,12 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
             } else {
                 for (int k = 0; k < 4 && x + k <= X1; k++) a.depth[at + k] = d4[k];
             }
+            if constexpr (IDS) {
+                uint32_t id[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) id[k] = key_id<ZTEST, LOAD>(keys[ly * TILE_W + lx + k]);
+                store_ids4(a.ids, at, vec_ok, x, X1, id);
+            }
         }
         if (!__any(zero_seen)) return false;    // (wave-uniform; no barrier follows)
     }
@@ -2688,6 +2729,19 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                 }
             }
         }
+        if constexpr (IDS) {
+            // the IDs last, re-read from the keys: nothing of them is live across the pixel loop or the stores above (the empty asm
+            // keeps the compiler from holding the loop's key loads in registers until here instead: PLAIN colour kernels 91 -> 96 + spills)
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                if (!on[g]) continue;
+                uint32_t id[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) id[k] = key_id<ZTEST, LOAD>(keys[ly[g] * TILE_W + lx[g] + k]);
+                store_ids4(a.ids, (size_t)(y[g] - a.tg.row_begin) * (size_t)W + (size_t)x[g], vec_ok, x[g], X1, id);
+            }
+        }
     }
     }   // !K32
     return false;
@@ -2696,18 +2750,19 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
 // The kernels proper: the reference's fragment stage — colour and depth-only frames (SWR_FLAG_NO_COLOR) as separate kernels, so
 // that each has its own register allocation (tools/vgprs.sh: 86 depth-only, 87 colour, 88 Metal rules; the budget of 88 above) —
 // and the extended one.  PLAIN = the colour kernels of scenes with more than 2^20 primitives (no winner table: raster_tile).
-// LOAD = the load frames' twin of each kernel (SWR_FLAG_LOAD), same register budget.
-template <bool ZTEST, int VAR = 0, bool METAL = false, bool COLOR = false, bool PLAIN = false, bool LOAD = false>
+// LOAD = the load frames' twin of each kernel (SWR_FLAG_LOAD), same register budget.  IDS = the twin that also writes the ID image
+// (SWR_FLAG_PRIMITIVE_IDS); depth-only z-tested CPU-rules frames with IDs take k_raster<true, 0, false, false, false, LOAD, true>.
+template <bool ZTEST, int VAR = 0, bool METAL = false, bool COLOR = false, bool PLAIN = false, bool LOAD = false, bool IDS = false>
 __global__ __launch_bounds__(RASTER_THREADS, SWR_RASTER_MIN_WAVES) __attribute__((amdgpu_num_vgpr(SWR_RASTER_VGPRS)))
 void k_raster(RasterArgs a) {
     __shared__ RasterLds64 L;
-    raster_tile<ZTEST, VAR, METAL, false, COLOR, PLAIN, false, LOAD>(a, L);
+    raster_tile<ZTEST, VAR, METAL, false, COLOR, PLAIN, false, LOAD, IDS>(a, L);
 }
-template <bool ZTEST, bool METAL = false, bool PLAIN = false, bool LOAD = false>
+template <bool ZTEST, bool METAL = false, bool PLAIN = false, bool LOAD = false, bool IDS = false>
 __global__ __launch_bounds__(RASTER_THREADS, PLAIN ? 4 : SWR_RASTER_MIN_WAVES_EXT)
 void k_raster_ext(RasterArgs a) {
     __shared__ RasterLds64 L;
-    raster_tile<ZTEST, 0, METAL, true, true, PLAIN, false, LOAD>(a, L);
+    raster_tile<ZTEST, 0, METAL, true, true, PLAIN, false, LOAD, IDS>(a, L);
 }
 // Depth-only z-tested frames under the CPU rules: 32-bit keys first; the rare tile whose result they cannot vouch for (a
 // zero, whose sign is the first-drawn winner's) is rastered again, by the same workgroup, with the 64-bit keys.  One LDS block for both.
@@ -3072,10 +3127,10 @@ bool launch_sort_bins(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
 // Does this frame take k_raster_depth (32-bit depth keys)?  Depth-only, z-tested, CPU rules, and the scene has not been moved
 // to the 64-bit kernel by the host (DeviceFrame::k32).
 bool frame_uses_k32(const DeviceFrame& f) {
-    return f.k32 && (f.flags & SWR_FLAG_DEPTH_TEST) && (f.flags & SWR_FLAG_NO_COLOR) && !(f.flags & SWR_FLAG_METAL_RULES);
+    return f.k32 && !(f.flags & SWR_FLAG_PRIMITIVE_IDS) && (f.flags & SWR_FLAG_DEPTH_TEST) && (f.flags & SWR_FLAG_NO_COLOR) && !(f.flags & SWR_FLAG_METAL_RULES);
 }
 
-template <bool LOAD>
+template <bool LOAD, bool IDS>
 static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     RasterArgs a;
     a.geo = f.geo; a.geo_full = f.geo_full; a.tri_rgb = f.tri_rgb;
@@ -3098,6 +3153,7 @@ static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop
     a.insort = f.insort;
     a.src_color = LOAD ? f.src_color : nullptr;
     a.src_depth = LOAD ? f.src_depth : nullptr;
+    a.ids = IDS ? f.ids : nullptr;
     // (a load frame's z-tested keys carry the packed word + 1: the last primitive of a scene of exactly 2^20 would wrap)
     a.pack_local = f.ntri < (1ll << WTAB_PRIM_BITS) + (LOAD ? 0 : 1) ? 1 : 0;
     const bool plain = !a.pack_local;      // more than 2^20 primitives: the colour kernels without the winner table
@@ -3114,20 +3170,20 @@ static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop
     const unsigned tiles = ntiles << a.vs_log;
     const bool ext = f.material.shader != SWR_SHADER_PASSTHROUGH && a.color != nullptr;
     if (f.flags & SWR_FLAG_METAL_RULES) {
-        if (ext && plain) SWR_LAUNCH(stop, (k_raster_ext<true, true, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (ext) SWR_LAUNCH(stop, (k_raster_ext<true, true, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, true, true, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, true, true, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else SWR_LAUNCH(stop, (k_raster<true, 0, true, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        if (ext && plain) SWR_LAUNCH(stop, (k_raster_ext<true, true, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (ext) SWR_LAUNCH(stop, (k_raster_ext<true, true, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, true, true, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, true, true, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else SWR_LAUNCH(stop, (k_raster<true, 0, true, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
         return stop != nullptr;
     }
     if (ext) {
         if (f.flags & SWR_FLAG_DEPTH_TEST) {
-            if (plain) SWR_LAUNCH(stop, (k_raster_ext<true, false, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-            else SWR_LAUNCH(stop, (k_raster_ext<true, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+            if (plain) SWR_LAUNCH(stop, (k_raster_ext<true, false, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+            else SWR_LAUNCH(stop, (k_raster_ext<true, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
         } else {
-            if (plain) SWR_LAUNCH(stop, (k_raster_ext<false, false, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-            else SWR_LAUNCH(stop, (k_raster_ext<false, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+            if (plain) SWR_LAUNCH(stop, (k_raster_ext<false, false, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+            else SWR_LAUNCH(stop, (k_raster_ext<false, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
         }
         return stop != nullptr;
     }
@@ -3135,7 +3191,7 @@ static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop
     // timing-only ablations of k_raster<ztest> (results invalid): compiled only into lib/libswr_hip_ablation.so
     // (`make ablation`, used by tools/variants.sh); the product library has neither the kernels nor the switch
     static const int variant = getenv("SWR_DEBUG_VARIANT") ? atoi(getenv("SWR_DEBUG_VARIANT")) : 0;
-    if (!LOAD && (f.flags & SWR_FLAG_DEPTH_TEST) && variant > 0 && !a.color) {
+    if (!LOAD && !IDS && (f.flags & SWR_FLAG_DEPTH_TEST) && variant > 0 && !a.color) {
         switch (variant) {
 #define SWR_V(N) case N: hipLaunchKernelGGL((k_raster<true, N>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a); return false;
             SWR_V(1) SWR_V(2) SWR_V(3) SWR_V(4) SWR_V(5) SWR_V(8) SWR_V(9) SWR_V(10) SWR_V(11)
@@ -3145,20 +3201,22 @@ static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop
     }
 #endif
     if (f.flags & SWR_FLAG_DEPTH_TEST) {
-        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (frame_uses_k32(f)) SWR_LAUNCH(stop, k_raster_depth<LOAD>, dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else SWR_LAUNCH(stop, (k_raster<true, 0, false, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (!IDS && frame_uses_k32(f)) SWR_LAUNCH(stop, k_raster_depth<LOAD>, dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else SWR_LAUNCH(stop, (k_raster<true, 0, false, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
     } else {
-        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<false, 0, false, true, true, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color) SWR_LAUNCH(stop, (k_raster<false, 0, false, true, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else SWR_LAUNCH(stop, (k_raster<false, 0, false, false, false, LOAD>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<false, 0, false, true, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else if (a.color) SWR_LAUNCH(stop, (k_raster<false, 0, false, true, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+        else SWR_LAUNCH(stop, (k_raster<false, 0, false, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
     }
     return stop != nullptr;
 }
 
 bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
-    return (f.flags & SWR_FLAG_LOAD) ? launch_raster_t<true>(f, s, stop) : launch_raster_t<false>(f, s, stop);
+    const bool load = (f.flags & SWR_FLAG_LOAD) != 0;
+    if (f.flags & SWR_FLAG_PRIMITIVE_IDS) return load ? launch_raster_t<true, true>(f, s, stop) : launch_raster_t<false, true>(f, s, stop);
+    return load ? launch_raster_t<true, false>(f, s, stop) : launch_raster_t<false, false>(f, s, stop);
 }
 
 }  // namespace swr

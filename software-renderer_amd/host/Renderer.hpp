@@ -217,6 +217,12 @@ public:
         int rc = swr_draw_list(ctx_, list.data(), (int32_t)list.size(), flags);
         if (rc) throw RenderError(rc, swr_last_error(ctx_));
     }
+    // The ID image of the last frame, drawn with SWR_FLAG_PRIMITIVE_IDS (swr_read_ids): width * height words, the triangle index (draw
+    // lists: the position in the concatenation of the items) visible at every pixel, SWR_ID_NONE where the frame kept no fragment.
+    void readPrimitiveIds(uint32_t* dst) {
+        int rc = swr_read_ids(ctx_, dst);
+        if (rc) throw RenderError(rc, swr_last_error(ctx_));
+    }
 private:
     swr_context* ctx_ = nullptr;
 };
@@ -261,12 +267,17 @@ public:
     bool staticScene = false;
     uint64_t sceneVersion = 1;
     bool realLines = false;             // see Renderer::realLines
+    // true: every render() also writes the ID image (SWR_FLAG_PRIMITIVE_IDS; triangle passes only), read with readPrimitiveIds —
+    // what a Metal app gets from a second colour attachment written with [[primitive_id]]
+    bool primitiveIds = false;
     void render(const RenderPass& renderPass) {
         const bool lines = realLines && renderPass.primitiveType == PrimitiveType::line;
         ctx_.render(renderPass, (metalRules ? (uint32_t)SWR_FLAG_METAL_RULES : (depthTest ? (uint32_t)SWR_FLAG_DEPTH_TEST : 0u)) |
-                                    (lines ? (uint32_t)SWR_FLAG_REAL_LINES : 0u),
+                                    (lines ? (uint32_t)SWR_FLAG_REAL_LINES : 0u) | (primitiveIds ? (uint32_t)SWR_FLAG_PRIMITIVE_IDS : 0u),
                     staticScene ? sceneVersion : 0);
     }
+    // the ID image of the last render() (primitiveIds = true): colorBuffer.width * height words, row-major (mouse picking)
+    void readPrimitiveIds(uint32_t* dst) { ctx_.readPrimitiveIds(dst); }
 private:
     detail::Context ctx_;
 };
