@@ -7,11 +7,14 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
+                                   [--cull back [--front-ccw]]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
 --pick X,Y also writes every frame's ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy of the mesh and which of its
 triangles are visible at pixel (X, Y): mouse picking (use it with --objects N).
+--cull {none,back,front} [--front-ccw] turns on face culling (Metal's setCullMode / setFrontFacingWinding): triangles that face
+away (back) or towards the viewer (front) are not drawn; front is clockwise as displayed unless --front-ccw.
 
 The demo mesh is a UV sphere standing in for ModelIO's `MDLMesh(sphereWithExtent: 0.4, segments: 13x13,
 inwardNormals: true)` (App.swift:124) with colour = |normal| (App.swift:133).  `--obj` loads a
@@ -230,13 +233,21 @@ def object_transforms(time: float, n: int):
     return out
 
 
+def cull_flags(cull: str = "none", front_ccw: bool = False) -> int:
+    """Face culling (Metal's setCullMode / setFrontFacingWinding): none / back / front, front = clockwise as displayed unless
+    front_ccw."""
+    b = swr_amd.binding
+    return {"none": 0, "back": b.FLAG_CULL_BACK, "front": b.FLAG_CULL_FRONT}[cull] | (b.FLAG_FRONT_CCW if front_ccw else 0)
+
+
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
-        time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None):
+        time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
     mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
-    frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel."""
+    frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel.
+    cull / front_ccw: face culling (cull_flags)."""
     vertices, indices = load_mesh(obj) if obj else sphere_mesh()
-    flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | (swr_amd.binding.FLAG_PRIMITIVE_IDS if pick else 0)
+    flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | (swr_amd.binding.FLAG_PRIMITIVE_IDS if pick else 0) | cull_flags(cull, front_ccw)
     results = []
     with swr_amd.Context() as ctx:
         ctx.scene_upload(vertices, indices)            # RenderPass.vertices / .indices, App.swift:163
@@ -270,14 +281,14 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
 
 
 def run_streamed(frames: int, size: int, obj: str | None = None, depth_test: bool = False, time0: float = 0.0,
-                 device_count: int = 1, on_frame=None):
+                 device_count: int = 1, on_frame=None, cull: str = "none", front_ccw: bool = False):
     """The same loop the way a host that wants every frame should drive it: two page-locked
     image sets alternate; frame k is being copied to the host (swr_present, asynchronous, every band of a multi-GPU
     context into its rows of the ONE image) while frame k+1 is drawn; the host touches frame k only after
     swr_present_wait.  `on_frame(k, colour, depth)` sees the host images (valid until the next but one present).
     Returns the frames (copies)."""
     vertices, indices = load_mesh(obj) if obj else sphere_mesh()
-    flags = S.FLAG_DEPTH_TEST if depth_test else 0
+    flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | cull_flags(cull, front_ccw)
     sets = [(swr_amd.HostImage((size, size, 4), np.uint8), swr_amd.HostImage((size, size), np.float32)) for _ in range(2)]
     results = []
 
@@ -318,12 +329,15 @@ if __name__ == "__main__":
     ap.add_argument("--gpus", type=int, default=1, help="bands / GPUs of the one context (with --stream)")
     ap.add_argument("--objects", type=int, default=1, help="copies of the mesh, each with its own matrix: one draw list per frame")
     ap.add_argument("--pick", default=None, help="X,Y: print the copy and the triangle under that pixel every frame (primitive IDs)")
+    ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
+    ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
     a = ap.parse_args()
     if a.stream:
-        res = run_streamed(a.frames, a.size, a.ply or a.obj, a.depth_test, device_count=a.gpus)
+        res = run_streamed(a.frames, a.size, a.ply or a.obj, a.depth_test, device_count=a.gpus, cull=a.cull, front_ccw=a.front_ccw)
         print(f"{a.frames} frames streamed, coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
     pick = tuple(int(t) for t in a.pick.split(",")) if a.pick else None
-    _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick)
+    _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick, cull=a.cull,
+                      front_ccw=a.front_ccw)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

@@ -77,10 +77,32 @@ enum {
     SWR_FLAG_LOAD = 1u << 4,       /* LOAD ACTION (ABI 6; Metal's MTLLoadActionLoad): the frame is Renderer.render(renderPass:) WITHOUT the
                                       clear of Renderer.swift:205-206 — the same loop continues from the image already there (see
                                       "Load frames" below) */
-    SWR_FLAG_PRIMITIVE_IDS = 1u << 5 /* the frame also writes an ID image: which triangle is visible at every pixel (Metal: a second
+    SWR_FLAG_PRIMITIVE_IDS = 1u << 5, /* the frame also writes an ID image: which triangle is visible at every pixel (Metal: a second
                                       colour attachment written with [[primitive_id]]); read it with swr_read_ids (see "Primitive
                                       IDs" below) */
+    SWR_FLAG_CULL_BACK = 1u << 6,  /* face culling (Metal's setCullMode(.back)): back-facing triangles are not drawn (see "Face culling") */
+    SWR_FLAG_CULL_FRONT = 1u << 7, /* front-facing triangles are not drawn; with SWR_FLAG_CULL_BACK every triangle with a facing is dropped */
+    SWR_FLAG_FRONT_CCW = 1u << 8   /* front = counter-clockwise as displayed (Metal's setFrontFacingWinding(.counterClockwise));
+                                      without it front = clockwise as displayed (MTLWindingClockwise, Metal's default) */
 };
+
+/* ---- Face culling (SWR_FLAG_CULL_BACK / _CULL_FRONT / _FRONT_CCW) — DESIGN.md §14 ------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6): a library that accepts the bits has the feature; an older one refuses them with
+ * SWR_ERR_BAD_ARG.
+ *   Facing comes from the integer vertices the triangle is rasterised with — the truncated screen coordinates, or under
+ *     SWR_FLAG_METAL_RULES the rounded-then-truncated ones — a, b, c in index order, pixel coordinates (x right, y down, row 0 at
+ *     the top): A = (bx - ax) * (cy - ay) - (cx - ax) * (by - ay), exact.  A > 0: clockwise as displayed; A < 0: counter-clockwise.
+ *     Example: NDC (-0.5,-0.5), (0.5,-0.5), (0,0.5) (counter-clockwise with y up) maps to pixels (W/4, 3H/4), (3W/4, 3H/4), (W/2, H/4):
+ *     A = -W*H/4 < 0, counter-clockwise as displayed (the y flip of the screen map keeps the visual orientation).
+ *   Front-facing: A > 0, or A < 0 with SWR_FLAG_FRONT_CCW; back-facing: the other sign.  A == 0 has no facing and is never culled
+ *     (under the CPU rules such triangles draw as before; the Metal rules skip them anyway).  Triangles setup already skips stay
+ *     skipped.
+ *   Every triangle entry point: swr_draw, swr_draw_primitives(SWR_PRIMITIVE_TRIANGLE), swr_draw_list (each item's facing from its
+ *     own transform: a mirroring matrix flips the winding, uncompensated, as in Metal and GL), swr_render.  .vertices and .line
+ *     frames accept the bits and ignore them.
+ *   A culled frame is bit for bit the frame without the bits of the same scene with the culled triangles removed from the index
+ *     list, order kept — colour, depth and IDs, which keep the original numbering (triangle index p, draw-list order number).
+ *   swr_timings.triangles still counts submitted triangles; tile_pairs only the pairs binned. */
 
 /* ---- Primitive IDs (SWR_FLAG_PRIMITIVE_IDS) — DESIGN.md §13 --------------------------------------------------------------
  * No ABI bump (SWR_ABI_VERSION stays 6): the presence of the swr_read_ids symbol is the feature test.

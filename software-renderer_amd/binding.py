@@ -17,6 +17,9 @@ FLAG_METAL_RULES = 4
 FLAG_REAL_LINES = 8      # .line primitives: the reference's DDA (Renderer.swift:405-419) instead of its empty stub (:289-293)
 FLAG_LOAD = 16           # load action (ABI 6): the frame starts from the image already there instead of the clear (include/swr.h)
 FLAG_PRIMITIVE_IDS = 32  # the frame also writes an ID image: which triangle is visible at every pixel (Context.read_ids)
+FLAG_CULL_BACK = 64      # face culling: back-facing triangles are not drawn (include/swr.h "Face culling")
+FLAG_CULL_FRONT = 128    # front-facing triangles are not drawn (with FLAG_CULL_BACK: every triangle with a facing)
+FLAG_FRONT_CCW = 256     # front = counter-clockwise as displayed; without it clockwise (Metal's default winding)
 ID_NONE = 0xFFFFFFFF     # SWR_ID_NONE: a pixel where the frame keeps no fragment
 
 # every symbol include/swr.h declares (checked by tests/test_abi.py)

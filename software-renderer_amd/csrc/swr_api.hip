@@ -1435,7 +1435,7 @@ int check_draw_args(swr_context* c, uint32_t flags, int32_t primitive_type) {
         primitive_type != SWR_PRIMITIVE_VERTICES)
         return fail(c, SWR_ERR_UNSUPPORTED, "unknown primitive type %d", primitive_type);
     if (flags & ~(uint32_t)(SWR_FLAG_DEPTH_TEST | SWR_FLAG_NO_COLOR | SWR_FLAG_METAL_RULES | SWR_FLAG_REAL_LINES | SWR_FLAG_LOAD |
-                            SWR_FLAG_PRIMITIVE_IDS))
+                            SWR_FLAG_PRIMITIVE_IDS | SWR_FLAG_CULL_BACK | SWR_FLAG_CULL_FRONT | SWR_FLAG_FRONT_CCW))
         return fail(c, SWR_ERR_BAD_ARG, "unknown flag bits 0x%x", flags);
     if ((flags & SWR_FLAG_REAL_LINES) && primitive_type != SWR_PRIMITIVE_LINE)
         return fail(c, SWR_ERR_BAD_ARG, "SWR_FLAG_REAL_LINES only applies to .line primitives");

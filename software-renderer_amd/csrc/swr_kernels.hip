@@ -222,7 +222,13 @@ struct SetupArgs {
     Target tg;
     float4x4 m;
     int metal;              // SWR_FLAG_METAL_RULES: Shaders.metal / GpuRenderer.swift rules
+    int faces;              // face culling: FACES_DROP_CW | FACES_DROP_CCW, by the sign of the integer area
 };
+
+// SetupArgs::faces, from SWR_FLAG_CULL_BACK / _CULL_FRONT / _FRONT_CCW (faces_of): which sign of the signed area
+// A = (bx - ax)(cy - ay) - (cx - ax)(by - ay) of the integer vertices is not drawn.  A > 0 is clockwise as displayed.
+constexpr int FACES_DROP_CW = 1;    // A > 0
+constexpr int FACES_DROP_CCW = 2;   // A < 0
 
 constexpr uint32_t RANGE_NONE_X = 0x00000001u;   // tx0 = 1, tx1 = 0: empty rectangle
 
@@ -344,6 +350,14 @@ __device__ __forceinline__ uint2 setup_triangle_r(const SetupArgs& a, int64_t p,
     if (ok) {
 #pragma unroll
         for (int k = 0; k < 3; k++) { ix[k] = (int)sx[k]; iy[k] = (int)sy[k]; }  // :251 truncation
+    }
+    // Face culling: the signed area of the integer vertices in index order decides the facing, exactly (deltas of
+    // coordinates below 2^30 are below 2^31, the products below 2^62).  A == 0 has no facing and is never dropped.  Wave-uniform
+    // branch: frames without the cull bits skip it.
+    if (a.faces) {
+        const int64_t l = (int64_t)(ix[1] - ix[0]) * (int64_t)(iy[2] - iy[0]);
+        const int64_t r = (int64_t)(ix[2] - ix[0]) * (int64_t)(iy[1] - iy[0]);
+        ok = ok && !((a.faces & FACES_DROP_CW) && l > r) && !((a.faces & FACES_DROP_CCW) && l < r);
     }
     // det == 0 (vertices collinear after truncation) is drawn like any other triangle under the CPU rules: T()
     // (:95-100) then holds +-inf / NaN, the clamp of :119-122 maps such colours to 0 / 1 and a NaN depth fails
@@ -2929,6 +2943,13 @@ void launch_validate_indices(const int64_t* indices, int64_t count, int64_t vert
                        vertex_count, counters);
 }
 
+// Front = clockwise as displayed (A > 0), or counter-clockwise with SWR_FLAG_FRONT_CCW; the cull bits name the side not drawn.
+static int faces_of(uint32_t flags) {
+    const int front = (flags & SWR_FLAG_FRONT_CCW) ? FACES_DROP_CCW : FACES_DROP_CW;
+    const int back = front ^ (FACES_DROP_CW | FACES_DROP_CCW);
+    return ((flags & SWR_FLAG_CULL_FRONT) ? front : 0) | ((flags & SWR_FLAG_CULL_BACK) ? back : 0);
+}
+
 static SetupArgs make_setup_args(const DeviceFrame& f) {
     SetupArgs a;
     a.tri_xyz = f.tri_xyz; a.box64 = f.box64; a.reordered = f.reordered; a.ntri = f.ntri;
@@ -2936,6 +2957,7 @@ static SetupArgs make_setup_args(const DeviceFrame& f) {
     a.geo = f.geo; a.geo_full = f.geo_full;
     a.tile_count = f.tile_count; a.ranges = f.ranges; a.tg = f.tg;
     a.metal = (f.flags & SWR_FLAG_METAL_RULES) ? 1 : 0;
+    a.faces = faces_of(f.flags);
     for (int c = 0; c < 4; c++)
         a.m.columns[c] = make_float4(f.m[4 * c + 0], f.m[4 * c + 1], f.m[4 * c + 2], f.m[4 * c + 3]);
     return a;

@@ -128,8 +128,18 @@ struct Material {
 // (Renderer.swift:205-206 clear first); load = the pass draws on top of what colorBuffer / depthBuffer already hold.
 enum class LoadAction { clear, load };
 
+// Face culling (Metal's MTLCullMode / MTLWinding; include/swr.h "Face culling"): which facing is not drawn, and which winding as
+// displayed is the front.  The defaults draw every triangle, as the reference does.
+enum class CullMode { none, front, back };
+enum class Winding { clockwise, counterClockwise };
+inline uint32_t faceCullingFlags(CullMode cullMode, Winding frontFacingWinding) {
+    return (cullMode == CullMode::back ? (uint32_t)SWR_FLAG_CULL_BACK : 0u) |
+           (cullMode == CullMode::front ? (uint32_t)SWR_FLAG_CULL_FRONT : 0u) |
+           (frontFacingWinding == Winding::counterClockwise ? (uint32_t)SWR_FLAG_FRONT_CCW : 0u);
+}
+
 // Renderer.swift:191-200 (+ the optional extended fragment stage: empty attributes / passthrough material
-// = the reference's RenderPass exactly; + the load action, clear by default = the reference)
+// = the reference's RenderPass exactly; + the load action, clear by default = the reference; + face culling, none by default)
 struct RenderPass {
     ColorImage colorBuffer;
     DepthImage depthBuffer;
@@ -140,6 +150,8 @@ struct RenderPass {
     std::vector<VertexAttributes> attributes = {};
     Material material = {};
     LoadAction loadAction = LoadAction::clear;
+    CullMode cullMode = CullMode::none;
+    Winding frontFacingWinding = Winding::clockwise;
 };
 
 // One draw of a draw list (swr_draw_item, include/swr.h): indices [firstIndex, firstIndex + indexCount) of the resident scene
@@ -178,7 +190,8 @@ public:
         rp.indices = p.indices.data();
         rp.index_count = (int64_t)p.indices.size();
         rp.primitive_type = (int32_t)p.primitiveType;
-        rp.flags = flags | (p.loadAction == LoadAction::load ? (uint32_t)SWR_FLAG_LOAD : 0u);
+        rp.flags = flags | (p.loadAction == LoadAction::load ? (uint32_t)SWR_FLAG_LOAD : 0u) |
+                   faceCullingFlags(p.cullMode, p.frontFacingWinding);
         for (int c = 0; c < 4; c++)
             for (int r = 0; r < 4; r++) rp.transform[4 * c + r] = p.transform.columns[c][r];
         swr_material mat{};
@@ -205,8 +218,10 @@ public:
         if (rc) throw RenderError(rc, swr_last_error(ctx_));
     }
     // One frame of several draws (swr_draw_list) on the scene and target the last render() with a sceneId left resident; the
-    // image is the context's, as after that render() (its colour / depth buffers are not written).
-    void drawList(const std::vector<DrawItem>& items, uint32_t flags) {
+    // image is the context's, as after that render() (its colour / depth buffers are not written).  The cull mode and winding hold
+    // for every item; each item's facing comes from its own transform.
+    void drawList(const std::vector<DrawItem>& items, uint32_t flags, CullMode cullMode = CullMode::none,
+                  Winding frontFacingWinding = Winding::clockwise) {
         std::vector<swr_draw_item> list(items.size());
         for (size_t k = 0; k < items.size(); k++) {
             list[k].first_index = items[k].firstIndex;
@@ -214,7 +229,7 @@ public:
             for (int c = 0; c < 4; c++)
                 for (int r = 0; r < 4; r++) list[k].transform[4 * c + r] = items[k].transform.columns[c][r];
         }
-        int rc = swr_draw_list(ctx_, list.data(), (int32_t)list.size(), flags);
+        int rc = swr_draw_list(ctx_, list.data(), (int32_t)list.size(), flags | faceCullingFlags(cullMode, frontFacingWinding));
         if (rc) throw RenderError(rc, swr_last_error(ctx_));
     }
     // The ID image of the last frame, drawn with SWR_FLAG_PRIMITIVE_IDS (swr_read_ids): width * height words, the triangle index (draw
