@@ -82,8 +82,10 @@ enum {
                                       IDs" below) */
     SWR_FLAG_CULL_BACK = 1u << 6,  /* face culling (Metal's setCullMode(.back)): back-facing triangles are not drawn (see "Face culling") */
     SWR_FLAG_CULL_FRONT = 1u << 7, /* front-facing triangles are not drawn; with SWR_FLAG_CULL_BACK every triangle with a facing is dropped */
-    SWR_FLAG_FRONT_CCW = 1u << 8   /* front = counter-clockwise as displayed (Metal's setFrontFacingWinding(.counterClockwise));
+    SWR_FLAG_FRONT_CCW = 1u << 8,  /* front = counter-clockwise as displayed (Metal's setFrontFacingWinding(.counterClockwise));
                                       without it front = clockwise as displayed (MTLWindingClockwise, Metal's default) */
+    SWR_FLAG_DEPTH_CLIP = 1u << 10 /* clip every triangle against the near (z >= 0) and far (z <= w) planes before the divide, like
+                                      Metal's default MTLDepthClipMode.clip (see "Depth clipping") */
 };
 
 /* ---- Face culling (SWR_FLAG_CULL_BACK / _CULL_FRONT / _FRONT_CCW) — DESIGN.md §14 ------------------------------------------
@@ -103,6 +105,34 @@ enum {
  *   A culled frame is bit for bit the frame without the bits of the same scene with the culled triangles removed from the index
  *     list, order kept — colour, depth and IDs, which keep the original numbering (triangle index p, draw-list order number).
  *   swr_timings.triangles still counts submitted triangles; tile_pairs only the pairs binned. */
+
+/* ---- Depth clipping (SWR_FLAG_DEPTH_CLIP) — DESIGN.md §15 --------------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6): a library that accepts the bit has the feature; an older one refuses it with
+ * SWR_ERR_BAD_ARG.  Without the bit nothing changes: every vertex goes from clip space straight to xyz / w.  (Bit 9 stays unused:
+ * it is the bit earlier releases are tested to refuse as unknown.)
+ *   Clip-space vertices r = (x, y, z, w): vertex_shader as setup computes it (draw lists: each item's own transform).
+ *   Inside the near plane iff d_near = z >= 0, inside the far plane iff d_far = w - z >= 0 (binary32).  A triangle with a
+ *     non-finite clip-space component is dropped (a documented deviation, like DESIGN.md §2.6).
+ *   A triangle with all three vertices inside both planes is drawn exactly as without the bit.  Any other triangle is clipped
+ *     against the near plane, then the far plane, each pass Sutherland-Hodgman over the edges (P_i, P_i+1) in vertex order,
+ *     cyclic: P_i is emitted iff d(P_i) >= 0; an edge with one endpoint at d > 0 and the other at d < 0 adds the intersection,
+ *     computed from the inside endpoint I towards the outside one O: t = d_I / (d_I - d_O), every carried component
+ *     c = c_I + t * (c_O - c_I), one rounding per operation, no FMA.  A vertex at d == 0 is inside and never duplicated.
+ *     Carried: x, y, z, w, the colour and (the extended fragment stage) normal and uv.  A polygon of fewer than 3 vertices is
+ *     dropped.
+ *   The polygon P_0 .. P_n-1 (n <= 5) becomes the fan (P_0, P_k, P_k+1), k = 1 .. n-2, in that order (winding kept).  Each
+ *     sub-triangle is then a triangle of the scene in every respect (divide, screen map, truncation or the Metal snap, facing and
+ *     culling, raster, z-test, fragment_shader); it takes the original triangle's place in the draw order, in fan order (painter's
+ *     order: the later sub-triangle wins; the z-test: the earlier one wins an exact tie).
+ *   IDs (SWR_FLAG_PRIMITIVE_IDS): every sub-triangle reports the original number (triangle index p, or draw-list order number).
+ *   Restated: a clip frame is bit for bit the frame without the bit of the scene in which every triangle is replaced by its fan,
+ *     every fan vertex given in NDC (x/w, y/w, z/w) with its interpolated colour and attributes, drawn with the identity transform
+ *     and the same other flags — IDs mapped back to the original numbering.  The identity turns an NDC coordinate of -0 into +0:
+ *     a clip-space z of exactly -0 is drawn with depth +0 under the bit.
+ *   swr_draw, swr_draw_primitives(SWR_PRIMITIVE_TRIANGLE), swr_draw_list, swr_render.  .vertices and .line frames accept the bit
+ *     and ignore it.  swr_timings.triangles counts submitted triangles; tile_pairs the pairs binned, fan triangles included.
+ *   A frame with the bit may have at most SWR_DEPTH_CLIP_MAX_TRIANGLES submitted triangles (more: SWR_ERR_UNSUPPORTED). */
+#define SWR_DEPTH_CLIP_MAX_TRIANGLES (1 << 24)
 
 /* ---- Primitive IDs (SWR_FLAG_PRIMITIVE_IDS) — DESIGN.md §13 --------------------------------------------------------------
  * No ABI bump (SWR_ABI_VERSION stays 6): the presence of the swr_read_ids symbol is the feature test.

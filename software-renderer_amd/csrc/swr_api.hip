@@ -233,6 +233,8 @@ struct swr_context {
         // draw-list frames: the item table (pinned staging -> device, on the frame's own stream, before its binning)
         // and the frame's per-slot colours / attributes / original-index table (k_list_gather)
         DevBuf items, lrgb, lnrm, linv;
+        // depth-clip frames: the frame's clip stream (n + 2F slots) and the pre-pass's tables (swr_clip.hip)
+        DevBuf cxyz, crgb, cnrm, cmap, cbox, csums;
         ListItem* items_host = nullptr;     // pinned; rewritten only after items_copied (its last copy) has completed
         size_t items_cap = 0;
         hipEvent_t items_copied = nullptr;
@@ -334,6 +336,12 @@ struct swr_context {
     bool list_affine = false;
     bool list_identity = false;         // frame slot == stream slot and order number == original index for every item
     bool last_list = false;             // the last frame was a draw list
+    bool last_clip = false;             // the last frame was a depth-clip frame (SWR_FLAG_DEPTH_CLIP) of clip_n submitted triangles
+    int64_t clip_n = 0;
+    int64_t clip_fan = 0;               // fan capacity F: a clip frame of n triangles has n + 2F slots (each crossing triangle adds <= 2)
+    int64_t clip_total = -1;            // the post-clip count of the last clip frame when the host had to know it (else -1)
+    uint32_t* h_clip = nullptr;         // pinned, device-mapped: [PAIR_RING] per frame, the post-clip count of a clip frame whose fans
+    uint32_t* h_clip_dev = nullptr;     // overflowed its slots (0: none); [PAIR_RING] the post-clip count the host asked for
     int64_t list_plan_max = 0;          // largest binning size (work units * 64) of a list since the upload (fixed-bin limits)
     // last draw (for the overflow redo and for swr_render)
     float last_m[16]{};
@@ -710,6 +718,143 @@ void make_list_frame(swr_context* c, int si, DeviceFrame& f) {
     }
 }
 
+// the slots of a clip frame: n + 2F, at most 3n (each triangle gives at most three)
+inline int64_t clip_slots(const swr_context* c) { return std::min<int64_t>(3 * c->clip_n, c->clip_n + 2 * c->clip_fan); }
+
+// ---- depth-clip frames ----------------------------------------------------------------------------------------------
+// The frame over the clip stream of its lane: n + 2F slots (n submitted triangles, of the scene or of the draw list), the identity
+// transform, slot = order number.  The pre-pass (launch_clip_prep) reads the scene's stream with the frame's transform(s) — a draw
+// list's items from the device copy staged for the frame — and the frame itself is binned like a scene of n + 2F primitives.
+void make_clip_frame(swr_context* c, int si, uint64_t frame, DeviceFrame& f) {
+    swr_context::Slot& sl = c->slot[si];
+    ClipPrep& p = f.clip;
+    p.src_xyz = (const float4*)c->tri_xyz.p;
+    p.src_rgb = (const float4*)c->tri_rgb.p;
+    p.src_nrm = c->has_attrs ? (const float4*)c->tri_nrm.p : nullptr;
+    p.src_inv = (const uint32_t*)c->inv.p;
+    p.src_reordered = c->reordered ? 1 : 0;
+    p.n = c->clip_n;
+    p.bound = clip_slots(c);
+    p.over = c->h_clip_dev + (frame % swr_context::PAIR_RING);
+    memcpy(p.m, f.m, sizeof p.m);
+    p.items = c->last_list ? f.items : nullptr;
+    p.nitems = c->last_list ? f.nitems : 0;
+    p.sums = (uint32_t*)sl.csums.p;
+    p.xyz = (float4*)sl.cxyz.p; p.rgb = (float4*)sl.crgb.p;
+    p.nrm = p.src_nrm ? (float4*)sl.cnrm.p : nullptr;
+    p.map = (uint32_t*)sl.cmap.p; p.box = (float4*)sl.cbox.p;
+    // the frame itself: a plain (not a list) frame over the clip stream
+    f.items = nullptr; f.nitems = 0; f.units = 0; f.list_affine = 0;
+    f.gather = {};
+    f.tri_xyz = p.xyz; f.tri_rgb = p.rgb; f.tri_nrm = p.nrm; f.box64 = p.box;
+    f.inv = nullptr; f.reordered = 0;
+    for (int k = 0; k < 16; k++) f.m[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+    f.ntri = p.bound;
+    // order numbers are dense over the post-clip count: below the slot count, or below the count itself when the host needed it
+    f.order_space = c->clip_total >= 0 ? std::max<int64_t>(c->clip_total, 1) : std::max<int64_t>(p.bound, 1);
+    // (32-bit depth keys: the clip frame's zero depths on the near plane are its own; they do not move the scene's state)
+    f.redo_dev = nullptr; f.k32 = 0;
+    const int tiles = tiles_of(c->tg);
+    f.fixed_bins = (c->fixed_mode && f.ntri > 0) ? 1 : 0;
+    if (f.fixed_bins) {
+        f.plan = plan_binning(f.ntri, tiles, false);
+        if (c->synced_upto == c->posted)     // (an idle context: twice the workgroups, as make_frame)
+            f.plan.G = (int)std::max<int64_t>(1, std::min<int64_t>(SWR_TUNE_IDLE_BIN_G, std::max<int64_t>(f.plan.G, (f.ntri + 63) / 64 / 8)));
+    } else {
+        f.plan = plan_binning(f.ntri, tiles, true);     // exact-size bins: the global-atomic chain (its tables need no per-G sizing)
+    }
+}
+
+// A depth-clip frame of n submitted triangles: the lane buffers for n + 2F slots and bins that can take them (every stream idle when
+// anything grows), as swr_draw_list sizes them for a list of n + 2F triangles; the post-clip count first when the PLAIN switch needs it.
+int prepare_clip(swr_context* c, int64_t n, uint32_t flags, const float* m) {
+    if (n > (int64_t)SWR_DEPTH_CLIP_MAX_TRIANGLES)
+        return fail(c, SWR_ERR_UNSUPPORTED, "SWR_FLAG_DEPTH_CLIP: %lld triangles (at most %d)", (long long)n, SWR_DEPTH_CLIP_MAX_TRIANGLES);
+    if (n != c->clip_n || c->clip_fan <= 0) c->clip_fan = std::max<int64_t>(1024, n / 64);   // (grown by check_frames on overflow)
+    c->clip_n = n;
+    int rc;
+    const size_t V = (size_t)std::max<int64_t>(clip_slots(c), 1);
+    const size_t S = (size_t)(n + 255) / 256 + 1;            // the pre-pass's workgroup sums + the total
+    const bool attrs = c->has_attrs && c->tri_nrm.p;
+    auto small = [&](const swr_context::Slot& sl) {
+        return sl.geo.bytes < V * sizeof(GeomRec) || sl.geo_full.bytes < V * sizeof(GeomFull) || sl.ranges.bytes < V * sizeof(uint2) ||
+               sl.cxyz.bytes < V * 48 || sl.crgb.bytes < V * 48 || (attrs && sl.cnrm.bytes < V * 48) || sl.cmap.bytes < V * 4 ||
+               sl.cbox.bytes < (V + 63) / 64 * 32 || sl.csums.bytes < S * 4;
+    };
+    bool grow = false;
+    for (auto& sl : c->slot) grow = grow || small(sl);
+    if (grow) {
+        if ((rc = sync_streams(c))) return rc;
+        for (auto& sl : c->slot) {
+            if ((rc = ensure(c, sl.geo, V * sizeof(GeomRec)))) return rc;
+            if ((rc = ensure(c, sl.geo_full, V * sizeof(GeomFull)))) return rc;
+            if ((rc = ensure(c, sl.ranges, V * sizeof(uint2)))) return rc;
+            if ((rc = ensure(c, sl.cxyz, V * 48))) return rc;
+            if ((rc = ensure(c, sl.crgb, V * 48))) return rc;
+            if (attrs && (rc = ensure(c, sl.cnrm, V * 48))) return rc;
+            if ((rc = ensure(c, sl.cmap, V * 4))) return rc;
+            if ((rc = ensure(c, sl.cbox, (V + 63) / 64 * 32))) return rc;
+            if ((rc = ensure(c, sl.csums, S * 4))) return rc;
+        }
+    }
+    const int64_t tris = (int64_t)V, plan = ((int64_t)V + 63) / 64 * 64;
+    const int tiles = tiles_of(c->tg);
+    if (c->fixed_mode && n > 0) {
+        const uint32_t cmax = fixed_cap_max(plan, tiles);
+        if (cmax < c->cap_tile) {
+            if ((rc = sync_streams(c))) return rc;
+            c->fixed_mode = false;
+            c->fixed_allowed = false;
+        } else {
+            uint64_t want = std::max<uint64_t>(std::max<uint64_t>(64, (uint64_t)(6 * tris / tiles)), (uint64_t)std::min<int64_t>(tris, 1024));
+            want = std::min<uint64_t>((want + 63) & ~63ull, fixed_cap_max(std::max<int64_t>(c->ni / 3, plan), tiles));
+            if (want > c->cap_tile) {
+                if ((rc = sync_streams(c))) return rc;
+                if ((rc = ensure_bins(c, (size_t)tiles * want))) return rc;
+                c->cap_tile = (uint32_t)want;
+            }
+        }
+    }
+    if (!c->fixed_mode && n > 0) {
+        const uint32_t want = (uint32_t)std::min<uint64_t>((uint64_t)tris * 2 + 65536, 0xFFFFFFF0ull);
+        if (want > c->capacity) {
+            if ((rc = sync_streams(c))) return rc;
+            if ((rc = ensure_capacity(c, want))) return rc;
+        }
+    }
+    // (the fixed-bin limits of check_frames and of later lists cover the clip frame's binning size too)
+    c->list_plan_max = std::max<int64_t>(c->list_plan_max, plan);
+    // The PLAIN / winner-table switch of the raster is judged on the post-clip count.  Below the threshold with all n + 2F slots
+    // it needs nothing; otherwise the host counts first (every stream idle, the count kernels alone, one wait): a scene of about
+    // 2^20 triangles or more, and only when its slot count reaches the threshold.
+    c->clip_total = -1;
+    const int64_t thr = ((int64_t)1 << 20) + ((flags & SWR_FLAG_LOAD) ? 0 : 1);
+    if (n > 0 && (int64_t)V >= thr) {
+        if ((rc = sync_streams(c))) return rc;
+        DeviceFrame f{};
+        f.vertices = (const swr_vertex*)c->vertices.p;
+        f.tri_xyz = (const float4*)c->tri_xyz.p;
+        f.tri_rgb = (const float4*)c->tri_rgb.p;
+        f.tri_nrm = (const float4*)c->tri_nrm.p;
+        f.inv = (const uint32_t*)c->inv.p;
+        f.reordered = c->reordered ? 1 : 0;
+        f.tg = c->tg;
+        memcpy(f.m, m ? m : c->last_m, sizeof f.m);
+        if (!m) {
+            // a draw list: its items reach the device with the frame (stage_list), so its count is not known here: the bound holds
+        } else {
+            make_clip_frame(c, 0, c->frame_no, f);
+            f.clip.count_only = 1;
+            launch_bin(f, c->stream, nullptr);
+            const int64_t nb = (n + 255) / 256;
+            HIP_TRY(c, hipMemcpyAsync(&c->h_clip[swr_context::PAIR_RING], f.clip.sums + nb, 4, hipMemcpyDeviceToHost, c->stream));
+            if ((rc = wait_stream(c, c->stream, "the depth-clip count"))) return sticky(c) ? sticky(c) : rc;
+            c->clip_total = (int64_t)c->h_clip[swr_context::PAIR_RING];
+        }
+    }
+    return SWR_OK;
+}
+
 // What the binning share of a draw-list frame enqueues in front of its binning, on the frame's stream (captured by value: in the
 // two-stream pipeline a helper thread enqueues it later).
 struct ListPrep {
@@ -846,6 +991,8 @@ int enqueue_frame(swr_context* c) {
         const int rc = stage_list(c, si, frame, lp);
         if (rc) { c->frame_no = frame; return rc; }
     }
+    c->h_clip[frame % swr_context::PAIR_RING] = 0u;
+    if (c->last_clip) make_clip_frame(c, si, frame, f);
     hipEvent_t* ev = nullptr;
     if (c->timing >= 2 || (c->timing == 1 && (c->frame_no % (uint64_t)c->timing_every) == 0)) {
         if (c->seq - c->harvested >= (uint64_t)swr_context::RING) {   // ring full: drain it
@@ -1435,7 +1582,8 @@ int check_draw_args(swr_context* c, uint32_t flags, int32_t primitive_type) {
         primitive_type != SWR_PRIMITIVE_VERTICES)
         return fail(c, SWR_ERR_UNSUPPORTED, "unknown primitive type %d", primitive_type);
     if (flags & ~(uint32_t)(SWR_FLAG_DEPTH_TEST | SWR_FLAG_NO_COLOR | SWR_FLAG_METAL_RULES | SWR_FLAG_REAL_LINES | SWR_FLAG_LOAD |
-                            SWR_FLAG_PRIMITIVE_IDS | SWR_FLAG_CULL_BACK | SWR_FLAG_CULL_FRONT | SWR_FLAG_FRONT_CCW))
+                            SWR_FLAG_PRIMITIVE_IDS | SWR_FLAG_CULL_BACK | SWR_FLAG_CULL_FRONT | SWR_FLAG_FRONT_CCW |
+                            SWR_FLAG_DEPTH_CLIP))
         return fail(c, SWR_ERR_BAD_ARG, "unknown flag bits 0x%x", flags);
     if ((flags & SWR_FLAG_REAL_LINES) && primitive_type != SWR_PRIMITIVE_LINE)
         return fail(c, SWR_ERR_BAD_ARG, "SWR_FLAG_REAL_LINES only applies to .line primitives");
@@ -1480,6 +1628,9 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
         if ((rc = check_frames(c))) return rc;
     }
     if ((rc = ensure_ids(c, flags))) return rc;
+    // depth clipping: triangles only (.vertices and .line frames accept the bit and ignore it)
+    if (primitive_type != SWR_PRIMITIVE_TRIANGLE) flags &= ~(uint32_t)SWR_FLAG_DEPTH_CLIP;
+    if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, c->ni / 3, flags, transform))) return rc;
     memcpy(c->last_m, transform, sizeof c->last_m);
     if (flags & SWR_FLAG_LOAD) {
         if (c->src_clear) {
@@ -1495,6 +1646,7 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
     c->ids_valid = (flags & SWR_FLAG_PRIMITIVE_IDS) != 0;
     c->last_prim = primitive_type;
     c->last_list = false;
+    c->last_clip = (flags & SWR_FLAG_DEPTH_CLIP) != 0;
     return enqueue_frame(c);
 }
 
@@ -1657,6 +1809,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
         }
     }
     c->list_plan_max = std::max<int64_t>(c->list_plan_max, units * 64);
+    if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, tris, flags, nullptr))) return rc;
     c->list.swap(list);
     c->list_tris = tris;
     c->list_units = units;
@@ -1675,6 +1828,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
     c->ids_valid = (flags & SWR_FLAG_PRIMITIVE_IDS) != 0;
     c->last_prim = SWR_PRIMITIVE_TRIANGLE;
     c->last_list = true;
+    c->last_clip = (flags & SWR_FLAG_DEPTH_CLIP) != 0;
     return enqueue_frame(c);
 }
 
@@ -1738,6 +1892,8 @@ int check_frames(swr_context* c) {
     // entries of the fullest tile region
     auto used = [&](uint64_t f) { return c->fixed_mode ? fill_word(c, f) : pair_word(c, f); };
     auto limit = [&]() { return c->fixed_mode ? c->cap_tile : c->capacity; };
+    // a depth-clip frame whose fan triangles overflowed its slots was rastered empty too: its word holds the post-clip count
+    auto clip_over = [&](uint64_t f) { return (uint64_t)c->h_clip[f % swr_context::PAIR_RING]; };
     for (int attempt = 0; attempt < 8; attempt++) {
         int rc;
         if ((rc = sync_streams(c))) return rc;
@@ -1747,12 +1903,14 @@ int check_frames(swr_context* c) {
         uint32_t need = pairs;
         uint32_t total_pairs = pair_word(c, L);               // (for the switch to exact bins)
         bool bad_prev = c->src_bad;                            // the image of frame f - 1 is wrong
+        uint64_t clip_need = clip_over(L);
         for (uint64_t f = c->frames_checked; f < L; f++) {
             const uint32_t pf = used(f);
             if (pf > limit()) { need = std::max(need, pf); total_pairs = std::max(total_pairs, pair_word(c, f)); }
+            clip_need = std::max(clip_need, clip_over(f));
             // an earlier frame that overflowed was rastered empty — and a load frame built on such an image is as wrong: that matters
             // only if it was copied to the host
-            const bool bad = pf > limit() || (c->frame_load[f % swr_context::PAIR_RING] && bad_prev);
+            const bool bad = pf > limit() || clip_over(f) != 0 || (c->frame_load[f % swr_context::PAIR_RING] && bad_prev);
             if (bad && c->frame_presented[f % swr_context::PAIR_RING]) {
                 if (!dropped || pf > dropped_pairs) { dropped_frame = f; dropped_pairs = pf; }
                 dropped = true;
@@ -1784,6 +1942,13 @@ int check_frames(swr_context* c) {
                 if ((rc = ensure_capacity(c, (uint32_t)want))) return rc;
             }
         }
+        if (clip_need) {
+            // more crossing triangles than the fan capacity: grow it (every stream is idle), the redraw below takes the new slots
+            if ((rc = sync_copies(c))) return rc;
+            const int64_t extra = (int64_t)clip_need - c->clip_n;
+            c->clip_fan = std::max<int64_t>(2 * c->clip_fan, (extra + 1) / 2 + extra / 8 + 64);
+            if (c->last_clip && (rc = prepare_clip(c, c->clip_n, c->last_flags, nullptr))) return rc;
+        }
         if (c->frame_load[L % swr_context::PAIR_RING] && c->src_bad) {
             // the last frame loaded a wrong image: a redraw cannot repair it — reported (whether it was copied or not: it is what the
             // next load frame, swr_present or swr_read_* would see), and so is every load frame built on it until an image is replaced
@@ -1795,7 +1960,7 @@ int check_frames(swr_context* c) {
                         "(the bins have been grown) — redraw the chain from a clear frame, swr_target_set or swr_target_write",
                         (unsigned long long)L);
         }
-        if (pairs <= old_limit) {
+        if (pairs <= old_limit && !clip_over(L)) {
             c->draw_pending = false;
             c->src_bad = false;
             c->present_pending = false;        // the last frame is verified: a later repair must not copy into a stale destination
@@ -1806,6 +1971,7 @@ int check_frames(swr_context* c) {
             return finish();
         }
         // the last frame overflowed: redraw it into the same framebuffer, copy it again
+        c->h_clip[L % swr_context::PAIR_RING] = 0u;          // (its fan overflow is repaired by the redraw)
         const bool was_presented = c->present_pending && c->frame_presented[L % swr_context::PAIR_RING];
         c->fb_cur = c->fb_last;
         if ((rc = enqueue_frame(c))) return rc;
@@ -1922,7 +2088,8 @@ void destroy_single(swr_context* c) {
     for (hipEvent_t e : c->pace_ev) if (e) hipEventDestroy(e);
     for (auto& sl : c->slot) {
         DevBuf* sb[] = {&sl.geo, &sl.geo_full, &sl.ranges, &sl.bins, &sl.bin_matrix, &sl.live, &sl.tilebuf, &sl.biglist,
-                        &sl.items, &sl.lrgb, &sl.lnrm, &sl.linv};
+                        &sl.items, &sl.lrgb, &sl.lnrm, &sl.linv, &sl.cxyz, &sl.crgb, &sl.cnrm, &sl.cmap, &sl.cbox,
+                        &sl.csums};
         for (DevBuf* b : sb) if (b->p) hipFree(b->p);
         if (sl.items_host) hipHostFree(sl.items_host);
         if (sl.items_copied) hipEventDestroy(sl.items_copied);
@@ -1945,6 +2112,7 @@ void destroy_single(swr_context* c) {
     if (c->bin_stream_own) hipStreamDestroy(c->bin_stream_own);
     if (c->h_pairs) hipHostFree(c->h_pairs);
     if (c->h_misc) hipHostFree(c->h_misc);
+    if (c->h_clip) hipHostFree(c->h_clip);
     if (c->ev_ok)
         for (int r = 0; r < swr_context::RING; r++)
             for (int i = 0; i < 5; i++) hipEventDestroy(c->ev[r][i]);
@@ -1969,7 +2137,9 @@ int create_single(int dev, swr_context** out, int helpers, uint32_t wait_budget_
         (e = hipStreamCreateWithFlags(&c->copy_stream[1], hipStreamNonBlocking)) != hipSuccess ||
         (e = hipHostMalloc((void**)&c->h_pairs, (2 * swr_context::PAIR_RING + 2) * 4, hipHostMallocMapped)) != hipSuccess ||
         (e = hipHostGetDevicePointer((void**)&c->h_pairs_dev, c->h_pairs, 0)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&c->h_misc, CNT_WORDS * 4, hipHostMallocDefault)) != hipSuccess) {
+        (e = hipHostMalloc((void**)&c->h_misc, CNT_WORDS * 4, hipHostMallocDefault)) != hipSuccess ||
+        (e = hipHostMalloc((void**)&c->h_clip, (swr_context::PAIR_RING + 1) * 4, hipHostMallocMapped)) != hipSuccess ||
+        (e = hipHostGetDevicePointer((void**)&c->h_clip_dev, c->h_clip, 0)) != hipSuccess) {
         int rc = fail(nullptr, SWR_ERR_HIP, "context init on device %d failed: %s", dev, hipGetErrorString(e));
         destroy_single(c);
         return rc;
@@ -1977,6 +2147,7 @@ int create_single(int dev, swr_context** out, int helpers, uint32_t wait_budget_
     memset(c->h_pairs, 0, (2 * swr_context::PAIR_RING + 2) * 4);
     c->h_pairs[swr_context::PAIR_RING] = 0xFFFFFFFFu;     // fullest bin: unknown
     memset(c->h_misc, 0, CNT_WORDS * 4);
+    memset(c->h_clip, 0, (swr_context::PAIR_RING + 1) * 4);
     {
         // SWR_PIPELINE=0: binning and raster share one stream (no overlap of consecutive frames)
         const char* pl = getenv("SWR_PIPELINE");

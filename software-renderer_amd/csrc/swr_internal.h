@@ -64,6 +64,28 @@ static_assert(sizeof(ListItem) == 80, "ListItem must be 80 bytes");
 constexpr int LIST_ITEM_BITS = 12;  // k_bin<.., LIST> packs (item, group of the item) into 32 bits: item < SWR_DRAW_LIST_MAX = 2^12
 static_assert(SWR_DRAW_LIST_MAX <= (1 << LIST_ITEM_BITS), "item ids must fit the packed work unit");
 
+// Depth clipping (SWR_FLAG_DEPTH_CLIP, swr_clip.hip): the per-frame pre-pass that turns the submitted triangles (n of them: the
+// scene's, or a draw list's order numbers) into the frame's own stream of 3n slots — the post-clip triangles in NDC, slot = order
+// number, the rest marked invalid — which the frame then bins and rasters with the identity transform.
+struct ClipPrep {
+    const float4* src_xyz;         // the scene's triangle stream (DeviceFrame::tri_xyz / tri_rgb / tri_nrm / inv / reordered)
+    const float4* src_rgb;
+    const float4* src_nrm;         // NULL: the scene has no attributes
+    const uint32_t* src_inv;
+    int32_t src_reordered;
+    int64_t n;                     // submitted triangles
+    int64_t bound;                 // frame slots: n + 2 x the fan capacity, at most 3n (0: not a clip frame)
+    float m[16];                   // swr_draw's transform (draw lists: the items' own)
+    const ListItem* items;         // draw lists: the frame's items on the device (else NULL)
+    int32_t nitems;
+    uint32_t* sums;                // [ceil(n / 256) + 1] fan triangles per pre-pass workgroup -> their exclusive offsets + the total
+    float4* xyz; float4* rgb; float4* nrm;   // [3 * bound] the frame's stream (nrm NULL without attributes)
+    uint32_t* map;                 // [bound] order number -> original number (the ID image)
+    float4* box;                   // [2 * ceil(bound / 64)] box of every 64-slot group
+    uint32_t* over;                // device-visible pinned word of the frame: the post-clip count if it exceeded `bound`, else 0
+    int32_t count_only;            // launch_bin: only the count and its scan (sums[ceil(n / 256)] = the post-clip count), no frame
+};
+
 // Geometry of the LDS binning path (see plan_binning in swr_kernels.hip).
 struct BinPlan {
     bool use_lds;
@@ -137,6 +159,10 @@ struct DeviceFrame {
     int32_t list_affine;           // every item's transform has the last row (0, 0, 0, 1): k_bin<.., AFF, LIST>
     // inv_out != NULL: the binning launch first gathers the frame's own per-slot tables (k_list_gather) from the scene's
     struct { const float4* rgb; const float4* nrm; float4* rgb_out; float4* nrm_out; uint32_t* inv_out; } gather;
+    // depth-clip frames (SWR_FLAG_DEPTH_CLIP): clip.bound > 0; ntri = clip.bound, tri_xyz / tri_rgb / tri_nrm / box64 = the clip
+    // stream, m = identity, not reordered, not a list (a clipped draw list is a plain frame over its clip stream)
+    ClipPrep clip;
+    int64_t order_space;           // > 0: the frame's order numbers lie below this (the PLAIN / winner-table switch); 0: ntri
 };
 
 void launch_validate_indices(const int64_t* indices, int64_t count, int64_t vertex_count,
@@ -170,5 +196,10 @@ bool launch_sort_bins(const DeviceFrame& f, hipStream_t s, hipEvent_t stop = nul
 bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop = nullptr);
 bool frame_uses_k32(const DeviceFrame& f);   // the frame's raster is k_raster_depth (32-bit depth keys, sorts its bins itself)
 void launch_points_or_lines(const DeviceFrame& f, int primitive_type, hipStream_t s);
+
+// swr_clip.hip: the clip pre-pass in front of a clip frame's binning (launch_bin / launch_setup_bin start with it) and the ID map
+// behind its raster (launch_raster ends with it, carrying `stop`)
+void launch_clip_prep(const DeviceFrame& f, hipStream_t s);
+bool launch_clip_ids(const DeviceFrame& f, hipStream_t s, hipEvent_t stop);
 
 }  // namespace swr

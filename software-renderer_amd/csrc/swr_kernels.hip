@@ -3028,6 +3028,7 @@ static bool bin_h16(int per) { return SWR_TUNE_HIST16 && (int64_t)per * 64 < 655
 static void launch_list_gather(const DeviceFrame& f, hipStream_t s);
 void launch_setup_bin(const DeviceFrame& f, hipStream_t s) {
     if (f.ntri <= 0) return;
+    launch_clip_prep(f, s);
     launch_list_gather(f, s);
     const SetupArgs a = make_setup_args(f);
     const int ntiles = f.tg.tiles_x * f.tg.tiles_y;
@@ -3072,6 +3073,8 @@ uint32_t fixed_cap_max(int64_t ntri, int ntiles) {
 }
 
 bool launch_bin(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
+    launch_clip_prep(f, s);
+    if (f.clip.count_only) return false;       // (swr_api.hip: the post-clip count of a frame, ahead of it)
     launch_list_gather(f, s);
     BinArgs b;
     b.a = make_setup_args(f);
@@ -3177,7 +3180,8 @@ static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop
     a.src_depth = LOAD ? f.src_depth : nullptr;
     a.ids = IDS ? f.ids : nullptr;
     // (a load frame's z-tested keys carry the packed word + 1: the last primitive of a scene of exactly 2^20 would wrap)
-    a.pack_local = f.ntri < (1ll << WTAB_PRIM_BITS) + (LOAD ? 0 : 1) ? 1 : 0;
+    // (depth-clip frames: their order numbers lie below the post-clip count, or a bound of it, not below their slot count)
+    a.pack_local = (f.order_space > 0 ? f.order_space : f.ntri) < (1ll << WTAB_PRIM_BITS) + (LOAD ? 0 : 1) ? 1 : 0;
     const bool plain = !a.pack_local;      // more than 2^20 primitives: the colour kernels without the winner table
     const unsigned ntiles = (unsigned)(f.tg.tiles_x * f.tg.tiles_y);
     if (ntiles == 0) return false;
@@ -3237,6 +3241,11 @@ static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop
 
 bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     const bool load = (f.flags & SWR_FLAG_LOAD) != 0;
+    // a depth-clip frame's IDs are order numbers of its clip stream: mapped to the original numbers behind the raster
+    if (f.clip.bound > 0 && f.ids && f.tg.tiles_x * f.tg.tiles_y > 0) {
+        if (f.flags & SWR_FLAG_PRIMITIVE_IDS) load ? launch_raster_t<true, true>(f, s, nullptr) : launch_raster_t<false, true>(f, s, nullptr);
+        return launch_clip_ids(f, s, stop);
+    }
     if (f.flags & SWR_FLAG_PRIMITIVE_IDS) return load ? launch_raster_t<true, true>(f, s, stop) : launch_raster_t<false, true>(f, s, stop);
     return load ? launch_raster_t<true, false>(f, s, stop) : launch_raster_t<false, false>(f, s, stop);
 }
