@@ -240,14 +240,23 @@ def cull_flags(cull: str = "none", front_ccw: bool = False) -> int:
     return {"none": 0, "back": b.FLAG_CULL_BACK, "front": b.FLAG_CULL_FRONT}[cull] | (b.FLAG_FRONT_CCW if front_ccw else 0)
 
 
+def view_flags(clip: bool = False, perspective: bool = False) -> int:
+    """Depth clipping (Metal's MTLDepthClipMode.clip: a camera may move into the scene) and perspective-correct interpolation of
+    colour and varyings (Metal's [[center_perspective]]): both off by default, as in the reference."""
+    b = swr_amd.binding
+    return (b.FLAG_DEPTH_CLIP if clip else 0) | (b.FLAG_PERSPECTIVE if perspective else 0)
+
+
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
-        time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False):
+        time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False,
+        clip: bool = False, perspective: bool = False):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
     mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
     frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel.
-    cull / front_ccw: face culling (cull_flags)."""
+    cull / front_ccw: face culling (cull_flags); clip / perspective: view_flags."""
     vertices, indices = load_mesh(obj) if obj else sphere_mesh()
     flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | (swr_amd.binding.FLAG_PRIMITIVE_IDS if pick else 0) | cull_flags(cull, front_ccw)
+    flags |= view_flags(clip, perspective)
     results = []
     with swr_amd.Context() as ctx:
         ctx.scene_upload(vertices, indices)            # RenderPass.vertices / .indices, App.swift:163
@@ -281,14 +290,15 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
 
 
 def run_streamed(frames: int, size: int, obj: str | None = None, depth_test: bool = False, time0: float = 0.0,
-                 device_count: int = 1, on_frame=None, cull: str = "none", front_ccw: bool = False):
+                 device_count: int = 1, on_frame=None, cull: str = "none", front_ccw: bool = False, clip: bool = False,
+                 perspective: bool = False):
     """The same loop the way a host that wants every frame should drive it: two page-locked
     image sets alternate; frame k is being copied to the host (swr_present, asynchronous, every band of a multi-GPU
     context into its rows of the ONE image) while frame k+1 is drawn; the host touches frame k only after
     swr_present_wait.  `on_frame(k, colour, depth)` sees the host images (valid until the next but one present).
     Returns the frames (copies)."""
     vertices, indices = load_mesh(obj) if obj else sphere_mesh()
-    flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | cull_flags(cull, front_ccw)
+    flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | cull_flags(cull, front_ccw) | view_flags(clip, perspective)
     sets = [(swr_amd.HostImage((size, size, 4), np.uint8), swr_amd.HostImage((size, size), np.float32)) for _ in range(2)]
     results = []
 
@@ -331,13 +341,16 @@ if __name__ == "__main__":
     ap.add_argument("--pick", default=None, help="X,Y: print the copy and the triangle under that pixel every frame (primitive IDs)")
     ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
     ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
+    ap.add_argument("--clip", action="store_true", help="depth clipping: triangles clipped against the near and far planes")
+    ap.add_argument("--perspective", action="store_true", help="perspective-correct interpolation of colour and varyings")
     a = ap.parse_args()
     if a.stream:
-        res = run_streamed(a.frames, a.size, a.ply or a.obj, a.depth_test, device_count=a.gpus, cull=a.cull, front_ccw=a.front_ccw)
+        res = run_streamed(a.frames, a.size, a.ply or a.obj, a.depth_test, device_count=a.gpus, cull=a.cull, front_ccw=a.front_ccw,
+                           clip=a.clip, perspective=a.perspective)
         print(f"{a.frames} frames streamed, coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
     pick = tuple(int(t) for t in a.pick.split(",")) if a.pick else None
     _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick, cull=a.cull,
-                      front_ccw=a.front_ccw)
+                      front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

@@ -84,8 +84,10 @@ enum {
     SWR_FLAG_CULL_FRONT = 1u << 7, /* front-facing triangles are not drawn; with SWR_FLAG_CULL_BACK every triangle with a facing is dropped */
     SWR_FLAG_FRONT_CCW = 1u << 8,  /* front = counter-clockwise as displayed (Metal's setFrontFacingWinding(.counterClockwise));
                                       without it front = clockwise as displayed (MTLWindingClockwise, Metal's default) */
-    SWR_FLAG_DEPTH_CLIP = 1u << 10 /* clip every triangle against the near (z >= 0) and far (z <= w) planes before the divide, like
+    SWR_FLAG_DEPTH_CLIP = 1u << 10, /* clip every triangle against the near (z >= 0) and far (z <= w) planes before the divide, like
                                       Metal's default MTLDepthClipMode.clip (see "Depth clipping") */
+    SWR_FLAG_PERSPECTIVE = 1u << 11 /* interpolate colour and varyings with perspective correction, like Metal's [[center_perspective]]
+                                      and GL's smooth (see "Perspective-correct interpolation") */
 };
 
 /* ---- Face culling (SWR_FLAG_CULL_BACK / _CULL_FRONT / _FRONT_CCW) — DESIGN.md §14 ------------------------------------------
@@ -133,6 +135,26 @@ enum {
  *     and ignore it.  swr_timings.triangles counts submitted triangles; tile_pairs the pairs binned, fan triangles included.
  *   A frame with the bit may have at most SWR_DEPTH_CLIP_MAX_TRIANGLES submitted triangles (more: SWR_ERR_UNSUPPORTED). */
 #define SWR_DEPTH_CLIP_MAX_TRIANGLES (1 << 24)
+
+/* ---- Perspective-correct interpolation (SWR_FLAG_PERSPECTIVE) — DESIGN.md §16 ----------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6): a library that accepts the bit has the feature; an older one refuses it with
+ * SWR_ERR_BAD_ARG.  Without the bit nothing changes.  With it only the weights colour and the varyings (the extended stage's normal
+ * and uv) are interpolated with change: coverage, depth, the z-test, tie rules and IDs are bit for bit those of the frame without it.
+ *   For a triangle with corners a, b, c in index order, rw_a, rw_b, rw_c is the clip-space w of each corner, as vertex_shader computes
+ *     it in setup: the frame's transform (swr_draw, swr_draw_primitives(SWR_PRIMITIVE_TRIANGLE), swr_render); the item's own
+ *     (swr_draw_list); under SWR_FLAG_DEPTH_CLIP the clipper's w of the fan vertex (an original vertex keeps its own, an intersection
+ *     gets w_I + t * (w_O - w_I)).
+ *   rw_a == rw_b == rw_c (float ==): the screen weights unchanged — the frame is bit for bit the frame without the bit.  This holds for
+ *     every affine transform (w is exactly 1).
+ *   Otherwise, once per triangle q_k = 1 / rw_k; per pixel, with the rule set's own screen weights (w0, w1, w2) (the
+ *     divider formula under SWR_FLAG_METAL_RULES): u0 = w0 * q_a, u1 = w1 * q_b, u2 = w2 * q_c, s = (u0 + u1) + u2, rs = 1 / s,
+ *     p0 = u0 * rs, p1 = u1 * rs, p2 = u2 * rs — IEEE binary32, one rounding per operation, no FMA, both divisions correctly
+ *     rounded.  Colour, normal and uv are interpolated with (p0, p1, p2) in each rule set's expression order; the depth stays
+ *     za*w0 + zb*w1 + zc*w2 (screen-linear, as in Metal and GL).
+ *   No special cases: negative w, s == 0 and NaN weights follow IEEE arithmetic (the colour clamp maps NaN to 0); a corner with
+ *     rw == 0 has non-finite screen coordinates and its triangle is skipped.
+ *   SWR_FLAG_NO_COLOR, .vertices and .line frames accept the bit; it has no effect on them.  It combines with every other flag,
+ *     multi-band contexts, draw lists and swr_render. */
 
 /* ---- Primitive IDs (SWR_FLAG_PRIMITIVE_IDS) — DESIGN.md §13 --------------------------------------------------------------
  * No ABI bump (SWR_ABI_VERSION stays 6): the presence of the swr_read_ids symbol is the feature test.

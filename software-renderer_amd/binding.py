@@ -21,6 +21,7 @@ FLAG_CULL_BACK = 64      # face culling: back-facing triangles are not drawn (in
 FLAG_CULL_FRONT = 128    # front-facing triangles are not drawn (with FLAG_CULL_BACK: every triangle with a facing)
 FLAG_FRONT_CCW = 256     # front = counter-clockwise as displayed; without it clockwise (Metal's default winding)
 FLAG_DEPTH_CLIP = 1024   # depth clipping: triangles clipped against the near (z >= 0) and far (z <= w) planes (include/swr.h "Depth clipping")
+FLAG_PERSPECTIVE = 2048  # perspective-correct interpolation of colour and varyings (include/swr.h "Perspective-correct interpolation")
 ID_NONE = 0xFFFFFFFF     # SWR_ID_NONE: a pixel where the frame keeps no fragment
 
 # every symbol include/swr.h declares (checked by tests/test_abi.py)

@@ -235,6 +235,8 @@ struct swr_context {
         DevBuf items, lrgb, lnrm, linv;
         // depth-clip frames: the frame's clip stream (n + 2F slots) and the pre-pass's tables (swr_clip.hip)
         DevBuf cxyz, crgb, cnrm, cmap, cbox, csums;
+        // perspective frames: the frame's per-slot (q_a, q_b, q_c, bypass) table (k_persp_fill / k_clip_emit)
+        DevBuf pq;
         ListItem* items_host = nullptr;     // pinned; rewritten only after items_copied (its last copy) has completed
         size_t items_cap = 0;
         hipEvent_t items_copied = nullptr;
@@ -338,6 +340,8 @@ struct swr_context {
     bool last_list = false;             // the last frame was a draw list
     bool last_clip = false;             // the last frame was a depth-clip frame (SWR_FLAG_DEPTH_CLIP) of clip_n submitted triangles
     int64_t clip_n = 0;
+    bool last_persp = false;            // the last frame interpolates colour with perspective correction (SWR_FLAG_PERSPECTIVE, a colour
+                                        // frame of triangles through a non-affine transform): its slot's pq table is filled and read
     int64_t clip_fan = 0;               // fan capacity F: a clip frame of n triangles has n + 2F slots (each crossing triangle adds <= 2)
     int64_t clip_total = -1;            // the post-clip count of the last clip frame when the host had to know it (else -1)
     uint32_t* h_clip = nullptr;         // pinned, device-mapped: [PAIR_RING] per frame, the post-clip count of a clip frame whose fans
@@ -681,6 +685,7 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
     f.tg = c->tg;
     memcpy(f.m, m, sizeof f.m);
     f.flags = flags;
+    f.pq = c->last_persp ? (float4*)sl.pq.p : nullptr;
     return f;
 }
 
@@ -743,6 +748,7 @@ void make_clip_frame(swr_context* c, int si, uint64_t frame, DeviceFrame& f) {
     p.xyz = (float4*)sl.cxyz.p; p.rgb = (float4*)sl.crgb.p;
     p.nrm = p.src_nrm ? (float4*)sl.cnrm.p : nullptr;
     p.map = (uint32_t*)sl.cmap.p; p.box = (float4*)sl.cbox.p;
+    p.pq = f.pq;                        // (k_clip_emit fills the perspective table of the clip stream's slots)
     // the frame itself: a plain (not a list) frame over the clip stream
     f.items = nullptr; f.nitems = 0; f.units = 0; f.list_affine = 0;
     f.gather = {};
@@ -763,6 +769,27 @@ void make_clip_frame(swr_context* c, int si, uint64_t frame, DeviceFrame& f) {
     } else {
         f.plan = plan_binning(f.ntri, tiles, true);     // exact-size bins: the global-atomic chain (its tables need no per-G sizing)
     }
+}
+
+// ---- perspective-correct interpolation ----------------------------------------------------------------------------
+// Does a frame with these flags read a perspective table?  SWR_FLAG_PERSPECTIVE on a colour frame of triangles whose transform (every
+// item's, for a draw list) is not affine: under an affine map every w is exactly 1, and the screen weights are what the flag gives.
+inline bool persp_frame(uint32_t flags, int32_t primitive_type, bool affine) {
+    return (flags & SWR_FLAG_PERSPECTIVE) && !(flags & SWR_FLAG_NO_COLOR) && primitive_type == SWR_PRIMITIVE_TRIANGLE && !affine;
+}
+inline bool affine_transform(const float m[16]) { return m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f; }
+
+// Every lane's perspective table for a frame of `slots` slots (grown with every stream idle).
+int ensure_persp(swr_context* c, int64_t slots) {
+    const size_t bytes = (size_t)std::max<int64_t>(slots, 1) * 16;
+    bool grow = false;
+    for (auto& sl : c->slot) grow = grow || sl.pq.bytes < bytes;
+    if (!grow) return SWR_OK;
+    int rc = sync_streams(c);
+    if (rc) return rc;
+    for (auto& sl : c->slot)
+        if ((rc = ensure(c, sl.pq, bytes))) return rc;
+    return SWR_OK;
 }
 
 // A depth-clip frame of n submitted triangles: the lane buffers for n + 2F slots and bins that can take them (every stream idle when
@@ -1583,7 +1610,7 @@ int check_draw_args(swr_context* c, uint32_t flags, int32_t primitive_type) {
         return fail(c, SWR_ERR_UNSUPPORTED, "unknown primitive type %d", primitive_type);
     if (flags & ~(uint32_t)(SWR_FLAG_DEPTH_TEST | SWR_FLAG_NO_COLOR | SWR_FLAG_METAL_RULES | SWR_FLAG_REAL_LINES | SWR_FLAG_LOAD |
                             SWR_FLAG_PRIMITIVE_IDS | SWR_FLAG_CULL_BACK | SWR_FLAG_CULL_FRONT | SWR_FLAG_FRONT_CCW |
-                            SWR_FLAG_DEPTH_CLIP))
+                            SWR_FLAG_DEPTH_CLIP | SWR_FLAG_PERSPECTIVE))
         return fail(c, SWR_ERR_BAD_ARG, "unknown flag bits 0x%x", flags);
     if ((flags & SWR_FLAG_REAL_LINES) && primitive_type != SWR_PRIMITIVE_LINE)
         return fail(c, SWR_ERR_BAD_ARG, "SWR_FLAG_REAL_LINES only applies to .line primitives");
@@ -1631,6 +1658,8 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
     // depth clipping: triangles only (.vertices and .line frames accept the bit and ignore it)
     if (primitive_type != SWR_PRIMITIVE_TRIANGLE) flags &= ~(uint32_t)SWR_FLAG_DEPTH_CLIP;
     if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, c->ni / 3, flags, transform))) return rc;
+    const bool persp = persp_frame(flags, primitive_type, affine_transform(transform));
+    if (persp && (rc = ensure_persp(c, (flags & SWR_FLAG_DEPTH_CLIP) ? clip_slots(c) : c->ni / 3))) return rc;
     memcpy(c->last_m, transform, sizeof c->last_m);
     if (flags & SWR_FLAG_LOAD) {
         if (c->src_clear) {
@@ -1647,6 +1676,7 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
     c->last_prim = primitive_type;
     c->last_list = false;
     c->last_clip = (flags & SWR_FLAG_DEPTH_CLIP) != 0;
+    c->last_persp = persp;
     return enqueue_frame(c);
 }
 
@@ -1810,6 +1840,8 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
     }
     c->list_plan_max = std::max<int64_t>(c->list_plan_max, units * 64);
     if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, tris, flags, nullptr))) return rc;
+    const bool persp = persp_frame(flags, SWR_PRIMITIVE_TRIANGLE, affine);
+    if (persp && (rc = ensure_persp(c, (flags & SWR_FLAG_DEPTH_CLIP) ? clip_slots(c) : tris))) return rc;
     c->list.swap(list);
     c->list_tris = tris;
     c->list_units = units;
@@ -1829,6 +1861,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
     c->last_prim = SWR_PRIMITIVE_TRIANGLE;
     c->last_list = true;
     c->last_clip = (flags & SWR_FLAG_DEPTH_CLIP) != 0;
+    c->last_persp = persp;
     return enqueue_frame(c);
 }
 
@@ -1948,6 +1981,7 @@ int check_frames(swr_context* c) {
             const int64_t extra = (int64_t)clip_need - c->clip_n;
             c->clip_fan = std::max<int64_t>(2 * c->clip_fan, (extra + 1) / 2 + extra / 8 + 64);
             if (c->last_clip && (rc = prepare_clip(c, c->clip_n, c->last_flags, nullptr))) return rc;
+            if (c->last_clip && c->last_persp && (rc = ensure_persp(c, clip_slots(c)))) return rc;
         }
         if (c->frame_load[L % swr_context::PAIR_RING] && c->src_bad) {
             // the last frame loaded a wrong image: a redraw cannot repair it — reported (whether it was copied or not: it is what the
@@ -2089,7 +2123,7 @@ void destroy_single(swr_context* c) {
     for (auto& sl : c->slot) {
         DevBuf* sb[] = {&sl.geo, &sl.geo_full, &sl.ranges, &sl.bins, &sl.bin_matrix, &sl.live, &sl.tilebuf, &sl.biglist,
                         &sl.items, &sl.lrgb, &sl.lnrm, &sl.linv, &sl.cxyz, &sl.crgb, &sl.cnrm, &sl.cmap, &sl.cbox,
-                        &sl.csums};
+                        &sl.csums, &sl.pq};
         for (DevBuf* b : sb) if (b->p) hipFree(b->p);
         if (sl.items_host) hipHostFree(sl.items_host);
         if (sl.items_copied) hipEventDestroy(sl.items_copied);

@@ -202,6 +202,13 @@ __device__ __forceinline__ void put_corner(const ClipPrep& p, int64_t at, const 
     if (p.nrm) p.nrm[at] = make_float4(c[7], c[8], c[9], c[10]);
 }
 
+// The perspective table entry of a frame slot (SWR_FLAG_PERSPECTIVE, k_persp_fill): the clip-space w of its three corners — an
+// original vertex's own, an intersection's w_I + t (w_O - w_I) — as (q_a, q_b, q_c, bypass).
+__device__ __forceinline__ void put_persp(const ClipPrep& p, int64_t slot, float wa, float wb, float wc) {
+    const bool bypass = wa == wb && wb == wc;
+    p.pq[slot] = make_float4(__fdiv_rn(1.0f, wa), __fdiv_rn(1.0f, wb), __fdiv_rn(1.0f, wc), bypass ? 1.0f : 0.0f);
+}
+
 // Fan triangle s of triangle v at slot (= order number) base + s.  A post-clip count above the frame's slots (more crossing
 // triangles than the fan capacity) leaves every slot invalid — the frame is rastered empty — and reports the count to the host
 // (ClipPrep::over), which grows the capacity and redraws, as for a bin overflow.
@@ -233,6 +240,7 @@ __global__ __launch_bounds__(CLIP_THREADS) void k_clip_emit(ClipPrep p) {
 #pragma unroll
         for (int k = 0; k < 3; k++) put_corner(p, 3 * base + k, c[k]);
         p.map[base] = (uint32_t)v;
+        if (p.pq) put_persp(p, base, c[0][3], c[1][3], c[2][3]);
         return;
     }
     for (uint32_t s = 0; s < cnt; s++) {
@@ -241,6 +249,7 @@ __global__ __launch_bounds__(CLIP_THREADS) void k_clip_emit(ClipPrep p) {
         put_corner(p, 3 * slot + 1, q.c[s + 1]);
         put_corner(p, 3 * slot + 2, q.c[s + 2]);
         p.map[slot] = (uint32_t)v;
+        if (p.pq) put_persp(p, slot, q.c[0][3], q.c[s + 1][3], q.c[s + 2][3]);
     }
 }
 

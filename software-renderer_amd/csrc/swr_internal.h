@@ -83,6 +83,7 @@ struct ClipPrep {
     uint32_t* map;                 // [bound] order number -> original number (the ID image)
     float4* box;                   // [2 * ceil(bound / 64)] box of every 64-slot group
     uint32_t* over;                // device-visible pinned word of the frame: the post-clip count if it exceeded `bound`, else 0
+    float4* pq;                    // [bound] perspective frames (DeviceFrame::pq): (q_a, q_b, q_c, bypass) of every fan triangle, else NULL
     int32_t count_only;            // launch_bin: only the count and its scan (sums[ceil(n / 256)] = the post-clip count), no frame
 };
 
@@ -163,6 +164,9 @@ struct DeviceFrame {
     // stream, m = identity, not reordered, not a list (a clipped draw list is a plain frame over its clip stream)
     ClipPrep clip;
     int64_t order_space;           // > 0: the frame's order numbers lie below this (the PLAIN / winner-table switch); 0: ntri
+    // SWR_FLAG_PERSPECTIVE colour frames through a non-affine transform: [ntri] per slot the raster sees, (q_a, q_b,
+    // q_c, bypass) — filled in front of the binning (k_persp_fill; depth-clip frames: k_clip_emit); NULL: the screen weights
+    float4* pq;
 };
 
 void launch_validate_indices(const int64_t* indices, int64_t count, int64_t vertex_count,

@@ -1107,6 +1107,32 @@ __global__ __launch_bounds__(256) void k_list_gather(const ListItem* __restrict_
     }
 }
 
+// Perspective-correct interpolation (SWR_FLAG_PERSPECTIVE): the frame's per-slot table (q_a, q_b, q_c, bypass) that
+// the colour resolve reads for a winner.  rw_k = the clip-space w of corner k as vertex_shader computes it in setup (the frame's
+// transform; a draw list: the item's own), q_k = 1 / rw_k, bypass = 1 when the three are equal (the screen weights as they are).
+// Slots are those the raster sees: stream slots, or a draw list's frame slots.  (Depth-clip frames: k_clip_emit fills the table.)
+__global__ __launch_bounds__(256) void k_persp_fill(const ListItem* __restrict__ items, int nitems, int64_t nslots,
+                                                    const float4* __restrict__ tri_xyz, float4x4 m, float4* __restrict__ pq) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < nslots; f += stride) {
+        int64_t s = f;
+        float4x4 M = m;
+        if (items) {
+            const int k = list_find<false>(items, nitems, (uint32_t)f);
+            s = (int64_t)items[k].first + (f - (int64_t)items[k].vbase);
+            M = list_matrix(items, k);
+        }
+        float rw[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float4 x = tri_xyz[3 * s + c];     // (w: the original index, not an input of the vertex stage)
+            rw[c] = vertex_shader(make_float3(x.x, x.y, x.z), make_float3(0.0f, 0.0f, 0.0f), M).pos.w;
+        }
+        const bool bypass = rw[0] == rw[1] && rw[1] == rw[2];
+        pq[f] = make_float4(1.0f / rw[0], 1.0f / rw[1], 1.0f / rw[2], bypass ? 1.0f : 0.0f);
+    }
+}
+
 // Second walk over the triangles' tile rectangles; a returning atomic on the tile's cursor
 // (initialised to tile_start by k_scan) hands out the bin position.  Visibility keys make the
 // raster order-independent, so bins need no particular order.
@@ -1286,6 +1312,8 @@ struct RasterArgs {
     const uint8_t* src_color;   // load frames (SWR_FLAG_LOAD): the image the frame starts from, band-local like color / depth and never
     const float* src_depth;     // the same buffers (read-only for the frame)
     uint32_t* ids;              // SWR_FLAG_PRIMITIVE_IDS: the frame's ID image, band-local like depth (IDS instances only)
+    const float4* persp;        // SWR_FLAG_PERSPECTIVE colour frames through a non-affine transform: per stream slot (q_a, q_b, q_c, bypass)
+                                // (k_persp_fill); NULL: colour and varyings take the screen weights (wave-uniform)
 };
 constexpr int REDO_SAMPLE = 8;
 
@@ -1502,6 +1530,16 @@ __device__ __forceinline__ void metal_weights_shared_rcp(const MetalTri& m, int 
     w0 = div_exact(m.A0 * (sx - m.p3x) + m.B0 * (sy - m.p3y));                    // :144-145
     w1 = div_exact(m.A1 * (sx - m.p3x) + m.B1 * (sy - m.p3y));                    // :147-148
     w2 = 1.0f - w0 - w1;                                                          // :149
+}
+
+// Perspective-correct interpolation (SWR_FLAG_PERSPECTIVE, include/swr.h): the rule set's screen weights -> the
+// weights colour and the varyings are interpolated with, q_k = 1 / clip-space w of corner k.  One rounding per operation, the
+// division correctly rounded; the depth keeps the screen weights.
+__device__ __forceinline__ void persp_weights(float qa, float qb, float qc, float& w0, float& w1, float& w2) {
+    const float u0 = w0 * qa, u1 = w1 * qb, u2 = w2 * qc;
+    const float s = (u0 + u1) + u2;
+    const float rs = 1.0f / s;
+    w0 = u0 * rs; w1 = u1 * rs; w2 = u2 * rs;
 }
 
 // ---- wave64 scans on DPP (all 64 lanes must be active) ---------------------------------------
@@ -2249,16 +2287,24 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
     if constexpr (WTAB_OK) {
         // record: [0..9] weights (CPU rules: T() 4, cf 2, z 3, - ; Metal rules: p3 2, A0 B0 A1 B1, divider, z 3), [10..18] colours a b c,
         // extended stage: [19..27] normals a b c, [28..33] (u, v) a b c.  An odd stride in words: neighbouring records in different banks.
+        // Perspective frames (a.persp) append [REC_F..REC_F+3] = (q_a, q_b, q_c, bypass): a longer stride and fewer records per round
+        // for them only — the frames without the flag keep their capacity (wave-uniform choice).
         constexpr int REC_F = EXT ? 34 : 19;
         constexpr int REC_STRIDE = REC_F | 1;
+        constexpr int REC_STRIDE_P = (REC_F + 4) | 1;
         constexpr int WTAB_BYTES = (int)(sizeof(L.keys) + sizeof(L.tabAB) + sizeof(L.tabP) + sizeof(L.queue));   // contiguous, dead after the raster
         constexpr int PIX_OFF = WTAB_BYTES - TILE_W * TILE_H * 2;
         constexpr int WTAB_RCAP = PIX_OFF / (REC_STRIDE * 4);
+        constexpr int WTAB_RCAP_P = PIX_OFF / (REC_STRIDE_P * 4);
         static_assert(offsetof(RasterLds64, queue) + sizeof(L.queue) == (size_t)WTAB_BYTES && offsetof(RasterLds64, keys) == 0, "records | positions alias keys .. queue");
+        static_assert(WTAB_RCAP_P * REC_STRIDE_P * 4 <= PIX_OFF && WTAB_RCAP_P > 0, "perspective records fit below the positions");
+        const bool persp = a.persp != nullptr;
+        const uint32_t rstride = persp ? (uint32_t)REC_STRIDE_P : (uint32_t)REC_STRIDE;
+        const uint32_t rcap = persp ? (uint32_t)WTAB_RCAP_P : (uint32_t)WTAB_RCAP;
         if (wtab) {
             uint16_t* const pix = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(&L) + PIX_OFF);
             float* const recs = reinterpret_cast<float*>(&L);
-            const bool direct = m <= (uint32_t)WTAB_RCAP;        // every bin entry gets the record of its own position: no bitmap
+            const bool direct = m <= rcap;                       // every bin entry gets the record of its own position: no bitmap
             struct Gathered { int4 g0; float4 g1; float4 ca, cb, cc, na, nb, nc; };
             auto gather = [&](uint32_t slot) {
                 Gathered G;
@@ -2277,7 +2323,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
             auto build = [&](uint32_t rid, uint32_t slot, const Gathered& G) {
                 int vx[3], vy[3];
                 decode_vertices(a.geo_full, slot, G.g0, G.g1, vx, vy);
-                float* r = recs + rid * REC_STRIDE;
+                float* r = recs + rid * rstride;
                 if (METAL) {
                     MetalTri mt;
                     metal_consts(vx, vy, G.g1.x, G.g1.y, G.g1.z, mt);
@@ -2289,6 +2335,11 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                 }
                 r[7] = G.g1.x; r[8] = G.g1.y; r[9] = G.g1.z;
                 r[10] = G.ca.x; r[11] = G.ca.y; r[12] = G.ca.z; r[13] = G.cb.x; r[14] = G.cb.y; r[15] = G.cb.z; r[16] = G.cc.x; r[17] = G.cc.y; r[18] = G.cc.z;
+                if (persp) {
+                    asm volatile("" ::: "memory");
+                    const float4 q = a.persp[slot];
+                    r[REC_F + 0] = q.x; r[REC_F + 1] = q.y; r[REC_F + 2] = q.z; r[REC_F + 3] = q.w;
+                }
                 if (EXT) {
                     r[19] = G.na.x; r[20] = G.na.y; r[21] = G.na.z; r[22] = G.nb.x; r[23] = G.nb.y; r[24] = G.nb.z; r[25] = G.nc.x; r[26] = G.nc.y; r[27] = G.nc.z;
                     r[28] = G.na.w; r[29] = G.ca.w; r[30] = G.nb.w; r[31] = G.cb.w; r[32] = G.nc.w; r[33] = G.cc.w;
@@ -2360,10 +2411,10 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
             };
             // one pixel from record rid
             auto shade = [&](uint32_t rid, int x, int y, uint32_t& c, float& d) {
-                const float* r = recs + rid * REC_STRIDE;
+                const float* r = recs + rid * rstride;
                 float v[REC_F];
 #pragma unroll
-                for (int j = 0; j < REC_F; j++) v[j] = r[j];
+                for (int j = 0; j < 10; j++) v[j] = r[j];
                 float w0, w1, w2;
                 if (METAL) {
                     MetalTri mt;
@@ -2379,6 +2430,12 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                 }
                 d = INFINITY;                                                 // (:206; painter's order leaves the depth image alone)
                 if (ZTEST) d = v[7] * w0 + v[8] * w1 + v[9] * w2;              // :257
+                if (persp) {
+                    asm volatile("" ::: "memory");
+                    if (r[REC_F + 3] == 0.0f) persp_weights(r[REC_F + 0], r[REC_F + 1], r[REC_F + 2], w0, w1, w2);
+                }
+#pragma unroll
+                for (int j = 10; j < REC_F; j++) v[j] = r[j];
                 VertexOut vin;
                 vin.pos = make_float4((float)x + 0.5f, (float)y + 0.5f, d, 1.0f);
                 vin.color = make_float3(v[10] * w0 + v[13] * w1 + v[16] * w2,     // :266
@@ -2404,14 +2461,14 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
             // Passes 2 and 3, in ROUNDS of WTAB_RCAP winners: one round for every tile of the BASELINE scenes; a tile of ~1 000 two-pixel
             // triangles has ~600 winners and takes two.  A pixel is shaded and stored by the round its winner's number falls into
             // (pixels without a winner by the first); a tile of one round stores four pixels at a time.
-            const bool one_round = nrec <= (uint32_t)WTAB_RCAP;
-            for (uint32_t base = 0u; base < max(nrec, 1u); base += (uint32_t)WTAB_RCAP) {
+            const bool one_round = nrec <= rcap;
+            for (uint32_t base = 0u; base < max(nrec, 1u); base += rcap) {
                 if (base) __syncthreads();       // the round before has read its records
                 // 2: one lane per bin entry (that owns a pixel): its record
                 for (uint32_t i = (uint32_t)tid; i < m; i += RASTER_THREADS) {
                     const bool mine = direct || ((L.winners[i >> 5].x >> (i & 31u)) & 1u);
                     const uint32_t rid = mine ? rid_of(i) - base : 0xFFFFFFFFu;
-                    if (rid >= (uint32_t)WTAB_RCAP) continue;
+                    if (rid >= rcap) continue;
                     if (i >= (uint32_t)RASTER_THREADS || base) {      // (else: gathered before pass 1)
                         slot_first = a.bins[b0 + i] & bin_mask;
                         G_first = gather(slot_first);
@@ -2442,7 +2499,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                         if (x + k > X1) continue;
                         if (ps[k] == 0xFFFFu) { if (base == 0u) stored |= 1u << k; continue; }
                         const uint32_t rid = rid_of(ps[k]) - base;
-                        if (rid < (uint32_t)WTAB_RCAP) { shade(rid, x + k, y, cpix[k], dpix[k]); stored |= 1u << k; }
+                        if (rid < rcap) { shade(rid, x + k, y, cpix[k], dpix[k]); stored |= 1u << k; }
                     }
                     if constexpr (LOAD) {
                         // a load frame: pixels without a winner keep the loaded image (painter's order: its depth everywhere).  Read
@@ -2667,6 +2724,11 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                         w2 = 1.0f - w0 - w1;
                     }
                     if (ZTEST) d[g] = q3[g].x * w0 + q3[g].y * w1 + q3[g].z * w2;
+                    if (want_color && a.persp) {
+                        // (read per pixel, not cached with the winner: nothing more is live across the pixel loop)
+                        const float4 q = a.persp[slot[g]];
+                        if (q.w == 0.0f) persp_weights(q.x, q.y, q.z, w0, w1, w2);
+                    }
                     if (want_color) {
                         VertexOut vin;
                         vin.pos = make_float4((float)(x[g] + k) + 0.5f, (float)y[g] + 0.5f, d[g], 1.0f);
@@ -3026,10 +3088,12 @@ hipError_t prepare_device() {
 static bool bin_h16(int per) { return SWR_TUNE_HIST16 && (int64_t)per * 64 < 65536; }
 
 static void launch_list_gather(const DeviceFrame& f, hipStream_t s);
+static void launch_persp_fill(const DeviceFrame& f, hipStream_t s);
 void launch_setup_bin(const DeviceFrame& f, hipStream_t s) {
     if (f.ntri <= 0) return;
     launch_clip_prep(f, s);
     launch_list_gather(f, s);
+    launch_persp_fill(f, s);
     const SetupArgs a = make_setup_args(f);
     const int ntiles = f.tg.tiles_x * f.tg.tiles_y;
     if (f.plan.use_lds) {
@@ -3057,6 +3121,15 @@ static void launch_list_gather(const DeviceFrame& f, hipStream_t s) {
                        f.gather.nrm, f.gather.rgb_out, f.gather.nrm_out, f.gather.inv_out);
 }
 
+// the perspective table of a frame that has one (DeviceFrame::pq), in front of its binning; depth-clip frames fill theirs in k_clip_emit
+static void launch_persp_fill(const DeviceFrame& f, hipStream_t s) {
+    if (f.ntri <= 0 || !f.pq || f.clip.bound > 0) return;
+    float4x4 m;
+    for (int c = 0; c < 4; c++) m.columns[c] = make_float4(f.m[4 * c + 0], f.m[4 * c + 1], f.m[4 * c + 2], f.m[4 * c + 3]);
+    const unsigned blocks = (unsigned)std::min<int64_t>(2048, (f.ntri + 255) / 256);
+    hipLaunchKernelGGL(k_persp_fill, dim3(blocks), dim3(256), 0, s, f.items, (int)f.nitems, f.ntri, f.tri_xyz, m, f.pq);
+}
+
 // Can the frame be binned by the single-launch k_bin (fixed-stride bins), and how large may a tile region be?  Needs the
 // LDS path's 16-bit histogram, class tags, 32-bit offsets into the region table, and cursor halves that stay below 2^16:
 // region size + the primitives one workgroup owns < 65536.
@@ -3076,6 +3149,7 @@ bool launch_bin(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     launch_clip_prep(f, s);
     if (f.clip.count_only) return false;       // (swr_api.hip: the post-clip count of a frame, ahead of it)
     launch_list_gather(f, s);
+    launch_persp_fill(f, s);
     BinArgs b;
     b.a = make_setup_args(f);
     b.fill = f.fill; b.fill_next = f.fill_next; b.bins = f.bins; b.cap = f.cap_tile;
@@ -3179,6 +3253,7 @@ static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop
     a.src_color = LOAD ? f.src_color : nullptr;
     a.src_depth = LOAD ? f.src_depth : nullptr;
     a.ids = IDS ? f.ids : nullptr;
+    a.persp = a.color ? f.pq : nullptr;
     // (a load frame's z-tested keys carry the packed word + 1: the last primitive of a scene of exactly 2^20 would wrap)
     // (depth-clip frames: their order numbers lie below the post-clip count, or a bound of it, not below their slot count)
     a.pack_local = (f.order_space > 0 ? f.order_space : f.ntri) < (1ll << WTAB_PRIM_BITS) + (LOAD ? 0 : 1) ? 1 : 0;

@@ -143,8 +143,16 @@ inline uint32_t faceCullingFlags(CullMode cullMode, Winding frontFacingWinding) 
 enum class DepthClipMode { none, clip };
 inline uint32_t depthClipFlags(DepthClipMode mode) { return mode == DepthClipMode::clip ? (uint32_t)SWR_FLAG_DEPTH_CLIP : 0u; }
 
+// How colour and the varyings are interpolated (include/swr.h "Perspective-correct interpolation"): screenLinear = the reference
+// (the screen-space weights); perspective = corrected by the clip-space w of each corner, like Metal's [[center_perspective]].
+enum class InterpolationMode { screenLinear, perspective };
+inline uint32_t interpolationFlags(InterpolationMode mode) {
+    return mode == InterpolationMode::perspective ? (uint32_t)SWR_FLAG_PERSPECTIVE : 0u;
+}
+
 // Renderer.swift:191-200 (+ the optional extended fragment stage: empty attributes / passthrough material
-// = the reference's RenderPass exactly; + the load action, clear by default = the reference; + face culling, none by default)
+// = the reference's RenderPass exactly; + the load action, clear by default = the reference; + face culling, none by default;
+// + depth clipping, none by default; + the interpolation mode, screen-linear by default)
 struct RenderPass {
     ColorImage colorBuffer;
     DepthImage depthBuffer;
@@ -158,6 +166,7 @@ struct RenderPass {
     CullMode cullMode = CullMode::none;
     Winding frontFacingWinding = Winding::clockwise;
     DepthClipMode depthClipMode = DepthClipMode::none;
+    InterpolationMode interpolationMode = InterpolationMode::screenLinear;
 };
 
 // One draw of a draw list (swr_draw_item, include/swr.h): indices [firstIndex, firstIndex + indexCount) of the resident scene
@@ -197,7 +206,8 @@ public:
         rp.index_count = (int64_t)p.indices.size();
         rp.primitive_type = (int32_t)p.primitiveType;
         rp.flags = flags | (p.loadAction == LoadAction::load ? (uint32_t)SWR_FLAG_LOAD : 0u) |
-                   faceCullingFlags(p.cullMode, p.frontFacingWinding) | depthClipFlags(p.depthClipMode);
+                   faceCullingFlags(p.cullMode, p.frontFacingWinding) | depthClipFlags(p.depthClipMode) |
+                   interpolationFlags(p.interpolationMode);
         for (int c = 0; c < 4; c++)
             for (int r = 0; r < 4; r++) rp.transform[4 * c + r] = p.transform.columns[c][r];
         swr_material mat{};
@@ -227,7 +237,8 @@ public:
     // image is the context's, as after that render() (its colour / depth buffers are not written).  The cull mode and winding hold
     // for every item; each item's facing comes from its own transform.
     void drawList(const std::vector<DrawItem>& items, uint32_t flags, CullMode cullMode = CullMode::none,
-                  Winding frontFacingWinding = Winding::clockwise, DepthClipMode depthClipMode = DepthClipMode::none) {
+                  Winding frontFacingWinding = Winding::clockwise, DepthClipMode depthClipMode = DepthClipMode::none,
+                  InterpolationMode interpolationMode = InterpolationMode::screenLinear) {
         std::vector<swr_draw_item> list(items.size());
         for (size_t k = 0; k < items.size(); k++) {
             list[k].first_index = items[k].firstIndex;
@@ -236,7 +247,8 @@ public:
                 for (int r = 0; r < 4; r++) list[k].transform[4 * c + r] = items[k].transform.columns[c][r];
         }
         int rc = swr_draw_list(ctx_, list.data(), (int32_t)list.size(), flags | faceCullingFlags(cullMode, frontFacingWinding) |
-                                                                      depthClipFlags(depthClipMode));
+                                                                      depthClipFlags(depthClipMode) |
+                                                                      interpolationFlags(interpolationMode));
         if (rc) throw RenderError(rc, swr_last_error(ctx_));
     }
     // The ID image of the last frame, drawn with SWR_FLAG_PRIMITIVE_IDS (swr_read_ids): width * height words, the triangle index (draw
