@@ -107,29 +107,8 @@ def restate(v, i, m, attrs=None, order=None):
     return V, A, np.arange(nv, dtype=np.int64), np.array(fmap, dtype=np.int64), fans
 
 
-# ---- colour-coded IDs (as tests/test_cull.py) -------------------------------------------------------------------------------------
-MASK21 = (1 << 21) - 1
-LIVE = -1
-
-
-def coded(vertices, indices, invert=False):
-    i = np.asarray(indices, dtype=np.int64).reshape(-1)
-    v = np.array(np.asarray(vertices, dtype=f32).reshape(-1, 8)[i], copy=True)
-    t = np.repeat(np.arange(i.size // 3, dtype=np.int64), 3)
-    if invert:
-        t = t ^ MASK21
-    for ch in range(3):
-        v[:, 4 + ch] = ((2 * ((t >> (7 * ch)) & 127) + 1) / 255.0).astype(f32)
-    return v, np.arange(i.size, dtype=np.int64)
-
-
-def decode(c, invert=False):
-    ids = (c[..., 2].astype(np.int64) >> 1) | ((c[..., 1].astype(np.int64) >> 1) << 7) | ((c[..., 0].astype(np.int64) >> 1) << 14)
-    if invert:
-        ids = ids ^ MASK21
-    ids = ids.astype(np.uint32)
-    ids[c[..., 3] == 0] = NONE
-    return ids
+# ---- colour-coded IDs: tests/kernel_matrix.py's (shared with tests/frame_model.py) -----------------------------------------------
+from kernel_matrix import LIVE, MASK21, coded, decode  # noqa: E402,F401
 
 
 def oracle_frame(oracle, v, i, w, h, flags, shading=None, color=None, depth=None):

@@ -306,6 +306,10 @@ def test_parity_soup(swr, oracle, rules, shader, load, ids):
         got = frame(ctx, m, flags | PERSP)
     check(got, want, f"soup {rules} shader {shader} load {load} ids {ids}", ref)
     assert got[1].tobytes() == want_d.tobytes()                  # the model's depth is the oracle's
+    # depth and IDs from the model as well (tests/frame_model.py: the C oracle's depth, colour-coded IDs), not only from the frame
+    # the library draws without the flag
+    import frame_model as FM
+    FM.same(got, FM.expect(oracle, FM.FrameSpec(v, i, W, H, flags | PERSP, m, shading=sh), start), f"soup {rules} {shader} {load} {ids}: model")
     assert not np.array_equal(got[0], ref[0])                    # (the flag does something here)
 
 
@@ -327,6 +331,8 @@ def test_parity_torus_app_transform(swr, oracle, rules, shader):
         ref = frame(ctx, m, flags)
         got = frame(ctx, m, flags | PERSP)
     check(got, want, f"torus {rules} shader {shader}", ref)
+    import frame_model as FM
+    FM.same(got, FM.expect(oracle, FM.FrameSpec(v, i, W, H, flags | PERSP, m, shading=sh)), f"torus {rules} shader {shader}: model")
     if rules != "painter":
         c_or, d_or, _, code = (oracle.render_metal(v, i, m, W, H, shading=sh) if rules == "metal" else
                                oracle.render(v, i, m, W, H, DT | oracle.TINV_PER_TRIANGLE, shading=sh))
