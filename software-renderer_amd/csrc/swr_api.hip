@@ -251,9 +251,9 @@ struct swr_context {
     int last_slot = 0;
     uint32_t capacity = 0;              // exact bins: (triangle,tile) pairs every slot's `bins` holds
     // Fixed-stride bins (k_bin: ONE binning launch per frame): tile t owns bins[t * cap_tile, (t + 1) * cap_tile).  The
-    // per-tile fill counters live in four rotating blocks (frame % 4) while the working sets rotate by three: k_bin of
-    // frame N zeroes the block of frame N + 1, which was last read by the raster of frame N - 3 — the raster whose
-    // completion lets the binning of frame N start.
+    // per-tile fill counters live in NFILL = NSLOT + 1 rotating blocks (frame % NFILL) while the working sets rotate by NSLOT:
+    // k_bin of frame N zeroes the block of frame N + 1, which was last read by the raster of frame N - NSLOT — the raster
+    // whose completion lets the binning of frame N start.
     static constexpr int NFILL = NSLOT + 1;      // k_bin(N) zeroes the fill block of frame N + 1: its last reader must be the raster of frame N - NSLOT
     DevBuf fillbuf[NFILL];              // [CNT_WORDS counters][tiles fills]
     bool fill_dirty[NFILL] = {};        // block was used and nothing has zeroed it since (then the frame memsets it first)
@@ -262,7 +262,7 @@ struct swr_context {
     // wait packet, no completion signal, no helper thread that polls — and consecutive frames onto NSLOT different streams.
     // Everything a frame writes belongs to its lane: the working set (slot = lane), its two fill blocks (k_bin of the lane's
     // n-th frame zeroes the block of its (n + 1)-th, last read by a raster that is earlier on the same stream) and its
-    // framebuffer (fb advances with every draw; the buffer a frame writes was last written three frames earlier — same lane).
+    // framebuffer (fb advances with every draw; the buffer a frame writes was last written NSLOT frames earlier — same lane).
     // Frames of different lanes overlap freely on the chip.  What the two-stream pipeline of rounds 1-3 paid per frame — a
     // 5 us gap behind every kernel that carries a completion signal, the polls of two helper threads — is gone: cfg4 76 -> 67 us
     // per frame, and a thin band (1/8 of the frame: bound by its kernel chain, not by the chip) 24.5 -> 15.9 us
@@ -432,6 +432,9 @@ int sticky(swr_context* c) {
     return f;
 }
 
+// `rc` of a failed wait — or, when the context has failed for good meanwhile, that failure
+inline int or_sticky(swr_context* c, int rc) { const int f = sticky(c); return f ? f : rc; }
+
 // Bounded waiting: spin, then yield, never beyond the context's budget; gives up at once when the context has failed.
 struct Deadline {
     std::chrono::steady_clock::time_point end;
@@ -540,7 +543,7 @@ int sync_streams(swr_context* c) {
     if (c->lanes_ok)
         for (hipStream_t ls : c->lane_stream)
             if (!rc && ls) rc = wait_stream(c, ls, "frame lane");
-    if (rc) return sticky(c) ? sticky(c) : rc;
+    if (rc) return or_sticky(c, rc);
     c->synced_upto = c->posted;      // NOT frame_no: enqueue_frame may sync after it has numbered the frame it is about to post
     for (bool& r : c->read_recorded) r = false;     // every load frame's read of its source has completed: nothing to wait for
     return SWR_OK;
@@ -551,13 +554,76 @@ int sync_copies(swr_context* c) {
     if (c->ras_worker) rc = c->ras_worker->drain();    // posted swr_present copies
     if (!rc) rc = wait_stream(c, c->copy_stream[0], "colour copy stream");
     if (!rc) rc = wait_stream(c, c->copy_stream[1], "depth copy stream");
-    if (rc) return sticky(c) ? sticky(c) : rc;
+    if (rc) return or_sticky(c, rc);
     return SWR_OK;
 }
 
 inline int tiles_of(const Target& t) { return t.tiles_x * t.tiles_y; }
 inline uint32_t& pair_word(swr_context* c, uint64_t frame) { return c->h_pairs[frame % swr_context::PAIR_RING]; }
 inline uint32_t& fill_word(swr_context* c, uint64_t frame) { return c->h_pairs[swr_context::PAIR_RING + 1 + frame % swr_context::PAIR_RING]; }
+
+// ---- growing what every lane owns ---------------------------------------------------------------------------------------------
+// A table of (working-set buffer, bytes a frame needs): if any lane's buffer is smaller, every stream is drained once and every
+// lane's buffer grown.  Each size is written once, in the table; an entry that applies only under a condition is not added.
+struct LaneSizes {
+    struct Entry { DevBuf swr_context::Slot::* buf; size_t bytes; } e[12];
+    int n = 0;
+    void add(DevBuf swr_context::Slot::* buf, size_t bytes) { e[n].buf = buf; e[n].bytes = bytes; n++; }
+};
+int grow_lanes(swr_context* c, const LaneSizes& t) {
+    bool grow = false;
+    for (auto& sl : c->slot)
+        for (int k = 0; k < t.n; k++) grow = grow || (sl.*t.e[k].buf).bytes < t.e[k].bytes;
+    if (!grow) return SWR_OK;
+    int rc = sync_streams(c);
+    if (rc) return rc;
+    for (auto& sl : c->slot)
+        for (int k = 0; k < t.n; k++)
+            if ((rc = ensure(c, sl.*t.e[k].buf, t.e[k].bytes))) return rc;
+    return SWR_OK;
+}
+
+// ---- the first guess of the bins ------------------------------------------------------------------------------------------------
+// Fixed-stride bins, entries per tile region for `tris` triangles on `tiles` tiles, at most `cmax`.  A primitive enters a tile's
+// region at most once, so a region of `tris` entries can never overflow: small frames get that; large ones six times the mean load
+// of a tile, at least 1024 entries (a fuller tile makes the host grow the regions and redraw once).
+inline uint32_t first_cap_tile(int64_t tris, int tiles, uint32_t cmax) {
+    const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(64, (uint64_t)(6 * tris / tiles)), (uint64_t)std::min<int64_t>(tris, 1024));
+    return (uint32_t)std::min<uint64_t>((want + 63) & ~63ull, cmax);
+}
+// Exact-size bins: (triangle,tile) pairs for `tris` triangles
+inline uint32_t first_capacity(int64_t tris) { return (uint32_t)std::min<uint64_t>((uint64_t)tris * 2 + 65536, 0xFFFFFFF0ull); }
+
+// The bins must be able to take a frame of `tris` triangles whose binning size is `plan` (a draw list: its k_bin work units * 64; a
+// clip frame: its slots), sized by the first guess as size_bins sizes them for the scene: they only grow, with every stream idle.
+// A frame beyond what k_bin can hold (a workgroup's share of the work below the cursor limit) moves the context to the exact-size
+// bins, as a scene that needs more than a region would.
+int fit_bins(swr_context* c, int64_t tris, int64_t plan) {
+    int rc;
+    const int tiles = tiles_of(c->tg);
+    if (c->fixed_mode && tris > 0) {
+        if (fixed_cap_max(plan, tiles) < c->cap_tile) {
+            if ((rc = sync_streams(c))) return rc;
+            c->fixed_mode = false;
+            c->fixed_allowed = false;
+        } else {
+            // (capped for the scene's own frames too: a region survives into them, and their cursors must stay below 2^16)
+            const uint32_t want = first_cap_tile(tris, tiles, fixed_cap_max(std::max<int64_t>(c->ni / 3, plan), tiles));
+            if (want > c->cap_tile) {
+                if ((rc = sync_streams(c))) return rc;
+                if ((rc = ensure_bins(c, (size_t)tiles * want))) return rc;
+                c->cap_tile = want;
+            }
+        }
+    }
+    if (!c->fixed_mode && tris > 0 && first_capacity(tris) > c->capacity) {
+        if ((rc = sync_streams(c))) return rc;
+        if ((rc = ensure_capacity(c, first_capacity(tris)))) return rc;
+    }
+    // (the fixed-bin limits of check_frames and of later frames cover this frame's binning size too)
+    c->list_plan_max = std::max<int64_t>(c->list_plan_max, plan);
+    return SWR_OK;
+}
 
 // Size the bins for the scene / target pair (both known; every stream idle).  Fixed-stride bins where k_bin can be used:
 // a first guess of six times the mean load per tile (the host grows it when a frame overflows), exact bins otherwise.
@@ -569,7 +635,7 @@ int size_bins(swr_context* c) {
         int rc0 = ensure(c, c->redo_cnt, 16);
         if (rc0) return rc0;
         HIP_TRY(c, hipMemsetAsync(c->redo_cnt.p, 0, 16, c->stream));
-        if ((rc0 = wait_stream(c, c->stream, "raster stream (redo counter)"))) return sticky(c) ? sticky(c) : rc0;
+        if ((rc0 = wait_stream(c, c->stream, "raster stream (redo counter)"))) return or_sticky(c, rc0);
         c->h_pairs[2 * swr_context::PAIR_RING + 1] = 0u;
         c->sized_ntri = ntri; c->sized_tiles = tiles;
     }
@@ -584,12 +650,8 @@ int size_bins(swr_context* c) {
     const uint32_t cmax = (c->fixed_allowed && !no_fixed) ? fixed_cap_max(ntri, tiles) : 0u;
     int rc;
     if (cmax) {
-        // a primitive enters a tile's region at most once, so a region of `ntri` entries can never overflow: small scenes
-        // get that; large ones six times the mean load of a tile, at least 1024 entries (a fuller tile makes the host grow
-        // the regions and redraw once)
-        uint64_t want = std::max<uint64_t>(std::max<uint64_t>(64, (uint64_t)(6 * ntri / tiles)), (uint64_t)std::min<int64_t>(ntri, 1024));
-        want = std::min<uint64_t>((want + 63) & ~63ull, cmax);
-        if (!c->fixed_mode || c->cap_tile < want || c->cap_tile > cmax) c->cap_tile = (uint32_t)want;   // a grown region survives a new transform
+        const uint32_t want = first_cap_tile(ntri, tiles, cmax);
+        if (!c->fixed_mode || c->cap_tile < want || c->cap_tile > cmax) c->cap_tile = want;   // a grown region survives a new transform
         if ((rc = ensure_bins(c, (size_t)tiles * c->cap_tile))) return rc;
         const size_t fb = (size_t)(CNT_WORDS + tiles) * 4;
         for (int k = 0; k < swr_context::NFILL; k++) {
@@ -603,13 +665,31 @@ int size_bins(swr_context* c) {
                 HIP_TRY(c, hipMemsetAsync(c->lanefill[l][k].p, 0, c->lanefill[l][k].bytes, c->stream));
                 c->lanefill_dirty[l][k] = false;
             }
-        if ((rc = wait_stream(c, c->stream, "raster stream (fill counters)"))) return sticky(c) ? sticky(c) : rc;
+        if ((rc = wait_stream(c, c->stream, "raster stream (fill counters)"))) return or_sticky(c, rc);
         c->fixed_mode = true;
         return SWR_OK;
     }
     c->fixed_mode = false;
-    const uint64_t want = (uint64_t)ntri * 2 + 65536;
-    return ensure_capacity(c, (uint32_t)std::min<uint64_t>(want, 0xFFFFFFF0ull));
+    return ensure_capacity(c, first_capacity(ntri));
+}
+
+#ifndef SWR_TUNE_IDLE_BIN_G
+#define SWR_TUNE_IDLE_BIN_G 512
+#endif
+// The binning geometry of a frame of `ntri` triangles.  A frame over a stream of its own (own_stream: a draw list, whose binning
+// size is its work units * 64, or a clip frame) is planned by that `size` under the fixed-stride bins and takes the global-atomic
+// chain under the exact-size ones (its tables need no per-G sizing).
+// An idle context (every earlier frame complete: a single frame, or the first of a burst) bins with twice the workgroups, idle_G
+// (an eighth of the frame's 64-primitive groups) at most SWR_TUNE_IDLE_BIN_G: with nothing else on the chip k_bin is a chain of round
+// trips at one wave per SIMD, and two waves per SIMD overlap them; beside a raster the extra waves only take issue slots from it
+// (round 2's sweeps), so frames posted while others are in flight keep one workgroup per CU.
+BinPlan plan_frame(const swr_context* c, int64_t ntri, int64_t size, int64_t idle_G, bool own_stream) {
+    const int tiles = tiles_of(c->tg);
+    const bool fixed = c->fixed_mode && ntri > 0;
+    BinPlan p = !own_stream ? plan_binning(ntri, tiles, c->dbg_bin_mode == 3) : fixed ? plan_binning(size, tiles, false) : plan_binning(ntri, tiles, true);
+    if (fixed && c->synced_upto == c->posted)
+        p.G = (int)std::max<int64_t>(1, std::min<int64_t>(SWR_TUNE_IDLE_BIN_G, std::max<int64_t>(p.G, idle_G)));
+    return p;
 }
 
 DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16], uint32_t flags) {
@@ -645,18 +725,7 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
     f.tile_start = tb + CNT_WORDS + tiles_of(c->tg);
     f.tile_cursor = tb + CNT_WORDS + 2 * tiles_of(c->tg) + 1;
     f.ranges = (uint2*)sl.ranges.p;
-    f.plan = plan_binning(f.ntri, tiles_of(c->tg), c->dbg_bin_mode == 3);
-#ifndef SWR_TUNE_IDLE_BIN_G
-#define SWR_TUNE_IDLE_BIN_G 512
-#endif
-    // An idle context (every earlier frame complete: a single frame, or the first of a burst) bins with twice the
-    // workgroups: with nothing else on the chip k_bin is a chain of round trips at one wave per SIMD, and two waves per
-    // SIMD overlap them; beside a raster the extra waves only take issue slots from it (round 2's sweeps), so frames
-    // posted while others are in flight keep one workgroup per CU.
-    if (c->fixed_mode && f.ntri > 0 && c->synced_upto == c->posted) {
-        const int64_t groups = (f.ntri + 63) / 64;
-        f.plan.G = (int)std::max<int64_t>(1, std::min<int64_t>(SWR_TUNE_IDLE_BIN_G, std::max<int64_t>(f.plan.G, (groups + 7) / 8)));
-    }
+    f.plan = plan_frame(c, f.ntri, f.ntri, ((f.ntri + 63) / 64 + 7) / 8, false);
     f.bin_matrix = (uint32_t*)sl.bin_matrix.p;
     f.live = (uint32_t*)sl.live.p;
     // Groups of the stream whose projected box misses this context's band (or the framebuffer) are skipped by
@@ -700,15 +769,8 @@ void make_list_frame(swr_context* c, int si, DeviceFrame& f) {
     f.nitems = (int32_t)c->list.size();
     f.units = c->list_units;
     f.list_affine = c->list_affine ? 1 : 0;
-    const int tiles = tiles_of(c->tg);
     f.fixed_bins = (c->fixed_mode && f.ntri > 0) ? 1 : 0;
-    if (f.fixed_bins) {
-        f.plan = plan_binning(f.units * 64, tiles, false);
-        if (c->synced_upto == c->posted)     // (an idle context: twice the workgroups, as make_frame)
-            f.plan.G = (int)std::max<int64_t>(1, std::min<int64_t>(SWR_TUNE_IDLE_BIN_G, std::max<int64_t>(f.plan.G, (f.units + 7) / 8)));
-    } else {
-        f.plan = plan_binning(f.ntri, tiles, true);
-    }
+    f.plan = plan_frame(c, f.ntri, f.units * 64, (f.units + 7) / 8, true);
     if (!c->list_identity && f.ntri > 0) {
         f.reordered = 1;                    // keys carry order numbers; inv maps them to frame slots
         f.inv = (const uint32_t*)sl.linv.p;
@@ -760,15 +822,9 @@ void make_clip_frame(swr_context* c, int si, uint64_t frame, DeviceFrame& f) {
     f.order_space = c->clip_total >= 0 ? std::max<int64_t>(c->clip_total, 1) : std::max<int64_t>(p.bound, 1);
     // (32-bit depth keys: the clip frame's zero depths on the near plane are its own; they do not move the scene's state)
     f.redo_dev = nullptr; f.k32 = 0;
-    const int tiles = tiles_of(c->tg);
     f.fixed_bins = (c->fixed_mode && f.ntri > 0) ? 1 : 0;
-    if (f.fixed_bins) {
-        f.plan = plan_binning(f.ntri, tiles, false);
-        if (c->synced_upto == c->posted)     // (an idle context: twice the workgroups, as make_frame)
-            f.plan.G = (int)std::max<int64_t>(1, std::min<int64_t>(SWR_TUNE_IDLE_BIN_G, std::max<int64_t>(f.plan.G, (f.ntri + 63) / 64 / 8)));
-    } else {
-        f.plan = plan_binning(f.ntri, tiles, true);     // exact-size bins: the global-atomic chain (its tables need no per-G sizing)
-    }
+    // (the idle raise rounds DOWN here, as it always has: it differs from the scene frame's between 131 073 and 262 080 slots)
+    f.plan = plan_frame(c, f.ntri, f.ntri, (f.ntri + 63) / 64 / 8, true);
 }
 
 // ---- perspective-correct interpolation ----------------------------------------------------------------------------
@@ -781,15 +837,9 @@ inline bool affine_transform(const float m[16]) { return m[3] == 0.0f && m[7] ==
 
 // Every lane's perspective table for a frame of `slots` slots (grown with every stream idle).
 int ensure_persp(swr_context* c, int64_t slots) {
-    const size_t bytes = (size_t)std::max<int64_t>(slots, 1) * 16;
-    bool grow = false;
-    for (auto& sl : c->slot) grow = grow || sl.pq.bytes < bytes;
-    if (!grow) return SWR_OK;
-    int rc = sync_streams(c);
-    if (rc) return rc;
-    for (auto& sl : c->slot)
-        if ((rc = ensure(c, sl.pq, bytes))) return rc;
-    return SWR_OK;
+    LaneSizes t;
+    t.add(&swr_context::Slot::pq, (size_t)std::max<int64_t>(slots, 1) * 16);
+    return grow_lanes(c, t);
 }
 
 // A depth-clip frame of n submitted triangles: the lane buffers for n + 2F slots and bins that can take them (every stream idle when
@@ -802,55 +852,15 @@ int prepare_clip(swr_context* c, int64_t n, uint32_t flags, const float* m) {
     int rc;
     const size_t V = (size_t)std::max<int64_t>(clip_slots(c), 1);
     const size_t S = (size_t)(n + 255) / 256 + 1;            // the pre-pass's workgroup sums + the total
-    const bool attrs = c->has_attrs && c->tri_nrm.p;
-    auto small = [&](const swr_context::Slot& sl) {
-        return sl.geo.bytes < V * sizeof(GeomRec) || sl.geo_full.bytes < V * sizeof(GeomFull) || sl.ranges.bytes < V * sizeof(uint2) ||
-               sl.cxyz.bytes < V * 48 || sl.crgb.bytes < V * 48 || (attrs && sl.cnrm.bytes < V * 48) || sl.cmap.bytes < V * 4 ||
-               sl.cbox.bytes < (V + 63) / 64 * 32 || sl.csums.bytes < S * 4;
-    };
-    bool grow = false;
-    for (auto& sl : c->slot) grow = grow || small(sl);
-    if (grow) {
-        if ((rc = sync_streams(c))) return rc;
-        for (auto& sl : c->slot) {
-            if ((rc = ensure(c, sl.geo, V * sizeof(GeomRec)))) return rc;
-            if ((rc = ensure(c, sl.geo_full, V * sizeof(GeomFull)))) return rc;
-            if ((rc = ensure(c, sl.ranges, V * sizeof(uint2)))) return rc;
-            if ((rc = ensure(c, sl.cxyz, V * 48))) return rc;
-            if ((rc = ensure(c, sl.crgb, V * 48))) return rc;
-            if (attrs && (rc = ensure(c, sl.cnrm, V * 48))) return rc;
-            if ((rc = ensure(c, sl.cmap, V * 4))) return rc;
-            if ((rc = ensure(c, sl.cbox, (V + 63) / 64 * 32))) return rc;
-            if ((rc = ensure(c, sl.csums, S * 4))) return rc;
-        }
-    }
-    const int64_t tris = (int64_t)V, plan = ((int64_t)V + 63) / 64 * 64;
-    const int tiles = tiles_of(c->tg);
-    if (c->fixed_mode && n > 0) {
-        const uint32_t cmax = fixed_cap_max(plan, tiles);
-        if (cmax < c->cap_tile) {
-            if ((rc = sync_streams(c))) return rc;
-            c->fixed_mode = false;
-            c->fixed_allowed = false;
-        } else {
-            uint64_t want = std::max<uint64_t>(std::max<uint64_t>(64, (uint64_t)(6 * tris / tiles)), (uint64_t)std::min<int64_t>(tris, 1024));
-            want = std::min<uint64_t>((want + 63) & ~63ull, fixed_cap_max(std::max<int64_t>(c->ni / 3, plan), tiles));
-            if (want > c->cap_tile) {
-                if ((rc = sync_streams(c))) return rc;
-                if ((rc = ensure_bins(c, (size_t)tiles * want))) return rc;
-                c->cap_tile = (uint32_t)want;
-            }
-        }
-    }
-    if (!c->fixed_mode && n > 0) {
-        const uint32_t want = (uint32_t)std::min<uint64_t>((uint64_t)tris * 2 + 65536, 0xFFFFFFF0ull);
-        if (want > c->capacity) {
-            if ((rc = sync_streams(c))) return rc;
-            if ((rc = ensure_capacity(c, want))) return rc;
-        }
-    }
-    // (the fixed-bin limits of check_frames and of later lists cover the clip frame's binning size too)
-    c->list_plan_max = std::max<int64_t>(c->list_plan_max, plan);
+    using Slot = swr_context::Slot;
+    LaneSizes t;
+    t.add(&Slot::geo, V * sizeof(GeomRec)); t.add(&Slot::geo_full, V * sizeof(GeomFull)); t.add(&Slot::ranges, V * sizeof(uint2));
+    t.add(&Slot::cxyz, V * 48); t.add(&Slot::crgb, V * 48);
+    if (c->has_attrs && c->tri_nrm.p) t.add(&Slot::cnrm, V * 48);
+    t.add(&Slot::cmap, V * 4); t.add(&Slot::cbox, (V + 63) / 64 * 32); t.add(&Slot::csums, S * 4);
+    if ((rc = grow_lanes(c, t))) return rc;
+    // (no submitted triangle: no slot, nothing to bin; the binning size is a whole number of 64-slot groups)
+    if ((rc = fit_bins(c, clip_slots(c), ((int64_t)V + 63) / 64 * 64))) return rc;
     // The PLAIN / winner-table switch of the raster is judged on the post-clip count.  Below the threshold with all n + 2F slots
     // it needs nothing; otherwise the host counts first (every stream idle, the count kernels alone, one wait): a scene of about
     // 2^20 triangles or more, and only when its slot count reaches the threshold.
@@ -875,7 +885,7 @@ int prepare_clip(swr_context* c, int64_t n, uint32_t flags, const float* m) {
             launch_bin(f, c->stream, nullptr);
             const int64_t nb = (n + 255) / 256;
             HIP_TRY(c, hipMemcpyAsync(&c->h_clip[swr_context::PAIR_RING], f.clip.sums + nb, 4, hipMemcpyDeviceToHost, c->stream));
-            if ((rc = wait_stream(c, c->stream, "the depth-clip count"))) return sticky(c) ? sticky(c) : rc;
+            if ((rc = wait_stream(c, c->stream, "the depth-clip count"))) return or_sticky(c, rc);
             c->clip_total = (int64_t)c->h_clip[swr_context::PAIR_RING];
         }
     }
@@ -952,21 +962,50 @@ int wait_for_copies_of(swr_context* c, int fb, hipStream_t s) {
     return SWR_OK;
 }
 
+// What a frame's binning chain needs besides the frame (by value: in the two-stream pipeline a helper thread enqueues it later).
+struct BinChain {
+    // global-atomic fallback: counters must start at zero.  Empty scene: no binning kernel runs at all, so the tile table
+    // (counts, starts, counters) is simply zeroed.
+    bool zero_tables = false;
+    size_t zero_bytes = 0;
+    bool fill_memset = false;           // fixed-stride bins: the frame's fill block is dirty (the k_bin before it took another path)
+    ListPrep lp;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;    // timing level 2
+};
+
+// The binning chain of frame `f` (working set si) onto stream s: zero what must be zero, the draw list's items, then k_bin — ONE
+// launch: cull, setup, histogram, region reservation, fill — or setup / scan / fill.  `stop` is bound to the chain's last kernel
+// (see swr_context::bind_events); *bound = a kernel carries it.  Where k_sort_bins goes and what orders the chain against other
+// streams is the scheduler's business.
+int enqueue_binning(swr_context* c, const DeviceFrame& f, int si, hipStream_t s, const BinChain& b, hipEvent_t stop, bool* bound) {
+    if (b.zero_tables) HIP_TRY(c, hipMemsetAsync(c->slot[si].tilebuf.p, 0, b.zero_bytes, s));
+    if (b.fill_memset) HIP_TRY(c, hipMemsetAsync(f.fill, 0, (size_t)(CNT_WORDS + tiles_of(f.tg)) * 4, s));
+    { const int rl = enqueue_list_prep(c, b.lp, s); if (rl) return rl; }
+    if (b.e0) HIP_TRY(c, hipEventRecord(b.e0, s));
+    if (f.fixed_bins) {
+        *bound = launch_bin(f, s, stop);
+        if (b.e1) HIP_TRY(c, hipEventRecord(b.e1, s));
+        if (b.e2) HIP_TRY(c, hipEventRecord(b.e2, s));
+    } else {
+        launch_setup_bin(f, s);
+        if (b.e1) HIP_TRY(c, hipEventRecord(b.e1, s));
+        launch_scan(f, s);
+        if (b.e2) HIP_TRY(c, hipEventRecord(b.e2, s));
+        *bound = launch_fill(f, s, stop);
+    }
+    return SWR_OK;
+}
+
 int enqueue_frame(swr_context* c) {
     if (const int f = sticky(c)) return f;      // a failed context posts nothing more
     c->hp_begin();
     {
         const BinPlan plan = plan_binning(c->ni / 3, tiles_of(c->tg), c->dbg_bin_mode == 3);
-        if (plan.use_lds && !c->fixed_mode) {
-            const size_t need = (size_t)plan.G * (size_t)tiles_of(c->tg) * 4;
-            bool grow = false;
-            for (auto& sl : c->slot) grow = grow || sl.bin_matrix.bytes < need;
-            if (grow) {
-                int rc = sync_streams(c);
-                if (rc) return rc;
-                for (auto& sl : c->slot)
-                    if ((rc = ensure(c, sl.bin_matrix, need))) return rc;
-            }
+        if (plan.use_lds && !c->fixed_mode) {      // (exact-size bins only: never on the single-launch path)
+            LaneSizes t;
+            t.add(&swr_context::Slot::bin_matrix, (size_t)plan.G * (size_t)tiles_of(c->tg) * 4);
+            const int rc = grow_lanes(c, t);
+            if (rc) return rc;
         }
     }
     c->fb_last = c->fb_cur;
@@ -1012,10 +1051,10 @@ int enqueue_frame(swr_context* c) {
     const int si = (int)(frame % swr_context::NSLOT);
     c->last_slot = si;
     DeviceFrame f = make_frame(c, si, frame, c->last_m, c->last_flags);
-    ListPrep lp;
+    BinChain bc;
     if (c->last_list) {
         make_list_frame(c, si, f);
-        const int rc = stage_list(c, si, frame, lp);
+        const int rc = stage_list(c, si, frame, bc.lp);
         if (rc) { c->frame_no = frame; return rc; }
     }
     c->h_clip[frame % swr_context::PAIR_RING] = 0u;
@@ -1078,22 +1117,21 @@ int enqueue_frame(swr_context* c) {
     if (!f.fixed_bins) fill_word(c, frame) = 0;
     // fixed-stride bins: this frame's fill block must be zero when k_bin starts (the k_bin before it did that, unless that
     // frame took another path); k_bin leaves it dirty and zeroes the next frame's
-    bool fill_memset = false;
     const bool lanes = lane_mode(c);
     if (f.fixed_bins && lanes) {
         const int par = (int)((frame / (uint64_t)swr_context::NSLOT) & 1u);
-        fill_memset = c->lanefill_dirty[si][par];
+        bc.fill_memset = c->lanefill_dirty[si][par];
         c->lanefill_dirty[si][par] = true;
         c->lanefill_dirty[si][par ^ 1] = false;
     } else if (f.fixed_bins) {
         const int fbk = (int)(frame % swr_context::NFILL);
-        fill_memset = c->fill_dirty[fbk];
+        bc.fill_memset = c->fill_dirty[fbk];
         c->fill_dirty[fbk] = true;
         c->fill_dirty[(fbk + 1) % swr_context::NFILL] = false;
     }
-    const bool zero_tables = !f.fixed_bins && (!f.plan.use_lds || f.ntri <= 0);
-    const size_t zero_bytes = (size_t)(CNT_WORDS + 3 * tiles_of(c->tg) + 1) * 4;
-    hipEvent_t e0 = (ev && all) ? ev[0] : nullptr, e1 = (ev && all) ? ev[1] : nullptr, e2 = (ev && all) ? ev[2] : nullptr;
+    bc.zero_tables = !f.fixed_bins && (!f.plan.use_lds || f.ntri <= 0);
+    bc.zero_bytes = (size_t)(CNT_WORDS + 3 * tiles_of(c->tg) + 1) * 4;
+    if (ev && all) { bc.e0 = ev[0]; bc.e1 = ev[1]; bc.e2 = ev[2]; }
     if (lanes) {
         // ---- FRAME LANES: the whole frame, binning and raster, back to back on the lane's stream (see swr_context::lane_stream)
         hipStream_t S = c->lane_stream[si];
@@ -1127,21 +1165,8 @@ int enqueue_frame(swr_context* c) {
         if (src_wait && hipEventRecord(c->src_ready, c->last_stream) != hipSuccess)
             return fail_frame(fatal(c, SWR_ERR_HIP, "frame %llu: recording the source frame's completion failed", (unsigned long long)frame));
         auto enq = [&]() -> int {
-            if (zero_tables) HIP_TRY(c, hipMemsetAsync(c->slot[si].tilebuf.p, 0, zero_bytes, S));
-            if (fill_memset) HIP_TRY(c, hipMemsetAsync(f.fill, 0, (size_t)(CNT_WORDS + tiles_of(f.tg)) * 4, S));
-            { const int rl = enqueue_list_prep(c, lp, S); if (rl) return rl; }
-            if (e0) HIP_TRY(c, hipEventRecord(e0, S));
-            if (f.fixed_bins) {
-                launch_bin(f, S, nullptr);
-                if (e1) HIP_TRY(c, hipEventRecord(e1, S));
-                if (e2) HIP_TRY(c, hipEventRecord(e2, S));
-            } else {
-                launch_setup_bin(f, S);
-                if (e1) HIP_TRY(c, hipEventRecord(e1, S));
-                launch_scan(f, S);
-                if (e2) HIP_TRY(c, hipEventRecord(e2, S));
-                launch_fill(f, S, nullptr);
-            }
+            bool bound;
+            { const int rb = enqueue_binning(c, f, si, S, bc, nullptr, &bound); if (rb) return rb; }
             if (!f.skip_sort) launch_sort_bins(f, S, nullptr);
             if (src_wait) HIP_TRY(c, hipStreamWaitEvent(S, c->src_ready, 0));
             if (ev) HIP_TRY(c, hipEventRecord(ev[3], S));
@@ -1177,7 +1202,7 @@ int enqueue_frame(swr_context* c) {
     // helpers or the caller's own thread?  (idle context: every earlier frame is complete)
     const bool streaming = sb != sr && (c->bin_worker || c->ras_worker) && !(c->inline_idle && c->synced_upto == c->posted);
     const bool paced = streaming && c->ras_worker != nullptr;      // cross-stream order by host polls instead of event waits
-    auto bin_share = [c, f, si, sb, sr, frame, zero_tables, zero_bytes, e0, e1, e2, sort_on_raster_stream, slot_wait, paced, fill_memset, lp]() -> int {
+    auto bin_share = [c, f, si, sb, sr, frame, bc, sort_on_raster_stream, slot_wait, paced]() -> int {
         swr_context::Slot& sl = c->slot[si];
         if (slot_wait) {
             // the first event-carrying raster at or after that frame (RAS_EVERY); its event must have been bound /
@@ -1191,27 +1216,10 @@ int enqueue_frame(swr_context* c) {
                 else HIP_TRY(c, hipStreamWaitEvent(sb, es.ras_done, 0));
             }
         }
-        // global-atomic fallback: counters must start at zero.  Empty scene: no binning kernel runs at all, so the
-        // tile table (counts, starts, counters) is simply zeroed.
-        if (zero_tables) HIP_TRY(c, hipMemsetAsync(sl.tilebuf.p, 0, zero_bytes, sb));
-        if (fill_memset) HIP_TRY(c, hipMemsetAsync(f.fill, 0, (size_t)(CNT_WORDS + tiles_of(f.tg)) * 4, sb));
-        { const int rl = enqueue_list_prep(c, lp, sb); if (rl) return rl; }
-        if (e0) HIP_TRY(c, hipEventRecord(e0, sb));
         // bin_done = the completion of the chain's last kernel itself (bound at launch) where there is one
         hipEvent_t stop = (sb != sr && c->bind_events) ? sl.bin_done : nullptr;
         bool bound;
-        if (f.fixed_bins) {
-            // ONE launch: cull, setup, histogram, region reservation, fill (k_bin)
-            bound = launch_bin(f, sb, (sort_on_raster_stream || f.skip_sort) ? stop : nullptr);
-            if (e1) HIP_TRY(c, hipEventRecord(e1, sb));
-            if (e2) HIP_TRY(c, hipEventRecord(e2, sb));
-        } else {
-            launch_setup_bin(f, sb);
-            if (e1) HIP_TRY(c, hipEventRecord(e1, sb));
-            launch_scan(f, sb);
-            if (e2) HIP_TRY(c, hipEventRecord(e2, sb));
-            bound = launch_fill(f, sb, (sort_on_raster_stream || f.skip_sort) ? stop : nullptr);
-        }
+        { const int rb = enqueue_binning(c, f, si, sb, bc, (sort_on_raster_stream || f.skip_sort) ? stop : nullptr, &bound); if (rb) return rb; }
         if (!sort_on_raster_stream && !f.skip_sort) bound = launch_sort_bins(f, sb, stop);
         if (sb != sr && !bound) HIP_TRY(c, hipEventRecord(sl.bin_done, sb));
         HIP_TRY(c, hipGetLastError());
@@ -1219,7 +1227,7 @@ int enqueue_frame(swr_context* c) {
     };
     if (frame >= (uint64_t)swr_context::RAS_RING) {
         const int rc = wait_counter(c, c->ras_enqueued, frame - (uint64_t)swr_context::RAS_RING, "the raster share of an earlier frame");
-        if (rc) { c->frame_no = frame; return sticky(c) ? sticky(c) : rc; }     // nothing was posted for this frame
+        if (rc) { c->frame_no = frame; return or_sticky(c, rc); }     // nothing was posted for this frame
     }
     swr_context::RasJob& rj = c->ras_job[frame % swr_context::RAS_RING];
     rj.f = f; rj.ev3 = ev ? ev[3] : nullptr; rj.ev4 = ev ? ev[4] : nullptr; rj.si = si; rj.sort_here = sort_on_raster_stream;
@@ -1482,7 +1490,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     }
     HIP_TRY(c, hipMemcpyAsync(c->h_misc, c->slot[0].tilebuf.p, CNT_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->up_ev[2], c->stream));
-    if ((rc = wait_stream(c, c->stream, "scene upload"))) return sticky(c) ? sticky(c) : rc;
+    if ((rc = wait_stream(c, c->stream, "scene upload"))) return or_sticky(c, rc);
     (void)hipEventElapsedTime(&c->up_h2d_ms, c->up_ev[0], c->up_ev[1]);
     (void)hipEventElapsedTime(&c->up_build_ms, c->up_ev[1], c->up_ev[2]);
     if (c->h_misc[CNT_BAD_INDEX])
@@ -1500,10 +1508,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
         c->fixed_mode = false;                              // (re-sized below or at swr_target_set)
         c->k32_ok = true;
     }
-    if (!c->has_target) {
-        const uint64_t want = (uint64_t)(index_count / 3) * 2 + 65536;
-        return ensure_capacity(c, (uint32_t)std::min<uint64_t>(want, 0xFFFFFFF0ull));
-    }
+    if (!c->has_target) return ensure_capacity(c, first_capacity(index_count / 3));
     return size_bins(c);
 }
 
@@ -1524,7 +1529,7 @@ int single_scene_attributes(swr_context* c, const swr_vertex_attr* attributes, i
     launch_gather_attrs((const swr_vertex_attr*)c->attrs.p, vertex_count, (const int64_t*)c->indices.p, c->ni / 3,
                         (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = wait_stream(c, c->stream, "attribute upload"))) return sticky(c) ? sticky(c) : rc;
+    if ((rc = wait_stream(c, c->stream, "attribute upload"))) return or_sticky(c, rc);
     c->has_attrs = true;
     return SWR_OK;
 }
@@ -1552,7 +1557,7 @@ int single_texture_upload(swr_context* c, const void* bgra8, int32_t width, int3
     HIP_TRY(c, hipMemcpyAsync(c->texture_bytes.p, bgra8, n * 4, hipMemcpyHostToDevice, c->stream));
     launch_texture_to_float((const uint32_t*)c->texture_bytes.p, (int64_t)n, (float4*)c->texture.p, c->stream);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = wait_stream(c, c->stream, "texture upload"))) return sticky(c) ? sticky(c) : rc;
+    if ((rc = wait_stream(c, c->stream, "texture upload"))) return or_sticky(c, rc);
     c->tex_w = width; c->tex_h = height;
     return SWR_OK;
 }
@@ -1631,16 +1636,9 @@ int ensure_ids(swr_context* c, uint32_t flags) {
     return SWR_OK;
 }
 
-int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32_t primitive_type) {
-    int rc = check_draw_args(c, flags, primitive_type);
-    if (rc) return rc;
-    {
-        const int per = primitive_type == SWR_PRIMITIVE_LINE ? 2 : 3;          // verticesCount, Renderer.swift:179-188
-        if (c->has_scene && c->ni % per != 0)                                  // assert, Renderer.swift:209
-            return fail(c, SWR_ERR_INDEX_COUNT, "index_count %lld is not a multiple of %d", (long long)c->ni, per);
-    }
-    if (!c->has_scene || !c->has_target)
-        return fail(c, SWR_ERR_NO_SCENE, "swr_draw needs swr_scene_upload and swr_target_set first");
+// What swr_draw and swr_draw_list do alike once their arguments are in order.  Before the frame: the material has what it needs, the
+// ring of per-frame words has room, the ID images are there.
+int begin_draw(swr_context* c, uint32_t flags, int32_t primitive_type) {
     if (primitive_type == SWR_PRIMITIVE_TRIANGLE && !(flags & SWR_FLAG_NO_COLOR) &&
         c->material.shader != SWR_SHADER_PASSTHROUGH) {
         if (!c->has_attrs)
@@ -1651,16 +1649,15 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->frame_no - c->frames_checked >= (uint64_t)swr_context::PAIR_RING - 2) {
         // the ring of per-frame pair totals is about to wrap over frames nobody has looked at: look now (before
-        // the new transform replaces the one a redo of the last frame would need)
-        if ((rc = check_frames(c))) return rc;
+        // the new transform or list replaces the one a redo of the last frame would need)
+        const int rc = check_frames(c);
+        if (rc) return rc;
     }
-    if ((rc = ensure_ids(c, flags))) return rc;
-    // depth clipping: triangles only (.vertices and .line frames accept the bit and ignore it)
-    if (primitive_type != SWR_PRIMITIVE_TRIANGLE) flags &= ~(uint32_t)SWR_FLAG_DEPTH_CLIP;
-    if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, c->ni / 3, flags, transform))) return rc;
-    const bool persp = persp_frame(flags, primitive_type, affine_transform(transform));
-    if (persp && (rc = ensure_persp(c, (flags & SWR_FLAG_DEPTH_CLIP) ? clip_slots(c) : c->ni / 3))) return rc;
-    memcpy(c->last_m, transform, sizeof c->last_m);
+    return ensure_ids(c, flags);
+}
+
+// ... and the frame itself: where a load frame reads and writes, what a redo of the frame needs, the enqueue.
+int end_draw(swr_context* c, uint32_t flags, int32_t primitive_type, bool list, bool persp) {
     if (flags & SWR_FLAG_LOAD) {
         if (c->src_clear) {
             flags &= ~(uint32_t)SWR_FLAG_LOAD;      // loading the cleared image IS the clear frame
@@ -1674,10 +1671,30 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
     c->last_flags = flags;
     c->ids_valid = (flags & SWR_FLAG_PRIMITIVE_IDS) != 0;
     c->last_prim = primitive_type;
-    c->last_list = false;
+    c->last_list = list;
     c->last_clip = (flags & SWR_FLAG_DEPTH_CLIP) != 0;
     c->last_persp = persp;
     return enqueue_frame(c);
+}
+
+int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32_t primitive_type) {
+    int rc = check_draw_args(c, flags, primitive_type);
+    if (rc) return rc;
+    {
+        const int per = primitive_type == SWR_PRIMITIVE_LINE ? 2 : 3;          // verticesCount, Renderer.swift:179-188
+        if (c->has_scene && c->ni % per != 0)                                  // assert, Renderer.swift:209
+            return fail(c, SWR_ERR_INDEX_COUNT, "index_count %lld is not a multiple of %d", (long long)c->ni, per);
+    }
+    if (!c->has_scene || !c->has_target)
+        return fail(c, SWR_ERR_NO_SCENE, "swr_draw needs swr_scene_upload and swr_target_set first");
+    if ((rc = begin_draw(c, flags, primitive_type))) return rc;
+    // depth clipping: triangles only (.vertices and .line frames accept the bit and ignore it)
+    if (primitive_type != SWR_PRIMITIVE_TRIANGLE) flags &= ~(uint32_t)SWR_FLAG_DEPTH_CLIP;
+    if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, c->ni / 3, flags, transform))) return rc;
+    const bool persp = persp_frame(flags, primitive_type, affine_transform(transform));
+    if (persp && (rc = ensure_persp(c, (flags & SWR_FLAG_DEPTH_CLIP) ? clip_slots(c) : c->ni / 3))) return rc;
+    memcpy(c->last_m, transform, sizeof c->last_m);
+    return end_draw(c, flags, primitive_type, false, persp);
 }
 
 // ---- swr_draw_list ----------------------------------------------------------------------------------------------
@@ -1727,7 +1744,7 @@ int restream(swr_context* c, const std::vector<uint32_t>& cuts) {
         launch_gather_attrs((const swr_vertex_attr*)c->attrs.p, c->nv, (const int64_t*)c->indices.p, ntri,
                             (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = wait_stream(c, c->stream, "stream rebuild (draw list)"))) return sticky(c) ? sticky(c) : rc;
+    if ((rc = wait_stream(c, c->stream, "stream rebuild (draw list)"))) return or_sticky(c, rc);
     c->cuts = cuts;
     return SWR_OK;
 }
@@ -1737,17 +1754,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
     int64_t tris = 0;
     int rc = check_list_args(c, items, n, flags, c->has_scene && c->has_target, c->ni, &tris);
     if (rc) return rc;
-    if (!(flags & SWR_FLAG_NO_COLOR) && c->material.shader != SWR_SHADER_PASSTHROUGH) {
-        if (!c->has_attrs)
-            return fail(c, SWR_ERR_BAD_ARG, "the material needs vertex attributes (swr_scene_attributes)");
-        if (c->material.shader == SWR_SHADER_TEXTURED_PHONG && c->tex_w <= 0)
-            return fail(c, SWR_ERR_BAD_ARG, "the material needs a texture (swr_texture_upload)");
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->frame_no - c->frames_checked >= (uint64_t)swr_context::PAIR_RING - 2) {
-        if ((rc = check_frames(c))) return rc;
-    }
-    if ((rc = ensure_ids(c, flags))) return rc;
+    if ((rc = begin_draw(c, flags, SWR_PRIMITIVE_TRIANGLE))) return rc;
     // the items, resolved: primitive ranges, frame bases, work units
     std::vector<ListItem> list((size_t)n);
     std::vector<uint32_t> need;             // the cuts the stream needs
@@ -1763,7 +1770,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
         memcpy(it.m, items[k].transform, sizeof it.m);
         if (it.count) {
             units += (int64_t)((it.first + it.count - 1) >> 6) - (int64_t)(it.first >> 6) + 1;
-            affine = affine && it.m[3] == 0.0f && it.m[7] == 0.0f && it.m[11] == 0.0f && it.m[15] == 1.0f;
+            affine = affine && affine_transform(it.m);
             identity = identity && it.first == it.vbase;
             if (it.first > 0) need.push_back(it.first);
             if ((int64_t)it.first + it.count < ntri) need.push_back(it.first + it.count);
@@ -1783,62 +1790,20 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
             if ((rc = restream(c, cuts))) return rc;
         }
     }
-    // per-slot buffers for V frame slots (grown with every stream idle)
+    // per-slot buffers for V frame slots (grown with every stream idle); the frame's own per-slot tables only where the raster reads them
     {
+        using Slot = swr_context::Slot;
         const size_t V = (size_t)std::max<int64_t>(tris, 1);
         const bool color = !(flags & SWR_FLAG_NO_COLOR);
-        const bool ext = color && c->material.shader != SWR_SHADER_PASSTHROUGH;
-        auto small = [&](const swr_context::Slot& sl) {
-            return sl.geo.bytes < V * sizeof(GeomRec) || sl.geo_full.bytes < V * sizeof(GeomFull) || sl.ranges.bytes < V * sizeof(uint2) ||
-                   sl.items.bytes < std::max<size_t>(1, (size_t)n) * sizeof(ListItem) ||
-                   (!identity && (sl.linv.bytes < V * 4 || (color && sl.lrgb.bytes < V * 48) || (ext && sl.lnrm.bytes < V * 48)));
-        };
-        bool grow = false;
-        for (auto& sl : c->slot) grow = grow || small(sl);
-        if (grow) {
-            if ((rc = sync_streams(c))) return rc;
-            for (auto& sl : c->slot) {
-                if ((rc = ensure(c, sl.geo, V * sizeof(GeomRec)))) return rc;
-                if ((rc = ensure(c, sl.geo_full, V * sizeof(GeomFull)))) return rc;
-                if ((rc = ensure(c, sl.ranges, V * sizeof(uint2)))) return rc;
-                if ((rc = ensure(c, sl.items, std::max<size_t>(1, (size_t)n) * sizeof(ListItem)))) return rc;
-                if (!identity) {
-                    if ((rc = ensure(c, sl.linv, V * 4))) return rc;
-                    if (color && (rc = ensure(c, sl.lrgb, V * 48))) return rc;
-                    if (ext && (rc = ensure(c, sl.lnrm, V * 48))) return rc;
-                }
-            }
-        }
+        LaneSizes t;
+        t.add(&Slot::geo, V * sizeof(GeomRec)); t.add(&Slot::geo_full, V * sizeof(GeomFull)); t.add(&Slot::ranges, V * sizeof(uint2));
+        t.add(&Slot::items, std::max<size_t>(1, (size_t)n) * sizeof(ListItem));
+        if (!identity) t.add(&Slot::linv, V * 4);
+        if (!identity && color) t.add(&Slot::lrgb, V * 48);
+        if (!identity && color && c->material.shader != SWR_SHADER_PASSTHROUGH) t.add(&Slot::lnrm, V * 48);
+        if ((rc = grow_lanes(c, t))) return rc;
     }
-    // fixed-stride bins: k_bin<.., LIST> must be able to hold the list's work (a workgroup's share of the units below the cursor
-    // limit); a list beyond that moves the context to the exact-size bins, as a scene that needs more than a region would
-    // The first guess of the bins, as size_bins makes it for a scene, by the list's V: they only grow (with every stream idle)
-    const int tiles = tiles_of(c->tg);
-    if (c->fixed_mode && tris > 0) {
-        const uint32_t cmax = fixed_cap_max(units * 64, tiles);
-        if (cmax < c->cap_tile) {
-            if ((rc = sync_streams(c))) return rc;
-            c->fixed_mode = false;
-            c->fixed_allowed = false;
-        } else {
-            uint64_t want = std::max<uint64_t>(std::max<uint64_t>(64, (uint64_t)(6 * tris / tiles)), (uint64_t)std::min<int64_t>(tris, 1024));
-            // (capped for the scene's own frames too: a region survives into them, and their cursors must stay below 2^16)
-            want = std::min<uint64_t>((want + 63) & ~63ull, fixed_cap_max(std::max<int64_t>(ntri, units * 64), tiles));
-            if (want > c->cap_tile) {
-                if ((rc = sync_streams(c))) return rc;
-                if ((rc = ensure_bins(c, (size_t)tiles * want))) return rc;
-                c->cap_tile = (uint32_t)want;
-            }
-        }
-    }
-    if (!c->fixed_mode && tris > 0) {
-        const uint32_t want = (uint32_t)std::min<uint64_t>((uint64_t)tris * 2 + 65536, 0xFFFFFFF0ull);
-        if (want > c->capacity) {
-            if ((rc = sync_streams(c))) return rc;
-            if ((rc = ensure_capacity(c, want))) return rc;
-        }
-    }
-    c->list_plan_max = std::max<int64_t>(c->list_plan_max, units * 64);
+    if ((rc = fit_bins(c, tris, units * 64))) return rc;
     if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, tris, flags, nullptr))) return rc;
     const bool persp = persp_frame(flags, SWR_PRIMITIVE_TRIANGLE, affine);
     if (persp && (rc = ensure_persp(c, (flags & SWR_FLAG_DEPTH_CLIP) ? clip_slots(c) : tris))) return rc;
@@ -1847,22 +1812,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
     c->list_units = units;
     c->list_affine = affine;
     c->list_identity = identity;
-    if (flags & SWR_FLAG_LOAD) {
-        if (c->src_clear) {
-            flags &= ~(uint32_t)SWR_FLAG_LOAD;
-        } else {
-            c->load_src = c->fb_last;
-            if (c->fb_cur == c->load_src) c->fb_cur = (c->load_src + 1) % swr_context::NFB;
-        }
-    }
-    c->src_clear = false;
-    c->last_flags = flags;
-    c->ids_valid = (flags & SWR_FLAG_PRIMITIVE_IDS) != 0;
-    c->last_prim = SWR_PRIMITIVE_TRIANGLE;
-    c->last_list = true;
-    c->last_clip = (flags & SWR_FLAG_DEPTH_CLIP) != 0;
-    c->last_persp = persp;
-    return enqueue_frame(c);
+    return end_draw(c, flags, SWR_PRIMITIVE_TRIANGLE, true, persp);
 }
 
 // swr_present of the frame in fb_last: both images in flight together, each on its own copy stream
@@ -2038,7 +1988,7 @@ int single_target_write(swr_context* c, const void* color_full, const float* dep
         }
         if (color_full) HIP_TRY(c, hipMemcpyAsync(c->color[fb].p, (const uint32_t*)color_full + off, px * 4, hipMemcpyHostToDevice, c->stream));
         if (depth_full) HIP_TRY(c, hipMemcpyAsync(c->depth[fb].p, depth_full + off, px * 4, hipMemcpyHostToDevice, c->stream));
-        if ((rc = wait_stream(c, c->stream, "image upload"))) return sticky(c) ? sticky(c) : rc;
+        if ((rc = wait_stream(c, c->stream, "image upload"))) return or_sticky(c, rc);
     }
     c->src_clear = false;
     c->src_bad = false;
@@ -2075,7 +2025,7 @@ int single_read(swr_context* c, int img, void* dst) {
     const int fb = c->fb_last;
     HIP_TRY(c, hipEventRecord(c->frame_done[fb], c->stream));
     if ((rc = copy_band(c, fb, img, dst, c->frame_no ? c->frame_no - 1 : 0))) return rc;
-    if ((rc = wait_stream(c, c->copy_stream[img == 2 ? 1 : img], "copy stream"))) return sticky(c) ? sticky(c) : rc;
+    if ((rc = wait_stream(c, c->copy_stream[img == 2 ? 1 : img], "copy stream"))) return or_sticky(c, rc);
     return SWR_OK;
 }
 

@@ -55,5 +55,6 @@ hipError_t hipMemsetAsync(void* dst, int v, size_t n, hipStream_t s);
 
 // test-side hooks of the fake runtime
 #include <functional>
-void fake_enqueue(hipStream_t s, std::function<void()> op, hipEvent_t stop = nullptr);   // a "kernel"
+// a "kernel"; name and bytes are what the FAKE_HIP_TRACE line of the call shows
+void fake_enqueue(hipStream_t s, std::function<void()> op, hipEvent_t stop = nullptr, const char* name = "kernel", size_t bytes = 0);
 void fake_kernel_delay_us(int us);                                                           // how long a stand-in kernel takes

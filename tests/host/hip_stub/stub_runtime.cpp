@@ -4,6 +4,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -22,6 +23,7 @@ struct fake_stream {
     std::deque<std::function<void()>> q;
     std::atomic<uint64_t> enq{0}, done{0};
     bool quit = false;
+    int ordinal = 0;                                      // creation order (FAKE_HIP_TRACE)
     std::thread th;
     fake_stream() {
         th = std::thread([this] {
@@ -54,12 +56,22 @@ static std::set<const void*> g_pinned;
 static thread_local hipError_t tl_last = hipSuccess;
 
 void fake_kernel_delay_us(int us) { g_delay_us.store(us); }
+// FAKE_HIP_TRACE=<file>: one line per enqueued call (name, stream ordinal, bytes), appended in enqueue order; off by default
+static void trace(const char* call, hipStream_t s, size_t bytes) {
+    static const char* const path = getenv("FAKE_HIP_TRACE");
+    if (!path) return;
+    static std::mutex m;
+    static FILE* const out = fopen(path, "a");
+    std::lock_guard<std::mutex> lk(m);
+    if (out) { fprintf(out, "%s %d %zu\n", call, s->ordinal, bytes); fflush(out); }
+}
 static void complete(fake_event* e, uint64_t gen) {
     { std::lock_guard<std::mutex> lk(e->m); e->when = std::chrono::steady_clock::now(); }
     uint64_t c = e->completed.load(std::memory_order_relaxed);
     while (c < gen && !e->completed.compare_exchange_weak(c, gen, std::memory_order_release)) {}
 }
-void fake_enqueue(hipStream_t s, std::function<void()> op, hipEvent_t stop) {
+void fake_enqueue(hipStream_t s, std::function<void()> op, hipEvent_t stop, const char* name, size_t bytes) {
+    trace(name, s, bytes);
     uint64_t gen = 0;
     if (stop) gen = stop->recorded.fetch_add(1, std::memory_order_acq_rel) + 1;
     s->push([op, stop, gen] {
@@ -92,7 +104,12 @@ hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void* p) {
     tl_last = hipErrorInvalidValue;
     return hipErrorInvalidValue;
 }
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new fake_stream(); return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
+    static std::atomic<int> created{0};
+    *s = new fake_stream();
+    (*s)->ordinal = created.fetch_add(1);
+    return hipSuccess;
+}
 hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
 hipError_t hipStreamQuery(hipStream_t s) {
     if (s->done.load(std::memory_order_acquire) >= s->enq.load(std::memory_order_acquire)) return hipSuccess;
@@ -104,6 +121,7 @@ hipError_t hipEventCreate(hipEvent_t* e) { *e = new fake_event(); return hipSucc
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new fake_event(); return hipSuccess; }
 hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    trace("hipEventRecord", s, 0);
     const uint64_t gen = e->recorded.fetch_add(1, std::memory_order_acq_rel) + 1;
     s->push([e, gen] { complete(e, gen); });
     return hipSuccess;
@@ -115,6 +133,7 @@ hipError_t hipEventQuery(hipEvent_t e) {
 }
 hipError_t hipEventSynchronize(hipEvent_t e) { while (hipEventQuery(e) != hipSuccess) std::this_thread::yield(); tl_last = hipSuccess; return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    trace("hipStreamWaitEvent", s, 0);
     const uint64_t gen = e->recorded.load(std::memory_order_acquire);
     s->push([e, gen] { while (e->completed.load(std::memory_order_acquire) < gen) std::this_thread::yield(); });
     return hipSuccess;
@@ -128,10 +147,12 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     return hipSuccess;
 }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t s) {
+    trace("hipMemcpyAsync", s, n);
     s->push([dst, src, n] { memcpy(dst, src, n); });
     return hipSuccess;
 }
 hipError_t hipMemsetAsync(void* dst, int v, size_t n, hipStream_t s) {
+    trace("hipMemsetAsync", s, n);
     s->push([dst, v, n] { memset(dst, v, n); });
     return hipSuccess;
 }
