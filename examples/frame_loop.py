@@ -249,11 +249,14 @@ def view_flags(clip: bool = False, perspective: bool = False) -> int:
 
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
         time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False,
-        clip: bool = False, perspective: bool = False):
+        clip: bool = False, perspective: bool = False, glass: int | None = None):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
     mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
     frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel.
-    cull / front_ccw: face culling (cull_flags); clip / perspective: view_flags."""
+    cull / front_ccw: face culling (cull_flags); clip / perspective: view_flags.
+    glass = A (0..255): after the opaque frame a second, shifted and smaller instance of the mesh is drawn over it as a blend load
+    frame (SWR_FLAG_BLEND | SWR_FLAG_LOAD, SWR_BLEND_OVER at opacity A): you see the first instance through it; the depth image stays
+    the opaque frame's (not with --pick or --perspective)."""
     vertices, indices = load_mesh(obj) if obj else sphere_mesh()
     flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | (swr_amd.binding.FLAG_PRIMITIVE_IDS if pick else 0) | cull_flags(cull, front_ccw)
     flags |= view_flags(clip, perspective)
@@ -271,6 +274,13 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
                 m = S.app_transform(time)               # App.swift:169-183
                 items = [(0, indices.size, m)]
                 ctx.draw(m, flags)                      # renderer.render(renderPass:), App.swift:185
+            if glass is not None:
+                # the transparent pass: tested against the opaque scene's depth (with --depth-test), blended in draw order, no depth write
+                g = S.app_transform(time + 0.8, scale=0.7).reshape(4, 4).copy()
+                g[:, 0] += np.float32(0.25) * g[:, 3]
+                ctx.blend_set(swr_amd.binding.BLEND_OVER, glass)
+                ctx.draw(np.ascontiguousarray(g.reshape(16), dtype=np.float32),
+                         flags | swr_amd.binding.FLAG_BLEND | swr_amd.binding.FLAG_LOAD)
             color, depth = ctx.read_color(), ctx.read_depth()
             if pick:
                 # mouse picking: the ID under the pixel, mapped to (copy, triangle of the mesh) over the list's item bases
@@ -343,7 +353,16 @@ if __name__ == "__main__":
     ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
     ap.add_argument("--clip", action="store_true", help="depth clipping: triangles clipped against the near and far planes")
     ap.add_argument("--perspective", action="store_true", help="perspective-correct interpolation of colour and varyings")
+    ap.add_argument("--glass", type=int, default=None, metavar="A",
+                    help="draw a second instance over the mesh as a blend load frame with opacity A (0..255): alpha blending")
     a = ap.parse_args()
+    if a.glass is not None:
+        if not 0 <= a.glass <= 255:
+            ap.error("--glass: the opacity is 0..255")
+        if a.pick or a.perspective:
+            ap.error("--glass does not combine with --pick or --perspective (blend frames write no IDs and interpolate screen-linearly)")
+        if a.stream:
+            ap.error("--glass is not part of the --stream loop")
     if a.stream:
         res = run_streamed(a.frames, a.size, a.ply or a.obj, a.depth_test, device_count=a.gpus, cull=a.cull, front_ccw=a.front_ccw,
                            clip=a.clip, perspective=a.perspective)
@@ -351,6 +370,6 @@ if __name__ == "__main__":
         sys.exit(0)
     pick = tuple(int(t) for t in a.pick.split(",")) if a.pick else None
     _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick, cull=a.cull,
-                      front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective)
+                      front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

@@ -86,9 +86,54 @@ enum {
                                       without it front = clockwise as displayed (MTLWindingClockwise, Metal's default) */
     SWR_FLAG_DEPTH_CLIP = 1u << 10, /* clip every triangle against the near (z >= 0) and far (z <= w) planes before the divide, like
                                       Metal's default MTLDepthClipMode.clip (see "Depth clipping") */
-    SWR_FLAG_PERSPECTIVE = 1u << 11 /* interpolate colour and varyings with perspective correction, like Metal's [[center_perspective]]
+    SWR_FLAG_PERSPECTIVE = 1u << 11, /* interpolate colour and varyings with perspective correction, like Metal's [[center_perspective]]
                                       and GL's smooth (see "Perspective-correct interpolation") */
+    SWR_FLAG_BLEND = 1u << 12      /* every fragment is blended into the pixel, in draw order, instead of replacing it (Metal's
+                                      isBlendingEnabled; see "Alpha blending"); the state is set with swr_blend_set */
 };
+
+/* ---- Alpha blending (SWR_FLAG_BLEND, swr_blend_set) — DESIGN.md §18 ----------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6): the presence of the swr_blend_set symbol is the feature test; an older library refuses the
+ * flag bit with SWR_ERR_BAD_ARG.  Without the bit nothing changes.  (Bit 9 stays unused and refused.)
+ * The blend state (swr_blend, below) persists on the context like the material: it applies to every later frame drawn with the bit,
+ * on every band or device, swr_render included; a frame uses the state that was set when it was posted.
+ *
+ * Fragments and order.  A blend frame is Renderer.render(renderPass:) with one change: a fragment does not replace the pixel, it is
+ * blended into it.
+ *   Fragments: exactly those the same frame without the bit would generate — coverage of the active rule set (CPU scanline spans, or
+ *     the Metal inside test), after face culling and depth clipping, the same skipped triangles.
+ *   Order: fragments are taken per pixel in primitive order — index order, or for a draw list the order number (item order first);
+ *     depth-clip fan triangles in fan order, in their original's place.
+ *   Starting image: under SWR_FLAG_LOAD the image already there, exactly as for load frames ("Load frames" below); without it the
+ *     cleared image, colour (0,0,0,0), depth +inf.
+ * Depth.  The depth image is never written: after the frame it equals the starting depth image bit for bit, NaNs, -0 and +inf
+ *   included.  With SWR_FLAG_DEPTH_TEST (always under SWR_FLAG_METAL_RULES) a fragment contributes iff d < depth[x,y] of the STARTING
+ *   image, d the rule set's own depth expression; a NaN or +inf d never passes.  Without the z-test every fragment contributes.
+ *   This is the standard transparent pass: test against the opaque scene, write no depth.
+ * Arithmetic.  All integer and exact: no float blend, nothing drifts, opacity 0 and 255 are identities.
+ *   Source bytes (sb, sg, sr) of a fragment: the bytes the frame without the bit would store for it if it won the pixel — same
+ *     interpolation, clamp and quantiser as the rule set (trunc under the CPU rules, rint under the Metal rules); sa = 255.
+ *   SWR_BLEND_OVER, A = opacity, d the pixel's current byte, per channel b, g, r, a:  d' = (s*A + d*(255 - A) + 127) / 255
+ *     (integer division).
+ *   SWR_BLEND_ADD:  d' = min(255, d + (s*A + 127) / 255).
+ * Combinations.
+ *   SWR_FLAG_NO_COLOR with the bit: SWR_ERR_BAD_ARG.
+ *   SWR_FLAG_PRIMITIVE_IDS, SWR_FLAG_PERSPECTIVE, or a material whose shader is not SWR_SHADER_PASSTHROUGH: SWR_ERR_UNSUPPORTED.
+ *   .vertices and .line frames accept the bit and ignore it, like the cull and clip bits.
+ *   Cull, clip, load, depth test, Metal rules, draw lists (swr_draw_list), multi-band contexts and swr_render all combine with it.
+ * Properties that follow.
+ *   (a) OVER with opacity 255 and no z-test: the colour image is bit for bit that of the same frame without the bit (painter's order).
+ *   (b) Opacity 0: the colour image equals the starting colour image.
+ *   (c) A blend draw list is bit for bit the chain of its one-item blend frames, the first with the list's own load or clear start
+ *       and the rest SWR_FLAG_LOAD — with the z-test too, because depth never changes.
+ * Bin overflow: the load-frame rules apply unchanged.  An overflowed blend frame is rastered as "no triangles", so it shows the
+ *   starting image; it is redrawn from the same starting image, or reported with SWR_ERR_FRAME_DROPPED. */
+enum { SWR_BLEND_OVER = 0, SWR_BLEND_ADD = 1 };
+typedef struct swr_blend {
+    int32_t mode;        /* SWR_BLEND_* */
+    int32_t opacity;     /* 0..255 */
+    int32_t reserved[2]; /* 0 */
+} swr_blend;             /* 16 bytes */
 
 /* ---- Face culling (SWR_FLAG_CULL_BACK / _CULL_FRONT / _FRONT_CCW) — DESIGN.md §14 ------------------------------------------
  * No ABI bump (SWR_ABI_VERSION stays 6): a library that accepts the bits has the feature; an older one refuses them with
@@ -385,6 +430,10 @@ int swr_scene_upload(swr_context* ctx, const swr_vertex* vertices, int64_t verte
 int swr_scene_attributes(swr_context* ctx, const swr_vertex_attr* attributes, int64_t vertex_count);
 int swr_material_set(swr_context* ctx, const swr_material* material);
 int swr_texture_upload(swr_context* ctx, const void* bgra8, int32_t width, int32_t height);
+/* The blend state of SWR_FLAG_BLEND frames (see "Alpha blending" above); NULL restores the default, SWR_BLEND_OVER with opacity 255.
+ * An opacity outside 0..255, an unknown mode or a non-zero reserved word: SWR_ERR_BAD_ARG, and the state is unchanged.  Frames
+ * already posted keep the state they were posted with. */
+int swr_blend_set(swr_context* ctx, const swr_blend* blend);
 
 /* colorBuffer / depthBuffer size (Renderer.swift:192-193).  row_begin/row_end select the
  * tile-row band [row_begin,row_end) of the framebuffer this context owns; pass

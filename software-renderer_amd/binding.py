@@ -22,6 +22,8 @@ FLAG_CULL_FRONT = 128    # front-facing triangles are not drawn (with FLAG_CULL_
 FLAG_FRONT_CCW = 256     # front = counter-clockwise as displayed; without it clockwise (Metal's default winding)
 FLAG_DEPTH_CLIP = 1024   # depth clipping: triangles clipped against the near (z >= 0) and far (z <= w) planes (include/swr.h "Depth clipping")
 FLAG_PERSPECTIVE = 2048  # perspective-correct interpolation of colour and varyings (include/swr.h "Perspective-correct interpolation")
+FLAG_BLEND = 4096        # alpha blending: every fragment is blended into the pixel in draw order (include/swr.h "Alpha blending")
+BLEND_OVER, BLEND_ADD = 0, 1   # swr_blend.mode
 ID_NONE = 0xFFFFFFFF     # SWR_ID_NONE: a pixel where the frame keeps no fragment
 
 # every symbol include/swr.h declares (checked by tests/test_abi.py)
@@ -33,6 +35,7 @@ ABI_SYMBOLS = [
     "swr_timing_sample", "swr_context_bands", "swr_context_band_info", "swr_host_alloc", "swr_host_free",
     "swr_host_register", "swr_host_unregister", "swr_present", "swr_present_wait", "swr_device_count",
     "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list", "swr_read_ids",
+    "swr_blend_set",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -74,6 +77,11 @@ class Material(ctypes.Structure):
                    (ctypes.c_float * 4)(*[float(x) for x in sh.light_dir], 0.0),
                    (ctypes.c_float * 4)(*[float(x) for x in sh.half_dir], 0.0),
                    float(sh.ambient), float(sh.diffuse), float(sh.specular), 0.0)
+
+
+class Blend(ctypes.Structure):
+    """swr_blend (include/swr.h): the state of FLAG_BLEND frames."""
+    _fields_ = [("mode", ctypes.c_int32), ("opacity", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
 class Config(ctypes.Structure):
@@ -196,6 +204,12 @@ def load_library():
     try:
         L.swr_read_ids.argtypes = [vp, vp]
         L.swr_read_ids.restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
+    try:
+        L.swr_blend_set.argtypes = [vp, ctypes.POINTER(Blend)]
+        L.swr_blend_set.restype = ctypes.c_int
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
             raise
@@ -331,6 +345,15 @@ class Context:
 
     def material_set(self, material: "Material | None"):
         self._check(self._L.swr_material_set(self._h, ctypes.byref(material) if material is not None else None))
+
+    def blend_set(self, mode: int = BLEND_OVER, opacity: int = 255, blend: "Blend | None" = None, default: bool = False):
+        """swr_blend_set: the state of every later FLAG_BLEND frame (BLEND_OVER / BLEND_ADD, opacity 0..255); a ready-made Blend
+        is passed as it is; default=True passes NULL (OVER, opacity 255)."""
+        if default:
+            self._check(self._L.swr_blend_set(self._h, None))
+            return
+        b = blend if blend is not None else Blend(int(mode), int(opacity), (ctypes.c_int32 * 2)(0, 0))
+        self._check(self._L.swr_blend_set(self._h, ctypes.byref(b)))
 
     def texture_upload(self, texture: np.ndarray):
         t = np.ascontiguousarray(texture, dtype=np.uint8)

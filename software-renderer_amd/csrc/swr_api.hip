@@ -120,7 +120,7 @@ struct Worker {
 }  // namespace
 
 static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && sizeof(swr_vertex_attr) == 32 &&
-              sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28,
+              sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -169,6 +169,7 @@ struct swr_context {
     DevBuf attrs, tri_nrm, texture, texture_bytes;   // texture: float4 texels; texture_bytes: upload staging
     bool has_attrs = false;
     swr_material material{};            // shader 0 = the reference's passthrough stage
+    swr_blend blend{SWR_BLEND_OVER, 255, {0, 0}};   // swr_blend_set: the state of SWR_FLAG_BLEND frames
     int32_t tex_w = 0, tex_h = 0;
 
     // target band (RenderPass.colorBuffer / .depthBuffer), double-buffered in HBM: swr_present copies the frame just
@@ -350,6 +351,7 @@ struct swr_context {
     // last draw (for the overflow redo and for swr_render)
     float last_m[16]{};
     uint32_t last_flags = 0;
+    swr_blend last_blend{SWR_BLEND_OVER, 255, {0, 0}};   // the blend state the last frame was posted with (a redo draws with it again)
     int last_prim = SWR_PRIMITIVE_TRIANGLE;
     bool draw_pending = false;
 
@@ -755,6 +757,7 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
     memcpy(f.m, m, sizeof f.m);
     f.flags = flags;
     f.pq = c->last_persp ? (float4*)sl.pq.p : nullptr;
+    f.blend = c->last_blend;
     return f;
 }
 
@@ -1099,6 +1102,8 @@ int enqueue_frame(swr_context* c) {
     // bit 31 of that word: the latest rastered frame met triangles that cover hundreds of tiles — this frame's k_bin puts them on
     // the deferred list and k_sort_bins appends them per tile (swr_kernels.hip, BIN_BIG_TILES); 0xFFFFFFFF = nothing known yet
     f.defer_big = (fullest != 0xFFFFFFFFu && (fullest & 0x80000000u)) ? 1 : 0;
+    // a blend frame orders its bins itself (k_blend_order strips the class tags): no k_sort_bins, so nothing is deferred to it
+    if (f.flags & SWR_FLAG_BLEND) { f.skip_sort = 1; f.defer_big = 0; }
     // 32-bit depth keys: one tile in REDO_SAMPLE (8) reports when it had to be rastered again (~6x the time of a tile that did
     // not); from 2 % of the tiles on the 64-bit kernel is the cheaper one for this scene
     if (f.k32) {
@@ -1544,6 +1549,15 @@ int single_material_set(swr_context* c, const swr_material* m) {
     return SWR_OK;
 }
 
+int single_blend_set(swr_context* c, const swr_blend* b) {
+    if (!b) { c->blend = swr_blend{SWR_BLEND_OVER, 255, {0, 0}}; return SWR_OK; }
+    if (b->mode != SWR_BLEND_OVER && b->mode != SWR_BLEND_ADD) return fail(c, SWR_ERR_BAD_ARG, "swr_blend_set: unknown mode %d", b->mode);
+    if (b->opacity < 0 || b->opacity > 255) return fail(c, SWR_ERR_BAD_ARG, "swr_blend_set: opacity %d outside [0,255]", b->opacity);
+    if (b->reserved[0] != 0 || b->reserved[1] != 0) return fail(c, SWR_ERR_BAD_ARG, "swr_blend_set: reserved words must be 0");
+    c->blend = *b;          // copied into the next frames as they are posted (end_draw)
+    return SWR_OK;
+}
+
 int single_texture_upload(swr_context* c, const void* bgra8, int32_t width, int32_t height) {
     if (const int f = sticky(c)) return f;
     if (!bgra8 || width <= 0 || height <= 0 || width > 16384 || height > 16384)
@@ -1615,12 +1629,18 @@ int check_draw_args(swr_context* c, uint32_t flags, int32_t primitive_type) {
         return fail(c, SWR_ERR_UNSUPPORTED, "unknown primitive type %d", primitive_type);
     if (flags & ~(uint32_t)(SWR_FLAG_DEPTH_TEST | SWR_FLAG_NO_COLOR | SWR_FLAG_METAL_RULES | SWR_FLAG_REAL_LINES | SWR_FLAG_LOAD |
                             SWR_FLAG_PRIMITIVE_IDS | SWR_FLAG_CULL_BACK | SWR_FLAG_CULL_FRONT | SWR_FLAG_FRONT_CCW |
-                            SWR_FLAG_DEPTH_CLIP | SWR_FLAG_PERSPECTIVE))
+                            SWR_FLAG_DEPTH_CLIP | SWR_FLAG_PERSPECTIVE | SWR_FLAG_BLEND))
         return fail(c, SWR_ERR_BAD_ARG, "unknown flag bits 0x%x", flags);
     if ((flags & SWR_FLAG_REAL_LINES) && primitive_type != SWR_PRIMITIVE_LINE)
         return fail(c, SWR_ERR_BAD_ARG, "SWR_FLAG_REAL_LINES only applies to .line primitives");
     if ((flags & SWR_FLAG_PRIMITIVE_IDS) && primitive_type != SWR_PRIMITIVE_TRIANGLE)
         return fail(c, SWR_ERR_UNSUPPORTED, "SWR_FLAG_PRIMITIVE_IDS: triangles only");
+    // alpha blending: triangles only (.vertices and .line frames accept the bit and ignore it)
+    if ((flags & SWR_FLAG_BLEND) && primitive_type == SWR_PRIMITIVE_TRIANGLE) {
+        if (flags & SWR_FLAG_NO_COLOR) return fail(c, SWR_ERR_BAD_ARG, "SWR_FLAG_BLEND blends colour: not with SWR_FLAG_NO_COLOR");
+        if (flags & (SWR_FLAG_PRIMITIVE_IDS | SWR_FLAG_PERSPECTIVE))
+            return fail(c, SWR_ERR_UNSUPPORTED, "SWR_FLAG_BLEND does not combine with SWR_FLAG_PRIMITIVE_IDS or SWR_FLAG_PERSPECTIVE");
+    }
     return SWR_OK;
 }
 
@@ -1639,6 +1659,8 @@ int ensure_ids(swr_context* c, uint32_t flags) {
 // What swr_draw and swr_draw_list do alike once their arguments are in order.  Before the frame: the material has what it needs, the
 // ring of per-frame words has room, the ID images are there.
 int begin_draw(swr_context* c, uint32_t flags, int32_t primitive_type) {
+    if (primitive_type == SWR_PRIMITIVE_TRIANGLE && (flags & SWR_FLAG_BLEND) && c->material.shader != SWR_SHADER_PASSTHROUGH)
+        return fail(c, SWR_ERR_UNSUPPORTED, "SWR_FLAG_BLEND needs the passthrough fragment stage (swr_material_set(ctx, NULL))");
     if (primitive_type == SWR_PRIMITIVE_TRIANGLE && !(flags & SWR_FLAG_NO_COLOR) &&
         c->material.shader != SWR_SHADER_PASSTHROUGH) {
         if (!c->has_attrs)
@@ -1669,6 +1691,7 @@ int end_draw(swr_context* c, uint32_t flags, int32_t primitive_type, bool list, 
     }
     c->src_clear = false;
     c->last_flags = flags;
+    c->last_blend = c->blend;
     c->ids_valid = (flags & SWR_FLAG_PRIMITIVE_IDS) != 0;
     c->last_prim = primitive_type;
     c->last_list = list;
@@ -1689,7 +1712,7 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
         return fail(c, SWR_ERR_NO_SCENE, "swr_draw needs swr_scene_upload and swr_target_set first");
     if ((rc = begin_draw(c, flags, primitive_type))) return rc;
     // depth clipping: triangles only (.vertices and .line frames accept the bit and ignore it)
-    if (primitive_type != SWR_PRIMITIVE_TRIANGLE) flags &= ~(uint32_t)SWR_FLAG_DEPTH_CLIP;
+    if (primitive_type != SWR_PRIMITIVE_TRIANGLE) flags &= ~(uint32_t)(SWR_FLAG_DEPTH_CLIP | SWR_FLAG_BLEND);
     if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, c->ni / 3, flags, transform))) return rc;
     const bool persp = persp_frame(flags, primitive_type, affine_transform(transform));
     if (persp && (rc = ensure_persp(c, (flags & SWR_FLAG_DEPTH_CLIP) ? clip_slots(c) : c->ni / 3))) return rc;
@@ -2325,6 +2348,18 @@ int swr_material_set(swr_context* c, const swr_material* m) {
         return group_run(c, [=](swr_context* k) { return single_material_set(k, has ? &copy : nullptr); });
     }
     return single_material_set(c, m);
+}
+
+int swr_blend_set(swr_context* c, const swr_blend* b) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    if (is_group(c)) {
+        // (validated on the group first: a rejected state reaches no band)
+        int rc = single_blend_set(c, b);
+        if (rc) return rc;
+        const swr_blend copy = c->blend;
+        return group_run(c, [=](swr_context* k) { return single_blend_set(k, &copy); });
+    }
+    return single_blend_set(c, b);
 }
 
 int swr_texture_upload(swr_context* c, const void* bgra8, int32_t width, int32_t height) {

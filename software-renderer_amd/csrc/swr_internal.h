@@ -167,6 +167,8 @@ struct DeviceFrame {
     // SWR_FLAG_PERSPECTIVE colour frames through a non-affine transform: [ntri] per slot the raster sees, (q_a, q_b,
     // q_c, bypass) — filled in front of the binning (k_persp_fill; depth-clip frames: k_clip_emit); NULL: the screen weights
     float4* pq;
+    // SWR_FLAG_BLEND frames: the blend state as it was when the frame was posted (launch_raster: k_raster_blend)
+    swr_blend blend;
 };
 
 void launch_validate_indices(const int64_t* indices, int64_t count, int64_t vertex_count,

@@ -2859,6 +2859,308 @@ void k_raster_depth(RasterArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Alpha blending (SWR_FLAG_BLEND, include/swr.h "Alpha blending"): k_blend_order + k_raster_blend
+// ------------------------------------------------------------------------------------------
+// A blend frame keeps setup and binning as they are and replaces the raster: every fragment contributes, per pixel in primitive
+// order, so nothing here is a commutative minimum.  k_blend_order puts every tile's bin into order-number order (in place: the
+// entries become order numbers, class tags stripped); k_raster_blend walks the ordered bin, the four waves of a tile owning eight of
+// its rows each and a lane one column of them, colour and starting depth in registers from the first load to the only store.  No two
+// waves share a pixel: no barrier, no LDS, no atomics.
+struct BlendArgs {
+    const GeomRec* geo;
+    const GeomFull* geo_full;
+    const uint32_t* inv;        // order number -> slot (only when reordered)
+    int reordered;              // the order number is in GeomRec.flags (else: the slot itself)
+    const float4* tri_rgb;
+    const uint32_t* tile_start;
+    uint32_t* bins;
+    const uint32_t* counters;
+    uint32_t capacity;
+    const uint32_t* fill;       // fixed-stride bins: [CNT_WORDS counters][ntiles fills]; NULL = exact bins
+    uint32_t fixed_cap;
+    uint32_t* host_pairs;       // (as RasterArgs: the frame's pair total / largest fill / sort heuristic word for the host)
+    uint32_t* host_fill;
+    uint32_t* host_max;
+    int tag_class;
+    uint8_t* color;
+    float* depth;
+    const uint8_t* src_color;   // LOAD instances: the starting image (never color / depth)
+    const float* src_depth;
+    Target tg;
+    int mode, opacity;          // swr_blend
+};
+
+// the tile's bin; an overflowed frame has none (it shows the starting image; the host grows the bins and redraws it)
+__device__ __forceinline__ void blend_bin(const BlendArgs& a, int tile, uint32_t& b0, uint32_t& b1) {
+    b0 = 0u; b1 = 0u;
+    if (a.fixed_cap) {
+        if (a.fill[CNT_MAXFILL] <= a.fixed_cap) { b0 = (uint32_t)tile * a.fixed_cap; b1 = b0 + a.fill[CNT_WORDS + tile]; }
+    } else if (a.counters[CNT_PAIRS] <= a.capacity) {
+        b0 = a.tile_start[tile]; b1 = a.tile_start[tile + 1];
+    }
+}
+
+// One workgroup per tile: bin entries -> order numbers, sorted ascending.  A bitonic network whose comparators all put the smaller
+// value at the lower index (the first step of a merge mirrors, the others are half-cleaners), so a bin of any length sorts as the
+// front of a power of two whose tail holds +inf: a comparator that reaches into the tail never swaps.  Runs of BLEND_ORDER_CH
+// entries are sorted, and the short steps of the longer merges done, in LDS; only the steps that span runs go through global memory
+// (bins of more than 4 096 entries: rare, and the only ones that pay for it).
+constexpr uint32_t BLEND_ORDER_CH = 4096u;
+__global__ __launch_bounds__(256) void k_blend_order(BlendArgs a) {
+    __shared__ uint32_t s[BLEND_ORDER_CH];
+    const uint32_t tid = threadIdx.x;
+    uint32_t b0, b1;
+    blend_bin(a, (int)blockIdx.x, b0, b1);
+    const uint32_t m = b1 - b0;
+    if (m == 0u) return;                                   // (workgroup-uniform)
+    uint32_t* const bin = a.bins + b0;
+    const uint32_t bin_mask = a.tag_class ? (1u << CLASS_SHIFT) - 1u : 0xFFFFFFFFu;
+    uint32_t n2 = 1u;
+    while (n2 < m) n2 <<= 1;
+    const uint32_t nl = min(n2, BLEND_ORDER_CH);           // entries of one run
+    auto cmpx = [&](uint32_t lo, uint32_t hi) {
+        const uint32_t x = s[lo], y = s[hi];
+        if (x > y) { s[lo] = y; s[hi] = x; }
+    };
+    // runs: entry -> order number, the whole network up to the run length
+    for (uint32_t c0 = 0u; c0 < m; c0 += nl) {
+        for (uint32_t i = tid; i < nl; i += 256u) {
+            uint32_t key = 0xFFFFFFFFu;
+            if (c0 + i < m) {
+                const uint32_t slot = bin[c0 + i] & bin_mask;
+                key = a.reordered ? a.geo[slot].flags >> GEOM_ORIG_SHIFT : slot;
+            }
+            s[i] = key;
+        }
+        __syncthreads();
+        for (uint32_t k = 2u; k <= nl; k <<= 1) {
+            for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
+                const uint32_t lj = 31u - (uint32_t)__clz((int)j);      // (j and k are powers of two: shifts and masks, no division)
+                for (uint32_t t = tid; t < nl / 2u; t += 256u) {
+                    const uint32_t q = t & (j - 1u), lo2 = (t >> lj) << (lj + 1u);    // the comparator's block of 2j entries
+                    if (j == k >> 1) cmpx(lo2 + q, lo2 + k - 1u - q);
+                    else cmpx(lo2 + q, lo2 + q + j);
+                }
+                __syncthreads();
+            }
+        }
+        for (uint32_t i = tid; i < nl; i += 256u) if (c0 + i < m) bin[c0 + i] = s[i];
+        __syncthreads();
+    }
+    // merges of more than one run
+    for (uint32_t k = 2u * BLEND_ORDER_CH; k <= n2; k <<= 1) {
+        for (uint32_t j = k >> 1; j >= BLEND_ORDER_CH; j >>= 1) {
+            const uint32_t lj = 31u - (uint32_t)__clz((int)j);
+            for (uint32_t t = tid; t < n2 / 2u; t += 256u) {
+                const uint32_t q = t & (j - 1u), lo = ((t >> lj) << (lj + 1u)) + q;
+                const uint32_t hi = j == k >> 1 ? lo - q + k - 1u - q : lo + j;
+                if (hi < m) {
+                    const uint32_t x = bin[lo], y = bin[hi];
+                    if (x > y) { bin[lo] = y; bin[hi] = x; }
+                }
+            }
+            __syncthreads();
+        }
+        for (uint32_t c0 = 0u; c0 < m; c0 += BLEND_ORDER_CH) {
+            for (uint32_t i = tid; i < BLEND_ORDER_CH; i += 256u) s[i] = c0 + i < m ? bin[c0 + i] : 0xFFFFFFFFu;
+            __syncthreads();
+            for (uint32_t j = BLEND_ORDER_CH >> 1; j > 0u; j >>= 1) {
+                const uint32_t lj = 31u - (uint32_t)__clz((int)j);
+                for (uint32_t t = tid; t < BLEND_ORDER_CH / 2u; t += 256u) {
+                    const uint32_t lo = ((t >> lj) << (lj + 1u)) + (t & (j - 1u));
+                    cmpx(lo, lo + j);
+                }
+                __syncthreads();
+            }
+            for (uint32_t i = tid; i < BLEND_ORDER_CH; i += 256u) if (c0 + i < m) bin[c0 + i] = s[i];
+            __syncthreads();
+        }
+    }
+}
+
+// x / 255 for 0 <= x < 65536, exact
+__device__ __forceinline__ uint32_t div255(uint32_t x) { return (x * 0x8081u) >> 23; }
+// one channel (include/swr.h): OVER d' = (s*A + d*(255 - A) + 127) / 255;  ADD d' = min(255, d + (s*A + 127) / 255)
+__device__ __forceinline__ uint32_t blend_channel(uint32_t s, uint32_t d, uint32_t A, bool add) {
+    return add ? min(255u, d + div255(s * A + 127u)) : div255(s * A + d * (255u - A) + 127u);
+}
+
+constexpr int BLEND_WROWS = TILE_H / (RASTER_THREADS / 64);     // rows of the tile one wave owns
+static_assert(BLEND_WROWS == 8 && TILE_W == 64, "a lane owns one column of eight rows; a row's span packs into 16 bits");
+// ZTEST: a fragment contributes iff d < the STARTING depth (never written); METAL: the Metal rules (always z-tested); LOAD: the starting
+// image is a.src_color / a.src_depth, else the cleared one.
+// Per batch of 64 bin entries, lane = triangle: record, vertices, T() (or the divider constants), vertex colours and the spans of the
+// wave's eight rows clipped to the tile (row_span, 16 bits a row) — gathers and setup of 64 triangles in flight together.  Then the
+// triangles that touch the wave's rows, in order, one at a time: their constants broadcast from the owner lane, lane = column, for
+// every non-empty row the weights, depth, test, colour bytes and blend exactly as the key kernels' raster and resolve compute them.
+template <bool ZTEST, bool METAL, bool LOAD>
+__global__ __launch_bounds__(RASTER_THREADS) void k_raster_blend(BlendArgs a) {
+    static_assert(!METAL || ZTEST, "the Metal rules always z-test");
+    const int tile = (int)blockIdx.x;
+    const int tx = tile % a.tg.tiles_x, ty = tile / a.tg.tiles_x;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int X0 = tx * TILE_W, Y0 = a.tg.row_begin + ty * TILE_H;
+    const int X1 = min(X0 + TILE_W, a.tg.width) - 1;
+    const int Y1 = min(Y0 + TILE_H, a.tg.row_end) - 1;
+    if (a.fixed_cap && blockIdx.x == 0 && threadIdx.x == 0) {       // (what k_raster reports to the host, raster_tile)
+        *a.host_pairs = a.fill[CNT_PAIRS];
+        *a.host_fill = a.fill[CNT_MAXFILL];
+        if (a.host_max) *a.host_max = a.fill[CNT_MAXFILL] | ((a.fill[CNT_BIGLIST] | a.fill[CNT_BIGSEEN]) ? 0x80000000u : 0u);
+    }
+    const int Yw0 = Y0 + (tid >> 6) * BLEND_WROWS;                  // this wave's rows
+    const int Yw1 = min(Yw0 + BLEND_WROWS - 1, Y1);
+    if (Yw0 > Y1) return;                                           // (wave-uniform; the kernel has no barrier)
+    const int x = X0 + lane;
+    const size_t W = (size_t)a.tg.width;
+    uint32_t col[BLEND_WROWS], dep[BLEND_WROWS];                    // the column's pixels; depth as bits (NaN payloads, -0 travel untouched)
+#pragma unroll
+    for (int r = 0; r < BLEND_WROWS; r++) {
+        col[r] = 0u;                                                // Pixel(0,0,0,0) (:205)
+        dep[r] = 0x7F800000u;                                       // +inf (:206)
+        if (LOAD && x <= X1 && Yw0 + r <= Yw1) {
+            const size_t at = (size_t)(Yw0 + r - a.tg.row_begin) * W + (size_t)x;
+            col[r] = reinterpret_cast<const uint32_t*>(a.src_color)[at];
+            dep[r] = reinterpret_cast<const uint32_t*>(a.src_depth)[at];
+        }
+    }
+    uint32_t b0, b1;
+    blend_bin(a, tile, b0, b1);
+    const uint32_t m = b1 - b0;
+    const uint32_t A = (uint32_t)a.opacity;
+    const bool add = a.mode == SWR_BLEND_ADD;
+    const float fx = (float)x + 0.5f;                               // pixel centre (:245, Shaders.metal:133)
+    for (uint32_t i0 = 0u; i0 < m; i0 += 64u) {
+        // ---- lane = triangle ----
+        const bool have = i0 + (uint32_t)lane < m;
+        bool active = false;
+        float t00 = 0.0f, t01 = 0.0f, t10 = 0.0f, t11 = 0.0f, cfx = 0.0f, cfy = 0.0f, za = 0.0f, zb = 0.0f, zc = 0.0f;
+        float c0r = 0.0f, c0g = 0.0f, c0b = 0.0f, c1r = 0.0f, c1g = 0.0f, c1b = 0.0f, c2r = 0.0f, c2g = 0.0f, c2b = 0.0f;
+        uint32_t span[BLEND_WROWS / 2] = {0u, 0u, 0u, 0u};          // row r: lo | hi << 8 (tile-local) in half r & 1 of word r >> 1; 0x003F = none
+#pragma unroll
+        for (int r = 0; r < BLEND_WROWS / 2; r++) span[r] = 0x003F003Fu;
+        if (have) {
+            const uint32_t ord = a.bins[b0 + i0 + (uint32_t)lane];
+            const uint32_t slot = a.reordered ? a.inv[ord] : ord;
+            const int4 q0 = reinterpret_cast<const int4*>(a.geo + slot)[0];
+            const float4 q1 = reinterpret_cast<const float4*>(a.geo + slot)[1];
+            int vx[3], vy[3];
+            decode_vertices(a.geo_full, slot, q0, q1, vx, vy);
+            const uint32_t fl = __float_as_uint(q1.w);
+            const int o0 = (fl >> GEOM_ORD_SHIFT) & 3, o1 = (fl >> (GEOM_ORD_SHIFT + 2)) & 3, o2 = (fl >> (GEOM_ORD_SHIFT + 4)) & 3;
+            auto pick = [](int o, int p, int q, int r) { return o == 0 ? p : (o == 1 ? q : r); };
+            Chains ch;
+            ch.s0x = pick(o0, vx[0], vx[1], vx[2]); ch.s0y = pick(o0, vy[0], vy[1], vy[2]);
+            ch.s1x = pick(o1, vx[0], vx[1], vx[2]); ch.s1y = pick(o1, vy[0], vy[1], vy[2]);
+            ch.s2x = pick(o2, vx[0], vx[1], vx[2]); ch.s2y = pick(o2, vy[0], vy[1], vy[2]);
+            ch.small = (fl & GEOM_SMALL) != 0;
+            ch.r01 = __builtin_amdgcn_rcpf((float)(ch.s1y - ch.s0y));       // (as the cooperative walk of raster_tile)
+            ch.r12 = __builtin_amdgcn_rcpf((float)(ch.s2y - ch.s1y));
+            ch.r02 = __builtin_amdgcn_rcpf((float)(ch.s2y - ch.s0y));
+            const int minx = min(vx[0], min(vx[1], vx[2])), maxx = max(vx[0], max(vx[1], vx[2]));
+            const int ya = max(ch.s0y, Yw0);
+            const int yb = min(METAL ? ch.s2y - 1 : ch.s2y, Yw1);           // (Metal rules: the ROI's last row is never inside, raster_tile)
+            const int bxa = max(minx, X0), bxb = min(maxx, X1);
+            active = ya <= yb && bxa <= bxb;
+            if (active) {
+                bool any_row = false;
+#pragma unroll
+                for (int r = 0; r < BLEND_WROWS; r++) {
+                    const int y = Yw0 + r;
+                    int lo = 0, hi = -1;
+                    if (y >= ya && y <= yb) {
+                        if (METAL) { lo = bxa; hi = bxb; }                  // the ROI's x-range; the inside test decides per pixel
+                        else { row_span(ch, y, lo, hi); lo = max(lo, X0); hi = min(hi, X1); }
+                    }
+                    if (lo <= hi) {
+                        any_row = true;
+                        const uint32_t w = (uint32_t)(lo - X0) | ((uint32_t)(hi - X0) << 8);
+                        span[r >> 1] = (r & 1) ? (span[r >> 1] & 0x0000FFFFu) | (w << 16) : (span[r >> 1] & 0xFFFF0000u) | w;
+                    }
+                }
+                active = any_row;
+            }
+            if (active) {
+                if (METAL) {
+                    MetalTri mt;
+                    metal_consts(vx, vy, q1.x, q1.y, q1.z, mt);
+                    t00 = mt.A0; t01 = mt.B0; t10 = mt.A1; t11 = mt.B1; cfx = mt.p3x; cfy = mt.p3y;
+                } else {
+                    tinv_of(vx[0], vy[0], vx[1], vy[1], vx[2], vy[2], t00, t01, t10, t11);
+                    cfx = (float)vx[2] + 0.5f; cfy = (float)vy[2] + 0.5f;
+                }
+                za = q1.x; zb = q1.y; zc = q1.z;
+                const float* cp = reinterpret_cast<const float*>(a.tri_rgb + 3 * (size_t)slot);
+                c0r = cp[0]; c0g = cp[1]; c0b = cp[2]; c1r = cp[4]; c1g = cp[5]; c1b = cp[6]; c2r = cp[8]; c2g = cp[9]; c2b = cp[10];
+            }
+        }
+        // ---- lane = column: the batch's triangles that touch this wave's rows, in order ----
+        unsigned long long todo = __ballot(active);
+        while (todo) {
+            const int src = __builtin_amdgcn_readfirstlane((int)__ffsll((long long)todo) - 1);
+            todo &= todo - 1ull;
+            const float u00 = bcast_f(t00, src), u01 = bcast_f(t01, src), u10 = bcast_f(t10, src), u11 = bcast_f(t11, src);
+            const float ucx = bcast_f(cfx, src), ucy = bcast_f(cfy, src);
+            const float uza = bcast_f(za, src), uzb = bcast_f(zb, src), uzc = bcast_f(zc, src);
+            const float a_r = bcast_f(c0r, src), a_g = bcast_f(c0g, src), a_b = bcast_f(c0b, src);
+            const float b_r = bcast_f(c1r, src), b_g = bcast_f(c1g, src), b_b = bcast_f(c1b, src);
+            const float c_r = bcast_f(c2r, src), c_g = bcast_f(c2g, src), c_b = bcast_f(c2b, src);
+            uint32_t usp[BLEND_WROWS / 2];
+#pragma unroll
+            for (int r = 0; r < BLEND_WROWS / 2; r++) usp[r] = (uint32_t)bcast_i((int)span[r], src);
+            MetalTri mt;
+            if (METAL) {
+                mt.A0 = u00; mt.B0 = u01; mt.A1 = u10; mt.B1 = u11; mt.p3x = ucx; mt.p3y = ucy;
+                mt.divider = mt.B1 * mt.A0 - mt.B0 * mt.A1;     // == (p1-p3)x(p2-p3): same products, same rounding (raster_tile)
+                mt.z0 = uza; mt.z1 = uzb; mt.z2 = uzc;
+            }
+#pragma unroll
+            for (int r = 0; r < BLEND_WROWS; r++) {
+                const uint32_t w = (usp[r >> 1] >> ((r & 1) * 16)) & 0xFFFFu;
+                const int lo = (int)(w & 0xFFu), hi = (int)(w >> 8);
+                if (lo > hi) continue;                          // (wave-uniform)
+                if (lane < lo || lane > hi) continue;
+                const int y = Yw0 + r;
+                float w0, w1, w2;
+                bool pass = true;
+                if (METAL) {
+                    metal_weights_shared_rcp(mt, x, y, w0, w1, w2);                                            // Shaders.metal:133-149
+                    pass = 0.0f <= w0 && w0 <= 1.0f && 0.0f <= w1 && w1 <= 1.0f && 0.0f <= w2 && w2 <= 1.0f;   // :153
+                } else {
+                    const float dx = fx - ucx;
+                    const float dy = ((float)y + 0.5f) - ucy;
+                    w0 = u00 * dx + u01 * dy;
+                    w1 = u10 * dx + u11 * dy;
+                    w2 = 1.0f - w0 - w1;                                                                       // :92
+                }
+                if (ZTEST) {
+                    const float d = uza * w0 + uzb * w1 + uzc * w2;                                            // :257
+                    pass = pass && d < __uint_as_float(dep[r]);     // strict '<' against the starting depth: a NaN or +inf d never passes
+                }
+                if (!pass) continue;
+                const float fr = a_r * w0 + b_r * w1 + c_r * w2;                                               // :266
+                const float fg = a_g * w0 + b_g * w1 + c_g * w2;
+                const float fb = a_b * w0 + b_b * w1 + c_b * w2;
+                // Pixel(float3:) truncates (:116-128); the Metal path's bgra8Unorm store rounds to nearest even (raster_tile's resolve)
+                float ub = fminf(fmaxf(fb, 0.0f), 1.0f) * 255.0f, ug = fminf(fmaxf(fg, 0.0f), 1.0f) * 255.0f;
+                float ur = fminf(fmaxf(fr, 0.0f), 1.0f) * 255.0f;
+                if (METAL) { ub = rintf(ub); ug = rintf(ug); ur = rintf(ur); }
+                const uint32_t d = col[r];
+                col[r] = blend_channel((uint32_t)ub, d & 0xFFu, A, add) | (blend_channel((uint32_t)ug, (d >> 8) & 0xFFu, A, add) << 8) |
+                         (blend_channel((uint32_t)ur, (d >> 16) & 0xFFu, A, add) << 16) | (blend_channel(255u, d >> 24, A, add) << 24);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < BLEND_WROWS; r++) {
+        if (x <= X1 && Yw0 + r <= Yw1) {
+            const size_t at = (size_t)(Yw0 + r - a.tg.row_begin) * W + (size_t)x;
+            reinterpret_cast<uint32_t*>(a.color)[at] = col[r];
+            reinterpret_cast<uint32_t*>(a.depth)[at] = dep[r];      // the depth image is never written by a fragment: the starting bits
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // PrimitiveType .vertices (Renderer.swift:295-302) and .line (empty stub, :289-293)
 // ------------------------------------------------------------------------------------------
 // .vertices plots every transformed vertex reference at (Int(sx), Int(sy)) with its own colour, in
@@ -3229,6 +3531,35 @@ bool frame_uses_k32(const DeviceFrame& f) {
     return f.k32 && !(f.flags & SWR_FLAG_PRIMITIVE_IDS) && (f.flags & SWR_FLAG_DEPTH_TEST) && (f.flags & SWR_FLAG_NO_COLOR) && !(f.flags & SWR_FLAG_METAL_RULES);
 }
 
+// A blend frame's raster (SWR_FLAG_BLEND): its bins put in order, then k_raster_blend.  The host has kept PRIMITIVE_IDS, PERSPECTIVE,
+// NO_COLOR and the extended fragment stage away from it.
+static bool launch_raster_blend(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
+    const unsigned ntiles = (unsigned)(f.tg.tiles_x * f.tg.tiles_y);
+    if (ntiles == 0) return false;
+    const bool load = (f.flags & SWR_FLAG_LOAD) != 0;
+    BlendArgs a;
+    a.geo = f.geo; a.geo_full = f.geo_full; a.inv = f.inv; a.reordered = f.reordered; a.tri_rgb = f.tri_rgb;
+    a.tile_start = f.tile_start; a.bins = f.bins; a.counters = f.counters; a.capacity = f.capacity;
+    a.fill = f.fixed_bins ? f.fill : nullptr;
+    a.fixed_cap = f.fixed_bins ? f.cap_tile : 0u;
+    a.host_pairs = f.host_counters; a.host_fill = f.host_fill; a.host_max = f.host_max;
+    a.tag_class = f.ntri < (1ll << CLASS_SHIFT) ? 1 : 0;
+    a.color = f.color; a.depth = f.depth;
+    a.src_color = load ? f.src_color : nullptr;
+    a.src_depth = load ? f.src_depth : nullptr;
+    a.tg = f.tg;
+    a.mode = f.blend.mode; a.opacity = f.blend.opacity;
+    if (f.ntri > 0) hipLaunchKernelGGL(k_blend_order, dim3(ntiles), dim3(256), 0, s, a);
+#define SWR_BLEND_GO(ZT, MT) \
+    do { if (load) SWR_LAUNCH(stop, (k_raster_blend<ZT, MT, true>), dim3(ntiles), dim3(RASTER_THREADS), 0, s, a); \
+         else SWR_LAUNCH(stop, (k_raster_blend<ZT, MT, false>), dim3(ntiles), dim3(RASTER_THREADS), 0, s, a); } while (0)
+    if (f.flags & SWR_FLAG_METAL_RULES) SWR_BLEND_GO(true, true);
+    else if (f.flags & SWR_FLAG_DEPTH_TEST) SWR_BLEND_GO(true, false);
+    else SWR_BLEND_GO(false, false);
+#undef SWR_BLEND_GO
+    return stop != nullptr;
+}
+
 template <bool LOAD, bool IDS>
 static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     RasterArgs a;
@@ -3315,6 +3646,7 @@ static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop
 }
 
 bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
+    if (f.flags & SWR_FLAG_BLEND) return launch_raster_blend(f, s, stop);
     const bool load = (f.flags & SWR_FLAG_LOAD) != 0;
     // a depth-clip frame's IDs are order numbers of its clip stream: mapped to the original numbers behind the raster
     if (f.clip.bound > 0 && f.ids && f.tg.tiles_x * f.tg.tiles_y > 0) {

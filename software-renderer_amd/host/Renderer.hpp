@@ -150,6 +150,16 @@ inline uint32_t interpolationFlags(InterpolationMode mode) {
     return mode == InterpolationMode::perspective ? (uint32_t)SWR_FLAG_PERSPECTIVE : 0u;
 }
 
+// Alpha blending (include/swr.h "Alpha blending"; Metal's isBlendingEnabled on the colour attachment): a renderer whose blend state is
+// enabled draws every triangle pass as a blend frame — every fragment blended into the image in draw order, the depth image never
+// written.  opacity 0..255; the passthrough material only.
+enum class BlendMode : int32_t { over = SWR_BLEND_OVER, add = SWR_BLEND_ADD };
+struct BlendState {
+    bool enabled = false;
+    BlendMode mode = BlendMode::over;
+    int32_t opacity = 255;
+};
+
 // Renderer.swift:191-200 (+ the optional extended fragment stage: empty attributes / passthrough material
 // = the reference's RenderPass exactly; + the load action, clear by default = the reference; + face culling, none by default;
 // + depth clipping, none by default; + the interpolation mode, screen-linear by default)
@@ -191,7 +201,13 @@ public:
     Context& operator=(const Context&) = delete;
     // sceneId != 0: the caller's promise that p.vertices / p.indices / p.attributes / the texture hold what they held at
     // the last call with this id (swr_render_pass.scene_id): nothing is uploaded, the pass costs one resident frame + the gather
-    void render(const RenderPass& p, uint32_t flags, uint64_t sceneId = 0) {
+    void render(const RenderPass& p, uint32_t flags, uint64_t sceneId = 0, const BlendState& blend = BlendState{}) {
+        if (blend.enabled) {
+            const swr_blend b{(int32_t)blend.mode, blend.opacity, {0, 0}};
+            const int rcb = swr_blend_set(ctx_, &b);
+            if (rcb) throw RenderError(rcb, swr_last_error(ctx_));
+            flags |= (uint32_t)SWR_FLAG_BLEND;
+        }
         swr_render_pass rp{};
         rp.scene_id = sceneId;
         rp.color = p.colorBuffer.pointer;
@@ -276,9 +292,10 @@ public:
     // (Renderer.swift:289-293), the pass only clears; true = draw every line with the reference's own DDA
     // (draw(line:with:in:), Renderer.swift:405-419; SWR_FLAG_REAL_LINES)
     bool realLines = false;
+    BlendState blend;                   // enabled: triangle passes are blend frames (SWR_FLAG_BLEND), usually with LoadAction::load
     void render(const RenderPass& renderPass) {
         const bool lines = realLines && renderPass.primitiveType == PrimitiveType::line;
-        ctx_.render(renderPass, lines ? (uint32_t)SWR_FLAG_REAL_LINES : 0u, staticScene ? sceneVersion : 0);
+        ctx_.render(renderPass, lines ? (uint32_t)SWR_FLAG_REAL_LINES : 0u, staticScene ? sceneVersion : 0, blend);
     }
 private:
     detail::Context ctx_;
@@ -304,11 +321,12 @@ public:
     // true: every render() also writes the ID image (SWR_FLAG_PRIMITIVE_IDS; triangle passes only), read with readPrimitiveIds —
     // what a Metal app gets from a second colour attachment written with [[primitive_id]]
     bool primitiveIds = false;
+    BlendState blend;                   // see Renderer::blend (not together with primitiveIds: SWR_ERR_UNSUPPORTED)
     void render(const RenderPass& renderPass) {
         const bool lines = realLines && renderPass.primitiveType == PrimitiveType::line;
         ctx_.render(renderPass, (metalRules ? (uint32_t)SWR_FLAG_METAL_RULES : (depthTest ? (uint32_t)SWR_FLAG_DEPTH_TEST : 0u)) |
                                     (lines ? (uint32_t)SWR_FLAG_REAL_LINES : 0u) | (primitiveIds ? (uint32_t)SWR_FLAG_PRIMITIVE_IDS : 0u),
-                    staticScene ? sceneVersion : 0);
+                    staticScene ? sceneVersion : 0, blend);
     }
     // the ID image of the last render() (primitiveIds = true): colorBuffer.width * height words, row-major (mouse picking)
     void readPrimitiveIds(uint32_t* dst) { ctx_.readPrimitiveIds(dst); }

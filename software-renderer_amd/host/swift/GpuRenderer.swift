@@ -26,6 +26,9 @@ final class GpuRenderer {
     /// costs one resident frame plus the gather instead of a 120 MB upload.  false: upload on every call.
     var staticScene = false
     var sceneVersion: UInt64 = 1
+    /// Alpha blending (include/swr.h "Alpha blending"; Metal's isBlendingEnabled): non-nil = every triangle pass is a blend frame —
+    /// each fragment blended into the image in draw order with this mode and opacity (0...255), depth never written.
+    var blend: swr_blend? = nil
 
     /// deviceCount > 1: ONE renderer drives that many GPUs — the framebuffer is cut into tile-row bands, every band is
     /// copied straight into its rows of the caller's image (swr_config.device_count; include/swr.h).
@@ -47,6 +50,11 @@ final class GpuRenderer {
         pass.depth_bytes_per_row = Int64(renderPass.depthBuffer.bytesPerRow)
         pass.primitive_type = renderPass.primitiveType == .triangle ? 0 : (renderPass.primitiveType == .line ? 1 : 2)
         pass.flags = metalRules ? UInt32(SWR_FLAG_METAL_RULES) : (depthTest ? UInt32(SWR_FLAG_DEPTH_TEST) : 0)
+        if var b = blend {
+            let rcb = swr_blend_set(ctx, &b)
+            precondition(rcb == SWR_OK, String(cString: swr_last_error(ctx)))
+            pass.flags |= UInt32(SWR_FLAG_BLEND)
+        }
         pass.scene_id = staticScene ? sceneVersion : 0
         withUnsafeBytes(of: renderPass.transform) { src in          // matrix_float4x4 = 4 float4 columns
             withUnsafeMutableBytes(of: &pass.transform) { $0.copyMemory(from: src) }

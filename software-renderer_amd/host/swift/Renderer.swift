@@ -99,6 +99,9 @@ final class Renderer {
     /// render(renderPass:) resident on the GPU until `sceneVersion` changes.
     var staticScene = false
     var sceneVersion: UInt64 = 1
+    /// Alpha blending (include/swr.h "Alpha blending"): non-nil = every triangle pass is a blend frame — each fragment blended into
+    /// the image in draw order with this mode and opacity (0...255); the depth image is never written.
+    var blend: swr_blend? = nil
 
     private var ctx: OpaquePointer?
 
@@ -125,6 +128,11 @@ final class Renderer {
         case .vertices: pass.primitive_type = Int32(SWR_PRIMITIVE_VERTICES)
         }
         pass.flags = depthTest ? UInt32(SWR_FLAG_DEPTH_TEST) : 0
+        if var b = blend {
+            let rcb = swr_blend_set(ctx, &b)
+            precondition(rcb == SWR_OK, String(cString: swr_last_error(ctx)))
+            pass.flags |= UInt32(SWR_FLAG_BLEND)
+        }
         pass.scene_id = staticScene ? sceneVersion : 0
         withUnsafeBytes(of: renderPass.transform) { src in          // 4 columns of 4 floats, column-major, 64 bytes
             withUnsafeMutableBytes(of: &pass.transform) { $0.copyMemory(from: src) }
