@@ -7,7 +7,7 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
@@ -15,6 +15,10 @@ per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over 
 triangles are visible at pixel (X, Y): mouse picking (use it with --objects N).
 --cull {none,back,front} [--front-ccw] turns on face culling (Metal's setCullMode / setFrontFacingWinding): triangles that face
 away (back) or towards the viewer (front) are not drawn; front is clockwise as displayed unless --front-ccw.
+
+--ssaa S (2 or 4) draws every frame at S*size x S*size and resolves it on the device with an S x S box filter
+(swr_read_color_resolved / swr_read_depth_resolved): anti-aliased edges, alpha = the coverage of the pixel; only the size x size image
+crosses to the host.  With --pick the ID image stays at sample resolution and X,Y address the size x size image.  Default 1: as before.
 
 The demo mesh is a UV sphere standing in for ModelIO's `MDLMesh(sphereWithExtent: 0.4, segments: 13x13,
 inwardNormals: true)` (App.swift:124) with colour = |normal| (App.swift:133).  `--obj` loads a
@@ -249,21 +253,22 @@ def view_flags(clip: bool = False, perspective: bool = False) -> int:
 
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
         time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False,
-        clip: bool = False, perspective: bool = False, glass: int | None = None):
+        clip: bool = False, perspective: bool = False, glass: int | None = None, ssaa: int = 1):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
     mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
     frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel.
     cull / front_ccw: face culling (cull_flags); clip / perspective: view_flags.
     glass = A (0..255): after the opaque frame a second, shifted and smaller instance of the mesh is drawn over it as a blend load
     frame (SWR_FLAG_BLEND | SWR_FLAG_LOAD, SWR_BLEND_OVER at opacity A): you see the first instance through it; the depth image stays
-    the opaque frame's (not with --pick or --perspective)."""
+    the opaque frame's (not with --pick or --perspective).
+    ssaa = S (2 or 4): the frames are drawn at S * size and resolved on the device to size x size (the depth is sample (0,0))."""
     vertices, indices = load_mesh(obj) if obj else sphere_mesh()
     flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | (swr_amd.binding.FLAG_PRIMITIVE_IDS if pick else 0) | cull_flags(cull, front_ccw)
     flags |= view_flags(clip, perspective)
     results = []
     with swr_amd.Context() as ctx:
         ctx.scene_upload(vertices, indices)            # RenderPass.vertices / .indices, App.swift:163
-        ctx.target_set(size, size)                      # MetalView.Coordinator.width/height, App.swift:52-53
+        ctx.target_set(ssaa * size, ssaa * size)        # MetalView.Coordinator.width/height, App.swift:52-53 (times the samples per axis)
         time = time0
         for k in range(frames):
             if objects > 1:
@@ -281,11 +286,14 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
                 ctx.blend_set(swr_amd.binding.BLEND_OVER, glass)
                 ctx.draw(np.ascontiguousarray(g.reshape(16), dtype=np.float32),
                          flags | swr_amd.binding.FLAG_BLEND | swr_amd.binding.FLAG_LOAD)
-            color, depth = ctx.read_color(), ctx.read_depth()
+            if ssaa > 1:
+                color, depth = ctx.read_color_resolved(ssaa), ctx.read_depth_resolved(ssaa)
+            else:
+                color, depth = ctx.read_color(), ctx.read_depth()
             if pick:
                 # mouse picking: the ID under the pixel, mapped to (copy, triangle of the mesh) over the list's item bases
                 x, y = pick
-                ids = ctx.read_ids()
+                ids = ctx.read_ids()[::ssaa, ::ssaa]     # (IDs are not resolved: sample (0,0) of the pixel, like the depth)
                 obj_k, tri = swr_amd.binding.list_ids_to_items(ids[y:y + 1, x:x + 1], items)
                 if obj_k[0, 0] < 0:
                     print(f"frame {k}: pixel ({x}, {y}): nothing")
@@ -355,7 +363,11 @@ if __name__ == "__main__":
     ap.add_argument("--perspective", action="store_true", help="perspective-correct interpolation of colour and varyings")
     ap.add_argument("--glass", type=int, default=None, metavar="A",
                     help="draw a second instance over the mesh as a blend load frame with opacity A (0..255): alpha blending")
+    ap.add_argument("--ssaa", type=int, choices=[1, 2, 4], default=1,
+                    help="supersampling: draw at S x size and resolve S x S samples per pixel on the device")
     a = ap.parse_args()
+    if a.ssaa != 1 and a.stream:
+        ap.error("--ssaa is not part of the --stream loop (there is no asynchronous resolved present)")
     if a.glass is not None:
         if not 0 <= a.glass <= 255:
             ap.error("--glass: the opacity is 0..255")
@@ -370,6 +382,6 @@ if __name__ == "__main__":
         sys.exit(0)
     pick = tuple(int(t) for t in a.pick.split(",")) if a.pick else None
     _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick, cull=a.cull,
-                      front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass)
+                      front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass, ssaa=a.ssaa)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

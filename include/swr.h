@@ -135,6 +135,46 @@ typedef struct swr_blend {
     int32_t reserved[2]; /* 0 */
 } swr_blend;             /* 16 bytes */
 
+/* ---- Supersampled resolve (swr_read_color_resolved, swr_read_depth_resolved, swr_render_resolved) — DESIGN.md §19 ------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the three symbols is the feature test.  Nothing existing
+ * changes.  Supersampling is Metal's storeAction = .multisampleResolve with sample-rate shading: the frame is drawn at S*w x S*h with
+ * the same transform — every rule set, flag, blend frame, band and draw list as it is — and an S x S box filter, on the device,
+ * brings it down to w x h.  Only the small image crosses to the host.
+ *
+ * W x H is the target set by swr_target_set; w = W / S, h = H / S (swr_resolve.factor = S).
+ *   Colour.  For output pixel (x, y) and each channel c of b, g, r, a:
+ *       out = (Σ_{j<S} Σ_{i<S} src[S·y+j][S·x+i][c] + S·S/2) / (S·S), integer division.
+ *     Nothing is gamma-corrected.  A cleared pixel is (0,0,0,0) and a covered one has a = 255, so the resolved alpha is the coverage
+ *     of the pixel (255 = every sample covered), usable for compositing the anti-aliased image over a background.
+ *   Depth, SWR_RESOLVE_DEPTH_SAMPLE0.  The bits of src[S·y][S·x].
+ *   Depth, SWR_RESOLVE_DEPTH_MIN.  Take m = sample (0,0), then the other samples in row-major order (j outer, i inner):
+ *       if (s < m || (m != m && s == s)) m = s
+ *     The result is the bits of m.  NaNs lose to any number; if all samples are NaN the first one's bits are kept, payload included;
+ *     of equal zeros the first met is kept, so -0 and +0 survive as they are; +inf (the cleared depth) and denormals compare exactly.
+ *   factor == 1.  The destination is byte for byte what swr_read_color / swr_read_depth deliver.
+ *   Completion.  The calls complete everything first, like swr_read_*: an overflowed last frame is repaired before it is resolved, and
+ *     the image resolved is that of the last frame.  The full-size images on the device are not modified: a following SWR_FLAG_LOAD
+ *     frame, swr_read_color, swr_read_depth and swr_read_ids see them unchanged.  After a SWR_FLAG_NO_COLOR frame the resolved colour is
+ *     as unspecified as swr_read_color's.
+ *   Bands.  Each band resolves its own rows [row_begin, row_end) into rows [row_begin/S, row_end/S) of the caller's w x h image; rows
+ *     outside the band(s) are left untouched.  row_begin is a multiple of the tile height (32) and row_end is either a multiple of 32
+ *     or equal to H, so with H a multiple of S no sample block straddles two bands.  Multi-device contexts fan out like swr_read_*.
+ *   Errors.  SWR_ERR_BAD_ARG: a NULL argument, a factor outside {1, 2, 4}, an unknown filter, a non-zero reserved word, or W or H not
+ *     a multiple of S (or a band whose row_end is neither);  SWR_ERR_NO_SCENE: no target;  a failed context returns its sticky error,
+ *     as elsewhere.
+ * swr_render_resolved(ctx, pass, resolve) is swr_render with pass->width, pass->height, pass->color and pass->depth describing the
+ *   DESTINATION, w x h: the frame is drawn at S·w x S·h with the pass's transform and flags, then resolved into the caller's images.
+ *   scene_id caching works as in swr_render; swr_render_times.gather_ms covers the resolve plus the copy; frames is 2 after a
+ *   repaired overflow.  SWR_FLAG_LOAD: SWR_ERR_UNSUPPORTED (the starting image would be at the wrong resolution).  SWR_FLAG_NO_COLOR:
+ *   the colour is not resolved, and color may be NULL.  .vertices and .line passes resolve like any other.  With
+ *   SWR_FLAG_PRIMITIVE_IDS the ID image stays at sample resolution: swr_read_ids delivers S·w x S·h words (IDs are not resolved). */
+enum { SWR_RESOLVE_DEPTH_SAMPLE0 = 0, SWR_RESOLVE_DEPTH_MIN = 1 };
+typedef struct swr_resolve {
+    int32_t factor;        /* S: 1, 2 or 4 samples per axis */
+    int32_t depth_filter;  /* SWR_RESOLVE_DEPTH_* (ignored by swr_read_color_resolved, but checked) */
+    int32_t reserved[2];   /* 0 */
+} swr_resolve;             /* 16 bytes */
+
 /* ---- Face culling (SWR_FLAG_CULL_BACK / _CULL_FRONT / _FRONT_CCW) — DESIGN.md §14 ------------------------------------------
  * No ABI bump (SWR_ABI_VERSION stays 6): a library that accepts the bits has the feature; an older one refuses them with
  * SWR_ERR_BAD_ARG.
@@ -517,6 +557,12 @@ int swr_present_wait(swr_context* ctx);
 int swr_read_color(swr_context* ctx, void* dst_full_image);
 int swr_read_depth(swr_context* ctx, float* dst_full_image);
 int swr_read_ids(swr_context* ctx, uint32_t* dst_full_image);   /* SWR_FLAG_PRIMITIVE_IDS frames (see "Primitive IDs" above) */
+/* Supersampled resolve (see "Supersampled resolve" above): swr_sync + the S x S box filter on the device + the copy of the small
+ * image + wait.  The destination has (W/S) x (H/S) elements; page-locked and pageable destinations both work, as for swr_read_*. */
+int swr_read_color_resolved(swr_context* ctx, const swr_resolve* resolve, void*  dst);  /* (W/S) x (H/S) BGRA8 */
+int swr_read_depth_resolved(swr_context* ctx, const swr_resolve* resolve, float* dst);  /* (W/S) x (H/S) floats */
+/* swr_render at S·width x S·height, resolved into the pass's width x height images (both images in one launch per band). */
+int swr_render_resolved(swr_context* ctx, const swr_render_pass* pass, const swr_resolve* resolve);
 
 /* Timing instrumentation: hipEvents on the context stream.  level 0 = off, 1 = two events around
  * the dominant kernel (k_raster) only, 2 = around every stage (each event costs a few us of

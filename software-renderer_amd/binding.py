@@ -24,6 +24,7 @@ FLAG_DEPTH_CLIP = 1024   # depth clipping: triangles clipped against the near (z
 FLAG_PERSPECTIVE = 2048  # perspective-correct interpolation of colour and varyings (include/swr.h "Perspective-correct interpolation")
 FLAG_BLEND = 4096        # alpha blending: every fragment is blended into the pixel in draw order (include/swr.h "Alpha blending")
 BLEND_OVER, BLEND_ADD = 0, 1   # swr_blend.mode
+RESOLVE_DEPTH_SAMPLE0, RESOLVE_DEPTH_MIN = 0, 1   # swr_resolve.depth_filter (include/swr.h "Supersampled resolve")
 ID_NONE = 0xFFFFFFFF     # SWR_ID_NONE: a pixel where the frame keeps no fragment
 
 # every symbol include/swr.h declares (checked by tests/test_abi.py)
@@ -35,7 +36,7 @@ ABI_SYMBOLS = [
     "swr_timing_sample", "swr_context_bands", "swr_context_band_info", "swr_host_alloc", "swr_host_free",
     "swr_host_register", "swr_host_unregister", "swr_present", "swr_present_wait", "swr_device_count",
     "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list", "swr_read_ids",
-    "swr_blend_set",
+    "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -82,6 +83,11 @@ class Material(ctypes.Structure):
 class Blend(ctypes.Structure):
     """swr_blend (include/swr.h): the state of FLAG_BLEND frames."""
     _fields_ = [("mode", ctypes.c_int32), ("opacity", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+class Resolve(ctypes.Structure):
+    """swr_resolve (include/swr.h): the factor S (1, 2 or 4 samples per axis) and the depth filter of a supersampled resolve."""
+    _fields_ = [("factor", ctypes.c_int32), ("depth_filter", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
 class Config(ctypes.Structure):
@@ -212,6 +218,15 @@ def load_library():
         L.swr_blend_set.restype = ctypes.c_int
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
+    try:
+        L.swr_read_color_resolved.argtypes = [vp, ctypes.POINTER(Resolve), vp]
+        L.swr_read_depth_resolved.argtypes = [vp, ctypes.POINTER(Resolve), vp]
+        L.swr_render_resolved.argtypes = [vp, ctypes.POINTER(RenderPass), ctypes.POINTER(Resolve)]
+        for name in ("swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved"):
+            getattr(L, name).restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
             raise
     L.swr_target_write.argtypes = [vp, vp, vp]
     L.swr_target_write.restype = ctypes.c_int
@@ -512,6 +527,36 @@ class Context:
         self._check(self._L.swr_read_ids(self._h, out.ctypes.data))
         return out
 
+    @staticmethod
+    def _dst_ptr(x):
+        return x.ptr if isinstance(x, HostImage) else x.ctypes.data
+
+    def read_color_resolved(self, factor: int, out=None, resolve: "Resolve | None" = None) -> np.ndarray:
+        """swr_read_color_resolved: the last frame's colour image through the factor x factor box filter, computed on the device —
+        (height / factor, width / factor, 4) uint8; alpha is the coverage of the pixel.  `out`: a NumPy array or a HostImage of that
+        size; rows outside the context's band(s) are left untouched.  A ready-made Resolve is passed as it is."""
+        r = resolve if resolve is not None else Resolve(int(factor), RESOLVE_DEPTH_SAMPLE0, (ctypes.c_int32 * 2)(0, 0))
+        f = max(1, int(r.factor))
+        if out is None:
+            out = np.zeros((self.height // f, self.width // f, 4), dtype=np.uint8)
+        arr = out.array if isinstance(out, HostImage) else out
+        assert arr.flags.c_contiguous and (arr.nbytes == (self.width // f) * (self.height // f) * 4 or (resolve is not None and out is not None))
+        self._check(self._L.swr_read_color_resolved(self._h, ctypes.byref(r), self._dst_ptr(out)))
+        return arr
+
+    def read_depth_resolved(self, factor: int, depth_filter: int = RESOLVE_DEPTH_SAMPLE0, out=None,
+                            resolve: "Resolve | None" = None) -> np.ndarray:
+        """swr_read_depth_resolved: (height / factor, width / factor) float32 — sample (0,0) of every block (RESOLVE_DEPTH_SAMPLE0)
+        or the block's minimum, NaNs losing (RESOLVE_DEPTH_MIN)."""
+        r = resolve if resolve is not None else Resolve(int(factor), int(depth_filter), (ctypes.c_int32 * 2)(0, 0))
+        f = max(1, int(r.factor))
+        if out is None:
+            out = np.zeros((self.height // f, self.width // f), dtype=np.float32)
+        arr = out.array if isinstance(out, HostImage) else out
+        assert arr.flags.c_contiguous and (arr.nbytes == (self.width // f) * (self.height // f) * 4 or (resolve is not None and out is not None))
+        self._check(self._L.swr_read_depth_resolved(self._h, ctypes.byref(r), self._dst_ptr(out)))
+        return arr
+
     def timing_enable(self, level=2):
         """0/False off, 1 = events around k_raster only, 2/True = around every stage."""
         level = 2 if level is True else (0 if level is False else int(level))
@@ -542,10 +587,20 @@ class Context:
     # -- one-shot path: Renderer.render(renderPass:) / GpuRenderer.render(renderPass:) -----
     def render(self, vertices, indices, transform, width, height, flags=0, primitive_type=0,
                color=None, depth=None, shading=None, scene_id=0):
+        return self._render(None, vertices, indices, transform, width, height, flags, primitive_type, color, depth, shading, scene_id)
+
+    def render_resolved(self, vertices, indices, transform, width, height, flags=0, primitive_type=0,
+                        color=None, depth=None, shading=None, scene_id=0, factor=2, depth_filter=RESOLVE_DEPTH_SAMPLE0):
+        """swr_render_resolved: Context.render with (width, height, color, depth) describing the DESTINATION; the frame is drawn at
+        factor * width x factor * height and resolved on the device (include/swr.h "Supersampled resolve").  FLAG_LOAD is refused."""
+        r = Resolve(int(factor), int(depth_filter), (ctypes.c_int32 * 2)(0, 0))
+        return self._render(r, vertices, indices, transform, width, height, flags, primitive_type, color, depth, shading, scene_id)
+
+    def _render(self, resolve, vertices, indices, transform, width, height, flags, primitive_type, color, depth, shading, scene_id):
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 8)
         i = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
         m = np.ascontiguousarray(transform, dtype=np.float32).reshape(16)
-        if (flags & FLAG_LOAD) and (depth is None or (color is None and not (flags & FLAG_NO_COLOR))):
+        if resolve is None and (flags & FLAG_LOAD) and (depth is None or (color is None and not (flags & FLAG_NO_COLOR))):
             raise ValueError("render with FLAG_LOAD: color / depth are the starting image and must be given")
         if color is None and not (flags & FLAG_NO_COLOR):
             color = np.full((height, width, 4), 0xCD, dtype=np.uint8)
@@ -570,8 +625,13 @@ class Context:
             if shading.texture is not None:
                 t = np.ascontiguousarray(shading.texture, dtype=np.uint8)
                 rp.texture, rp.tex_width, rp.tex_height = t.ctypes.data, t.shape[1], t.shape[0]
-        self._check(self._L.swr_render(self._h, ctypes.byref(rp)))
-        self.width, self.height, self.row_begin, self.row_end = width, height, 0, height     # (swr_render sets the target: read_ids)
+        if resolve is None:
+            self._check(self._L.swr_render(self._h, ctypes.byref(rp)))
+            S = 1
+        else:
+            self._check(self._L.swr_render_resolved(self._h, ctypes.byref(rp), ctypes.byref(resolve)))
+            S = int(resolve.factor)      # the target is the supersampled one: read_ids delivers S * width x S * height words
+        self.width, self.height, self.row_begin, self.row_end = S * width, S * height, 0, S * height     # (swr_render sets the target: read_ids)
         return color, depth
 
 

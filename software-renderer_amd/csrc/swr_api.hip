@@ -34,6 +34,14 @@
 
 #include "swr_internal.h"
 
+// The host layer is also built without the kernels, against stand-in launch functions (tests/host/hip_stub); a stand-in set that
+// predates the supersampled resolve does not define its launch.  The reference is weak so that such a program still links; the library
+// always carries k_resolve, and a resolved read without it fails loudly (single_read_resolved).
+namespace swr {
+__attribute__((weak)) void launch_resolve(const void* color, const void* depth, void* color_out, void* depth_out, int width, int rows,
+                                          int factor, int depth_filter, hipStream_t s);
+}
+
 using namespace swr;
 
 namespace {
@@ -120,7 +128,8 @@ struct Worker {
 }  // namespace
 
 static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && sizeof(swr_vertex_attr) == 32 &&
-              sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16,
+              sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16 &&
+              sizeof(swr_resolve) == 16,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -188,7 +197,10 @@ struct swr_context {
     // that never asks pays no memory); ids_valid = the last frame wrote one (cleared by swr_target_set / swr_target_write)
     DevBuf ids[NFB];
     bool ids_valid = false;
-    int fb_cur = 0;                     // the next swr_draw renders into this buffer
+    // supersampled resolve: the band's resolved colour and depth images, (W/S) x (band rows/S), sized by the first
+    // resolved read (k_resolve writes them, copy_band carries them to the host; the framebuffers themselves are only read)
+    DevBuf rs_color, rs_depth;
+    int fb_cur = 0;                    // the next swr_draw renders into this buffer
     int fb_last = 0;                    // the buffer of the last swr_draw (what swr_present / swr_read_* copy)
     hipStream_t last_stream = nullptr;  // the stream that carries the last frame's raster (swr_present records frame_done behind it)
     hipStream_t copy_stream[2] = {nullptr, nullptr};   // colour, depth: both images in flight together
@@ -1352,17 +1364,22 @@ int ensure_stage(swr_context* c, int img) {
     return SWR_OK;
 }
 
-// Enqueue the copy of image `img` (0 colour, 1 depth) of framebuffer `fb`, this context's band only, into rows
-// [row_begin, row_end) of the caller's full-size host image, on the image's own copy stream, behind frame_done[fb].
+// The band's image `img` (0 colour, 1 depth, 2 IDs) in framebuffer `fb`
+inline const void* fb_image(const swr_context* c, int fb, int img) {
+    return img == 0 ? c->color[fb].p : img == 1 ? c->depth[fb].p : c->ids[fb].p;
+}
+
+// Enqueue the copy of a band-local device image `src_band` — rows of `row` bytes: a framebuffer image of `fb` (fb_image), or the
+// band's resolved image computed from it — into rows [r0, r1) of the caller's host image (rows of the same pitch: for a framebuffer
+// image the band's [row_begin, row_end) of the full-size image), on copy stream `img` (0 the colour's, 1 the depth's: the ID image
+// rides on the depth's, through its staging), behind frame_done[fb].
 // Page-locked destination: ONE hipMemcpyAsync straight into the caller's rows (returns at once).  Pageable
 // destination: pipelined through two pinned 8 MiB chunks (D2H of chunk k+1 overlaps the memcpy of chunk k; blocks).
-int copy_band(swr_context* c, int fb, int img, void* dst_full, uint64_t frame) {
-    const size_t row = (size_t)c->tg.width * 4;
-    const size_t bytes = (size_t)(c->tg.row_end - c->tg.row_begin) * row;
+int copy_band(swr_context* c, int fb, int img, const void* src_band, size_t row, int64_t r0, int64_t r1, void* dst_full, uint64_t frame) {
+    const size_t bytes = (size_t)(r1 - r0) * row;
     if (!bytes) return SWR_OK;
-    uint8_t* dst = (uint8_t*)dst_full + (size_t)c->tg.row_begin * row;
-    const uint8_t* src = (const uint8_t*)(img == 0 ? c->color[fb].p : img == 1 ? c->depth[fb].p : c->ids[fb].p);
-    if (img == 2) img = 1;      // the ID image (swr_read_ids) goes on the depth image's copy stream, through its staging
+    uint8_t* dst = (uint8_t*)dst_full + (size_t)r0 * row;
+    const uint8_t* src = (const uint8_t*)src_band;
     hipStream_t s = c->copy_stream[img];
     HIP_TRY(c, hipStreamWaitEvent(s, c->frame_done[fb], 0));
     if (is_pinned(dst)) {
@@ -1848,8 +1865,9 @@ int enqueue_present(swr_context* c, void* color_full, float* depth_full) {
     auto copies = [c, fb, want_color, color_full, depth_full, frame, fs]() -> int {
         int rc;
         HIP_TRY(c, hipEventRecord(c->frame_done[fb], fs));
-        if (want_color && (rc = copy_band(c, fb, 0, color_full, frame))) return rc;
-        if (depth_full && (rc = copy_band(c, fb, 1, depth_full, frame))) return rc;
+        const size_t row = (size_t)c->tg.width * 4;
+        if (want_color && (rc = copy_band(c, fb, 0, fb_image(c, fb, 0), row, c->tg.row_begin, c->tg.row_end, color_full, frame))) return rc;
+        if (depth_full && (rc = copy_band(c, fb, 1, fb_image(c, fb, 1), row, c->tg.row_begin, c->tg.row_end, depth_full, frame))) return rc;
         return SWR_OK;
     };
     if (lane_mode(c)) {
@@ -2047,8 +2065,63 @@ int single_read(swr_context* c, int img, void* dst) {
     if (tiles_of(c->tg) == 0) return SWR_OK;
     const int fb = c->fb_last;
     HIP_TRY(c, hipEventRecord(c->frame_done[fb], c->stream));
-    if ((rc = copy_band(c, fb, img, dst, c->frame_no ? c->frame_no - 1 : 0))) return rc;
-    if ((rc = wait_stream(c, c->copy_stream[img == 2 ? 1 : img], "copy stream"))) return or_sticky(c, rc);
+    const int cs = img == 2 ? 1 : img;      // the ID image goes on the depth image's copy stream
+    if ((rc = copy_band(c, fb, cs, fb_image(c, fb, img), (size_t)c->tg.width * 4, c->tg.row_begin, c->tg.row_end, dst,
+                        c->frame_no ? c->frame_no - 1 : 0))) return rc;
+    if ((rc = wait_stream(c, c->copy_stream[cs], "copy stream"))) return or_sticky(c, rc);
+    return SWR_OK;
+}
+
+// what a swr_resolve may hold (the target's size is checked against it where the target is known: check_resolve_target)
+int check_resolve_args(swr_context* c, const swr_resolve& rs) {
+    if (rs.factor != 1 && rs.factor != 2 && rs.factor != 4)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_resolve: factor %d is not 1, 2 or 4", rs.factor);
+    if (rs.depth_filter != SWR_RESOLVE_DEPTH_SAMPLE0 && rs.depth_filter != SWR_RESOLVE_DEPTH_MIN)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_resolve: unknown depth filter %d", rs.depth_filter);
+    if (rs.reserved[0] || rs.reserved[1]) return fail(c, SWR_ERR_BAD_ARG, "swr_resolve: reserved words must be 0");
+    return SWR_OK;
+}
+
+int check_resolve_target(swr_context* c, const swr_resolve& rs, const Target& t) {
+    if (t.width % rs.factor || t.height % rs.factor)
+        return fail(c, SWR_ERR_BAD_ARG, "supersampled resolve: the target %dx%d is not a multiple of the factor %d", t.width, t.height, rs.factor);
+    // (row_begin is a multiple of the tile height; a row_end that is one too, or the height, passes: whole sample blocks per band)
+    if (t.row_end % rs.factor)
+        return fail(c, SWR_ERR_BAD_ARG, "supersampled resolve: the band's row_end %d is not a multiple of the factor %d", t.row_end, rs.factor);
+    return SWR_OK;
+}
+
+// swr_read_color_resolved / swr_read_depth_resolved (one image) and the gather of swr_render_resolved (both, one launch): the last
+// frame's band, resolved by rs.factor, into rows [row_begin / S, row_end / S) of the caller's (W/S) x (H/S) images.  NULL: not wanted.
+int single_read_resolved(swr_context* c, swr_resolve rs, void* color_dst, float* depth_dst) {
+    if (const int f = sticky(c)) return f;
+    int rc = check_resolve_args(c, rs);
+    if (rc) return rc;
+    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_*_resolved needs swr_target_set first");
+    if ((rc = check_resolve_target(c, rs, c->tg))) return rc;
+    if (rs.factor == 1) {       // one sample per pixel: the plain read
+        if (color_dst && (rc = single_read(c, 0, color_dst))) return rc;
+        return depth_dst ? single_read(c, 1, depth_dst) : SWR_OK;
+    }
+    if ((rc = single_sync(c))) return rc;       // (an overflowed last frame is repaired here)
+    if (tiles_of(c->tg) == 0) return SWR_OK;
+    const int S = rs.factor, fb = c->fb_last;
+    // (row_begin is a multiple of the tile height and row_end one too or the height, itself a multiple of S: whole sample blocks)
+    const int rows = c->tg.row_end - c->tg.row_begin;
+    const size_t row = (size_t)(c->tg.width / S) * 4, bytes = row * (size_t)(rows / S);
+    if (color_dst && (rc = ensure(c, c->rs_color, bytes))) return rc;
+    if (depth_dst && (rc = ensure(c, c->rs_depth, bytes))) return rc;
+    if (!launch_resolve) return fail(c, SWR_ERR_HIP, "this build has no k_resolve: there is no fallback for the supersampled resolve");
+    launch_resolve(color_dst ? c->color[fb].p : nullptr, depth_dst ? c->depth[fb].p : nullptr, c->rs_color.p, c->rs_depth.p,
+                   c->tg.width, rows, S, rs.depth_filter, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->frame_done[fb], c->stream));
+    const uint64_t frame = c->frame_no ? c->frame_no - 1 : 0;
+    const int64_t r0 = c->tg.row_begin / S, r1 = c->tg.row_end / S;
+    if (color_dst && (rc = copy_band(c, fb, 0, c->rs_color.p, row, r0, r1, color_dst, frame))) return rc;
+    if (depth_dst && (rc = copy_band(c, fb, 1, c->rs_depth.p, row, r0, r1, depth_dst, frame))) return rc;
+    if (color_dst && (rc = wait_stream(c, c->copy_stream[0], "colour copy stream"))) return or_sticky(c, rc);
+    if (depth_dst && (rc = wait_stream(c, c->copy_stream[1], "depth copy stream"))) return or_sticky(c, rc);
     return SWR_OK;
 }
 
@@ -2084,7 +2157,7 @@ void destroy_single(swr_context* c) {
                 (unsigned long long)c->hp_frames, c->hp_t[0] / c->hp_frames, c->hp_t[1] / c->hp_frames, c->hp_t[2] / c->hp_frames,
                 c->hp_t[3] / c->hp_frames, c->hp_t[4] / c->hp_frames, c->hp_t[5] / c->hp_frames);
     DevBuf* bufs[] = {&c->redo_cnt, &c->vertices, &c->indices, &c->tri_rgb, &c->tri_xyz, &c->inv, &c->box64, &c->stream_scratch, &c->sort_temp,
-                      &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev};
+                      &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth};
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
@@ -2463,6 +2536,27 @@ int swr_read_ids(swr_context* c, uint32_t* dst) {
     return single_read(c, 2, dst);
 }
 
+// the resolved read of one or both images (NULL: not wanted); a group checks what it can see before any band is touched
+static int read_resolved(swr_context* c, const swr_resolve* resolve, void* color_dst, float* depth_dst) {
+    const swr_resolve rs = *resolve;
+    if (!is_group(c)) return single_read_resolved(c, rs, color_dst, depth_dst);
+    int rc = check_resolve_args(c, rs);
+    if (rc) return rc;
+    if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_*_resolved needs swr_target_set first");
+    if ((rc = check_resolve_target(c, rs, c->group_tg))) return rc;
+    return group_run(c, [=](swr_context* k) { return single_read_resolved(k, rs, color_dst, depth_dst); });
+}
+
+int swr_read_color_resolved(swr_context* c, const swr_resolve* resolve, void* dst) {
+    if (!c || !resolve || !dst) return SWR_ERR_BAD_ARG;
+    return read_resolved(c, resolve, dst, nullptr);
+}
+
+int swr_read_depth_resolved(swr_context* c, const swr_resolve* resolve, float* dst) {
+    if (!c || !resolve || !dst) return SWR_ERR_BAD_ARG;
+    return read_resolved(c, resolve, nullptr, dst);
+}
+
 // ---- page-locked host images ---------------------------------------------------------------------------------------
 void* swr_host_alloc(size_t bytes) {
     void* p = nullptr;
@@ -2581,8 +2675,8 @@ int swr_get_timings(swr_context* c, swr_timings* out) {
     return SWR_OK;
 }
 
-int swr_render(swr_context* c, const swr_render_pass* p) {
-    if (!c || !p) return SWR_ERR_BAD_ARG;
+// swr_render (resolve == NULL) and swr_render_resolved share this body: only the target's size and the gather differ.
+static int render_pass(swr_context* c, const swr_render_pass* p, const swr_resolve* resolve) {
     if (p->primitive_type != SWR_PRIMITIVE_TRIANGLE && p->primitive_type != SWR_PRIMITIVE_LINE &&
         p->primitive_type != SWR_PRIMITIVE_VERTICES)
         return fail(c, SWR_ERR_UNSUPPORTED, "unknown primitive type %d", p->primitive_type);
@@ -2591,10 +2685,16 @@ int swr_render(swr_context* c, const swr_render_pass* p) {
                     p->primitive_type == SWR_PRIMITIVE_LINE ? 2 : 3);
     if (!p->depth || (!(p->flags & SWR_FLAG_NO_COLOR) && !p->color))
         return fail(c, SWR_ERR_BAD_ARG, "swr_render: colour/depth image pointer is NULL");
+    int rc;
+    const int64_t S = resolve ? resolve->factor : 1;             // the frame is drawn at S * width x S * height
+    if (resolve) {
+        if ((rc = check_resolve_args(c, *resolve))) return rc;
+        if (p->flags & SWR_FLAG_LOAD)
+            return fail(c, SWR_ERR_UNSUPPORTED, "swr_render_resolved: SWR_FLAG_LOAD is not supported (the starting image would be at the wrong resolution)");
+    }
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<float, std::milli>(b - a).count(); };
     const auto t0 = clk::now();
-    int rc;
     // Scene identity: the caller's promise that the arrays hold what they held at the last call with this id — the
     // resident copy (and the triangle stream built from it) is then used as it is, like the reference's GpuRenderer
     // keeps its MTLBuffers across calls (GpuRenderer.swift:32-33,41-67) for the app's one mesh (App.swift:153-185).
@@ -2629,13 +2729,26 @@ int swr_render(swr_context* c, const swr_render_pass* p) {
     const auto t1 = clk::now();
     // the pass carries its own fragment stage: NULL material = the reference's passthrough
     if ((rc = swr_material_set(c, p->material))) return rc;
-    if ((rc = swr_target_set(c, p->width, p->height, 0, p->height))) return rc;
+    if ((rc = swr_target_set(c, S * p->width, S * p->height, 0, S * p->height))) return rc;
     // a load frame: the caller's images are its starting image (inputs now, never cached)
     if ((p->flags & SWR_FLAG_LOAD) &&
         (rc = swr_target_write(c, (p->flags & SWR_FLAG_NO_COLOR) ? nullptr : p->color, p->depth))) return rc;
     const swr_context* kf = c->kids.empty() ? c : c->kids[0];
     const uint64_t frames0 = kf->frame_no;
     if ((rc = swr_draw_primitives(c, p->transform, p->flags, p->primitive_type))) return rc;
+    if (resolve) {
+        // the gather of a supersampled pass: the frame itself (an overflow is repaired), then both images resolved in one launch per
+        // band and the small images copied
+        if ((rc = swr_sync(c))) return rc;
+        const auto t2 = clk::now();
+        if ((rc = read_resolved(c, resolve, (p->flags & SWR_FLAG_NO_COLOR) ? nullptr : p->color, p->depth))) return rc;
+        const auto t3 = clk::now();
+        c->rt.draw_ms = ms(t1, t2);
+        c->rt.frames = (int32_t)(kf->frame_no - frames0);
+        c->rt.gather_ms = ms(t2, t3);
+        c->rt.total_ms = ms(t0, t3);
+        return SWR_OK;
+    }
     // colour and depth leave every device together (two copy streams each); synchronous on return like
     // scheduleAndWait (Metal+Extensions.swift:57-67)
     if ((rc = swr_present(c, (p->flags & SWR_FLAG_NO_COLOR) ? nullptr : p->color, p->depth))) return rc;
@@ -2648,6 +2761,16 @@ int swr_render(swr_context* c, const swr_render_pass* p) {
     c->rt.gather_ms = ms(t2, t3);
     c->rt.total_ms = ms(t0, t3);
     return SWR_OK;
+}
+
+int swr_render(swr_context* c, const swr_render_pass* p) {
+    if (!c || !p) return SWR_ERR_BAD_ARG;
+    return render_pass(c, p, nullptr);
+}
+
+int swr_render_resolved(swr_context* c, const swr_render_pass* p, const swr_resolve* resolve) {
+    if (!c || !p || !resolve) return SWR_ERR_BAD_ARG;
+    return render_pass(c, p, resolve);
 }
 
 int swr_render_timings(swr_context* c, swr_render_times* out) {

@@ -208,4 +208,9 @@ void launch_points_or_lines(const DeviceFrame& f, int primitive_type, hipStream_
 void launch_clip_prep(const DeviceFrame& f, hipStream_t s);
 bool launch_clip_ids(const DeviceFrame& f, hipStream_t s, hipEvent_t stop);
 
+// swr_resolve.hip: the S x S box filter of a supersampled band: `rows` source rows of `width` pixels (multiples of
+// factor, 2 or 4) -> width / factor x rows / factor pixels; a NULL source image is not resolved
+void launch_resolve(const void* color, const void* depth, void* color_out, void* depth_out, int width, int rows, int factor,
+                    int depth_filter, hipStream_t s);
+
 }  // namespace swr
