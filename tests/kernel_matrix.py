@@ -148,6 +148,66 @@ PATH_ROWS = [
 ROWS = raster_rows() + bin_rows()
 
 
+# ---- the blend and resolve kernels (separate lists: ROWS stays the 62 + 16 raster and binning instantiations) ----------------------
+BLEND = 4096
+BLEND_OVER, BLEND_ADD = 0, 1
+RESOLVE_SAMPLE0, RESOLVE_MIN = 0, 1
+DEBUG_STREAM_ORDER = 1
+
+
+@dataclasses.dataclass(frozen=True)
+class BlendRow:
+    """k_raster_blend<ZT, MT, LOAD> as written in launch_raster_blend (SWR_BLEND_GO expanded), or k_blend_order; the blend frame that
+    reaches it: flags (DT / METAL / LOAD, without the BLEND bit) and the swr_blend state."""
+    name: str
+    flags: int
+    mode: int
+    opacity: int
+
+    @property
+    def load(self):
+        return bool(self.flags & LOAD)
+
+
+def blend_rows():
+    rows, k = [], 0
+    for zt, mt, flags in ((False, False, 0), (True, False, DT), (True, True, METAL)):
+        for load in (False, True):
+            rows.append(BlendRow(f"k_raster_blend<{_b(zt)}, {_b(mt)}, {_b(load)}>", flags | (LOAD if load else 0),
+                                 (BLEND_OVER, BLEND_ADD)[k % 2], (128, 200, 77, 254, 1, 150)[k]))
+            k += 1
+    return rows + [BlendRow("k_blend_order", DT | LOAD, BLEND_OVER, 140)]
+
+
+@dataclasses.dataclass(frozen=True)
+class ResolveRow:
+    """k_resolve<S, DF, COLOR, DEPTH> as written in launch_resolve_sf, S and DF as launch_resolve passes them; the read that reaches
+    it: colour and depth in one launch is swr_render_resolved's gather, one image is swr_read_color_resolved / _depth_resolved."""
+    name: str
+    S: int
+    depth_filter: int
+    color: bool
+    depth: bool
+
+
+_FILTER_NAME = {RESOLVE_SAMPLE0: "SWR_RESOLVE_DEPTH_SAMPLE0", RESOLVE_MIN: "SWR_RESOLVE_DEPTH_MIN"}
+
+
+def resolve_rows():
+    rows = []
+    for S in (2, 4):
+        for filt in (RESOLVE_SAMPLE0, RESOLVE_MIN):
+            rows.append(ResolveRow(f"k_resolve<{S}, {_FILTER_NAME[filt]}, true, true>", S, filt, True, True))
+        rows.append(ResolveRow(f"k_resolve<{S}, 0, true, false>", S, RESOLVE_SAMPLE0, True, False))
+        for filt in (RESOLVE_SAMPLE0, RESOLVE_MIN):
+            rows.append(ResolveRow(f"k_resolve<{S}, {_FILTER_NAME[filt]}, false, true>", S, filt, False, True))
+    return rows
+
+
+BLEND_ROWS = blend_rows()
+RESOLVE_ROWS = resolve_rows()
+
+
 def full_name(name):
     """The name with the template defaults the demangler prints (k_bin's LIST = false)."""
     if name.startswith("k_bin<") and name.count(",") == 3:

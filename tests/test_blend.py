@@ -20,60 +20,8 @@ IDENT = K.IDENT
 gpu = pytest.mark.gpu
 
 
-# ---- the model ---------------------------------------------------------------------------------------------------------------------
-def blend_bytes(s, d, A, mode):
-    """The header's arithmetic, per channel, on integer arrays."""
-    s, d = np.asarray(s, dtype=np.int64), np.asarray(d, dtype=np.int64)
-    if mode == OVER:
-        return (s * A + d * (255 - A) + 127) // 255
-    return np.minimum(255, d + (s * A + 127) // 255)
-
-
-def primitives(oracle, spec):
-    """[(source colour image BGRA with alpha 255 where covered, fragment depth image or None)] of the frame's primitives in order,
-    after depth clipping (fans, in their original's place) and face culling; each drawn alone by the oracle."""
-    flags, w, h = spec.flags, spec.width, spec.height
-    (fv, ft, fm, _), _, _ = FM._geometry(spec)
-    keep = np.arange(ft.shape[0])
-    if flags & (CB | CF) and ft.shape[0]:
-        keep = K.kept_triangles(K.signed_areas(oracle, fv, ft.reshape(-1), fm, w, h, flags), flags)
-    out, tri = [], np.arange(3, dtype=np.int64)
-    for p in keep:
-        v3 = np.ascontiguousarray(fv[ft[p]])
-        if flags & METAL:
-            c, d = K.oracle_clear(oracle, v3, tri, fm, w, h, METAL)
-        else:
-            c, _ = K.oracle_clear(oracle, v3, tri, fm, w, h, 0)
-            d = K.oracle_clear(oracle, v3, tri, fm, w, h, DT | NC)[1] if flags & DT else None
-        out.append((c, d))
-    return out
-
-
-_PRIMS = {}
-
-
-def model(oracle, spec, mode, opacity, start=None):
-    """(colour, depth) of the blend frame `spec` (a frame_model.FrameSpec; flags without the BLEND bit) over `start` = (colour,
-    depth), or over the cleared image."""
-    h, w = spec.height, spec.width
-    if start is None or not spec.flags & LOAD:
-        c, d0 = np.zeros((h, w, 4), dtype=np.uint8), np.full((h, w), np.inf, dtype=np.float32)
-    else:
-        c, d0 = np.array(start[0], copy=True), np.array(start[1], copy=True)
-    key = None if spec.key is None else (spec.key, spec.flags & ~LOAD)
-    prims = _PRIMS[key] if key in _PRIMS else primitives(oracle, spec)
-    if key is not None:
-        _PRIMS[key] = prims
-    for cs, ds in prims:
-        hit = cs[..., 3] == 255
-        if ds is not None:
-            with np.errstate(invalid="ignore"):
-                hit = hit & (ds < d0)                   # strict '<' against the STARTING depth; NaN and +inf never pass
-        if hit.any():
-            src = cs[hit].astype(np.int64)
-            src[:, 3] = 255
-            c[hit] = blend_bytes(src, c[hit], opacity, mode).astype(np.uint8)
-    return c, d0
+# ---- the model (tests/frame_model.py holds it: the frame model uses it for blend frames) -----------------------------------------------
+blend_bytes, primitives, model = FM.blend_bytes, FM.primitives, FM.model
 
 
 def same(got, want, what=""):

@@ -10,7 +10,14 @@
 (c) `covering_rows`: a pairwise covering array over the same factors, each row ONE clear-or-load frame on a fresh context.
 
 Like tests/test_gpu_stress.py::test_random_call_sequences (which stays as it is), whose flags end at DEPTH_TEST | NO_COLOR.
-SWR_SEQUENCE_SEEDS=N adds N more sequences (seeds 100..) per scheduler: a soak."""
+SWR_SEQUENCE_SEEDS=N adds N more sequences (seeds 100..) per scheduler: a soak.
+
+(d) BLEND_SEEDS run the generator with `blend` switched on: SWR_FLAG_BLEND frames (draws, draw lists, one-shot renders) with
+    swr_blend_set changes between them, inside the same bursts and load chains, and resolved reads (swr_read_*_resolved,
+    swr_render_resolved) wherever a read is legal.  Switched off, the generator draws no random number it did not draw before:
+    the sequences of SEEDS are the ones they always were (tests/test_frame_model.py holds their digest).
+(e) `test_all_pairs_blend_frame`: frame_model.blend_covering_array, each row ONE blend frame on a fresh context, read back plainly
+    and through k_resolve."""
 import dataclasses
 import functools
 import os
@@ -24,11 +31,13 @@ import frame_model as FM
 import kernel_matrix as K
 import test_depth_clip as DC
 import test_perspective as TP
-from frame_model import CB, CCW, CF, CLIP, DT, IDS, LOAD, METAL, NC, PERSP, REAL_LINES  # noqa: F401
+import resolve_model as RM
+from frame_model import BLEND, CB, CCW, CF, CLIP, DT, IDS, LOAD, METAL, NC, PERSP, REAL_LINES  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SEEDS = (21, 22, 23)
+BLEND_SEEDS = (31, 32, 33)  # sequence(seed, blend=True)
 STEPS = 70
 SIZES = ((320, 192), (256, 160), (192, 96))
 SCENES = {"small": 300, "big": 1300, "zero": 300, "straddle": 1300}      # triangles: big >= 4 x small, zero == small, straddle == big
@@ -38,6 +47,13 @@ HOOK_SETS = ((),
              ((K.DEBUG_BIN_MODE, K.BIN_MODE_ATOMIC), (K.DEBUG_RASTER_SORT, 2)),
              ((K.DEBUG_RASTER_SORT, 0),))
 MODEL_BUDGET = 16000        # triangles a sequence may send through the NumPy perspective model (about 0.2 - 1 s per 1 500)
+# The blend model draws every primitive alone with the oracle, twice under the CPU rules' z-test (one colour and one depth frame):
+# 0.25 - 0.3 ms a draw at 320x192 and 0.15 ms at 192x96 on the machine DESIGN.md §17 was measured on.  BLEND_BUDGET is in draws at
+# 320x192 (about 4 s there): each distinct (scene, size, list, transform, rules, cull, clip) is paid once, whatever mode, opacity and
+# load bit it is drawn with.  With it a sequence of BLEND_SEEDS spends no more time in the model than twice a sequence of SEEDS.
+BLEND_BUDGET = 14000
+BLEND_AREA = tuple(w * h / (320 * 192) for w, h in ((320, 192), (256, 160), (192, 96)))
+OPACITIES = (0, 1, 128, 254, 255)
 IMAGES = 10                 # page-locked image pairs per target size: a burst presents at most 9 frames, one more for its head
 FIRST_FAN_CAPACITY = 1024   # swr_api.hip prepare_clip: a frame of n triangles has n + 2 * max(1024, n / 64) slots at first
 
@@ -59,6 +75,8 @@ class Frame:
     tf: str                 # "aff" | "per"
     prev: object = None     # what a SWR_FLAG_LOAD frame is drawn over: a Frame, ("write", seed), or None (the cleared image)
     scene_id: int = 0       # (render)
+    blend: object = None    # (mode, opacity) of the context when a SWR_FLAG_BLEND frame is drawn
+    resolve: object = None  # (render) (S, depth filter): swr_render_resolved into SIZES[size] / S
 
     def row(self):
         return FM.row_of(self.flags, self.shader, self.via == "list", self.tf == "per")
@@ -67,16 +85,40 @@ class Frame:
         return self.kind == "tri" and bool(self.flags & PERSP) and not self.flags & NC and self.tf == "per"
 
 
-BLOCKING = ("wait", "read", "sync", "upload", "target", "write", "render", "hooks", "timing", "pipeline")
+BLOCKING = ("wait", "read", "read_resolved", "sync", "upload", "target", "write", "render", "hooks", "timing", "pipeline")
 
 
-def sequence(seed, steps=STEPS):
+def sequence(seed, steps=STEPS, blend=False):
     """The operations of one sequence:
     ("hooks", pairs) ("upload", scene) ("target", size) ("shading", shader) ("write", seed) ("frame", Frame) ("render", Frame)
-    ("present", image) ("wait",) ("read",) ("sync",) ("timing", level) ("pipeline", on)."""
+    ("present", image) ("wait",) ("read",) ("sync",) ("timing", level) ("pipeline", on);
+    with blend: ("blend", mode, opacity) ("read_resolved", S, depth filter, "color" | "depth" | "both")."""
     rng = random.Random(seed)
     ops = [("hooks", hooks_of(seed))]
-    st = dict(scene=None, size=None, shader=0, cur=None, last=None, shown=False, pending=0, count=0, budget=MODEL_BUDGET, paid=set())
+    st = dict(scene=None, size=None, shader=0, cur=None, last=None, shown=False, pending=0, count=0, budget=MODEL_BUDGET, paid=set(),
+              blend=(FM.OVER, 255), bbudget=BLEND_BUDGET, bpaid=set())
+
+    def blend_set(mode, opacity):
+        if (mode, opacity) != st["blend"]:
+            ops.append(("blend", mode, opacity))             # context state, like the material: no frame is completed by it
+            st["blend"] = (mode, opacity)
+
+    def read_resolved(S=None, filt=None, which=None, then_read=None):
+        """A resolved read of the last frame (it completes everything, as a read does); about every second one is followed by a
+        plain read, which must still see the full-size image."""
+        f = st["last"]
+        if f is None:
+            return
+        S = S or rng.choice((2, 4))
+        filt = rng.choice((RM.SAMPLE0, RM.MIN)) if filt is None else filt
+        which = which or rng.choice(("color", "depth", "both"))
+        if f.flags & NC:
+            which = "depth"                                  # (the resolved colour is as unspecified as swr_read_color's)
+        ops.append(("read_resolved", S, filt, which))
+        if rng.random() < 0.5 if then_read is None else then_read:
+            ops.append(("read",))
+        st["pending"] = 0
+        ops.append(("wait",))
 
     def upload(scene):
         wait()
@@ -106,10 +148,13 @@ def sequence(seed, steps=STEPS):
             st["pending"] += 1
             st["shown"] = True
 
-    def frame(kind="tri", clip_ok=True, force=None, via=None):
-        """One frame with random factors (force: factor values that are given)."""
+    def frame(kind="tri", clip_ok=True, force=None, via=None, blended=None, resolve=None):
+        """One frame with random factors (force: factor values that are given).  blended: True / False, or None: by chance (only
+        with `blend`, and never against a forced factor a blend frame cannot have); "tail": whatever it costs the model."""
         row = {f: rng.choice(FM.FACTORS[f]) for f in FM.FACTORS}
         row.update(force or {})
+        if blend and kind == "tri" and blended is None:
+            blended = rng.random() < 0.3 and not any((force or {}).get(k) for k in ("no_color", "ids", "persp", "shader"))
         if not clip_ok:
             row["clip"] = 0
         if st["scene"] == "straddle" and not row["clip"]:
@@ -117,7 +162,24 @@ def sequence(seed, steps=STEPS):
             # a tile region of the first guess holds, and a frame inside a burst that overflows its bins is dropped
             row["transform"] = "affine"
         tf = "per" if row["transform"] == "perspective" else "aff"
-        flags = FM.flags_of(row)
+        if blended and kind == "tri":
+            # include/swr.h "Alpha blending", Combinations: the generator steers the row the way it steers `clip` above
+            row.update(no_color=0, ids=0, persp=0, shader=0)
+            assert FM.legal(dict(row, blend=1))
+            draws = (SCENES[st["scene"]] * (3 if row["clip"] else 1) + (60 if row["list"] else 0)) * (2 if row["rules"] == "ztest" else 1)
+            bcost = draws * BLEND_AREA[st["size"]]
+            key = (st["scene"], st["size"], row["list"], tf, row["rules"], row["cull"], row["ccw"], row["clip"])
+            if key in st["bpaid"]:
+                pass
+            elif bcost > st["bbudget"] and blended != "tail":
+                blended = False
+            else:
+                st["bbudget"] -= bcost
+                st["bpaid"].add(key)
+        blended = bool(blended) and kind == "tri"
+        if blended and rng.random() < 0.6:
+            blend_set(rng.choice((FM.OVER, FM.ADD)), rng.choice(OPACITIES))
+        flags = FM.flags_of(row) | (BLEND if blended else 0)
         cost = SCENES[st["scene"]] * (3 if row["clip"] else 1) * (2 if row["list"] else 1)
         if kind == "tri" and flags & PERSP and not flags & NC and tf == "per":
             # the NumPy model's share of the run stays bounded: each distinct frame it has to draw is paid for once
@@ -136,9 +198,12 @@ def sequence(seed, steps=STEPS):
             flags = (flags & (CB | CF | CCW | CLIP | PERSP)) | (REAL_LINES if kind == "lines" and rng.random() < 0.7 else 0)
             how = "draw"
         f = Frame(st["count"], st["scene"], st["size"], st["shader"], kind, flags, how, tf, st["cur"] if flags & LOAD else None)
+        if blended:
+            f.blend = st["blend"]
         st["count"] += 1
         if how == "render":
             f.scene_id = rng.choice((0, 40 + list(SCENES).index(f.scene)))
+            f.resolve = resolve
             if flags & LOAD:
                 f.prev = ("write", rng.randrange(1 << 16))
             wait()
@@ -165,14 +230,88 @@ def sequence(seed, steps=STEPS):
         for k in range(length):
             last = k == length - 1
             straddle = st["scene"] == "straddle"
-            frame(clip_ok=(not straddle) or (last and tail_clip), force=dict(force or {}, **({"clip": 1, "load": 0} if last and tail_clip else {})))
+            frame(clip_ok=(not straddle) or (last and tail_clip), force=dict(force or {}, **({"clip": 1, "load": 0} if last and tail_clip else {})),
+                  blended="tail" if blend and last and tail_clip else None)
             present()
+        if blend and tail_clip and st["last"].blend is not None:
+            # the overflowed blend frame is redrawn by the read below: with the state it was posted with (swr_context::last_blend),
+            # not with the one set meanwhile, chosen here so that the two give different images whatever the first one is
+            mode, opacity = st["last"].blend
+            blend_set(FM.ADD if mode == FM.OVER else FM.OVER, 200 if opacity < 128 else 30)
         if tail_clip or rng.random() < 0.5:
             ops.append(("read",))
             st["pending"] = 0                                # (a read completes everything: the presented images are there too)
             ops.append(("wait",))
         else:
             wait()
+
+    def mixed_burst():
+        """Blend and other frames next to each other, in both orders, with no wait: a depth-only frame (32-bit keys), an ID frame
+        and a shaded one among them, the blend state changed in between."""
+        wait()
+        straddle = st["scene"] == "straddle"
+        plain = (dict(rules="ztest", no_color=1, ids=0, load=0), None, dict(ids=1, no_color=0), None, dict(shader=rng.choice((1, 2)), no_color=0),
+                 None, dict(load=1))
+        for k, force in enumerate(plain):
+            if force is None:
+                blend_set(rng.choice((FM.OVER, FM.ADD)), OPACITIES[(seed + k) % len(OPACITIES)])
+                frame(clip_ok=not straddle, blended=True, force=dict(list=k // 2 % 2))
+            else:
+                frame(clip_ok=not straddle, blended=False, force=force)
+            present()
+        ops.append(("read",))
+        st["pending"] = 0
+        ops.append(("wait",))
+
+    def blend_chains():
+        """Blend load frames over a colour frame of the key kernels, a depth-only frame (the colour there is unspecified), a
+        swr_target_write image and another blend frame: three in a row each, one geometry for the model."""
+        straddle = st["scene"] == "straddle"
+        fixed = dict(rules=rng.choice(FM.FACTORS["rules"]), cull="none", ccw=0, clip=0, list=0, transform="affine")
+        for start in ("colour", "depth_only", "write", "blend"):
+            wait()
+            if start == "write":
+                s = rng.randrange(1 << 16)
+                ops.append(("write", s))
+                st.update(cur=("write", s), last=None)
+            elif start == "blend":
+                frame(clip_ok=not straddle, blended=True, force=dict(fixed, load=0))
+                present()
+            else:
+                frame(clip_ok=not straddle, blended=False, force=dict(load=0, **(dict(no_color=1, rules=rng.choice(("ztest", "metal")))
+                                                                                  if start == "depth_only" else dict(no_color=0))))
+                present()
+            for k in range(3):
+                blend_set(FM.OVER if k == 0 and start == "depth_only" else rng.choice((FM.OVER, FM.ADD)),
+                          (255, 128, 0)[k] if start == "depth_only" else rng.choice(OPACITIES))
+                frame(blended=True, force=dict(fixed, load=1))
+                present()
+            ops.append(("read",))
+            st["pending"] = 0
+            ops.append(("wait",))
+
+    def resolve_tour():
+        """Resolved reads where single-frame tests never issue them: on a small target first and on the largest one right after
+        the change (the resolve buffers grow), after a blend frame, a .vertices / .line frame and a depth-only frame, and in
+        front of a load frame and a plain read (the full-size images are not modified)."""
+        straddle = st["scene"] == "straddle"
+        target(2)
+        frame(clip_ok=not straddle, blended=False, force=dict(load=0, no_color=0))
+        read_resolved(4, RM.MIN, "both", then_read=False)
+        target(0)
+        frame(clip_ok=not straddle, blended=True, force=dict(load=0))
+        read_resolved(2, RM.SAMPLE0, "color", then_read=True)
+        frame(rng.choice(("points", "lines")))
+        read_resolved(2, RM.MIN, "depth", then_read=False)
+        frame(clip_ok=not straddle, blended=False, force=dict(no_color=1, rules="ztest", ids=0))
+        read_resolved(4, RM.SAMPLE0, "depth", then_read=False)
+        frame(clip_ok=not straddle, blended=False, force=dict(load=0, no_color=0))
+        read_resolved(rng.choice((2, 4)), rng.choice((RM.SAMPLE0, RM.MIN)), "both", then_read=False)
+        frame(clip_ok=not straddle, force=dict(load=1, no_color=0))
+        ops.append(("read",))
+        ops.append(("wait",))
+
+    scripted = {2: mixed_burst, 6: blend_chains, 10: mixed_burst, 40: blend_chains, 46: mixed_burst} if blend else {}
 
     # a scene with depths <= 0 first (the sticky move of a scene's depth-only frames to the 64-bit keys), then the scene of its size
     upload("zero")
@@ -181,12 +320,19 @@ def sequence(seed, steps=STEPS):
     ops.append(("read",))
     upload("small")
     burst(5, force=dict(rules="ztest", no_color=1, ids=0))
+    if blend:
+        resolve_tour()
     at_overflow = rng.randrange(steps // 4, steps // 2)
     for step in range(steps):
         if step == at_overflow:
             # more crossing triangles than the first fan capacity, behind frames of other kinds
             upload("straddle")
+            if blend and seed % 3 != 1:                      # (the blend model draws every fan triangle alone: on the smallest target)
+                target(2)
             burst(rng.randint(3, 6), tail_clip=True)
+            continue
+        if step in scripted:
+            scripted[step]()
             continue
         if step in (steps // 6, 4 * steps // 6, 5 * steps // 6):      # (every size and every scene comes up in every sequence)
             fresh = [x for x in range(len(SIZES)) if ("target", x) not in ops]
@@ -196,8 +342,13 @@ def sequence(seed, steps=STEPS):
             if fresh:
                 upload(fresh[0])
         op = rng.choice(["burst"] * 5 + ["persp"] * 2 + ["draw"] * 3 + ["points", "present", "read", "read", "wait", "sync", "upload", "upload", "target",
-                                                       "timing", "pipeline", "chain", "chain", "render", "render"])
-        if op == "burst":
+                                                       "timing", "pipeline", "chain", "chain", "render", "render"]
+                        + (["resolved"] * 4 + ["rrender"] * 2 if blend else []))
+        if op == "resolved":
+            read_resolved()
+        elif op == "rrender":
+            frame(via="render", clip_ok=st["scene"] != "straddle", force=dict(load=0), resolve=(rng.choice((2, 4)), rng.choice((RM.SAMPLE0, RM.MIN))))
+        elif op == "burst":
             burst(rng.randint(2, 9))
         elif op == "persp" and st["scene"] != "straddle":
             # neighbouring lanes with different perspective tables: draws and draw lists of one rule set in turn, two distinct
@@ -267,8 +418,8 @@ def runs(ops):
     out, cur = [], []
     for k, op in enumerate(ops):
         if op[0] == "frame":
-            nxt = next((o for o in ops[k + 1:] if o[0] != "shading"), ("end",))
-            cur.append((op[1], nxt[0] in ("present", "read")))
+            nxt = next((o for o in ops[k + 1:] if o[0] not in ("shading", "blend")), ("end",))
+            cur.append((op[1], nxt[0] in ("present", "read", "read_resolved")))
         elif op[0] in BLOCKING and cur:
             out.append(cur)
             cur = []
@@ -360,8 +511,8 @@ def spec_of(f):
     v, i, sh = scenes[f.scene]
     w, h = SIZES[f.size]
     shader = 0 if f.flags & NC else f.shader
-    return FM.FrameSpec(v, i, w, h, f.flags, mats[f.tf], items_of(f.scene, f.tf) if f.via == "list" else None, sh[shader],
-                        key=(f.scene, f.size, f.via == "list", f.tf, shader))
+    return FM.FrameSpec(v, i, w, h, f.flags & ~BLEND, mats[f.tf], items_of(f.scene, f.tf) if f.via == "list" else None, sh[shader],
+                        key=(f.scene, f.size, f.via == "list", f.tf, shader), blend=f.blend if f.flags & BLEND else None)
 
 
 _CLEAR = {}         # frame_model's clear frames, shared by every run of the module: a sequence is the same under every scheduler
@@ -409,6 +560,14 @@ def play(swr, oracle, ops, bands, stats=None):
                            f"flags {f.flags:#x})")
         stats["checked"] = stats.get("checked", 0) + 1
 
+    def check_resolved(got, f, S, filt, what):
+        t0 = time.perf_counter()
+        want = FM.resolved(image_of(oracle, f, memo), S, filt)
+        stats["model_s"] = stats.get("model_s", 0.0) + time.perf_counter() - t0
+        FM.same(got, want, f"{what}: frame {f.n} resolved by {S}, filter {filt} ({f.kind} {f.via} {f.tf} on {f.scene} {SIZES[f.size]}, "
+                           f"shader {f.shader}, flags {f.flags:#x}, blend {f.blend})")
+        stats["checked"] = stats.get("checked", 0) + 1
+
     try:
         with swr.Context(0, device_count=bands) as ctx:
             scene = size = None
@@ -428,6 +587,8 @@ def play(swr, oracle, ops, bands, stats=None):
                     last = None
                 elif op[0] == "shading":
                     ctx.shading_set(scenes[scene][2][op[1]])
+                elif op[0] == "blend":
+                    ctx.blend_set(op[1], op[2])
                 elif op[0] == "write":
                     ctx.target_write(*TP.start_images(op[1], *SIZES[size]))
                     last = None
@@ -443,6 +604,16 @@ def play(swr, oracle, ops, bands, stats=None):
                     f = op[1]
                     v, i, sh = scenes[f.scene]
                     w, h = SIZES[f.size]
+                    if f.resolve is not None:
+                        # swr_render_resolved: the destination is SIZES[size] / S, the frame (and its IDs) SIZES[size]
+                        S, filt = f.resolve
+                        c, d = ctx.render_resolved(v, i, mats[f.tf], w // S, h // S, f.flags, shading=sh[f.shader], scene_id=f.scene_id,
+                                                   factor=S, depth_filter=filt)
+                        check_resolved((c, d, None), f, S, filt, what)
+                        if f.flags & IDS:
+                            FM.same((None, None, ctx.read_ids()), image_of(oracle, f, memo), what + ": IDs at sample resolution")
+                        last = None
+                        continue
                     start = TP.start_images(f.prev[1], w, h) if f.flags & LOAD else (None, None)
                     c, d = ctx.render(v, i, mats[f.tf], w, h, f.flags, shading=sh[f.shader], scene_id=f.scene_id,
                                       color=None if f.flags & NC or start[0] is None else start[0].copy(),
@@ -464,6 +635,12 @@ def play(swr, oracle, ops, bands, stats=None):
                     ctx.sync()
                     check((None if f.flags & NC else ctx.read_color(), ctx.read_depth(),
                            ctx.read_ids() if f.flags & IDS and f.kind == "tri" else None), f, what)
+                elif op[0] == "read_resolved":
+                    # (no swr_sync in front: the call completes everything itself)
+                    f, (S, filt, which) = last, op[1:]
+                    gc = ctx.read_color_resolved(S) if which in ("color", "both") and not f.flags & NC else None
+                    gd = ctx.read_depth_resolved(S, filt) if which in ("depth", "both") else None
+                    check_resolved((gc, gd, None), f, S, filt, what)
                 elif op[0] == "sync":
                     ctx.sync()
                 elif op[0] == "timing":
@@ -485,12 +662,12 @@ _EXTRA = [100 + k for k in range(int(os.environ.get("SWR_SEQUENCE_SEEDS", "0")))
 
 @pytest.mark.parametrize("env", [{}, {"SWR_LANES": "0"}], ids=["lanes", "SWR_LANES=0"])
 @pytest.mark.parametrize("bands", [1, 3])
-@pytest.mark.parametrize("seed", list(SEEDS) + _EXTRA)
+@pytest.mark.parametrize("seed", list(SEEDS) + list(BLEND_SEEDS) + _EXTRA)
 def test_mixed_sequences(swr, oracle, monkeypatch, seed, bands, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     t0 = time.perf_counter()
-    stats = play(swr, oracle, sequence(seed), bands)
+    stats = play(swr, oracle, sequence(seed, blend=seed in BLEND_SEEDS), bands)
     print(f"seed {seed} bands {bands} {env}: {stats['checked']} images checked, {time.perf_counter() - t0:.1f} s "
           f"({stats['model_s']:.1f} s in the model)")
 
@@ -553,3 +730,37 @@ def test_all_pairs_single_frame(swr, oracle, k, target):
         ctx.sync()
         got = (None if s.flags & NC else ctx.read_color(), ctx.read_depth(), ctx.read_ids() if s.flags & IDS else None)
     FM.same(got, want, f"row {k} on {target}: {row}")
+
+
+# ---- (e) all-pairs single blend frames ------------------------------------------------------------------------------------------------
+def blend_pair_spec(row, target):
+    """pair_spec's scenes and matrices for a row of frame_model.BLEND_FACTORS."""
+    flags, state = FM.blend_flags_of(row)
+    s = pair_spec(dict(row, no_color=0, ids=0, persp=0, shader=0), target)
+    return dataclasses.replace(s, flags=flags, blend=state, key=("pairs", target, row["clip"], row["list"], row["transform"]))
+
+
+@pytest.mark.parametrize("k", range(len(FM.blend_covering_array())))
+def test_all_pairs_blend_frame(swr, oracle, k, target="small"):
+    """One blend frame per row, on the small target only (the per-primitive model would take minutes on the large one), compared
+    through a plain read and through swr_read_*_resolved with S = 2 (MIN for odd k, SAMPLE0 for even k)."""
+    row = FM.blend_covering_array()[k]
+    s = blend_pair_spec(row, target)
+    start = K.special_start(s.width, s.height, 0xB00 + k) if row["load"] else None
+    want = FM.expect(oracle, s, start, _CLEAR)
+    filt = RM.MIN if k % 2 else RM.SAMPLE0
+    with swr.Context(0) as ctx:
+        ctx.scene_upload(s.vertices, s.indices)
+        ctx.target_set(s.width, s.height)
+        if start is not None:
+            ctx.target_write(*start)
+        ctx.blend_set(*s.blend)
+        if s.items is not None:
+            ctx.draw_list(s.items, s.flags | BLEND)
+        else:
+            ctx.draw(s.transform, s.flags | BLEND)
+        ctx.sync()
+        got = (ctx.read_color(), ctx.read_depth(), None)
+        res = (ctx.read_color_resolved(2), ctx.read_depth_resolved(2, filt), None)
+    FM.same(got, want, f"blend row {k} on {target}: {row}")
+    FM.same(res, FM.resolved(want, 2, filt), f"blend row {k} on {target}, resolved by 2: {row}")

@@ -10,6 +10,7 @@ import kernel_matrix as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = os.path.join(ROOT, "software-renderer_amd", "csrc", "swr_kernels.hip")
+RESOLVE = os.path.join(ROOT, "software-renderer_amd", "csrc", "swr_resolve.hip")
 
 
 def _body(src, start, end):
@@ -37,6 +38,91 @@ def dispatch_kernels(src):
                 k = re.sub(r"\b%s\b" % p, a, k)
             out.add(k)
     return out
+
+
+def blend_kernels(src):
+    """The kernels launch_raster_blend can launch: the plain launches, and the SWR_BLEND_GO(ZT, MT) macro (its launches, one per
+    LOAD value) expanded for every call."""
+    body = _body(src, "static bool launch_raster_blend(", "\ntemplate <bool LOAD, bool IDS>")
+    macro = re.search(r"#define SWR_BLEND_GO\(([^)]*)\)((?:.*\\\n)*.*)\n", body)
+    names = [p.strip() for p in macro.group(1).split(",")]
+    templates = re.findall(r"SWR_LAUNCH\(\s*stop\s*,\s*\(?\s*(k_\w+<[^>]*>)", macro.group(2))
+    rest = body[:macro.start()] + body[macro.end():]
+    out = set(re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*(k_\w+(?:<[^>]*>)?)", rest))
+    out |= set(re.findall(r"SWR_LAUNCH\(\s*stop\s*,\s*\(?\s*(k_\w+(?:<[^>]*>)?)", rest))
+    for args in re.findall(r"SWR_BLEND_GO\(([^)]*)\);", rest):
+        for k in templates:
+            for p, a in zip(names, [x.strip() for x in args.split(",")]):
+                k = re.sub(r"\b%s\b" % p, a, k)
+            out.add(k)
+    return out
+
+
+def resolve_kernels(src):
+    """The kernels launch_resolve can launch: launch_resolve_sf<S, DF>'s launches with the S and DF of every call."""
+    sf = _body(src, "void launch_resolve_sf(", "\n}  // namespace")
+    templates = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*(k_\w+<[^>]*>)", sf)
+    calls = re.findall(r"launch_resolve_sf<\s*(\w+)\s*,\s*(\w+)\s*>\(", _body(src, "void launch_resolve(", "\n}  // namespace swr"))
+    return {re.sub(r"\bDF\b", df, re.sub(r"\bS\b", S, k)) for S, df in calls for k in templates}
+
+
+def test_blend_and_resolve_rows_are_the_dispatch():
+    with open(KERNELS) as f:
+        found = blend_kernels(f.read())
+    rows = [r.name for r in K.BLEND_ROWS]
+    assert len(rows) == len(set(rows)) == 7 and set(rows) == found, (sorted(found - set(rows)), sorted(set(rows) - found))
+    with open(RESOLVE) as f:
+        found = resolve_kernels(f.read())
+    rows = [r.name for r in K.RESOLVE_ROWS]
+    assert len(rows) == len(set(rows)) == 10 and set(rows) == found, (sorted(found - set(rows)), sorted(set(rows) - found))
+    assert not set(r.name for r in K.ROWS) & (set(r.name for r in K.BLEND_ROWS) | set(rows))
+
+
+def test_the_blend_and_resolve_parsers_see_a_new_variant():
+    with open(KERNELS) as f:
+        src = f.read()
+    at = src.index("    else SWR_BLEND_GO(false, false);")
+    grown = blend_kernels(src[:at] + "    else if (f.nitems) SWR_BLEND_GO(false, true);\n" + src[at:])
+    assert grown - blend_kernels(src) == {"k_raster_blend<false, true, true>", "k_raster_blend<false, true, false>"}
+    at = src.index("#define SWR_BLEND_GO(ZT, MT)")
+    grown = blend_kernels(src[:at] + "    hipLaunchKernelGGL(k_blend_merge, dim3(ntiles), dim3(256), 0, s, a);\n" + src[at:])
+    assert grown - blend_kernels(src) == {"k_blend_merge"}
+    with open(RESOLVE) as f:
+        src = f.read()
+    at = src.index("    } else {\n        if (mn) launch_resolve_sf<4")
+    grown = resolve_kernels(src[:at] + "    } else if (factor == 8) {\n        launch_resolve_sf<8, SWR_RESOLVE_DEPTH_MIN>(c, d, co, dz, w, npix, s);\n" + src[at:])
+    assert grown - resolve_kernels(src) == {"k_resolve<8, SWR_RESOLVE_DEPTH_MIN, true, true>", "k_resolve<8, 0, true, false>",
+                                            "k_resolve<8, SWR_RESOLVE_DEPTH_MIN, false, true>"}
+    at = src.index("    else hipLaunchKernelGGL((k_resolve<S, DF, false, true>)")
+    grown = resolve_kernels(src[:at] + "    else if (!w) hipLaunchKernelGGL((k_resolve<S, DF, false, false>), grid, block, 0, s, color);\n" + src[at:])
+    assert len(grown - resolve_kernels(src)) == 4
+
+
+def _blend_dispatch_model(flags, ntri):
+    """Which kernels launch_raster_blend launches for a blend frame."""
+    zt, mt = (True, True) if flags & K.METAL else ((True, False) if flags & K.DT else (False, False))
+    return (["k_blend_order"] if ntri > 0 else []) + [f"k_raster_blend<{K._b(zt)}, {K._b(mt)}, {K._b(flags & K.LOAD)}>"]
+
+
+def _resolve_dispatch_model(S, depth_filter, color, depth):
+    """Which kernel launch_resolve launches for the images wanted (colour alone: the filter is not instantiated)."""
+    df = {K.RESOLVE_SAMPLE0: "SWR_RESOLVE_DEPTH_SAMPLE0", K.RESOLVE_MIN: "SWR_RESOLVE_DEPTH_MIN"}[depth_filter]
+    assert S in (2, 4) and (color or depth)
+    if color and depth:
+        return f"k_resolve<{S}, {df}, true, true>"
+    return f"k_resolve<{S}, 0, true, false>" if color else f"k_resolve<{S}, {df}, false, true>"
+
+
+def test_every_blend_and_resolve_row_reaches_its_kernel():
+    for r in K.BLEND_ROWS:
+        assert not r.flags & ~(K.DT | K.METAL | K.LOAD) and r.mode in (K.BLEND_OVER, K.BLEND_ADD) and 0 < r.opacity < 255
+        assert r.name in _blend_dispatch_model(r.flags, 6000), r.name
+    assert _blend_dispatch_model(0, 0) == ["k_raster_blend<false, false, false>"]
+    seen = set()
+    for r in K.RESOLVE_ROWS:
+        assert _resolve_dispatch_model(r.S, r.depth_filter, r.color, r.depth) == r.name, r.name
+        seen.add((r.S, r.depth_filter if r.depth else None, r.color, r.depth))
+    assert len(seen) == 10
 
 
 def test_rows_are_the_dispatch():
