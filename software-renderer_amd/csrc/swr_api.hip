@@ -148,7 +148,7 @@ struct swr_context {
     // swr_debug_set (test hooks; the defaults are what a renderer gets)
     int dbg_stream_order = 1;           // 1 Morton-ordered stream, 0 caller's order, -1 as for >= 2^24 primitives
     int dbg_cull = 1;                   // per-band culling of 64-primitive groups
-    int dbg_bin_mode = 0;               // 0 auto, 1 exact-size bins, 2 fixed-stride bins everywhere, 3 global-atomic fallback
+    int dbg_bin_mode = 0;               // 0 auto (fixed-stride bins where they can hold the scene), 1 exact-size bins, 2 = 0, 3 global-atomic fallback
     int64_t dbg_oneshot_min_tris = (int64_t)1 << 18;
     bool dbg_k32 = true;                // depth-only z-tested frames on 32-bit depth keys
     int dbg_insort = 1;                 // ... which sort their bins inside the raster workgroups: 0 never, 1 on small grids, 2 always

@@ -316,10 +316,7 @@ void launch_clip_prep(const DeviceFrame& f, hipStream_t s) {
 bool launch_clip_ids(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     const int64_t npix = (int64_t)f.tg.width * (int64_t)(f.tg.row_end - f.tg.row_begin);
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (npix + 255) / 256));
-    if (stop) hipExtLaunchKernelGGL(k_clip_ids, dim3(blocks), dim3(256), 0, s, nullptr, stop, 0, f.ids, npix, (const uint32_t*)f.clip.map,
-                                    f.clip.bound);
-    else hipLaunchKernelGGL(k_clip_ids, dim3(blocks), dim3(256), 0, s, f.ids, npix, (const uint32_t*)f.clip.map, f.clip.bound);
-    return stop != nullptr;
+    return launch_on(stop, k_clip_ids, dim3(blocks), dim3(256), 0, s, f.ids, npix, (const uint32_t*)f.clip.map, f.clip.bound);
 }
 
 }  // namespace swr

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "../../include/swr.h"
 
 namespace swr {
@@ -171,6 +174,29 @@ struct DeviceFrame {
     swr_blend blend;
 };
 
+// with_bools(fn, b0, b1, ...) calls fn(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...): runtime bools become template
+// arguments.  fn is a generic lambda, `[&](auto LOAD, auto IDS) { ... k_x<LOAD, IDS> ... }`; its body is instantiated for all 2^N
+// combinations, so every template-id it names with a lifted parameter exists for both values of it.
+template <class F>
+decltype(auto) with_bools(F&& fn) { return fn(); }
+template <class F, class... Rest>
+decltype(auto) with_bools(F&& fn, bool b0, Rest... rest) {
+    return b0 ? with_bools([&](auto... c) -> decltype(auto) { return fn(std::true_type{}, c...); }, rest...)
+              : with_bools([&](auto... c) -> decltype(auto) { return fn(std::false_type{}, c...); }, rest...);
+}
+
+#ifdef __HIPCC__   // (the host layer's stand-alone tests compile swr_api.hip against a fake runtime that has no kernels to launch)
+// Launch with the completion of the kernel bound to `stop` when there is one (hipExtLaunchKernelGGL: the event is the kernel's own
+// completion signal — no marker packet behind the kernel, which would cost the next kernel of the queue ~6.5 us).  Returns whether
+// the kernel carries the event.
+template <class Kernel, class... Args>
+bool launch_on(hipEvent_t stop, Kernel k, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args&&... args) {
+    if (stop) hipExtLaunchKernelGGL(k, grid, block, (uint32_t)lds, s, nullptr, stop, 0, std::forward<Args>(args)...);
+    else hipLaunchKernelGGL(k, grid, block, (uint32_t)lds, s, std::forward<Args>(args)...);
+    return stop != nullptr;
+}
+#endif
+
 void launch_validate_indices(const int64_t* indices, int64_t count, int64_t vertex_count,
                              uint32_t* counters, hipStream_t s);
 hipError_t prepare_device();      // per-device kernel attributes (after hipSetDevice)
@@ -196,7 +222,7 @@ uint32_t fixed_cap_max(int64_t ntri, int ntiles);   // largest tile region k_bin
 bool launch_bin(const DeviceFrame& f, hipStream_t s, hipEvent_t stop = nullptr);
 void launch_setup_bin(const DeviceFrame& f, hipStream_t s);
 void launch_scan(const DeviceFrame& f, hipStream_t s);
-// stop != NULL: the event is bound to the (last) kernel launched, as its completion; returns whether a kernel carries it
+// stop != NULL: the event is bound to the (last) kernel launched, as its completion (launch_on); returns whether a kernel carries it
 bool launch_fill(const DeviceFrame& f, hipStream_t s, hipEvent_t stop = nullptr);
 bool launch_sort_bins(const DeviceFrame& f, hipStream_t s, hipEvent_t stop = nullptr);
 bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop = nullptr);

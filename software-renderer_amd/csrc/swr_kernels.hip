@@ -3259,6 +3259,15 @@ __global__ void k_points_resolve(const swr_vertex* __restrict__ vtx, const int64
 // ------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------
+// values every wrapper below derives from the frame
+static int tiles_of(const DeviceFrame& f) { return f.tg.tiles_x * f.tg.tiles_y; }
+static int tag_class(const DeviceFrame& f) { return f.ntri < (1ll << CLASS_SHIFT) ? 1 : 0; }   // bin entries carry a size class
+static float4x4 matrix_of(const DeviceFrame& f) {
+    float4x4 m;
+    for (int c = 0; c < 4; c++) m.columns[c] = make_float4(f.m[4 * c + 0], f.m[4 * c + 1], f.m[4 * c + 2], f.m[4 * c + 3]);
+    return m;
+}
+
 void launch_points_or_lines(const DeviceFrame& f, int primitive_type, hipStream_t s) {
     const int64_t n = (int64_t)f.tg.width * (int64_t)(f.tg.row_end - f.tg.row_begin);
     if (n <= 0) return;
@@ -3269,33 +3278,29 @@ void launch_points_or_lines(const DeviceFrame& f, int primitive_type, hipStream_
     // .line (as written: an empty stub) and colour-less passes only clear; .vertices and real lines first zero the order
     // scratch (= depth bits).  Load frames: the clear is a copy of the loaded image (only the depth scratch is zeroed for points / lines).
     const bool load = (f.flags & SWR_FLAG_LOAD) != 0;
-    const uint32_t* sc = (const uint32_t*)f.src_color;
-    const uint32_t* sd = (const uint32_t*)f.src_depth;
-    if (!load)
-        hipLaunchKernelGGL(k_clear_band<false>, dim3(blocks), dim3(256), 0, s, want_color ? (uint32_t*)f.color : nullptr,
-                           (uint32_t*)f.depth, n, (points || lines) ? 0u : 0x7F800000u, nullptr, nullptr);
-    else if (points || lines)
-        hipLaunchKernelGGL(k_clear_band<true>, dim3(blocks), dim3(256), 0, s, nullptr, (uint32_t*)f.depth, n, 0u, nullptr, nullptr);
-    else if (f.color != f.src_color || f.depth != f.src_depth)
-        hipLaunchKernelGGL(k_clear_band<true>, dim3(blocks), dim3(256), 0, s, want_color ? (uint32_t*)f.color : nullptr,
-                           (uint32_t*)f.depth, n, 0x7F800000u, sc, sd);
-    if (!points && !lines) return;
+    const uint32_t* sc = load ? (const uint32_t*)f.src_color : nullptr;
+    const uint32_t* sd = load ? (const uint32_t*)f.src_depth : nullptr;
+    const bool marks = points || lines;     // the depth image becomes the order scratch; a load frame's colour waits for the resolve
+    const bool copy = load && !marks;
+    uint32_t* const clear_color = want_color && !(load && marks) ? (uint32_t*)f.color : nullptr;
+    if (!copy || f.color != f.src_color || f.depth != f.src_depth)
+        with_bools([&](auto LOAD) {
+            hipLaunchKernelGGL(k_clear_band<LOAD>, dim3(blocks), dim3(256), 0, s, clear_color, (uint32_t*)f.depth, n,
+                               marks ? 0u : 0x7F800000u, copy ? sc : nullptr, copy ? sd : nullptr);
+        }, load);
+    if (!marks) return;
     const int64_t ni = f.index_count;
-    float4x4 m;
-    for (int c = 0; c < 4; c++)
-        m.columns[c] = make_float4(f.m[4 * c + 0], f.m[4 * c + 1], f.m[4 * c + 2], f.m[4 * c + 3]);
+    const float4x4 m = matrix_of(f);
     if (lines)
         hipLaunchKernelGGL(k_lines, dim3((unsigned)((ni / 2 + 63) / 64)), dim3(64), 0, s, f.vertices, f.indices, ni / 2, m, f.tg,
                            (uint32_t*)f.depth);
     else
         hipLaunchKernelGGL(k_points, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, s, f.vertices, f.indices, ni, m, f.tg,
                            (uint32_t*)f.depth);
-    if (load)
-        hipLaunchKernelGGL(k_points_resolve<true>, dim3(blocks), dim3(256), 0, s, f.vertices, f.indices, (uint32_t*)f.color,
+    with_bools([&](auto LOAD) {
+        hipLaunchKernelGGL(k_points_resolve<LOAD>, dim3(blocks), dim3(256), 0, s, f.vertices, f.indices, (uint32_t*)f.color,
                            (uint32_t*)f.depth, n, sc, sd);
-    else
-        hipLaunchKernelGGL(k_points_resolve<false>, dim3(blocks), dim3(256), 0, s, f.vertices, f.indices, (uint32_t*)f.color,
-                           (uint32_t*)f.depth, n, nullptr, nullptr);
+    }, load);
 }
 
 void launch_validate_indices(const int64_t* indices, int64_t count, int64_t vertex_count,
@@ -3322,8 +3327,7 @@ static SetupArgs make_setup_args(const DeviceFrame& f) {
     a.tile_count = f.tile_count; a.ranges = f.ranges; a.tg = f.tg;
     a.metal = (f.flags & SWR_FLAG_METAL_RULES) ? 1 : 0;
     a.faces = faces_of(f.flags);
-    for (int c = 0; c < 4; c++)
-        a.m.columns[c] = make_float4(f.m[4 * c + 0], f.m[4 * c + 1], f.m[4 * c + 2], f.m[4 * c + 3]);
+    a.m = matrix_of(f);
     return a;
 }
 
@@ -3356,32 +3360,24 @@ void launch_texture_to_float(const uint32_t* bgra, int64_t n, float4* out, hipSt
     hipLaunchKernelGGL(k_texture_to_float, dim3(2048), dim3(256), 0, s, bgra, n, out);
 }
 
+// k_bin's instantiation set, written once: launch_bin picks one of the 16, prepare_device walks them all.
+using BinKernel = void (*)(BinArgs);
+static BinKernel bin_kernel(bool metal, bool defer, bool affine, bool list) {
+    return with_bools([](auto MT, auto DEFER, auto AFF, auto LIST) -> BinKernel { return k_bin<256, MT, DEFER, AFF, LIST>; },
+                      metal, defer, affine, list);
+}
+
 // The LDS binning kernels may ask for the whole 160 KB of a CU (8K-class tile tables).  The attribute is per device
 // (per loaded code object): swr_context_create calls this after hipSetDevice for every device it opens.
 hipError_t prepare_device() {
+    const auto whole_lds = [](auto kernel) { return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
     hipError_t e;
-    if ((e = hipFuncSetAttribute((const void*)k_setup_hist<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_setup_hist<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-#define SWR_BIN_ATTR(MT, DF, AF) \
-    if ((e = hipFuncSetAttribute((const void*)k_bin<256, MT, DF, AF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    SWR_BIN_ATTR(false, false, false) SWR_BIN_ATTR(true, false, false) SWR_BIN_ATTR(false, true, false) SWR_BIN_ATTR(true, true, false)
-    SWR_BIN_ATTR(false, false, true) SWR_BIN_ATTR(true, false, true) SWR_BIN_ATTR(false, true, true) SWR_BIN_ATTR(true, true, true)
-#undef SWR_BIN_ATTR
-#define SWR_BIN_ATTR(MT, DF, AF) \
-    if ((e = hipFuncSetAttribute((const void*)k_bin<256, MT, DF, AF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    SWR_BIN_ATTR(false, false, false) SWR_BIN_ATTR(true, false, false) SWR_BIN_ATTR(false, true, false) SWR_BIN_ATTR(true, true, false)
-    SWR_BIN_ATTR(false, false, true) SWR_BIN_ATTR(true, false, true) SWR_BIN_ATTR(false, true, true) SWR_BIN_ATTR(true, true, true)
-#undef SWR_BIN_ATTR
-    return hipFuncSetAttribute((const void*)k_fill_lds<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if ((e = whole_lds(k_setup_hist<256, false>)) != hipSuccess) return e;
+    if ((e = whole_lds(k_setup_hist<256, true>)) != hipSuccess) return e;
+    for (int v = 0; v < 16; v++)
+        if ((e = whole_lds(bin_kernel(v & 1, v & 2, v & 4, v & 8))) != hipSuccess) return e;
+    return whole_lds(k_fill_lds<256>);
 }
-
-// Launch with the completion of the kernel bound to `stop` (hipExtLaunchKernelGGL: the event is the kernel's own
-// completion signal — no marker packet behind the kernel, which would cost the next kernel of the queue ~6.5 us).
-#define SWR_LAUNCH(stop, kernel, grid, block, lds, stream, ...)                                         \
-    do {                                                                                              \
-        if (stop) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, nullptr, stop, 0, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                        \
-    } while (0)
 
 // 16-bit LDS counters in the two binning walks: a workgroup's count for one tile is at most the primitives it owns
 // (k_fill_lds with 16-bit running counts in LDS and its bin positions gathered from its row of M was built too: alone
@@ -3397,13 +3393,14 @@ void launch_setup_bin(const DeviceFrame& f, hipStream_t s) {
     launch_list_gather(f, s);
     launch_persp_fill(f, s);
     const SetupArgs a = make_setup_args(f);
-    const int ntiles = f.tg.tiles_x * f.tg.tiles_y;
+    const int ntiles = tiles_of(f);
     if (f.plan.use_lds) {
         const int per = live_groups_per_workgroup(f.ntri, f.plan.G);
         const bool h16 = bin_h16(per);
         const size_t lds = (h16 ? (size_t)((ntiles + 1) / 2) * 4 : f.plan.lds_bytes) + (size_t)(per + 1) * 4;
-        if (h16) hipLaunchKernelGGL((k_setup_hist<256, true>), dim3(f.plan.G), dim3(256), lds, s, a, f.bin_matrix, f.live, per, ntiles);
-        else hipLaunchKernelGGL((k_setup_hist<256, false>), dim3(f.plan.G), dim3(256), lds, s, a, f.bin_matrix, f.live, per, ntiles);
+        with_bools([&](auto H16) {
+            hipLaunchKernelGGL((k_setup_hist<256, H16>), dim3(f.plan.G), dim3(256), lds, s, a, f.bin_matrix, f.live, per, ntiles);
+        }, h16);
         hipLaunchKernelGGL(k_colscan, dim3((ntiles + 15) / 16), dim3(256), 0, s, f.bin_matrix, f.plan.G, ntiles,
                            f.tile_count);
     } else if (f.items) {
@@ -3426,10 +3423,8 @@ static void launch_list_gather(const DeviceFrame& f, hipStream_t s) {
 // the perspective table of a frame that has one (DeviceFrame::pq), in front of its binning; depth-clip frames fill theirs in k_clip_emit
 static void launch_persp_fill(const DeviceFrame& f, hipStream_t s) {
     if (f.ntri <= 0 || !f.pq || f.clip.bound > 0) return;
-    float4x4 m;
-    for (int c = 0; c < 4; c++) m.columns[c] = make_float4(f.m[4 * c + 0], f.m[4 * c + 1], f.m[4 * c + 2], f.m[4 * c + 3]);
     const unsigned blocks = (unsigned)std::min<int64_t>(2048, (f.ntri + 255) / 256);
-    hipLaunchKernelGGL(k_persp_fill, dim3(blocks), dim3(256), 0, s, f.items, (int)f.nitems, f.ntri, f.tri_xyz, m, f.pq);
+    hipLaunchKernelGGL(k_persp_fill, dim3(blocks), dim3(256), 0, s, f.items, (int)f.nitems, f.ntri, f.tri_xyz, matrix_of(f), f.pq);
 }
 
 // Can the frame be binned by the single-launch k_bin (fixed-stride bins), and how large may a tile region be?  Needs the
@@ -3455,9 +3450,9 @@ bool launch_bin(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     BinArgs b;
     b.a = make_setup_args(f);
     b.fill = f.fill; b.fill_next = f.fill_next; b.bins = f.bins; b.cap = f.cap_tile;
-    b.ntiles = f.tg.tiles_x * f.tg.tiles_y;
+    b.ntiles = tiles_of(f);
     b.per = live_groups_per_workgroup(f.ntri, f.plan.G);
-    b.tag_class = f.ntri < (1ll << CLASS_SHIFT) ? 1 : 0;
+    b.tag_class = tag_class(f);
     b.items = f.items; b.nitems = f.nitems; b.units = f.units;
     if (f.items) b.per = (int)((f.units + f.plan.G - 1) / f.plan.G);
     // the deferring kernel (three registers more: it would not fit beside five raster waves) only for frames
@@ -3466,102 +3461,114 @@ bool launch_bin(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     const size_t lds = (size_t)((b.ntiles + 1) / 2) * 4 + (size_t)(b.per + 1) * 4 + 2 * (256 / 64) * 4 + 4;
     // the transform's last row is (0, 0, 0, 1): w == 1 for every finite vertex, no perspective divide (setup_triangle_r<.., AFF>)
     const bool aff = f.items ? f.list_affine != 0 : f.m[3] == 0.0f && f.m[7] == 0.0f && f.m[11] == 0.0f && f.m[15] == 1.0f;
-    if (f.items) {
-#define SWR_BIN_GOL(MT, DF, AF) SWR_LAUNCH(stop, (k_bin<256, MT, DF, AF, true>), dim3(f.plan.G), dim3(256), (uint32_t)lds, s, b)
-        if (aff) {
-            if (b.defer_ok) { if (b.a.metal) SWR_BIN_GOL(true, true, true); else SWR_BIN_GOL(false, true, true); }
-            else { if (b.a.metal) SWR_BIN_GOL(true, false, true); else SWR_BIN_GOL(false, false, true); }
-        } else {
-            if (b.defer_ok) { if (b.a.metal) SWR_BIN_GOL(true, true, false); else SWR_BIN_GOL(false, true, false); }
-            else { if (b.a.metal) SWR_BIN_GOL(true, false, false); else SWR_BIN_GOL(false, false, false); }
-        }
-#undef SWR_BIN_GOL
-        return stop != nullptr;
-    }
-#define SWR_BIN_GO2(MT, DF, AF) SWR_LAUNCH(stop, (k_bin<256, MT, DF, AF>), dim3(f.plan.G), dim3(256), (uint32_t)lds, s, b)
-    if (aff) {
-        if (b.defer_ok) { if (b.a.metal) SWR_BIN_GO2(true, true, true); else SWR_BIN_GO2(false, true, true); }
-        else { if (b.a.metal) SWR_BIN_GO2(true, false, true); else SWR_BIN_GO2(false, false, true); }
-    } else {
-        if (b.defer_ok) { if (b.a.metal) SWR_BIN_GO2(true, true, false); else SWR_BIN_GO2(false, true, false); }
-        else { if (b.a.metal) SWR_BIN_GO2(true, false, false); else SWR_BIN_GO2(false, false, false); }
-    }
-#undef SWR_BIN_GO2
-    return stop != nullptr;
+    return launch_on(stop, bin_kernel(b.a.metal != 0, b.defer_ok != 0, aff, f.items != nullptr), dim3(f.plan.G), dim3(256), lds, s, b);
 }
 
 void launch_scan(const DeviceFrame& f, hipStream_t s) {
     if (f.plan.use_lds && f.ntri > 0) return;   // LDS path: the scan is fused into k_fill_lds
-    const int n = f.tg.tiles_x * f.tg.tiles_y;
+    const int n = tiles_of(f);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, f.tile_count, f.tile_start, f.tile_cursor, n,
                        f.counters, f.host_counters, f.capacity);
 }
 
 bool launch_fill(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     if (f.ntri <= 0) return false;
-    const int ntiles = f.tg.tiles_x * f.tg.tiles_y;
     if (f.plan.use_lds) {
         const int per = live_groups_per_workgroup(f.ntri, f.plan.G);
-        const int tagged = f.ntri < (1ll << CLASS_SHIFT) ? 1 : 0;
-        SWR_LAUNCH(stop, k_fill_lds<256>, dim3(f.plan.G), dim3(256), (uint32_t)(f.plan.lds_bytes + 4 * 256), s,
-                   (const uint2*)f.ranges, f.ntri, (const uint32_t*)f.bin_matrix, (const uint32_t*)f.tile_count, f.tile_start,
-                   f.counters, f.host_counters, f.bins, f.capacity, (const uint32_t*)f.live, per, ntiles, (int)f.tg.tiles_x, tagged, f.host_max);
-    } else {
-        const unsigned blocks = (unsigned)((f.ntri + 255) / 256);
-        hipLaunchKernelGGL(k_fill, dim3(blocks), dim3(256), 0, s, f.ranges, f.ntri, f.tile_cursor, f.counters,
-                           f.bins, f.capacity, f.tg.tiles_x, f.ntri < (1ll << CLASS_SHIFT) ? 1 : 0);
-        return false;
+        return launch_on(stop, k_fill_lds<256>, dim3(f.plan.G), dim3(256), f.plan.lds_bytes + 4 * 256, s,
+                         (const uint2*)f.ranges, f.ntri, (const uint32_t*)f.bin_matrix, (const uint32_t*)f.tile_count, f.tile_start,
+                         f.counters, f.host_counters, f.bins, f.capacity, (const uint32_t*)f.live, per, tiles_of(f), (int)f.tg.tiles_x,
+                         tag_class(f), f.host_max);
     }
-    return stop != nullptr;
+    const unsigned blocks = (unsigned)((f.ntri + 255) / 256);
+    hipLaunchKernelGGL(k_fill, dim3(blocks), dim3(256), 0, s, f.ranges, f.ntri, f.tile_cursor, f.counters,
+                       f.bins, f.capacity, f.tg.tiles_x, tag_class(f));
+    return false;
 }
 
 bool launch_sort_bins(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
-    const unsigned tiles = (unsigned)(f.tg.tiles_x * f.tg.tiles_y);
+    const unsigned tiles = (unsigned)tiles_of(f);
     if (f.ntri <= 0 || tiles == 0 || f.skip_sort) return false;
-    SWR_LAUNCH(stop, k_sort_bins, dim3(tiles), dim3(SORT_THREADS), 0, s, f.bins, (const uint32_t*)f.tile_start,
-               (const uint32_t*)f.counters, f.capacity, f.ntri < (1ll << CLASS_SHIFT) ? 1 : 0,
-               (uint32_t*)(f.fixed_bins ? f.fill : nullptr), f.fixed_bins ? f.cap_tile : 0u,
-               (const uint4*)(f.fixed_bins ? f.biglist : nullptr), (int)f.tg.tiles_x);
-    return stop != nullptr;
+    return launch_on(stop, k_sort_bins, dim3(tiles), dim3(SORT_THREADS), 0, s, f.bins, (const uint32_t*)f.tile_start,
+                     (const uint32_t*)f.counters, f.capacity, tag_class(f),
+                     (uint32_t*)(f.fixed_bins ? f.fill : nullptr), f.fixed_bins ? f.cap_tile : 0u,
+                     (const uint4*)(f.fixed_bins ? f.biglist : nullptr), (int)f.tg.tiles_x);
 }
 
-// Does this frame take k_raster_depth (32-bit depth keys)?  Depth-only, z-tested, CPU rules, and the scene has not been moved
-// to the 64-bit kernel by the host (DeviceFrame::k32).
-bool frame_uses_k32(const DeviceFrame& f) {
-    return f.k32 && !(f.flags & SWR_FLAG_PRIMITIVE_IDS) && (f.flags & SWR_FLAG_DEPTH_TEST) && (f.flags & SWR_FLAG_NO_COLOR) && !(f.flags & SWR_FLAG_METAL_RULES);
-}
-
-// A blend frame's raster (SWR_FLAG_BLEND): its bins put in order, then k_raster_blend.  The host has kept PRIMITIVE_IDS, PERSPECTIVE,
-// NO_COLOR and the extended fragment stage away from it.
-static bool launch_raster_blend(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
-    const unsigned ntiles = (unsigned)(f.tg.tiles_x * f.tg.tiles_y);
-    if (ntiles == 0) return false;
-    const bool load = (f.flags & SWR_FLAG_LOAD) != 0;
-    BlendArgs a;
-    a.geo = f.geo; a.geo_full = f.geo_full; a.inv = f.inv; a.reordered = f.reordered; a.tri_rgb = f.tri_rgb;
+// The bin view of the raster kernels' arguments (RasterArgs and BlendArgs name these fields alike).
+template <class Args>
+static void fill_bin_view(Args& a, const DeviceFrame& f) {
     a.tile_start = f.tile_start; a.bins = f.bins; a.counters = f.counters; a.capacity = f.capacity;
     a.fill = f.fixed_bins ? f.fill : nullptr;
     a.fixed_cap = f.fixed_bins ? f.cap_tile : 0u;
     a.host_pairs = f.host_counters; a.host_fill = f.host_fill; a.host_max = f.host_max;
-    a.tag_class = f.ntri < (1ll << CLASS_SHIFT) ? 1 : 0;
+    a.tag_class = tag_class(f);
+}
+
+// Which raster kernel a frame without SWR_FLAG_BLEND takes, and the arguments that follow from the choice.
+struct RasterChoice {
+    bool load, ids;     // the LOAD / IDS twin of the kernel (SWR_FLAG_LOAD, SWR_FLAG_PRIMITIVE_IDS)
+    bool metal, ztest;  // the Metal rules always z-test
+    bool color;         // colour kernels; false: the depth-only ones (SWR_FLAG_NO_COLOR)
+    bool ext;           // the extended fragment stage (colour frames only)
+    bool plain;         // the colour kernels without the winner table: order numbers of 2^20 and more (RasterArgs::pack_local == 0)
+    bool k32;           // k_raster_depth: depth-only, z-tested, CPU rules, no IDs, and the host has not moved the scene to the
+                        // 64-bit kernel (DeviceFrame::k32)
+    int vs_log;         // 2^vs_log workgroups per tile
+};
+static RasterChoice raster_choice(const DeviceFrame& f) {
+    RasterChoice c;
+    c.load = (f.flags & SWR_FLAG_LOAD) != 0;
+    c.ids = (f.flags & SWR_FLAG_PRIMITIVE_IDS) != 0;
+    c.metal = (f.flags & SWR_FLAG_METAL_RULES) != 0;
+    c.ztest = c.metal || (f.flags & SWR_FLAG_DEPTH_TEST) != 0;
+    c.color = !(f.flags & SWR_FLAG_NO_COLOR);
+    c.ext = f.material.shader != SWR_SHADER_PASSTHROUGH && c.color;
+    // (a load frame's z-tested keys carry the packed word + 1: the last primitive of a scene of exactly 2^20 would wrap)
+    // (depth-clip frames: their order numbers lie below the post-clip count, or a bound of it, not below their slot count)
+    c.plain = (f.order_space > 0 ? f.order_space : f.ntri) >= (1ll << WTAB_PRIM_BITS) + (c.load ? 0 : 1);
+    c.k32 = f.k32 && !c.ids && c.ztest && !c.color && !c.metal;
+    // Small grids (a small window: the reference app's 512x512 is 128 tiles): four workgroups fit where one tile's
+    // would run, so four share a tile, each walking and resolving its own 8 rows of it — the per-triangle setup is paid
+    // four times, the row steps and the pixel work are divided (the app's sphere: k_raster 19.9 -> 12.8 us, Metal rules
+    // 25.6 -> 14.3 us).  Two per tile for 320-640 tiles (1/8 band of cfg4: 510 dense tiles) measured no gain (23.3 vs
+    // 24.6 us): those workgroups are bound by the gather -> setup latency chain of their chunks, not by their rows
+    // (profiles/r02/vsplit_ab.txt).  -DSWR_TUNE_VSPLIT=0/1/2 forces the log2 of the split.
+    constexpr int vs_mode = SWR_TUNE_VSPLIT;
+    c.vs_log = vs_mode >= 0 ? std::min(vs_mode, 2) : (tiles_of(f) * 4 <= 1280 ? 2 : 0);
+    return c;
+}
+
+bool frame_uses_k32(const DeviceFrame& f) { return raster_choice(f).k32; }
+
+// A blend frame's raster (SWR_FLAG_BLEND): its bins put in order, then k_raster_blend.  The host has kept PRIMITIVE_IDS, PERSPECTIVE,
+// NO_COLOR and the extended fragment stage away from it.
+static bool launch_raster_blend(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
+    const unsigned ntiles = (unsigned)tiles_of(f);
+    if (ntiles == 0) return false;
+    const bool load = (f.flags & SWR_FLAG_LOAD) != 0;
+    BlendArgs a;
+    a.geo = f.geo; a.geo_full = f.geo_full; a.inv = f.inv; a.reordered = f.reordered; a.tri_rgb = f.tri_rgb;
+    fill_bin_view(a, f);
     a.color = f.color; a.depth = f.depth;
     a.src_color = load ? f.src_color : nullptr;
     a.src_depth = load ? f.src_depth : nullptr;
     a.tg = f.tg;
     a.mode = f.blend.mode; a.opacity = f.blend.opacity;
     if (f.ntri > 0) hipLaunchKernelGGL(k_blend_order, dim3(ntiles), dim3(256), 0, s, a);
-#define SWR_BLEND_GO(ZT, MT) \
-    do { if (load) SWR_LAUNCH(stop, (k_raster_blend<ZT, MT, true>), dim3(ntiles), dim3(RASTER_THREADS), 0, s, a); \
-         else SWR_LAUNCH(stop, (k_raster_blend<ZT, MT, false>), dim3(ntiles), dim3(RASTER_THREADS), 0, s, a); } while (0)
-    if (f.flags & SWR_FLAG_METAL_RULES) SWR_BLEND_GO(true, true);
-    else if (f.flags & SWR_FLAG_DEPTH_TEST) SWR_BLEND_GO(true, false);
-    else SWR_BLEND_GO(false, false);
-#undef SWR_BLEND_GO
-    return stop != nullptr;
+    return with_bools([&](auto ZTEST, auto LOAD) {
+        const auto go = [&](auto kernel) { return launch_on(stop, kernel, dim3(ntiles), dim3(RASTER_THREADS), 0, s, a); };
+        if (f.flags & SWR_FLAG_METAL_RULES) return go(k_raster_blend<true, true, LOAD>);
+        return go(k_raster_blend<ZTEST, false, LOAD>);
+    }, (f.flags & SWR_FLAG_DEPTH_TEST) != 0, load);
 }
 
-template <bool LOAD, bool IDS>
-static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
+// Every other frame's raster: the kernel raster_choice names.  A parameter is lifted only where the kernels exist for both of its
+// values; COLOR = false with PLAIN = true, the Metal rules without z-test and k_raster_depth with IDs are never named.
+static bool launch_raster_keys(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
+    const RasterChoice c = raster_choice(f);
+    const unsigned ntiles = (unsigned)tiles_of(f);
+    if (ntiles == 0) return false;
     RasterArgs a;
     a.geo = f.geo; a.geo_full = f.geo_full; a.tri_rgb = f.tri_rgb;
     a.inv = f.inv; a.reordered = f.reordered;
@@ -3571,90 +3578,53 @@ static bool launch_raster_t(const DeviceFrame& f, hipStream_t s, hipEvent_t stop
     a.fs.half_dir = make_float3(f.material.half_dir[0], f.material.half_dir[1], f.material.half_dir[2]);
     a.fs.ambient = f.material.ambient; a.fs.diffuse = f.material.diffuse; a.fs.specular = f.material.specular;
     a.fs.texels = f.texels; a.fs.tex_w = f.tex_w; a.fs.tex_h = f.tex_h;
-    a.tile_start = f.tile_start; a.bins = f.bins;
-    a.counters = f.counters; a.capacity = f.capacity;
-    a.color = (f.flags & SWR_FLAG_NO_COLOR) ? nullptr : f.color;
+    fill_bin_view(a, f);
+    a.color = c.color ? f.color : nullptr;
     a.depth = f.depth; a.tg = f.tg;
-    a.tag_class = f.ntri < (1ll << CLASS_SHIFT) ? 1 : 0;
-    a.fill = f.fixed_bins ? f.fill : nullptr;
-    a.fixed_cap = f.fixed_bins ? f.cap_tile : 0u;
-    a.host_pairs = f.host_counters; a.host_fill = f.host_fill; a.host_max = f.host_max;
     a.redo_dev = f.redo_dev; a.host_redo = f.host_redo;
     a.insort = f.insort;
-    a.src_color = LOAD ? f.src_color : nullptr;
-    a.src_depth = LOAD ? f.src_depth : nullptr;
-    a.ids = IDS ? f.ids : nullptr;
-    a.persp = a.color ? f.pq : nullptr;
-    // (a load frame's z-tested keys carry the packed word + 1: the last primitive of a scene of exactly 2^20 would wrap)
-    // (depth-clip frames: their order numbers lie below the post-clip count, or a bound of it, not below their slot count)
-    a.pack_local = (f.order_space > 0 ? f.order_space : f.ntri) < (1ll << WTAB_PRIM_BITS) + (LOAD ? 0 : 1) ? 1 : 0;
-    const bool plain = !a.pack_local;      // more than 2^20 primitives: the colour kernels without the winner table
-    const unsigned ntiles = (unsigned)(f.tg.tiles_x * f.tg.tiles_y);
-    if (ntiles == 0) return false;
-    // Small grids (a small window: the reference app's 512x512 is 128 tiles): four workgroups fit where one tile's
-    // would run, so four share a tile, each walking and resolving its own 8 rows of it — the per-triangle setup is paid
-    // four times, the row steps and the pixel work are divided (the app's sphere: k_raster 19.9 -> 12.8 us, Metal rules
-    // 25.6 -> 14.3 us).  Two per tile for 320-640 tiles (1/8 band of cfg4: 510 dense tiles) measured no gain (23.3 vs
-    // 24.6 us): those workgroups are bound by the gather -> setup latency chain of their chunks, not by their rows
-    // (profiles/r02/vsplit_ab.txt).  -DSWR_TUNE_VSPLIT=0/1/2 forces the log2 of the split.
-    constexpr int vs_mode = SWR_TUNE_VSPLIT;
-    a.vs_log = vs_mode >= 0 ? std::min(vs_mode, 2) : (ntiles * 4 <= 1280 ? 2 : 0);
-    const unsigned tiles = ntiles << a.vs_log;
-    const bool ext = f.material.shader != SWR_SHADER_PASSTHROUGH && a.color != nullptr;
-    if (f.flags & SWR_FLAG_METAL_RULES) {
-        if (ext && plain) SWR_LAUNCH(stop, (k_raster_ext<true, true, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (ext) SWR_LAUNCH(stop, (k_raster_ext<true, true, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, true, true, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, true, true, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else SWR_LAUNCH(stop, (k_raster<true, 0, true, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        return stop != nullptr;
-    }
-    if (ext) {
-        if (f.flags & SWR_FLAG_DEPTH_TEST) {
-            if (plain) SWR_LAUNCH(stop, (k_raster_ext<true, false, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-            else SWR_LAUNCH(stop, (k_raster_ext<true, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        } else {
-            if (plain) SWR_LAUNCH(stop, (k_raster_ext<false, false, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-            else SWR_LAUNCH(stop, (k_raster_ext<false, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
+    a.src_color = c.load ? f.src_color : nullptr;
+    a.src_depth = c.load ? f.src_depth : nullptr;
+    a.ids = c.ids ? f.ids : nullptr;
+    a.persp = c.color ? f.pq : nullptr;
+    a.pack_local = c.plain ? 0 : 1;
+    a.vs_log = c.vs_log;
+    const unsigned tiles = ntiles << c.vs_log;
+    return with_bools([&](auto ZTEST, auto PLAIN, auto LOAD, auto IDS) {
+        const auto go = [&](auto kernel) { return launch_on(stop, kernel, dim3(tiles), dim3(RASTER_THREADS), 0, s, a); };
+        if (c.metal) {
+            if (c.ext) return go(k_raster_ext<true, true, PLAIN, LOAD, IDS>);
+            if (c.color) return go(k_raster<true, 0, true, true, PLAIN, LOAD, IDS>);
+            return go(k_raster<true, 0, true, false, false, LOAD, IDS>);
         }
-        return stop != nullptr;
-    }
+        if (c.ext) return go(k_raster_ext<ZTEST, false, PLAIN, LOAD, IDS>);
 #ifdef SWR_ABLATION
-    // timing-only ablations of k_raster<ztest> (results invalid): compiled only into lib/libswr_hip_ablation.so
-    // (`make ablation`, used by tools/variants.sh); the product library has neither the kernels nor the switch
-    static const int variant = getenv("SWR_DEBUG_VARIANT") ? atoi(getenv("SWR_DEBUG_VARIANT")) : 0;
-    if (!LOAD && !IDS && (f.flags & SWR_FLAG_DEPTH_TEST) && variant > 0 && !a.color) {
-        switch (variant) {
+        // timing-only ablations of k_raster<ztest> (results invalid): compiled only into lib/libswr_hip_ablation.so
+        // (`make ablation`, used by tools/variants.sh); the product library has neither the kernels nor the switch
+        static const int variant = getenv("SWR_DEBUG_VARIANT") ? atoi(getenv("SWR_DEBUG_VARIANT")) : 0;
+        if (!LOAD && !IDS && ZTEST && variant > 0 && !c.color) {
+            switch (variant) {
 #define SWR_V(N) case N: hipLaunchKernelGGL((k_raster<true, N>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a); return false;
-            SWR_V(1) SWR_V(2) SWR_V(3) SWR_V(4) SWR_V(5) SWR_V(8) SWR_V(9) SWR_V(10) SWR_V(11)
+                SWR_V(1) SWR_V(2) SWR_V(3) SWR_V(4) SWR_V(5) SWR_V(8) SWR_V(9) SWR_V(10) SWR_V(11)
 #undef SWR_V
-            default: break;
+                default: break;
+            }
         }
-    }
 #endif
-    if (f.flags & SWR_FLAG_DEPTH_TEST) {
-        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (!IDS && frame_uses_k32(f)) SWR_LAUNCH(stop, k_raster_depth<LOAD>, dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else SWR_LAUNCH(stop, (k_raster<true, 0, false, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-    } else {
-        if (a.color && plain) SWR_LAUNCH(stop, (k_raster<false, 0, false, true, true, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else if (a.color) SWR_LAUNCH(stop, (k_raster<false, 0, false, true, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-        else SWR_LAUNCH(stop, (k_raster<false, 0, false, false, false, LOAD, IDS>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);
-    }
-    return stop != nullptr;
+        if (c.color) return go(k_raster<ZTEST, 0, false, true, PLAIN, LOAD, IDS>);
+        if (c.k32) return go(k_raster_depth<LOAD>);
+        return go(k_raster<ZTEST, 0, false, false, false, LOAD, IDS>);
+    }, c.ztest, c.plain, c.load, c.ids);
 }
 
 bool launch_raster(const DeviceFrame& f, hipStream_t s, hipEvent_t stop) {
     if (f.flags & SWR_FLAG_BLEND) return launch_raster_blend(f, s, stop);
-    const bool load = (f.flags & SWR_FLAG_LOAD) != 0;
     // a depth-clip frame's IDs are order numbers of its clip stream: mapped to the original numbers behind the raster
-    if (f.clip.bound > 0 && f.ids && f.tg.tiles_x * f.tg.tiles_y > 0) {
-        if (f.flags & SWR_FLAG_PRIMITIVE_IDS) load ? launch_raster_t<true, true>(f, s, nullptr) : launch_raster_t<false, true>(f, s, nullptr);
+    if (f.clip.bound > 0 && f.ids && tiles_of(f) > 0) {
+        if (f.flags & SWR_FLAG_PRIMITIVE_IDS) launch_raster_keys(f, s, nullptr);
         return launch_clip_ids(f, s, stop);
     }
-    if (f.flags & SWR_FLAG_PRIMITIVE_IDS) return load ? launch_raster_t<true, true>(f, s, stop) : launch_raster_t<false, true>(f, s, stop);
-    return load ? launch_raster_t<true, false>(f, s, stop) : launch_raster_t<false, false>(f, s, stop);
+    return launch_raster_keys(f, s, stop);
 }
 
 }  // namespace swr

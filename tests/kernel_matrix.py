@@ -2,8 +2,9 @@
 expected images of such frames, built on the unchanged oracle.  A plain helper module of tests/test_kernel_matrix.py,
 tests/test_primitive_boundary.py and tests/test_kernel_matrix_table.py (not a conftest, not a test file).
 
-The rows are named by their template arguments exactly as written in launch_raster_t / launch_bin
-(software-renderer_amd/csrc/swr_kernels.hip), LOAD and IDS filled in; tests/test_kernel_matrix_table.py parses the dispatch and
+The rows are named by their template arguments exactly as written in launch_raster_keys / bin_kernel
+(software-renderer_amd/csrc/swr_kernels.hip), the parameters lifted by with_bools (ZTEST, PLAIN, LOAD, IDS; k_bin: all four, LIST
+written only where it is true) filled in; tests/test_kernel_matrix_table.py parses the dispatch and
 fails when a variant is added there without a row here.
 
 Expectations (include/swr.h):
@@ -79,7 +80,8 @@ def _b(x):
     return "true" if x else "false"
 
 
-# one entry per SWR_LAUNCH of launch_raster_t<LOAD, IDS>, in dispatch order: (name, flags, shader, scenes, only without IDS, hooks)
+# one entry per instantiation launch_raster_keys can reach, LOAD and IDS left open, in dispatch order:
+# (name, flags, shader, scenes, only without IDS, hooks)
 _BOTH = ("visible", "padded")
 _RASTER = [
     # Metal rules
@@ -120,7 +122,7 @@ def raster_rows():
 
 
 def bin_rows():
-    """The 16 k_bin<256, MT, DEFER, AFF, LIST> instantiations (SWR_BIN_GO2: draws, SWR_BIN_GOL: draw lists)."""
+    """The 16 k_bin<256, MT, DEFER, AFF, LIST> instantiations of bin_kernel (LIST = false: draws, true: draw lists)."""
     rows = []
     k = 0
     for metal in (False, True):
@@ -157,7 +159,7 @@ DEBUG_STREAM_ORDER = 1
 
 @dataclasses.dataclass(frozen=True)
 class BlendRow:
-    """k_raster_blend<ZT, MT, LOAD> as written in launch_raster_blend (SWR_BLEND_GO expanded), or k_blend_order; the blend frame that
+    """k_raster_blend<ZT, MT, LOAD> as written in launch_raster_blend (ZTEST, LOAD filled in), or k_blend_order; the blend frame that
     reaches it: flags (DT / METAL / LOAD, without the BLEND bit) and the swr_blend state."""
     name: str
     flags: int

@@ -1,5 +1,6 @@
 """The kernel matrix cannot rot (CPU): the rows of tests/kernel_matrix.py are exactly the kernels the dispatch can launch, and the
 expectation helpers hold the identities include/swr.h states."""
+import itertools
 import os
 import re
 
@@ -18,44 +19,66 @@ def _body(src, start, end):
     return src[a:src.index(end, a)]
 
 
-def dispatch_kernels(src):
-    """The kernels launch_raster_t<LOAD, IDS> (LOAD and IDS expanded to false / true, the SWR_ABLATION block skipped) and
-    launch_bin (its SWR_BIN_GOL / SWR_BIN_GO2 calls expanded) can launch, template arguments as written."""
-    raster = _body(src, "static bool launch_raster_t(", "\nbool launch_raster(")
-    raster = re.sub(r"#ifdef SWR_ABLATION.*?#endif", "", raster, flags=re.S)
+def _code(src):
+    """The source without the SWR_ABLATION block and without its comments."""
+    return re.sub(r"//[^\n]*", "", re.sub(r"#ifdef SWR_ABLATION.*?#endif", "", src, flags=re.S))
+
+
+def _block_end(text, at):
+    """The index behind the brace that closes the one opened at text[at]."""
+    depth = 0
+    for i in range(at, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[i], 0)
+        if depth == 0:
+            return i + 1
+    raise ValueError("unbalanced braces")
+
+
+def kernels_named(code):
+    """Every kernel a piece of launch code names (k_name or k_name<...>), template arguments as written.  The lifter: in the generic
+    lambda handed to with_bools, a template argument that is one of the lambda's `auto NAME` parameters is expanded to false and
+    true, since with_bools instantiates the lambda's body for both."""
+    lifted = []
+    for m in re.finditer(r"\bwith_bools\(\s*\[[^\]]*\]\s*\(([^)]*)\)[^{;]*\{", code):
+        lifted.append((m.end() - 1, _block_end(code, m.end() - 1), re.findall(r"\bauto\s+(\w+)", m.group(1))))
     out = set()
-    for k in re.findall(r"SWR_LAUNCH\(\s*stop\s*,\s*\(?\s*(k_\w+<[^>]*>)", raster):
-        for load in ("false", "true"):
-            for ids in ("false", "true"):
-                out.add(re.sub(r"\bIDS\b", ids, re.sub(r"\bLOAD\b", load, k)))
-    binning = _body(src, "bool launch_bin(", "\nvoid launch_scan(")
-    for macro, params, kernel in re.findall(r"#define (SWR_BIN_GO\w*)\(([^)]*)\)\s*SWR_LAUNCH\(\s*stop\s*,\s*\((k_bin<[^>]*>)\)",
-                                            binning):
-        names = [p.strip() for p in params.split(",")]
-        for args in re.findall(re.escape(macro) + r"\(([^)]*)\);", binning):
-            k = kernel
-            for p, a in zip(names, [x.strip() for x in args.split(",")]):
-                k = re.sub(r"\b%s\b" % p, a, k)
+    for m in re.finditer(r"\bk_\w+\b(?:<[^<>;]*>)?", code):
+        names = [n for a, b, ns in lifted if a <= m.start() < b for n in ns if re.search(r"\b%s\b" % n, m.group(0))]
+        for values in itertools.product(("false", "true"), repeat=len(names)):
+            k = m.group(0)
+            for n, v in zip(names, values):
+                k = re.sub(r"\b%s\b" % n, v, k)
             out.add(k)
     return out
+
+
+def dispatch_kernels(src):
+    """The kernels launch_raster_keys (the SWR_ABLATION block skipped) and launch_bin (with bin_kernel, which holds its k_bin
+    template-id) can launch."""
+    code = _code(src)
+    return (kernels_named(_body(code, "static bool launch_raster_keys(", "\nbool launch_raster("))
+            | kernels_named(_body(code, "static BinKernel bin_kernel(", "\n}\n"))
+            | kernels_named(_body(code, "bool launch_bin(", "\nvoid launch_scan(")))
 
 
 def blend_kernels(src):
-    """The kernels launch_raster_blend can launch: the plain launches, and the SWR_BLEND_GO(ZT, MT) macro (its launches, one per
-    LOAD value) expanded for every call."""
-    body = _body(src, "static bool launch_raster_blend(", "\ntemplate <bool LOAD, bool IDS>")
-    macro = re.search(r"#define SWR_BLEND_GO\(([^)]*)\)((?:.*\\\n)*.*)\n", body)
-    names = [p.strip() for p in macro.group(1).split(",")]
-    templates = re.findall(r"SWR_LAUNCH\(\s*stop\s*,\s*\(?\s*(k_\w+<[^>]*>)", macro.group(2))
-    rest = body[:macro.start()] + body[macro.end():]
-    out = set(re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*(k_\w+(?:<[^>]*>)?)", rest))
-    out |= set(re.findall(r"SWR_LAUNCH\(\s*stop\s*,\s*\(?\s*(k_\w+(?:<[^>]*>)?)", rest))
-    for args in re.findall(r"SWR_BLEND_GO\(([^)]*)\);", rest):
-        for k in templates:
-            for p, a in zip(names, [x.strip() for x in args.split(",")]):
-                k = re.sub(r"\b%s\b" % p, a, k)
-            out.add(k)
-    return out
+    """The kernels launch_raster_blend can launch."""
+    return kernels_named(_body(_code(src), "static bool launch_raster_blend(", "\nstatic bool launch_raster_keys("))
+
+
+def canonical(name, src):
+    """A template-id without the trailing arguments that repeat the defaults of the kernel's declaration (the rows write k_bin's
+    LIST only where it is true)."""
+    m = re.fullmatch(r"(k_\w+)<(.*)>", name)
+    if not m:
+        return name
+    at = src.index("void %s(" % m.group(1))
+    decl = src[src.rindex("template <", 0, at):at]
+    params = [p.partition("=")[2].strip() or None for p in decl[len("template <"):decl.index(">")].split(",")]
+    args = [a.strip() for a in m.group(2).split(",")]
+    while args and len(args) <= len(params) and params[len(args) - 1] == args[-1]:
+        args.pop()
+    return "%s<%s>" % (m.group(1), ", ".join(args))
 
 
 def resolve_kernels(src):
@@ -81,10 +104,10 @@ def test_blend_and_resolve_rows_are_the_dispatch():
 def test_the_blend_and_resolve_parsers_see_a_new_variant():
     with open(KERNELS) as f:
         src = f.read()
-    at = src.index("    else SWR_BLEND_GO(false, false);")
-    grown = blend_kernels(src[:at] + "    else if (f.nitems) SWR_BLEND_GO(false, true);\n" + src[at:])
+    at = src.index("        return go(k_raster_blend<ZTEST, false, LOAD>);")
+    grown = blend_kernels(src[:at] + "        if (f.nitems) return go(k_raster_blend<false, true, LOAD>);\n" + src[at:])
     assert grown - blend_kernels(src) == {"k_raster_blend<false, true, true>", "k_raster_blend<false, true, false>"}
-    at = src.index("#define SWR_BLEND_GO(ZT, MT)")
+    at = src.index("    return with_bools([&](auto ZTEST, auto LOAD) {\n        const auto go = [&](auto kernel) { return launch_on(stop, kernel, dim3(ntiles)")
     grown = blend_kernels(src[:at] + "    hipLaunchKernelGGL(k_blend_merge, dim3(ntiles), dim3(256), 0, s, a);\n" + src[at:])
     assert grown - blend_kernels(src) == {"k_blend_merge"}
     with open(RESOLVE) as f:
@@ -128,28 +151,34 @@ def test_every_blend_and_resolve_row_reaches_its_kernel():
 def test_rows_are_the_dispatch():
     with open(KERNELS) as f:
         src = f.read()
-    found = dispatch_kernels(src)
+    found = {canonical(k, src) for k in dispatch_kernels(src)}
     rows = [r.name for r in K.ROWS]
-    assert len(rows) == len(set(rows))
-    assert set(rows) == found, (f"in the dispatch without a row: {sorted(found - set(rows))}; "
-                                f"rows the dispatch does not launch: {sorted(set(rows) - found)}")
+    want = {canonical(n, src) for n in rows}
+    assert len(rows) == len(set(rows)) == len(want) and len(found) == len(dispatch_kernels(src))
+    assert want == found, (f"in the dispatch without a row: {sorted(found - want)}; "
+                           f"rows the dispatch does not launch: {sorted(want - found)}")
     assert len([n for n in rows if n.startswith("k_bin<")]) == 16 and len(rows) == 62 + 16
 
 
 def test_the_parser_sees_a_new_variant():
     with open(KERNELS) as f:
         src = f.read()
-    fake = "SWR_LAUNCH(stop, (k_raster<true, 0, false, true, false, LOAD, IDS, true>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a);"
-    at = src.index("        else if (a.color) SWR_LAUNCH(stop, (k_raster<true, 0, false, true, false")
+    fake = "if (c.color) return go(k_raster<true, 0, false, true, false, LOAD, IDS, true>);"
+    at = src.index("        if (c.k32) return go(k_raster_depth<LOAD>);")
     grown = dispatch_kernels(src[:at] + "        " + fake + "\n" + src[at:])
     assert len(grown - dispatch_kernels(src)) == 4
-    at = src.index("#undef SWR_BIN_GO2")
-    grown = dispatch_kernels(src[:at] + "        SWR_BIN_GO2(true, true, 7);\n" + src[at:])
+    at = src.index("    return launch_on(stop, bin_kernel(")
+    grown = dispatch_kernels(src[:at] + "    if (aff) return launch_on(stop, k_bin<256, true, true, 7>, dim3(f.plan.G), dim3(256), lds, s, b);\n"
+                             + src[at:])
     assert grown - dispatch_kernels(src) == {"k_bin<256, true, true, 7>"}
+    assert canonical("k_bin<256, true, true, 7>", src) == "k_bin<256, true, true, 7>"
+    at = src.index("k_bin<256, MT, DEFER, AFF, LIST>; }")
+    grown = dispatch_kernels(src[:at] + "k_bin<256, MT, DEFER, AFF, LIST, MT>; }" + src[at + len("k_bin<256, MT, DEFER, AFF, LIST>; }"):])
+    assert len(grown - dispatch_kernels(src)) == 16
 
 
 def _dispatch_model(flags, shader, ntri, k32=True):
-    """Which raster kernel launch_raster_t picks for a frame (the rows' frames are checked against this; the kernel trace of
+    """Which raster kernel launch_raster_keys picks for a frame (the rows' frames are checked against this; the kernel trace of
     tests/test_kernel_matrix.py against the rows)."""
     L, I = K._b(flags & K.LOAD), K._b(flags & K.IDS)
     plain = ntri >= (1 << K.PRIM_BITS) + (0 if flags & K.LOAD else 1)
