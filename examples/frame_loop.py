@@ -7,12 +7,14 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
 --pick X,Y also writes every frame's ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy of the mesh and which of its
 triangles are visible at pixel (X, Y): mouse picking (use it with --objects N).
+--ids writes the ID image too and after the last frame prints how many triangles of it are visible and how many
+pixels every copy covers, counted on the device (swr_count_ids: only the counts cross to the host, not the ID image).
 --cull {none,back,front} [--front-ccw] turns on face culling (Metal's setCullMode / setFrontFacingWinding): triangles that face
 away (back) or towards the viewer (front) are not drawn; front is clockwise as displayed unless --front-ccw.
 
@@ -253,17 +255,18 @@ def view_flags(clip: bool = False, perspective: bool = False) -> int:
 
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
         time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False,
-        clip: bool = False, perspective: bool = False, glass: int | None = None, ssaa: int = 1):
+        clip: bool = False, perspective: bool = False, glass: int | None = None, ssaa: int = 1, ids: bool = False):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
     mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
     frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel.
+    ids: the ID image is written, and after the last frame its visibility counts are printed (swr_count_ids).
     cull / front_ccw: face culling (cull_flags); clip / perspective: view_flags.
     glass = A (0..255): after the opaque frame a second, shifted and smaller instance of the mesh is drawn over it as a blend load
     frame (SWR_FLAG_BLEND | SWR_FLAG_LOAD, SWR_BLEND_OVER at opacity A): you see the first instance through it; the depth image stays
     the opaque frame's (not with --pick or --perspective).
     ssaa = S (2 or 4): the frames are drawn at S * size and resolved on the device to size x size (the depth is sample (0,0))."""
     vertices, indices = load_mesh(obj) if obj else sphere_mesh()
-    flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | (swr_amd.binding.FLAG_PRIMITIVE_IDS if pick else 0) | cull_flags(cull, front_ccw)
+    flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | (swr_amd.binding.FLAG_PRIMITIVE_IDS if pick or ids else 0) | cull_flags(cull, front_ccw)
     flags |= view_flags(clip, perspective)
     results = []
     with swr_amd.Context() as ctx:
@@ -304,6 +307,12 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
                 os.makedirs(out, exist_ok=True)
                 write_ppm(os.path.join(out, f"frame_{k:04d}.ppm"), color)
             time += 1.0 / 60.0                          # App.swift:155-157
+        if ids and frames > 0:
+            # visibility of the last frame, reduced on the device: pixels per triangle and per copy (samples, with --ssaa)
+            per_tri, none = ctx.count_ids(swr_amd.binding.COUNT_PER_PRIMITIVE)
+            per_copy, _ = ctx.count_ids(swr_amd.binding.COUNT_PER_ITEM)
+            print(f"last frame: {np.count_nonzero(per_tri)} of {per_tri.size} triangles visible, {none} of {(ssaa * size) ** 2} "
+                  f"pixels empty, pixels per copy: {per_copy.tolist()}")
     return vertices, indices, results
 
 
@@ -357,6 +366,8 @@ if __name__ == "__main__":
     ap.add_argument("--gpus", type=int, default=1, help="bands / GPUs of the one context (with --stream)")
     ap.add_argument("--objects", type=int, default=1, help="copies of the mesh, each with its own matrix: one draw list per frame")
     ap.add_argument("--pick", default=None, help="X,Y: print the copy and the triangle under that pixel every frame (primitive IDs)")
+    ap.add_argument("--ids", action="store_true",
+                    help="write the ID image and print the last frame's visibility counts: visible triangles, pixels per copy (swr_count_ids)")
     ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
     ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
     ap.add_argument("--clip", action="store_true", help="depth clipping: triangles clipped against the near and far planes")
@@ -371,8 +382,8 @@ if __name__ == "__main__":
     if a.glass is not None:
         if not 0 <= a.glass <= 255:
             ap.error("--glass: the opacity is 0..255")
-        if a.pick or a.perspective:
-            ap.error("--glass does not combine with --pick or --perspective (blend frames write no IDs and interpolate screen-linearly)")
+        if a.pick or a.ids or a.perspective:
+            ap.error("--glass does not combine with --pick, --ids or --perspective (blend frames write no IDs and interpolate screen-linearly)")
         if a.stream:
             ap.error("--glass is not part of the --stream loop")
     if a.stream:
@@ -382,6 +393,6 @@ if __name__ == "__main__":
         sys.exit(0)
     pick = tuple(int(t) for t in a.pick.split(",")) if a.pick else None
     _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick, cull=a.cull,
-                      front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass, ssaa=a.ssaa)
+                      front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass, ssaa=a.ssaa, ids=a.ids)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

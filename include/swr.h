@@ -258,6 +258,43 @@ typedef struct swr_resolve {
  *   swr_target_set / swr_target_write has been called since.  An overflowed last frame is redrawn with its flags, IDs included. */
 #define SWR_ID_NONE 0xFFFFFFFFu
 
+/* ---- Visibility counts (swr_count_ids) — DESIGN.md §20 ---------------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_count_ids symbol is the feature test.  Nothing
+ * existing changes.  The questions asked of an ID image are mostly reductions — which draws are visible at all and how many pixels
+ * does each cover (Metal's visibilityResultMode = .counting), which triangles lie under a selection rectangle or under one pixel.
+ * swr_count_ids answers them on the device, band by band; only the counts cross to the host.
+ *
+ * Let ids be exactly the W x H image swr_read_ids would deliver now, and R the half-open rectangle [x0, x1) x [y0, y1) of the query,
+ * in pixels of the full target (0 <= x0 <= x1 <= W, 0 <= y0 <= y1 <= H; an empty rectangle is legal and gives zeros; 1 x 1 is picking).
+ *   SWR_COUNT_PER_PRIMITIVE: counts[p] = the number of pixels of R with ids == p.  n must equal the last frame's primitive count:
+ *     index_count / 3 of the uploaded scene (swr_draw, swr_draw_primitives, swr_render), or for swr_draw_list the total over the items.
+ *     Culled triangles and depth-clip fans keep the original numbering, as in the ID image.
+ *   SWR_COUNT_PER_ITEM: counts[k] = the number of pixels of R whose ID lies in [vbase_k, vbase_k + index_count_k / 3), vbase_k as
+ *     under "Primitive IDs".  n must equal the last draw list's item_count; a frame that was not a draw list counts as a list of one
+ *     item (n == 1).  An empty item counts 0.  item_count == 0 means n == 0, and counts may then be NULL.
+ *   *none = the number of pixels of R equal to SWR_ID_NONE; none may be NULL.
+ *   Always: counts[0] + ... + counts[n-1] + *none == (x1 - x0) * (y1 - y0).  Every element of counts[0 .. n) is written, zeros
+ *     included.  Counts fit 32 bits (a target is at most 65535 x 65535).  All arithmetic is integer: the result is exact.
+ *   Completion.  The call completes everything first, like swr_read_ids: an overflowed last frame is redrawn, IDs included, before it
+ *     is counted.  The ID, colour and depth images on the device are not modified: a following swr_read_ids, SWR_FLAG_LOAD frame or
+ *     second swr_count_ids sees them unchanged.
+ *   Bands.  Each band counts the part of R that falls into its rows [row_begin, row_end); the library adds the bands' counts before
+ *     it returns (a multi-device context: one array for the caller, written once, after every band succeeded).  A context that owns
+ *     only a band of the target (swr_target_set with row_begin / row_end) counts the part of R in its rows; R itself is still checked
+ *     against the full W x H.
+ *   After swr_render (or swr_render_resolved) with SWR_FLAG_PRIMITIVE_IDS the rectangle is in pixels of the target that call set —
+ *     sample resolution, S*w x S*h, after a resolved render.
+ *   Errors.  SWR_ERR_BAD_ARG: a NULL ctx or q; a NULL counts with n > 0; an unknown group; a non-zero reserved word; a rectangle
+ *     outside the target or inverted; an n that is not the required value (the message names it); the conditions under which
+ *     swr_read_ids refuses (the last frame was drawn without SWR_FLAG_PRIMITIVE_IDS, or swr_target_set / swr_target_write came after
+ *     it).  SWR_ERR_NO_SCENE: no target.  A failed context returns its sticky error.  After an error nothing was written. */
+enum { SWR_COUNT_PER_PRIMITIVE = 0, SWR_COUNT_PER_ITEM = 1 };
+typedef struct swr_id_count {
+    int32_t group;          /* SWR_COUNT_* */
+    int32_t x0, y0, x1, y1; /* half-open rectangle [x0,x1) x [y0,y1), in pixels of the full W x H target */
+    int32_t reserved[3];    /* 0 */
+} swr_id_count;             /* 32 bytes */
+
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
  * continues from the image already there.
@@ -557,6 +594,9 @@ int swr_present_wait(swr_context* ctx);
 int swr_read_color(swr_context* ctx, void* dst_full_image);
 int swr_read_depth(swr_context* ctx, float* dst_full_image);
 int swr_read_ids(swr_context* ctx, uint32_t* dst_full_image);   /* SWR_FLAG_PRIMITIVE_IDS frames (see "Primitive IDs" above) */
+/* Visibility counts (see "Visibility counts" above): swr_sync + a reduction of the ID image on the device + the copy of the n + 1
+ * counters + wait.  counts has n elements; none may be NULL. */
+int swr_count_ids(swr_context* ctx, const swr_id_count* q, uint32_t* counts, int64_t n, uint32_t* none);
 /* Supersampled resolve (see "Supersampled resolve" above): swr_sync + the S x S box filter on the device + the copy of the small
  * image + wait.  The destination has (W/S) x (H/S) elements; page-locked and pageable destinations both work, as for swr_read_*. */
 int swr_read_color_resolved(swr_context* ctx, const swr_resolve* resolve, void*  dst);  /* (W/S) x (H/S) BGRA8 */

@@ -26,6 +26,7 @@ FLAG_BLEND = 4096        # alpha blending: every fragment is blended into the pi
 BLEND_OVER, BLEND_ADD = 0, 1   # swr_blend.mode
 RESOLVE_DEPTH_SAMPLE0, RESOLVE_DEPTH_MIN = 0, 1   # swr_resolve.depth_filter (include/swr.h "Supersampled resolve")
 ID_NONE = 0xFFFFFFFF     # SWR_ID_NONE: a pixel where the frame keeps no fragment
+COUNT_PER_PRIMITIVE, COUNT_PER_ITEM = 0, 1   # swr_id_count.group (include/swr.h "Visibility counts")
 
 # every symbol include/swr.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -36,7 +37,7 @@ ABI_SYMBOLS = [
     "swr_timing_sample", "swr_context_bands", "swr_context_band_info", "swr_host_alloc", "swr_host_free",
     "swr_host_register", "swr_host_unregister", "swr_present", "swr_present_wait", "swr_device_count",
     "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list", "swr_read_ids",
-    "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved",
+    "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -88,6 +89,12 @@ class Blend(ctypes.Structure):
 class Resolve(ctypes.Structure):
     """swr_resolve (include/swr.h): the factor S (1, 2 or 4 samples per axis) and the depth filter of a supersampled resolve."""
     _fields_ = [("factor", ctypes.c_int32), ("depth_filter", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+class IdCount(ctypes.Structure):
+    """swr_id_count (include/swr.h): the group (COUNT_PER_PRIMITIVE / COUNT_PER_ITEM) and the half-open rectangle of a visibility count."""
+    _fields_ = [("group", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32), ("y1", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3)]
 
 
 class Config(ctypes.Structure):
@@ -228,6 +235,12 @@ def load_library():
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
             raise
+    try:
+        L.swr_count_ids.argtypes = [vp, ctypes.POINTER(IdCount), vp, i64, vp]
+        L.swr_count_ids.restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
     L.swr_target_write.argtypes = [vp, vp, vp]
     L.swr_target_write.restype = ctypes.c_int
     L.swr_present_wait.argtypes = [vp]
@@ -323,6 +336,8 @@ class Context:
             raise SwrError(rc, (self._L.swr_last_error(None) or b"").decode())
         self.width = self.height = 0
         self.row_begin = self.row_end = 0
+        self._scene_prims = 0           # index_count / 3 of the resident scene
+        self._last_list = None          # (primitives, items) of the last frame when it was a draw list (count_ids' default n)
 
     def close(self):
         if self._h:
@@ -353,6 +368,7 @@ class Context:
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 8)
         i = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
         self._check(self._L.swr_scene_upload(self._h, v.ctypes.data, v.shape[0], i.ctypes.data, i.size))
+        self._scene_prims = i.size // 3
 
     def scene_attributes(self, attrs: np.ndarray):
         a = np.ascontiguousarray(attrs, dtype=np.float32).reshape(-1, 8)
@@ -406,6 +422,7 @@ class Context:
         rc = self._L.swr_draw_primitives(self._h, self._m_ptr, flags, primitive_type)
         if rc:
             self._check(rc)
+        self._last_list = None
 
     @staticmethod
     def draw_items(items) -> np.ndarray:
@@ -426,6 +443,7 @@ class Context:
         (first_index, index_count, transform) tuples or a DRAW_ITEM_DTYPE array.  The list is copied by the call."""
         a = self.draw_items(items)
         self._check(self._L.swr_draw_list(self._h, a.ctypes.data if a.size else None, a.size, flags))
+        self._last_list = (int((a["index_count"] // 3).sum()), int(a.size))
 
     def sync(self):
         self._check(self._L.swr_sync(self._h))
@@ -526,6 +544,24 @@ class Context:
         assert out.flags.c_contiguous and out.nbytes == self.width * self.height * 4
         self._check(self._L.swr_read_ids(self._h, out.ctypes.data))
         return out
+
+    def count_ids(self, group: int = COUNT_PER_PRIMITIVE, rect=None, n: int | None = None, query: "IdCount | None" = None):
+        """swr_count_ids: the ID image of the last frame reduced on the device — (counts, none): counts[p] the pixels of the rectangle
+        that show primitive p (COUNT_PER_PRIMITIVE) or counts[k] those that show a triangle of draw item k (COUNT_PER_ITEM; a frame
+        that was no draw list is one item), uint32, and the number of pixels with ID_NONE.  `rect` = (x0, y0, x1, y1), half-open, in
+        pixels of the full target; None: the whole target.  `n` defaults to what the context last drew.  A ready-made IdCount is
+        passed as it is."""
+        if query is None:
+            x0, y0, x1, y1 = rect if rect is not None else (0, 0, self.width, self.height)
+            query = IdCount(int(group), int(x0), int(y0), int(x1), int(y1), (ctypes.c_int32 * 3)(0, 0, 0))
+        if n is None:
+            prims, items = self._last_list if self._last_list is not None else (self._scene_prims, 1)
+            n = items if query.group == COUNT_PER_ITEM else prims
+        counts = np.zeros(max(int(n), 0), dtype=np.uint32)
+        none = ctypes.c_uint32(0)
+        self._check(self._L.swr_count_ids(self._h, ctypes.byref(query), counts.ctypes.data if counts.size else None, int(n),
+                                          ctypes.byref(none)))
+        return counts, int(none.value)
 
     @staticmethod
     def _dst_ptr(x):
@@ -632,6 +668,7 @@ class Context:
             self._check(self._L.swr_render_resolved(self._h, ctypes.byref(rp), ctypes.byref(resolve)))
             S = int(resolve.factor)      # the target is the supersampled one: read_ids delivers S * width x S * height words
         self.width, self.height, self.row_begin, self.row_end = S * width, S * height, 0, S * height     # (swr_render sets the target: read_ids)
+        self._scene_prims, self._last_list = i.size // 3, None
         return color, depth
 
 

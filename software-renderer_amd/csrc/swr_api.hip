@@ -40,6 +40,9 @@
 namespace swr {
 __attribute__((weak)) void launch_resolve(const void* color, const void* depth, void* color_out, void* depth_out, int width, int rows,
                                           int factor, int depth_filter, hipStream_t s);
+// (the same for the visibility counts: a stand-in set without swr_count.hip still links, and swr_count_ids then fails loudly)
+__attribute__((weak)) void launch_count_ids(const uint32_t* ids, int width, int x0, int x1, int y0, int y1, int per_item,
+                                            const ListItem* items, uint32_t* counters, int64_t n, hipStream_t s);
 }
 
 using namespace swr;
@@ -129,7 +132,7 @@ struct Worker {
 
 static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && sizeof(swr_vertex_attr) == 32 &&
               sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16 &&
-              sizeof(swr_resolve) == 16,
+              sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -200,6 +203,11 @@ struct swr_context {
     // supersampled resolve: the band's resolved colour and depth images, (W/S) x (band rows/S), sized by the first
     // resolved read (k_resolve writes them, copy_band carries them to the host; the framebuffers themselves are only read)
     DevBuf rs_color, rs_depth;
+    // visibility counts: the n + 1 counters of a query on the device (zeroed before every query, k_count_ids adds) and
+    // the band's own page-locked copy of them, both sized by the largest query so far
+    DevBuf count_dev;
+    uint32_t* count_host = nullptr;
+    size_t count_host_words = 0;
     int fb_cur = 0;                    // the next swr_draw renders into this buffer
     int fb_last = 0;                    // the buffer of the last swr_draw (what swr_present / swr_read_* copy)
     hipStream_t last_stream = nullptr;  // the stream that carries the last frame's raster (swr_present records frame_done behind it)
@@ -2125,6 +2133,61 @@ int single_read_resolved(swr_context* c, swr_resolve rs, void* color_dst, float*
     return SWR_OK;
 }
 
+// what a swr_id_count may hold, and its rectangle against the full target
+int check_count_args(swr_context* c, const swr_id_count& q, const uint32_t* counts, int64_t n) {
+    if (q.group != SWR_COUNT_PER_PRIMITIVE && q.group != SWR_COUNT_PER_ITEM)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: unknown group %d", q.group);
+    if (q.reserved[0] || q.reserved[1] || q.reserved[2]) return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: reserved words must be 0");
+    if (n < 0 || (n > 0 && !counts)) return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: counts is NULL or n is negative (n = %lld)", (long long)n);
+    return SWR_OK;
+}
+
+int check_count_rect(swr_context* c, const swr_id_count& q, const Target& t) {
+    if (q.x0 < 0 || q.y0 < 0 || q.x0 > q.x1 || q.y0 > q.y1 || q.x1 > t.width || q.y1 > t.height)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: the rectangle [%d,%d) x [%d,%d) is inverted or outside the target %dx%d",
+                    q.x0, q.x1, q.y0, q.y1, t.width, t.height);
+    return SWR_OK;
+}
+
+// swr_count_ids on one band: the part of the rectangle in the band's rows, counted into c->count_host[0 .. n] (word n: SWR_ID_NONE).
+// A band the rectangle misses, or one without tiles, launches nothing and leaves zeros there.
+int single_count_ids(swr_context* c, swr_id_count q, const uint32_t* counts, int64_t n) {
+    if (const int f = sticky(c)) return f;
+    int rc = check_count_args(c, q, counts, n);
+    if (rc) return rc;
+    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_count_ids needs swr_target_set first");
+    if ((rc = check_count_rect(c, q, c->tg))) return rc;
+    if (!c->ids_valid)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: the last frame was drawn without SWR_FLAG_PRIMITIVE_IDS, or swr_target_set / "
+                    "swr_target_write came after it");
+    const bool per_item = q.group == SWR_COUNT_PER_ITEM;
+    const int64_t need = per_item ? (c->last_list ? (int64_t)c->list.size() : 1) : (c->last_list ? c->list_tris : c->ni / 3);
+    if (n != need)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: n is %lld, but the last frame has %lld %s", (long long)n, (long long)need,
+                    per_item ? "draw items" : "primitives");
+    if ((rc = single_sync(c))) return rc;       // (an overflowed last frame is repaired here)
+    const size_t words = (size_t)n + 1;
+    if (c->count_host_words < words) {
+        if (c->count_host) { HIP_TRY(c, hipHostFree(c->count_host)); c->count_host = nullptr; c->count_host_words = 0; }
+        const size_t want = words + words / 8;
+        HIP_TRY(c, hipHostMalloc((void**)&c->count_host, want * 4, hipHostMallocDefault));
+        c->count_host_words = want;
+    }
+    memset(c->count_host, 0, words * 4);
+    const int y0 = std::max<int>(q.y0, c->tg.row_begin), y1 = std::min<int>(q.y1, c->tg.row_end);
+    if (tiles_of(c->tg) == 0 || y0 >= y1 || q.x0 >= q.x1) return SWR_OK;
+    if ((rc = ensure(c, c->count_dev, words * 4))) return rc;
+    if (!launch_count_ids) return fail(c, SWR_ERR_HIP, "this build has no k_count_ids: there is no fallback for the visibility counts");
+    HIP_TRY(c, hipMemsetAsync(c->count_dev.p, 0, words * 4, c->stream));
+    const ListItem* items = (per_item && c->last_list) ? (const ListItem*)c->slot[c->last_slot].items.p : nullptr;
+    launch_count_ids((const uint32_t*)c->ids[c->fb_last].p, c->tg.width, q.x0, q.x1, y0 - c->tg.row_begin, y1 - c->tg.row_begin,
+                     per_item ? 1 : 0, items, (uint32_t*)c->count_dev.p, n, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->count_host, c->count_dev.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_stream(c, c->stream, "raster stream (visibility counts)"))) return or_sticky(c, rc);
+    return SWR_OK;
+}
+
 void destroy_single(swr_context* c) {
     hipSetDevice(c->device);
     // helper jobs are bounded (every wait in them is) and give up at once on a failed context: the drains return
@@ -2157,7 +2220,7 @@ void destroy_single(swr_context* c) {
                 (unsigned long long)c->hp_frames, c->hp_t[0] / c->hp_frames, c->hp_t[1] / c->hp_frames, c->hp_t[2] / c->hp_frames,
                 c->hp_t[3] / c->hp_frames, c->hp_t[4] / c->hp_frames, c->hp_t[5] / c->hp_frames);
     DevBuf* bufs[] = {&c->redo_cnt, &c->vertices, &c->indices, &c->tri_rgb, &c->tri_xyz, &c->inv, &c->box64, &c->stream_scratch, &c->sort_temp,
-                      &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth};
+                      &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth, &c->count_dev};
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
@@ -2193,6 +2256,7 @@ void destroy_single(swr_context* c) {
     if (c->h_pairs) hipHostFree(c->h_pairs);
     if (c->h_misc) hipHostFree(c->h_misc);
     if (c->h_clip) hipHostFree(c->h_clip);
+    if (c->count_host) hipHostFree(c->count_host);
     if (c->ev_ok)
         for (int r = 0; r < swr_context::RING; r++)
             for (int i = 0; i < 5; i++) hipEventDestroy(c->ev[r][i]);
@@ -2534,6 +2598,34 @@ int swr_read_ids(swr_context* c, uint32_t* dst) {
     if (!c || !dst) return SWR_ERR_BAD_ARG;
     if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_read(k, 2, dst); });
     return single_read(c, 2, dst);
+}
+
+int swr_count_ids(swr_context* c, const swr_id_count* query, uint32_t* counts, int64_t n, uint32_t* none) {
+    if (!c || !query) return SWR_ERR_BAD_ARG;
+    const swr_id_count q = *query;
+    if (!is_group(c)) {
+        const int rc = single_count_ids(c, q, counts, n);
+        if (rc) return rc;
+        if (n) memcpy(counts, c->count_host, (size_t)n * 4);
+        if (none) *none = c->count_host[n];
+        return SWR_OK;
+    }
+    // a group checks what it can see before any band is touched; every band counts into staging of its own, and the caller's array is
+    // written once, after all of them succeeded
+    if (const int f = sticky(c)) return f;
+    int rc = check_count_args(c, q, counts, n);
+    if (rc) return rc;
+    if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_count_ids needs swr_target_set first");
+    if ((rc = check_count_rect(c, q, c->group_tg))) return rc;
+    if ((rc = group_run(c, [=](swr_context* k) { return single_count_ids(k, q, counts, n); }))) return rc;
+    if (n) memset(counts, 0, (size_t)n * 4);
+    uint32_t nn = 0;
+    for (const swr_context* k : c->kids) {
+        for (int64_t i = 0; i < n; i++) counts[i] += k->count_host[i];
+        nn += k->count_host[n];
+    }
+    if (none) *none = nn;
+    return SWR_OK;
 }
 
 // the resolved read of one or both images (NULL: not wanted); a group checks what it can see before any band is touched

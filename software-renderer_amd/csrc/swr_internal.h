@@ -239,4 +239,10 @@ bool launch_clip_ids(const DeviceFrame& f, hipStream_t s, hipEvent_t stop);
 void launch_resolve(const void* color, const void* depth, void* color_out, void* depth_out, int width, int rows, int factor,
                     int depth_filter, hipStream_t s);
 
+// swr_count.hip: visibility counts: the rectangle [x0, x1) x [y0, y1), band-local rows, of the band's ID image `ids`
+// (`width` words per row) into counters[0 .. n], zeroed by the caller on the same stream — counters[n] counts SWR_ID_NONE; per_item:
+// counters[k] the IDs of item k of `items` (n items; NULL: one item that holds every ID), else counters[p] the ID p
+void launch_count_ids(const uint32_t* ids, int width, int x0, int x1, int y0, int y1, int per_item, const ListItem* items,
+                      uint32_t* counters, int64_t n, hipStream_t s);
+
 }  // namespace swr
