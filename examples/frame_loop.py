@@ -7,7 +7,7 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
@@ -15,6 +15,9 @@ per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over 
 triangles are visible at pixel (X, Y): mouse picking (use it with --objects N).
 --ids writes the ID image too and after the last frame prints how many triangles of it are visible and how many
 pixels every copy covers, counted on the device (swr_count_ids: only the counts cross to the host, not the ID image).
+--occlusion (with --objects N and --depth-test) tests every copy's screen rectangle and nearest depth against the depth image of the
+previous frame before the next one is drawn, on the device (swr_query_depth: only one count per copy crosses to the host, not the
+depth image), and prints how many copies could be skipped because nothing of them would pass the z-test.
 --cull {none,back,front} [--front-ccw] turns on face culling (Metal's setCullMode / setFrontFacingWinding): triangles that face
 away (back) or towards the viewer (front) are not drawn; front is clockwise as displayed unless --front-ccw.
 
@@ -239,6 +242,23 @@ def object_transforms(time: float, n: int):
     return out
 
 
+def object_boxes(vertices: np.ndarray, matrices, width: int, height: int) -> np.ndarray:
+    """One swr_query_depth box per matrix: the screen rectangle of the transformed vertices, one pixel wider on every side and
+    clipped to the target, and their nearest depth moved a little nearer (the projection here is not bit for bit the device's, and
+    the box has to be conservative); rows (x0, y0, x1, y1, z) for Context.query_depth."""
+    h = np.concatenate([vertices[:, :3].astype(np.float64), np.ones((vertices.shape[0], 1))], axis=1)
+    rows = []
+    for m in matrices:
+        c = h @ np.asarray(m, dtype=np.float64).reshape(4, 4)       # (column-major: the rows of the reshape are the columns)
+        ndc = c[:, :3] / c[:, 3:4]
+        sx, sy = (ndc[:, 0] + 1.0) * 0.5 * width, (1.0 - (ndc[:, 1] + 1.0) * 0.5) * height
+        x0, x1 = int(np.clip(math.floor(sx.min()) - 1, 0, width)), int(np.clip(math.ceil(sx.max()) + 2, 0, width))
+        y0, y1 = int(np.clip(math.floor(sy.min()) - 1, 0, height)), int(np.clip(math.ceil(sy.max()) + 2, 0, height))
+        z = float(ndc[:, 2].min())
+        rows.append((x0, y0, max(x0, x1), max(y0, y1), z - 1e-5 * abs(z) - 1e-6))
+    return np.array(rows, dtype=np.float64).reshape(-1, 5)
+
+
 def cull_flags(cull: str = "none", front_ccw: bool = False) -> int:
     """Face culling (Metal's setCullMode / setFrontFacingWinding): none / back / front, front = clockwise as displayed unless
     front_ccw."""
@@ -255,11 +275,14 @@ def view_flags(clip: bool = False, perspective: bool = False) -> int:
 
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
         time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False,
-        clip: bool = False, perspective: bool = False, glass: int | None = None, ssaa: int = 1, ids: bool = False):
+        clip: bool = False, perspective: bool = False, glass: int | None = None, ssaa: int = 1, ids: bool = False,
+        occlusion: bool = False):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
     mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
     frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel.
     ids: the ID image is written, and after the last frame its visibility counts are printed (swr_count_ids).
+    occlusion: from the second frame on, every copy's screen rectangle and nearest depth are tested against the previous frame's depth
+    image before the frame is drawn (swr_query_depth), and the number of copies nothing of which would pass is printed.
     cull / front_ccw: face culling (cull_flags); clip / perspective: view_flags.
     glass = A (0..255): after the opaque frame a second, shifted and smaller instance of the mesh is drawn over it as a blend load
     frame (SWR_FLAG_BLEND | SWR_FLAG_LOAD, SWR_BLEND_OVER at opacity A): you see the first instance through it; the depth image stays
@@ -277,6 +300,11 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
             if objects > 1:
                 m = object_transforms(time, objects)
                 items = [(0, indices.size, mj) for mj in m]
+                if occlusion and k > 0:
+                    # the occlusion query of this frame's copies against the depth the previous frame left on the device (samples, with --ssaa)
+                    passed = ctx.query_depth(object_boxes(vertices, m, ssaa * size, ssaa * size))
+                    print(f"occlusion: frame {k}: {int((passed == 0).sum())} of {objects} objects could be skipped "
+                          f"(pixels that pass per object: {passed.tolist()})")
                 ctx.draw_list(items, flags)             # all copies in one frame
             else:
                 m = S.app_transform(time)               # App.swift:169-183
@@ -368,6 +396,9 @@ if __name__ == "__main__":
     ap.add_argument("--pick", default=None, help="X,Y: print the copy and the triangle under that pixel every frame (primitive IDs)")
     ap.add_argument("--ids", action="store_true",
                     help="write the ID image and print the last frame's visibility counts: visible triangles, pixels per copy (swr_count_ids)")
+    ap.add_argument("--occlusion", action="store_true",
+                    help="with --objects N: test every copy's screen rectangle and nearest depth against the previous frame's depth "
+                         "image on the device and print how many copies could be skipped (swr_query_depth)")
     ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
     ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
     ap.add_argument("--clip", action="store_true", help="depth clipping: triangles clipped against the near and far planes")
@@ -393,6 +424,7 @@ if __name__ == "__main__":
         sys.exit(0)
     pick = tuple(int(t) for t in a.pick.split(",")) if a.pick else None
     _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick, cull=a.cull,
-                      front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass, ssaa=a.ssaa, ids=a.ids)
+                      front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass, ssaa=a.ssaa, ids=a.ids,
+                      occlusion=a.occlusion)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

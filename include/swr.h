@@ -295,6 +295,44 @@ typedef struct swr_id_count {
     int32_t reserved[3];    /* 0 */
 } swr_id_count;             /* 32 bytes */
 
+/* ---- Depth queries (swr_query_depth) — DESIGN.md §21 -----------------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_query_depth symbol is the feature test.  Nothing
+ * existing changes.  swr_count_ids tells which objects that were drawn are visible; swr_query_depth tells whether an object that was
+ * not drawn, or is about to be, could be visible at all behind what the depth image already holds — the occlusion query of the
+ * hardware APIs (a bounding box drawn with colour and depth writes off, the passing fragments counted), without the 33 MB depth image
+ * of a 4K frame crossing to the host.  The caller supplies every object's screen rectangle and its nearest depth.
+ *
+ * Let depth be exactly the W x H image swr_read_depth would deliver now.  passed[k] = the number of pixels (x, y) of box k,
+ * x0 <= x < x1 and y0 <= y < y1, with boxes[k].z < depth[y][x], compared as binary32 '<': the pixels where a fragment of depth z
+ * would pass the strict z-test of SWR_FLAG_DEPTH_TEST.  What that rule fixes:
+ *     a stored NaN is never passed; a NaN z passes nowhere; z == depth does not pass; -0 and +0 are equal; +inf, the cleared depth,
+ *     is passed by every finite z and by -inf; a stored -inf is never passed; denormals compare exactly (nothing is flushed).
+ *   Boxes.  0 <= x0 <= x1 <= W and 0 <= y0 <= y1 <= H, in pixels of the full target; an empty rectangle is legal and gives 0.
+ *     Boxes may overlap and repeat.  n == 0 is legal, and boxes and passed may then be NULL.  Every element of passed[0 .. n) is
+ *     written.  At most SWR_DEPTH_QUERY_MAX boxes per call.
+ *   Exactness.  The counts are integers and exact: they do not depend on how the device gets there (it keeps a minimum, a maximum
+ *     and a NaN count per tile and reads only the pixels of tiles that straddle z).
+ *   The depth image.  No SWR_FLAG_PRIMITIVE_IDS is needed: the depth image exists after every frame — +inf after a painter's-order
+ *     frame, the starting depth after a blend frame, the written image after swr_target_write, the cleared image right after
+ *     swr_target_set (every pixel +inf, whatever the buffers held before: that answer needs no device).  The call is legal in all
+ *     of these.
+ *   After swr_render (or swr_render_resolved) the rectangles are in pixels of the target that call set — sample resolution,
+ *     S*w x S*h, after a resolved render.
+ *   Completion.  The call completes everything first, like swr_read_depth: an overflowed last frame is repaired before it is tested.
+ *     No image on the device is modified.
+ *   Bands.  Each band counts the part of every box in its rows [row_begin, row_end); the library adds the bands and writes the
+ *     caller's array once, after every band succeeded.  A context that owns only a band of the target (swr_target_set with
+ *     row_begin / row_end) counts the part of every box in its rows; the boxes are still checked against the full W x H.
+ *   Errors.  SWR_ERR_BAD_ARG: a NULL ctx; NULL boxes or passed with n > 0; n < 0; a non-zero reserved word; a rectangle inverted or
+ *     outside the target (the message names the first offending box index).  SWR_ERR_UNSUPPORTED: n > SWR_DEPTH_QUERY_MAX.
+ *     SWR_ERR_NO_SCENE: no target.  A failed context returns its sticky error.  After an error nothing was written. */
+typedef struct swr_depth_box {
+    int32_t x0, y0, x1, y1;   /* half-open rectangle [x0,x1) x [y0,y1), pixels of the full W x H target */
+    float   z;                /* the depth the box is tested with (its nearest depth, chosen by the caller) */
+    int32_t reserved[3];      /* 0 */
+} swr_depth_box;              /* 32 bytes */
+#define SWR_DEPTH_QUERY_MAX (1 << 16)
+
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
  * continues from the image already there.
@@ -597,6 +635,9 @@ int swr_read_ids(swr_context* ctx, uint32_t* dst_full_image);   /* SWR_FLAG_PRIM
 /* Visibility counts (see "Visibility counts" above): swr_sync + a reduction of the ID image on the device + the copy of the n + 1
  * counters + wait.  counts has n elements; none may be NULL. */
 int swr_count_ids(swr_context* ctx, const swr_id_count* q, uint32_t* counts, int64_t n, uint32_t* none);
+/* Depth queries (see "Depth queries" above): swr_sync + the copy of the n boxes + a reduction of the depth image on the device + the
+ * copy of the n counts + wait.  boxes and passed have n elements. */
+int swr_query_depth(swr_context* ctx, const swr_depth_box* boxes, int64_t n, uint32_t* passed);
 /* Supersampled resolve (see "Supersampled resolve" above): swr_sync + the S x S box filter on the device + the copy of the small
  * image + wait.  The destination has (W/S) x (H/S) elements; page-locked and pageable destinations both work, as for swr_read_*. */
 int swr_read_color_resolved(swr_context* ctx, const swr_resolve* resolve, void*  dst);  /* (W/S) x (H/S) BGRA8 */

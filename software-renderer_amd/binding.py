@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "swr_host_register", "swr_host_unregister", "swr_present", "swr_present_wait", "swr_device_count",
     "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list", "swr_read_ids",
     "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
+    "swr_query_depth",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -95,6 +96,18 @@ class IdCount(ctypes.Structure):
     """swr_id_count (include/swr.h): the group (COUNT_PER_PRIMITIVE / COUNT_PER_ITEM) and the half-open rectangle of a visibility count."""
     _fields_ = [("group", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32), ("y1", ctypes.c_int32),
                 ("reserved", ctypes.c_int32 * 3)]
+
+
+class DepthBox(ctypes.Structure):
+    """swr_depth_box (include/swr.h): the half-open rectangle of a depth query and the depth it is tested with."""
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32), ("y1", ctypes.c_int32), ("z", ctypes.c_float),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
+DEPTH_QUERY_MAX = 1 << 16    # SWR_DEPTH_QUERY_MAX: boxes per swr_query_depth call
+# swr_depth_box as a numpy record
+DEPTH_BOX_DTYPE = np.dtype([("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32), ("z", np.float32),
+                            ("reserved", np.int32, (3,))])
 
 
 class Config(ctypes.Structure):
@@ -238,6 +251,12 @@ def load_library():
     try:
         L.swr_count_ids.argtypes = [vp, ctypes.POINTER(IdCount), vp, i64, vp]
         L.swr_count_ids.restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
+    try:
+        L.swr_query_depth.argtypes = [vp, vp, i64, vp]
+        L.swr_query_depth.restype = ctypes.c_int
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
             raise
@@ -562,6 +581,30 @@ class Context:
         self._check(self._L.swr_count_ids(self._h, ctypes.byref(query), counts.ctypes.data if counts.size else None, int(n),
                                           ctypes.byref(none)))
         return counts, int(none.value)
+
+    @staticmethod
+    def depth_boxes(boxes) -> np.ndarray:
+        """A DEPTH_BOX_DTYPE array from an (n, 5) array of rows (x0, y0, x1, y1, z) — the rectangle's numbers must be integers — or a
+        DEPTH_BOX_DTYPE array, which is passed as it is (reserved words included)."""
+        if isinstance(boxes, np.ndarray) and boxes.dtype == DEPTH_BOX_DTYPE:
+            return np.ascontiguousarray(boxes).reshape(-1)
+        rows = np.asarray(boxes, dtype=np.float64).reshape(-1, 5)
+        a = np.zeros(rows.shape[0], dtype=DEPTH_BOX_DTYPE)
+        for j, f in enumerate(("x0", "y0", "x1", "y1")):
+            if not (rows[:, j] == np.rint(rows[:, j])).all():
+                raise ValueError("depth_boxes: the rectangles are in whole pixels")
+            a[f] = rows[:, j].astype(np.int32)
+        a["z"] = rows[:, 4].astype(np.float32)
+        return a
+
+    def query_depth(self, boxes) -> np.ndarray:
+        """swr_query_depth: uint32[n], for every box the number of its pixels where its z would pass the strict z-test against the
+        depth image as it is now (z < depth).  `boxes`: an (n, 5) array of rows (x0, y0, x1, y1, z), the rectangle half-open and in
+        pixels of the full target, or a DEPTH_BOX_DTYPE array."""
+        a = self.depth_boxes(boxes)
+        passed = np.zeros(a.size, dtype=np.uint32)
+        self._check(self._L.swr_query_depth(self._h, a.ctypes.data if a.size else None, a.size, passed.ctypes.data if a.size else None))
+        return passed
 
     @staticmethod
     def _dst_ptr(x):

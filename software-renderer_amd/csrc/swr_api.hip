@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <limits>
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -43,6 +44,10 @@ __attribute__((weak)) void launch_resolve(const void* color, const void* depth, 
 // (the same for the visibility counts: a stand-in set without swr_count.hip still links, and swr_count_ids then fails loudly)
 __attribute__((weak)) void launch_count_ids(const uint32_t* ids, int width, int x0, int x1, int y0, int y1, int per_item,
                                             const ListItem* items, uint32_t* counters, int64_t n, hipStream_t s);
+// (and for the depth queries: without swr_depth_query.hip swr_query_depth fails loudly)
+__attribute__((weak)) void launch_depth_query(const float* depth, int width, int rows, int row_begin, const swr_depth_box* boxes, int64_t n,
+                                              const uint32_t* large, int64_t nlarge, uint64_t total_area, void* scratch, uint32_t* passed,
+                                              hipStream_t s);
 }
 
 using namespace swr;
@@ -132,7 +137,7 @@ struct Worker {
 
 static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && sizeof(swr_vertex_attr) == 32 &&
               sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16 &&
-              sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32,
+              sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32 && sizeof(swr_depth_box) == 32,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -208,6 +213,12 @@ struct swr_context {
     DevBuf count_dev;
     uint32_t* count_host = nullptr;
     size_t count_host_words = 0;
+    // depth queries: the n boxes, the list of the large ones and the n counts of a query, in this order, on the device and
+    // in the band's own page-locked staging (words), both sized by the largest query so far; the tile summary k_depth_tiles writes
+    DevBuf query_dev, query_tiles;
+    uint32_t* query_host = nullptr;
+    size_t query_host_words = 0;
+    const uint32_t* query_passed = nullptr;     // the counts of the last query inside query_host
     int fb_cur = 0;                    // the next swr_draw renders into this buffer
     int fb_last = 0;                    // the buffer of the last swr_draw (what swr_present / swr_read_* copy)
     hipStream_t last_stream = nullptr;  // the stream that carries the last frame's raster (swr_present records frame_done behind it)
@@ -2188,6 +2199,79 @@ int single_count_ids(swr_context* c, swr_id_count q, const uint32_t* counts, int
     return SWR_OK;
 }
 
+// what swr_query_depth may be handed, and every box against the full target
+int check_query_args(swr_context* c, const swr_depth_box* boxes, int64_t n, const uint32_t* passed) {
+    if (n < 0 || (n > 0 && (!boxes || !passed)))
+        return fail(c, SWR_ERR_BAD_ARG, "swr_query_depth: boxes or passed is NULL, or n is negative (n = %lld)", (long long)n);
+    if (n > SWR_DEPTH_QUERY_MAX)
+        return fail(c, SWR_ERR_UNSUPPORTED, "swr_query_depth: %lld boxes, at most %d per call", (long long)n, SWR_DEPTH_QUERY_MAX);
+    return SWR_OK;
+}
+
+int check_query_boxes(swr_context* c, const swr_depth_box* boxes, int64_t n, const Target& t) {
+    for (int64_t k = 0; k < n; k++) {
+        const swr_depth_box& b = boxes[k];
+        if (b.reserved[0] || b.reserved[1] || b.reserved[2])
+            return fail(c, SWR_ERR_BAD_ARG, "swr_query_depth: box %lld: reserved words must be 0", (long long)k);
+        if (b.x0 < 0 || b.y0 < 0 || b.x0 > b.x1 || b.y0 > b.y1 || b.x1 > t.width || b.y1 > t.height)
+            return fail(c, SWR_ERR_BAD_ARG, "swr_query_depth: box %lld: the rectangle [%d,%d) x [%d,%d) is inverted or outside the target %dx%d",
+                        (long long)k, b.x0, b.x1, b.y0, b.y1, t.width, t.height);
+    }
+    return SWR_OK;
+}
+
+// swr_query_depth on one band: the part of every box in the band's rows, tested against the band's depth image — the buffer
+// single_read copies for swr_read_depth — into c->query_passed[0 .. n).  A band no box touches, or one without tiles, launches nothing
+// and leaves zeros there.
+int single_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, const uint32_t* passed) {
+    if (const int f = sticky(c)) return f;
+    int rc = check_query_args(c, boxes, n, passed);
+    if (rc) return rc;
+    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_query_depth needs swr_target_set first");
+    if ((rc = check_query_boxes(c, boxes, n, c->tg))) return rc;
+    if ((rc = single_sync(c))) return rc;       // (an overflowed last frame is repaired here)
+    c->query_passed = nullptr;
+    if (n == 0) return SWR_OK;
+    const size_t nn = (size_t)n, words = nn * 8 + nn + nn;      // boxes | large | passed
+    if (c->query_host_words < words) {
+        if (c->query_host) { HIP_TRY(c, hipHostFree(c->query_host)); c->query_host = nullptr; c->query_host_words = 0; }
+        const size_t want = words + words / 8;
+        HIP_TRY(c, hipHostMalloc((void**)&c->query_host, want * 4, hipHostMallocDefault));
+        c->query_host_words = want;
+    }
+    uint32_t* large = c->query_host + nn * 8;
+    uint32_t* out = c->query_host + nn * 9;
+    memcpy(c->query_host, boxes, nn * 32);
+    memset(out, 0, nn * 4);
+    c->query_passed = out;
+    // the boxes' parts in this band: their total area, and the ones large enough to be split across workgroups
+    uint64_t total_area = 0;
+    size_t nlarge = 0;
+    for (size_t k = 0; k < nn; k++) {
+        const swr_depth_box& b = boxes[k];
+        const int64_t h = (int64_t)std::min<int>(b.y1, c->tg.row_end) - (int64_t)std::max<int>(b.y0, c->tg.row_begin);
+        if (h <= 0 || b.x1 <= b.x0) continue;
+        const uint64_t area = (uint64_t)h * (uint64_t)(b.x1 - b.x0);
+        total_area += area;
+        if (area >= DEPTH_QUERY_SPLIT_AREA) large[nlarge++] = (uint32_t)k;
+        // right after swr_target_set the image is the cleared one, whatever the buffers hold (the clear itself waits for the first
+        // frame): every pixel is +inf, and the answer needs no device
+        if (c->src_clear && b.z < std::numeric_limits<float>::infinity()) out[k] = (uint32_t)area;
+    }
+    if (tiles_of(c->tg) == 0 || total_area == 0 || c->src_clear) return SWR_OK;
+    if ((rc = ensure(c, c->query_dev, words * 4))) return rc;
+    if ((rc = ensure(c, c->query_tiles, depth_query_scratch_bytes(c->tg.width, c->tg.row_end - c->tg.row_begin)))) return rc;
+    if (!launch_depth_query) return fail(c, SWR_ERR_HIP, "this build has no k_depth_boxes: there is no fallback for the depth queries");
+    uint32_t* dev = (uint32_t*)c->query_dev.p;
+    HIP_TRY(c, hipMemcpyAsync(dev, c->query_host, (nn * 8 + nlarge) * 4, hipMemcpyHostToDevice, c->stream));
+    launch_depth_query((const float*)c->depth[c->fb_last].p, c->tg.width, c->tg.row_end - c->tg.row_begin, c->tg.row_begin,
+                       (const swr_depth_box*)dev, n, dev + nn * 8, (int64_t)nlarge, total_area, c->query_tiles.p, dev + nn * 9, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, dev + nn * 9, nn * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_stream(c, c->stream, "raster stream (depth query)"))) return or_sticky(c, rc);
+    return SWR_OK;
+}
+
 void destroy_single(swr_context* c) {
     hipSetDevice(c->device);
     // helper jobs are bounded (every wait in them is) and give up at once on a failed context: the drains return
@@ -2220,7 +2304,8 @@ void destroy_single(swr_context* c) {
                 (unsigned long long)c->hp_frames, c->hp_t[0] / c->hp_frames, c->hp_t[1] / c->hp_frames, c->hp_t[2] / c->hp_frames,
                 c->hp_t[3] / c->hp_frames, c->hp_t[4] / c->hp_frames, c->hp_t[5] / c->hp_frames);
     DevBuf* bufs[] = {&c->redo_cnt, &c->vertices, &c->indices, &c->tri_rgb, &c->tri_xyz, &c->inv, &c->box64, &c->stream_scratch, &c->sort_temp,
-                      &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth, &c->count_dev};
+                      &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth, &c->count_dev, &c->query_dev,
+                      &c->query_tiles};
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
@@ -2257,6 +2342,7 @@ void destroy_single(swr_context* c) {
     if (c->h_misc) hipHostFree(c->h_misc);
     if (c->h_clip) hipHostFree(c->h_clip);
     if (c->count_host) hipHostFree(c->count_host);
+    if (c->query_host) hipHostFree(c->query_host);
     if (c->ev_ok)
         for (int r = 0; r < swr_context::RING; r++)
             for (int i = 0; i < 5; i++) hipEventDestroy(c->ev[r][i]);
@@ -2625,6 +2711,28 @@ int swr_count_ids(swr_context* c, const swr_id_count* query, uint32_t* counts, i
         nn += k->count_host[n];
     }
     if (none) *none = nn;
+    return SWR_OK;
+}
+
+int swr_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, uint32_t* passed) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    if (!is_group(c)) {
+        const int rc = single_query_depth(c, boxes, n, passed);
+        if (rc) return rc;
+        if (n) memcpy(passed, c->query_passed, (size_t)n * 4);
+        return SWR_OK;
+    }
+    // a group checks what it can see before any band is touched; every band counts into staging of its own, and the caller's array is
+    // written once, after all of them succeeded
+    if (const int f = sticky(c)) return f;
+    int rc = check_query_args(c, boxes, n, passed);
+    if (rc) return rc;
+    if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_query_depth needs swr_target_set first");
+    if ((rc = check_query_boxes(c, boxes, n, c->group_tg))) return rc;
+    if ((rc = group_run(c, [=](swr_context* k) { return single_query_depth(k, boxes, n, passed); }))) return rc;
+    if (n) memset(passed, 0, (size_t)n * 4);
+    for (const swr_context* k : c->kids)
+        for (int64_t i = 0; i < n; i++) passed[i] += k->query_passed[i];
     return SWR_OK;
 }
 

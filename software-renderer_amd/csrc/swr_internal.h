@@ -245,4 +245,18 @@ void launch_resolve(const void* color, const void* depth, void* color_out, void*
 void launch_count_ids(const uint32_t* ids, int width, int x0, int x1, int y0, int y1, int per_item, const ListItem* items,
                       uint32_t* counters, int64_t n, hipStream_t s);
 
+// swr_depth_query.hip: depth queries: passed[k] = the pixels of boxes[k] (full-target coordinates, already checked),
+// clipped to the band's rows [row_begin, row_begin + rows), with boxes[k].z < depth — the band's depth image, `width` floats per row.
+// Every passed[0 .. n) is written, by plain stores; nothing has to be zeroed.  `large` lists the nlarge boxes whose part in the band
+// holds at least DEPTH_QUERY_SPLIT_AREA pixels (ascending box indices, duplicates of a box are separate entries): their tiles are
+// split across workgroups.  total_area is the sum of the boxes' parts in the band, in pixels: a query far smaller than the band is
+// scanned directly, without the tile summary.  `scratch` holds the summary: depth_query_scratch_bytes(width, rows) bytes.
+// boxes, large, scratch and passed are device memory.
+constexpr uint32_t DEPTH_QUERY_SPLIT_AREA = 1u << 17;
+inline size_t depth_query_scratch_bytes(int width, int rows) {      // (16 bytes per tile of 64 columns x at least 8 rows)
+    return (size_t)((width + 63) / 64) * (size_t)((rows + 7) / 8) * 16;
+}
+void launch_depth_query(const float* depth, int width, int rows, int row_begin, const swr_depth_box* boxes, int64_t n,
+                        const uint32_t* large, int64_t nlarge, uint64_t total_area, void* scratch, uint32_t* passed, hipStream_t s);
+
 }  // namespace swr
