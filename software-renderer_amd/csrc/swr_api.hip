@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "swr_internal.h"
+#include "swr_frame_policy.h"
 
 // The host layer is also built without the kernels, against stand-in launch functions (tests/host/hip_stub); a stand-in set that
 // predates the supersampled resolve does not define its launch.  The reference is weak so that such a program still links; the library
@@ -63,6 +64,9 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+#ifndef SWR_TUNE_HELPER_SPIN
+#define SWR_TUNE_HELPER_SPIN 4000     // pause loops an idle Worker spins before it sleeps
+#endif
 // One host thread per sub-context of a group: HIP calls of different devices are enqueued in parallel and the
 // caller's thread pays a few microseconds per fan-out instead of N x (nine HIP calls).  Jobs run in FIFO order;
 // asynchronous posts (swr_draw, swr_present) return at once and a failure is kept until the next blocking call.
@@ -83,9 +87,6 @@ struct Worker {
                 if (q.empty()) {
                     // spin briefly before sleeping: frames arrive every few tens of microseconds
                     lk.unlock();
-#ifndef SWR_TUNE_HELPER_SPIN
-#define SWR_TUNE_HELPER_SPIN 4000
-#endif
                     for (int spin = 0; spin < SWR_TUNE_HELPER_SPIN; spin++) {
                         __builtin_ia32_pause();
                         if (pending.load(std::memory_order_acquire)) break;
@@ -241,18 +242,6 @@ struct swr_context {
     float* present_depth = nullptr;
     bool present_pending = false;
 
-#ifndef SWR_RAS_EVERY
-#define SWR_RAS_EVERY 1   // every n-th k_raster carries a completion event (see RAS_EVERY)
-#endif
-    // A kernel that carries a completion signal (ras_done) costs the NEXT kernel of its queue ~5 us
-    // (profiles/r02/c_kernel_trace_pipelined.txt).  The binning of frame N needs "k_raster(N - NSLOT) has finished"; it
-    // waits for the first event-carrying raster at or after that frame instead (same queue, in order), so only every
-    // RAS_EVERY-th raster needs one, at the price of RAS_EVERY - 1 extra working sets.  Measured (NSLOT / RAS_EVERY = 3 / 1,
-    // 4 / 2, 6 / 4; profiles/r02/ras_every_ab.txt): cfg4 0.0977 / 0.0993 / 0.0981 ms, 1/8 band 29.2 / 27.7 / 27.0 us — the
-    // gap on the raster queue is filled by the binning queue's kernels (the frame is bound by the sum of the work), so
-    // the default stays 3 / 1.
-    static constexpr int RAS_EVERY = SWR_RAS_EVERY;
-    static_assert(RAS_EVERY >= 1 && NSLOT > RAS_EVERY, "the event-carrying raster must be older than the frame being binned");
     // Per-frame working set, multi-buffered: the binning kernels of frame N+1 run on `bin_stream`
     // while k_raster of frame N runs on `stream` (HBM-bound vs LDS/VALU-bound: they overlap well).
     struct Slot {
@@ -260,8 +249,7 @@ struct swr_context {
         DevBuf biglist;        // fixed-stride bins: the frame's deferred large triangles (k_bin -> k_sort_bins)
         DevBuf live;           // per binning workgroup: count + surviving stream-group ids (k_setup_hist -> k_fill_lds)
         DevBuf tilebuf;        // [CNT_WORDS counters][tiles tile_count][tiles+1 tile_start][tiles cursor]
-        hipEvent_t bin_done = nullptr, ras_done = nullptr;
-        uint64_t ras_event_frame = ~0ull;   // the frame whose k_raster this slot's ras_done tracks (none yet)
+        hipEvent_t bin_done = nullptr;     // two-stream: the binning chain's completion; lanes: polled by the injected lost event only
         // draw-list frames: the item table (pinned staging -> device, on the frame's own stream, before its binning)
         // and the frame's per-slot colours / attributes / original-index table (k_list_gather)
         DevBuf items, lrgb, lnrm, linv;
@@ -275,20 +263,13 @@ struct swr_context {
         bool items_recorded = false;
         uint64_t items_frame = 0;           // the frame whose copy items_copied follows
     } slot[NSLOT];
-    hipStream_t bin_stream = nullptr;   // the stream binning is enqueued on (== stream when pipelining is off)
+    hipStream_t bin_stream = nullptr;   // the stream binning is enqueued on (== stream when pipelining is off); every scheduler: sched_of reads it
     hipStream_t bin_stream_own = nullptr;
     hipEvent_t up_chunk_ev = nullptr;   // one-shot upload: index chunk k resident / its stream built
     uint64_t frame_no = 0;
     uint64_t synced_upto = 0;           // every frame below this has completed (full stream sync seen by the caller)
     int last_slot = 0;
     uint32_t capacity = 0;              // exact bins: (triangle,tile) pairs every slot's `bins` holds
-    // Fixed-stride bins (k_bin: ONE binning launch per frame): tile t owns bins[t * cap_tile, (t + 1) * cap_tile).  The
-    // per-tile fill counters live in NFILL = NSLOT + 1 rotating blocks (frame % NFILL) while the working sets rotate by NSLOT:
-    // k_bin of frame N zeroes the block of frame N + 1, which was last read by the raster of frame N - NSLOT — the raster
-    // whose completion lets the binning of frame N start.
-    static constexpr int NFILL = NSLOT + 1;      // k_bin(N) zeroes the fill block of frame N + 1: its last reader must be the raster of frame N - NSLOT
-    DevBuf fillbuf[NFILL];              // [CNT_WORDS counters][tiles fills]
-    bool fill_dirty[NFILL] = {};        // block was used and nothing has zeroed it since (then the frame memsets it first)
     // ---- FRAME LANES (round 4; the default whenever frames may overlap).  The binning and the raster of ONE frame go back to
     // back onto ONE stream — kernels of a queue follow each other without a gap, and nothing else orders them: no event, no
     // wait packet, no completion signal, no helper thread that polls — and consecutive frames onto NSLOT different streams.
@@ -333,57 +314,83 @@ struct swr_context {
     int sized_tiles = -1;
     DevBuf redo_cnt;                    // the device counter behind that word
     uint64_t frames_checked = 0;        // frames [frames_checked, frame_no) have not had their pair total looked at
-    // Two host threads per context: every frame is ~9 HIP calls (3.5 us each); the binning stream's share (slot wait,
-    // three or four launches, event record) is enqueued by `bin_worker` while the caller's thread enqueues the raster
-    // stream's share (event wait, launches, event record) of the PREVIOUS frame — a thin band or a small scene is
-    // bound by the host's enqueue rate, not by the GPU.
-    Worker* bin_worker = nullptr;
-    // ... and a third one for the raster stream's share, for a different reason: a cross-stream hipStreamWaitEvent in
-    // front of a kernel costs that kernel ~10 us after its predecessor on the queue has ended, even when the event
-    // completed long before (profiles/r02/gaps_pipelined_before.txt) — a wait that is never enqueued costs nothing.
-    // `ras_worker` polls hipEventQuery(bin_done) of the frame and only then enqueues k_raster, with no wait in front
-    // (and `bin_worker` does the same with ras_done before it re-uses a working set).  swr_draw / swr_present only post.
-    // SWR_EVENT_WAITS=1: the caller's thread enqueues the raster share behind event waits (round-2 first half).
-    Worker* ras_worker = nullptr;
-    // bin_done / ras_done are bound to the kernels they follow (hipExtLaunchKernelGGL's stop event) instead of being
-    // recorded behind them: a marker packet between two kernels of a queue costs the second one ~6.5 us.  SWR_BIND_EVENTS=0: record.
-    bool bind_events = true;
-    // One frame at a time (an interactive app: swr_draw, swr_sync / swr_present_wait, idle, ...) does not need the
-    // helpers: when every earlier frame is known to be complete, the frame is enqueued by the caller's thread itself,
-    // ordered by event waits on the streams — the helpers may be asleep by then, and waking two threads costs more than
-    // the two wait packets (draw -> sync of cfg4 after 5 ms of idle: 205 -> 180 us; cfg2 94 -> 70 us,
-    // profiles/r02/cold_latency.txt).  Frames drawn while others are in flight go through the helpers.  SWR_INLINE_IDLE=0: never.
-    bool inline_idle = true;
+    // (every scheduler keeps these three in step — mark_posted — so that a swr_pipeline_enable toggle finds them where the other expects)
     std::atomic<uint64_t> bin_enqueued{0};      // frames whose binning (incl. the bin_done record) is on the binning stream
     std::atomic<uint64_t> ras_enqueued{0};      // frames whose raster (incl. the ras_done record) is on the raster stream
-    std::atomic<int> bin_error{0};
-    uint64_t posted = 0;                        // frames whose binning share has been handed to the helper (or run inline)
-    static constexpr int RAS_RING = 64;          // frames whose raster share may be waiting for ras_worker; swr_draw blocks beyond that
-    struct RasJob { DeviceFrame f; hipEvent_t ev3 = nullptr, ev4 = nullptr; int si = 0; bool sort_here = false; int fb = 0; bool paced = false; } ras_job[RAS_RING];
+    uint64_t posted = 0;                        // frames handed over: to the helper or run inline (two-stream), enqueued whole or abandoned (lanes)
+    // ---- THE TWO-STREAM PIPELINE (rounds 1-3: SWR_LANES=0) and its one-stream case (swr_pipeline_enable(0)): what only they use.  The
+    // lanes touch none of it, except that every scheduler drains the helpers (flush_raster, sync_copies: they may hold a present's copies).
+    struct TwoStream {
+#ifndef SWR_RAS_EVERY
+#define SWR_RAS_EVERY 1   // every n-th k_raster carries a completion event (see RAS_EVERY)
+#endif
+        // A kernel that carries a completion signal (ras_done) costs the NEXT kernel of its queue ~5 us
+        // (profiles/r02/c_kernel_trace_pipelined.txt).  The binning of frame N needs "k_raster(N - NSLOT) has finished"; it
+        // waits for the first event-carrying raster at or after that frame instead (same queue, in order), so only every
+        // RAS_EVERY-th raster needs one, at the price of RAS_EVERY - 1 extra working sets.  Measured (NSLOT / RAS_EVERY = 3 / 1,
+        // 4 / 2, 6 / 4; profiles/r02/ras_every_ab.txt): cfg4 0.0977 / 0.0993 / 0.0981 ms, 1/8 band 29.2 / 27.7 / 27.0 us — the
+        // gap on the raster queue is filled by the binning queue's kernels (the frame is bound by the sum of the work), so
+        // the default stays 3 / 1.
+        static constexpr int RAS_EVERY = SWR_RAS_EVERY;
+        static_assert(RAS_EVERY >= 1 && NSLOT > RAS_EVERY, "the event-carrying raster must be older than the frame being binned");
+        // Fixed-stride bins (k_bin: ONE binning launch per frame): tile t owns bins[t * cap_tile, (t + 1) * cap_tile).  The
+        // per-tile fill counters live in NFILL = NSLOT + 1 rotating blocks (frame % NFILL) while the working sets rotate by NSLOT:
+        // k_bin of frame N zeroes the block of frame N + 1, which was last read by the raster of frame N - NSLOT — the raster
+        // whose completion lets the binning of frame N start.
+        static constexpr int NFILL = NSLOT + 1;      // k_bin(N) zeroes the fill block of frame N + 1: its last reader must be the raster of frame N - NSLOT
+        DevBuf fillbuf[NFILL];              // [CNT_WORDS counters][tiles fills]
+        bool fill_dirty[NFILL] = {};        // block was used and nothing has zeroed it since (then the frame memsets it first)
+        // Two host threads per context: every frame is ~9 HIP calls (3.5 us each); the binning stream's share (slot wait,
+        // three or four launches, event record) is enqueued by `bin_worker` while the caller's thread enqueues the raster
+        // stream's share (event wait, launches, event record) of the PREVIOUS frame — a thin band or a small scene is
+        // bound by the host's enqueue rate, not by the GPU.
+        Worker* bin_worker = nullptr;
+        // ... and a third one for the raster stream's share, for a different reason: a cross-stream hipStreamWaitEvent in
+        // front of a kernel costs that kernel ~10 us after its predecessor on the queue has ended, even when the event
+        // completed long before (profiles/r02/gaps_pipelined_before.txt) — a wait that is never enqueued costs nothing.
+        // `ras_worker` polls hipEventQuery(bin_done) of the frame and only then enqueues k_raster, with no wait in front
+        // (and `bin_worker` does the same with ras_done before it re-uses a working set).  swr_draw / swr_present only post.
+        // SWR_EVENT_WAITS=1: the caller's thread enqueues the raster share behind event waits (round-2 first half).
+        Worker* ras_worker = nullptr;
+        // bin_done / ras_done are bound to the kernels they follow (hipExtLaunchKernelGGL's stop event) instead of being
+        // recorded behind them: a marker packet between two kernels of a queue costs the second one ~6.5 us.  SWR_BIND_EVENTS=0: record.
+        bool bind_events = true;
+        // One frame at a time (an interactive app: swr_draw, swr_sync / swr_present_wait, idle, ...) does not need the
+        // helpers: when every earlier frame is known to be complete, the frame is enqueued by the caller's thread itself,
+        // ordered by event waits on the streams — the helpers may be asleep by then, and waking two threads costs more than
+        // the two wait packets (draw -> sync of cfg4 after 5 ms of idle: 205 -> 180 us; cfg2 94 -> 70 us,
+        // profiles/r02/cold_latency.txt).  Frames drawn while others are in flight go through the helpers.  SWR_INLINE_IDLE=0: never.
+        bool inline_idle = true;
+        std::atomic<int> bin_error{0};
+        static constexpr int RAS_RING = 64;          // frames whose raster share may be waiting for ras_worker; swr_draw blocks beyond that
+        struct RasJob { DeviceFrame f; hipEvent_t ev3 = nullptr, ev4 = nullptr; int si = 0; bool sort_here = false; int fb = 0; bool paced = false; } ras_job[RAS_RING];
+        // per working set: the completion of the event-carrying k_raster that read it, and the frame whose k_raster it tracks (none yet)
+        struct RasDone { hipEvent_t ev = nullptr; uint64_t frame = ~0ull; } ras_done[NSLOT];
+    } ts;
     // ---- draw lists (swr_draw_list)
     bool stream_sorted = false;         // the stream is Morton-sorted: a list's ranges must be runs of slots (cut the stream at them)
     std::vector<uint32_t> cuts;         // primitive indices the stream is cut at now (sorted; empty: one segment, as uploaded)
     DevBuf cuts_dev;
-    std::vector<ListItem> list;         // the items of the last draw-list frame (its redo after an overflow needs them again)
-    int64_t list_tris = 0;              // its total
-    int64_t list_units = 0;             // its k_bin work units
-    bool list_affine = false;
-    bool list_identity = false;         // frame slot == stream slot and order number == original index for every item
-    bool last_list = false;             // the last frame was a draw list
-    bool last_clip = false;             // the last frame was a depth-clip frame (SWR_FLAG_DEPTH_CLIP) of clip_n submitted triangles
-    int64_t clip_n = 0;
-    bool last_persp = false;            // the last frame interpolates colour with perspective correction (SWR_FLAG_PERSPECTIVE, a colour
-                                        // frame of triangles through a non-affine transform): its slot's pq table is filled and read
+    // (clip_fan and clip_total are not in the record: they are how the context sizes a clip frame — check_frames grows the fan — not what was drawn)
     int64_t clip_fan = 0;               // fan capacity F: a clip frame of n triangles has n + 2F slots (each crossing triangle adds <= 2)
     int64_t clip_total = -1;            // the post-clip count of the last clip frame when the host had to know it (else -1)
     uint32_t* h_clip = nullptr;         // pinned, device-mapped: [PAIR_RING] per frame, the post-clip count of a clip frame whose fans
     uint32_t* h_clip_dev = nullptr;     // overflowed its slots (0: none); [PAIR_RING] the post-clip count the host asked for
     int64_t list_plan_max = 0;          // largest binning size (work units * 64) of a list since the upload (fixed-bin limits)
-    // last draw (for the overflow redo and for swr_render)
-    float last_m[16]{};
-    uint32_t last_flags = 0;
-    swr_blend last_blend{SWR_BLEND_OVER, 255, {0, 0}};   // the blend state the last frame was posted with (a redo draws with it again)
-    int last_prim = SWR_PRIMITIVE_TRIANGLE;
+    // The last draw: what its frame is built from (make_frame, make_list_frame, make_clip_frame) and what its redo after an overflow
+    // (check_frames) needs again.  The draw entry points fill it (begin_draw .. end_draw; prepare_clip sets clip_n); everything else reads.
+    struct DrawRecord {
+        float m[16]{};
+        uint32_t flags = 0;
+        swr_blend blend{SWR_BLEND_OVER, 255, {0, 0}};   // the blend state the frame was posted with (a redo draws with it again)
+        int prim = SWR_PRIMITIVE_TRIANGLE;
+        bool is_list = false;               // a draw list (swr_draw_list) of
+        std::vector<ListItem> list;         // these items (kept while it is the last draw: the redo stages them again),
+        int64_t list_tris = 0, list_units = 0;   // its total and its k_bin work units
+        bool list_affine = false, list_identity = false;   // identity: frame slot == stream slot and order number == original index for every item
+        bool clip = false; int64_t clip_n = 0;   // a depth-clip frame (SWR_FLAG_DEPTH_CLIP) of clip_n submitted triangles
+        bool persp = false;                 // perspective-correct colour (SWR_FLAG_PERSPECTIVE, triangles through a non-affine transform): its slot's pq table is filled and read
+    } last_draw;
     bool draw_pending = false;
 
     // timing: a ring of hipEvent sets recorded on the context stream around each kernel, so a
@@ -404,22 +411,17 @@ struct swr_context {
     bool hp_on = false;
     double hp_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t hp_frames = 0;
-    std::chrono::steady_clock::time_point hp_last;
-    std::chrono::steady_clock::time_point hp_last_r;    // the raster share's own clock (it may run on ras_worker)
-    void hp_begin_r() { if (hp_on) hp_last_r = std::chrono::steady_clock::now(); }
-    void hp_lap_r(int k) {
+    std::chrono::steady_clock::time_point hp_last, hp_last_r;    // hp_last_r: the raster share's own clock (it may run on ras_worker)
+    void hp_lap_on(std::chrono::steady_clock::time_point& last, int k) {
         if (!hp_on) return;
         const auto now = std::chrono::steady_clock::now();
-        hp_t[k] += std::chrono::duration<double, std::micro>(now - hp_last_r).count();
-        hp_last_r = now;
+        hp_t[k] += std::chrono::duration<double, std::micro>(now - last).count();
+        last = now;
     }
     void hp_begin() { if (hp_on) hp_last = std::chrono::steady_clock::now(); }
-    void hp_lap(int k) {
-        if (!hp_on) return;
-        const auto now = std::chrono::steady_clock::now();
-        hp_t[k] += std::chrono::duration<double, std::micro>(now - hp_last).count();
-        hp_last = now;
-    }
+    void hp_lap(int k) { hp_lap_on(hp_last, k); }
+    void hp_begin_r() { if (hp_on) hp_last_r = std::chrono::steady_clock::now(); }
+    void hp_lap_r(int k) { hp_lap_on(hp_last_r, k); }
 };
 
 namespace {
@@ -566,8 +568,12 @@ int wait_counter(swr_context* c, const std::atomic<uint64_t>& ctr, uint64_t g, c
     return SWR_OK;
 }
 
-// frames go onto the lanes (swr_context::lane_stream) whenever frames may overlap at all (pipelining on)
-inline bool lane_mode(const swr_context* c) { return c->lanes_ok && c->bin_stream != c->stream; }
+// The three schedulers of a frame.  OneStream: binning and raster on `stream` (swr_pipeline_enable(0), SWR_PIPELINE=0).  Lanes: whenever
+// frames may overlap at all (pipelining on), a frame's binning and raster go onto its lane (swr_context::lane_stream).  TwoStream
+// (SWR_LANES=0, or a lane stream could not be created): binning on `bin_stream`, raster on `stream` (swr_context::TwoStream).
+enum class Sched { OneStream, TwoStream, Lanes };
+inline Sched sched_of(const swr_context* c) { return c->bin_stream == c->stream ? Sched::OneStream : c->lanes_ok ? Sched::Lanes : Sched::TwoStream; }
+using TS = swr_context::TwoStream;
 
 int sync_streams(swr_context* c) {
     int rc = flush_raster(c, c->frame_no);      // everything drawn so far is on the streams
@@ -584,7 +590,7 @@ int sync_streams(swr_context* c) {
 
 int sync_copies(swr_context* c) {
     int rc = SWR_OK;
-    if (c->ras_worker) rc = c->ras_worker->drain();    // posted swr_present copies
+    if (c->ts.ras_worker) rc = c->ts.ras_worker->drain();    // posted swr_present copies
     if (!rc) rc = wait_stream(c, c->copy_stream[0], "colour copy stream");
     if (!rc) rc = wait_stream(c, c->copy_stream[1], "depth copy stream");
     if (rc) return or_sticky(c, rc);
@@ -687,10 +693,10 @@ int size_bins(swr_context* c) {
         if (!c->fixed_mode || c->cap_tile < want || c->cap_tile > cmax) c->cap_tile = want;   // a grown region survives a new transform
         if ((rc = ensure_bins(c, (size_t)tiles * c->cap_tile))) return rc;
         const size_t fb = (size_t)(CNT_WORDS + tiles) * 4;
-        for (int k = 0; k < swr_context::NFILL; k++) {
-            if ((rc = ensure(c, c->fillbuf[k], fb))) return rc;
-            HIP_TRY(c, hipMemsetAsync(c->fillbuf[k].p, 0, c->fillbuf[k].bytes, c->stream));
-            c->fill_dirty[k] = false;
+        for (int k = 0; k < TS::NFILL; k++) {
+            if ((rc = ensure(c, c->ts.fillbuf[k], fb))) return rc;
+            HIP_TRY(c, hipMemsetAsync(c->ts.fillbuf[k].p, 0, c->ts.fillbuf[k].bytes, c->stream));
+            c->ts.fill_dirty[k] = false;
         }
         for (int l = 0; l < swr_context::NSLOT; l++)
             for (int k = 0; k < 2; k++) {
@@ -725,7 +731,8 @@ BinPlan plan_frame(const swr_context* c, int64_t ntri, int64_t size, int64_t idl
     return p;
 }
 
-DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16], uint32_t flags) {
+// The frame of draw `d` on working set si, as a plain frame over the scene's stream (a list or clip frame is made of it below).
+DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const swr_context::DrawRecord& d) {
     swr_context::Slot& sl = c->slot[si];
     DeviceFrame f{};
     f.vertices = (const swr_vertex*)c->vertices.p;
@@ -753,7 +760,7 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
     f.redo_dev = (uint32_t*)c->redo_cnt.p;
     f.host_redo = c->h_pairs_dev + 2 * swr_context::PAIR_RING + 1;
     // (ID frames take the 64-bit keys, whose key carries the winner: they neither use nor move the scene's 32-bit-key state)
-    f.k32 = (c->k32_ok && c->dbg_k32 && f.redo_dev && !(flags & SWR_FLAG_PRIMITIVE_IDS)) ? 1 : 0;
+    f.k32 = (c->k32_ok && c->dbg_k32 && f.redo_dev && !(d.flags & SWR_FLAG_PRIMITIVE_IDS)) ? 1 : 0;
     f.tile_count = tb + CNT_WORDS;
     f.tile_start = tb + CNT_WORDS + tiles_of(c->tg);
     f.tile_cursor = tb + CNT_WORDS + 2 * tiles_of(c->tg) + 1;
@@ -768,27 +775,27 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
     f.capacity = c->capacity;
     f.fixed_bins = (c->fixed_mode && f.ntri > 0) ? 1 : 0;
     f.cap_tile = c->cap_tile;
-    if (lane_mode(c)) {       // the lane's two blocks alternate: this frame's, and the one its k_bin zeroes for the lane's next frame
+    if (sched_of(c) == Sched::Lanes) {       // the lane's two blocks alternate: this frame's, and the one its k_bin zeroes for the lane's next frame
         const int par = (int)((frame / (uint64_t)swr_context::NSLOT) & 1u);
         f.fill = (uint32_t*)c->lanefill[si][par].p;
         f.fill_next = (uint32_t*)c->lanefill[si][par ^ 1].p;
     } else {
-        f.fill = (uint32_t*)c->fillbuf[frame % swr_context::NFILL].p;
-        f.fill_next = (uint32_t*)c->fillbuf[(frame + 1) % swr_context::NFILL].p;
+        f.fill = (uint32_t*)c->ts.fillbuf[frame % TS::NFILL].p;
+        f.fill_next = (uint32_t*)c->ts.fillbuf[(frame + 1) % TS::NFILL].p;
     }
     f.host_fill = c->h_pairs_dev + swr_context::PAIR_RING + 1 + (frame % swr_context::PAIR_RING);
     f.biglist = (uint4*)sl.biglist.p;
     f.color = (uint8_t*)c->color[c->fb_cur].p;
     f.depth = (float*)c->depth[c->fb_cur].p;
-    const bool load = (flags & SWR_FLAG_LOAD) != 0;
+    const bool load = (d.flags & SWR_FLAG_LOAD) != 0;
     f.src_color = load ? (const uint8_t*)c->color[c->load_src].p : nullptr;
     f.src_depth = load ? (const float*)c->depth[c->load_src].p : nullptr;
-    f.ids = (flags & SWR_FLAG_PRIMITIVE_IDS) ? (uint32_t*)c->ids[c->fb_cur].p : nullptr;
+    f.ids = (d.flags & SWR_FLAG_PRIMITIVE_IDS) ? (uint32_t*)c->ids[c->fb_cur].p : nullptr;
     f.tg = c->tg;
-    memcpy(f.m, m, sizeof f.m);
-    f.flags = flags;
-    f.pq = c->last_persp ? (float4*)sl.pq.p : nullptr;
-    f.blend = c->last_blend;
+    memcpy(f.m, d.m, sizeof f.m);
+    f.flags = d.flags;
+    f.pq = d.persp ? (float4*)sl.pq.p : nullptr;
+    f.blend = d.blend;
     return f;
 }
 
@@ -796,16 +803,16 @@ DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const float m[16]
 // The frame of the last draw list: V = the list's total primitives, binned by k_bin<.., LIST> over (item, stream group) work units
 // (fixed-stride bins) or by k_list_setup + k_scan + k_fill (exact-size bins).  Unless every item's frame slots are its stream slots,
 // the raster reads the frame's own copies of the per-slot tables (k_list_gather).
-void make_list_frame(swr_context* c, int si, DeviceFrame& f) {
+void make_list_frame(swr_context* c, int si, const swr_context::DrawRecord& d, DeviceFrame& f) {
     swr_context::Slot& sl = c->slot[si];
-    f.ntri = c->list_tris;
+    f.ntri = d.list_tris;
     f.items = (const ListItem*)sl.items.p;
-    f.nitems = (int32_t)c->list.size();
-    f.units = c->list_units;
-    f.list_affine = c->list_affine ? 1 : 0;
+    f.nitems = (int32_t)d.list.size();
+    f.units = d.list_units;
+    f.list_affine = d.list_affine ? 1 : 0;
     f.fixed_bins = (c->fixed_mode && f.ntri > 0) ? 1 : 0;
     f.plan = plan_frame(c, f.ntri, f.units * 64, (f.units + 7) / 8, true);
-    if (!c->list_identity && f.ntri > 0) {
+    if (!d.list_identity && f.ntri > 0) {
         f.reordered = 1;                    // keys carry order numbers; inv maps them to frame slots
         f.inv = (const uint32_t*)sl.linv.p;
         f.gather.rgb = (const float4*)c->tri_rgb.p; f.gather.nrm = (const float4*)c->tri_nrm.p;
@@ -820,13 +827,13 @@ void make_list_frame(swr_context* c, int si, DeviceFrame& f) {
 }
 
 // the slots of a clip frame: n + 2F, at most 3n (each triangle gives at most three)
-inline int64_t clip_slots(const swr_context* c) { return std::min<int64_t>(3 * c->clip_n, c->clip_n + 2 * c->clip_fan); }
+inline int64_t clip_slots(const swr_context* c) { const int64_t n = c->last_draw.clip_n; return std::min<int64_t>(3 * n, n + 2 * c->clip_fan); }
 
 // ---- depth-clip frames ----------------------------------------------------------------------------------------------
 // The frame over the clip stream of its lane: n + 2F slots (n submitted triangles, of the scene or of the draw list), the identity
 // transform, slot = order number.  The pre-pass (launch_clip_prep) reads the scene's stream with the frame's transform(s) — a draw
 // list's items from the device copy staged for the frame — and the frame itself is binned like a scene of n + 2F primitives.
-void make_clip_frame(swr_context* c, int si, uint64_t frame, DeviceFrame& f) {
+void make_clip_frame(swr_context* c, int si, uint64_t frame, const swr_context::DrawRecord& d, DeviceFrame& f) {
     swr_context::Slot& sl = c->slot[si];
     ClipPrep& p = f.clip;
     p.src_xyz = (const float4*)c->tri_xyz.p;
@@ -834,12 +841,12 @@ void make_clip_frame(swr_context* c, int si, uint64_t frame, DeviceFrame& f) {
     p.src_nrm = c->has_attrs ? (const float4*)c->tri_nrm.p : nullptr;
     p.src_inv = (const uint32_t*)c->inv.p;
     p.src_reordered = c->reordered ? 1 : 0;
-    p.n = c->clip_n;
+    p.n = d.clip_n;
     p.bound = clip_slots(c);
     p.over = c->h_clip_dev + (frame % swr_context::PAIR_RING);
     memcpy(p.m, f.m, sizeof p.m);
-    p.items = c->last_list ? f.items : nullptr;
-    p.nitems = c->last_list ? f.nitems : 0;
+    p.items = d.is_list ? f.items : nullptr;
+    p.nitems = d.is_list ? f.nitems : 0;
     p.sums = (uint32_t*)sl.csums.p;
     p.xyz = (float4*)sl.cxyz.p; p.rgb = (float4*)sl.crgb.p;
     p.nrm = p.src_nrm ? (float4*)sl.cnrm.p : nullptr;
@@ -881,8 +888,8 @@ int ensure_persp(swr_context* c, int64_t slots) {
 int prepare_clip(swr_context* c, int64_t n, uint32_t flags, const float* m) {
     if (n > (int64_t)SWR_DEPTH_CLIP_MAX_TRIANGLES)
         return fail(c, SWR_ERR_UNSUPPORTED, "SWR_FLAG_DEPTH_CLIP: %lld triangles (at most %d)", (long long)n, SWR_DEPTH_CLIP_MAX_TRIANGLES);
-    if (n != c->clip_n || c->clip_fan <= 0) c->clip_fan = std::max<int64_t>(1024, n / 64);   // (grown by check_frames on overflow)
-    c->clip_n = n;
+    if (n != c->last_draw.clip_n || c->clip_fan <= 0) c->clip_fan = std::max<int64_t>(1024, n / 64);   // (grown by check_frames on overflow)
+    c->last_draw.clip_n = n;
     int rc;
     const size_t V = (size_t)std::max<int64_t>(clip_slots(c), 1);
     const size_t S = (size_t)(n + 255) / 256 + 1;            // the pre-pass's workgroup sums + the total
@@ -902,19 +909,18 @@ int prepare_clip(swr_context* c, int64_t n, uint32_t flags, const float* m) {
     const int64_t thr = ((int64_t)1 << 20) + ((flags & SWR_FLAG_LOAD) ? 0 : 1);
     if (n > 0 && (int64_t)V >= thr) {
         if ((rc = sync_streams(c))) return rc;
-        DeviceFrame f{};
-        f.vertices = (const swr_vertex*)c->vertices.p;
-        f.tri_xyz = (const float4*)c->tri_xyz.p;
-        f.tri_rgb = (const float4*)c->tri_rgb.p;
-        f.tri_nrm = (const float4*)c->tri_nrm.p;
-        f.inv = (const uint32_t*)c->inv.p;
-        f.reordered = c->reordered ? 1 : 0;
-        f.tg = c->tg;
-        memcpy(f.m, m ? m : c->last_m, sizeof f.m);
-        if (!m) {
-            // a draw list: its items reach the device with the frame (stage_list), so its count is not known here: the bound holds
-        } else {
-            make_clip_frame(c, 0, c->frame_no, f);
+        // (m == NULL, a draw list: its items reach the device with the frame (stage_list), so its count is not known here: the bound holds)
+        if (m) {
+            DeviceFrame f{};
+            f.vertices = (const swr_vertex*)c->vertices.p;
+            f.tri_xyz = (const float4*)c->tri_xyz.p;
+            f.tri_rgb = (const float4*)c->tri_rgb.p;
+            f.tri_nrm = (const float4*)c->tri_nrm.p;
+            f.inv = (const uint32_t*)c->inv.p;
+            f.reordered = c->reordered ? 1 : 0;
+            f.tg = c->tg;
+            memcpy(f.m, m, sizeof f.m);
+            make_clip_frame(c, 0, c->frame_no, c->last_draw, f);
             f.clip.count_only = 1;
             launch_bin(f, c->stream, nullptr);
             const int64_t nb = (n + 255) / 256;
@@ -941,18 +947,18 @@ int stage_list(swr_context* c, int si, uint64_t frame, ListPrep& lp) {
     int rc;
     if (!sl.items_copied) HIP_TRY(c, hipEventCreateWithFlags(&sl.items_copied, hipEventDisableTiming));
     if (sl.items_recorded && sl.items_frame < frame) {      // (a frame number posted again after a failed post: it never copied)
-        if (!lane_mode(c) && (rc = wait_counter(c, c->bin_enqueued, sl.items_frame, "the binning share of an earlier draw list"))) return rc;
+        if (sched_of(c) != Sched::Lanes && (rc = wait_counter(c, c->bin_enqueued, sl.items_frame, "the binning share of an earlier draw list"))) return rc;
         if ((rc = poll_event(c, sl.items_copied, "the copy of an earlier frame's draw list", sl.items_frame))) return rc;
         sl.items_recorded = false;
     }
-    const size_t n = c->list.size();
+    const size_t n = c->last_draw.list.size();
     if (sl.items_cap < n) {
         if (sl.items_host) { HIP_TRY(c, hipHostFree(sl.items_host)); sl.items_host = nullptr; sl.items_cap = 0; }
         const size_t want = std::max<size_t>(64, n);
         HIP_TRY(c, hipHostMalloc((void**)&sl.items_host, want * sizeof(ListItem), hipHostMallocDefault));
         sl.items_cap = want;
     }
-    if (n) memcpy(sl.items_host, c->list.data(), n * sizeof(ListItem));
+    if (n) memcpy(sl.items_host, c->last_draw.list.data(), n * sizeof(ListItem));
     sl.items_recorded = true;
     sl.items_frame = frame;
     lp.on = true;
@@ -1030,279 +1036,271 @@ int enqueue_binning(swr_context* c, const DeviceFrame& f, int si, hipStream_t s,
     return SWR_OK;
 }
 
+// The one epilogue of a frame that went onto the streams whole, or was abandoned: every frame below `upto` counts as posted, binned and
+// rastered.  A path that left a counter behind would hang wait_counter in the other scheduler after a swr_pipeline_enable toggle.  (Only
+// the two-stream frame advances them share by share.)  Sequentially consistent stores: the strongest order any of these sites used.
+void mark_posted(swr_context* c, uint64_t upto) { c->posted = upto; c->bin_enqueued.store(upto); c->ras_enqueued.store(upto); }
+
+// An empty band (a group with more sub-contexts than tile rows hands these out): nothing to bin, raster or copy
+int enqueue_empty_frame(swr_context* c) {
+    if (const int rc = flush_raster(c, c->frame_no)) return rc;
+    fill_word(c, c->frame_no) = 0;
+    c->frame_load[c->frame_no % swr_context::PAIR_RING] = false;     // (no pixels: nothing it could load wrongly)
+    pair_word(c, c->frame_no++) = 0;
+    mark_posted(c, c->frame_no);
+    c->draw_pending = true;
+    return SWR_OK;
+}
+
+// .vertices / .line: three small kernels on the raster stream with every stream idle, no binning; the pair counter reads 0
+int enqueue_points_frame(swr_context* c, const swr_context::DrawRecord& d) {
+    int rc = sync_streams(c); if (rc) return rc;
+    const bool lanes = sched_of(c) == Sched::Lanes, load = (d.flags & SWR_FLAG_LOAD) != 0;
+    const uint64_t frame = c->frame_no++;
+    DeviceFrame f = make_frame(c, 0, frame, d);
+    pair_word(c, frame) = 0; fill_word(c, frame) = 0;
+    c->frame_load[frame % swr_context::PAIR_RING] = load;
+    if ((rc = wait_for_copies_of(c, c->fb_cur, c->stream))) return rc;
+    launch_points_or_lines(f, d.prim, c->stream);
+    if (load && lanes) {
+        HIP_TRY(c, hipEventRecord(c->read_done[c->load_src], c->stream));
+        c->read_recorded[c->load_src] = true;
+    }
+    HIP_TRY(c, hipGetLastError());
+    mark_posted(c, c->frame_no);
+    c->draw_pending = true;
+    c->last_stream = c->stream;
+    if (lanes) c->fb_cur = (c->fb_last + 1) % swr_context::NFB;
+    return SWR_OK;
+}
+
+// *ev = the set of timing events of the frame about to be posted (swr_timing_enable), NULL when it is not timed
+int claim_timing_events(swr_context* c, hipEvent_t** ev) {
+    *ev = nullptr;
+    if (c->timing < 2 && !(c->timing == 1 && (c->frame_no % (uint64_t)c->timing_every) == 0)) return SWR_OK;
+    if (c->seq - c->harvested >= (uint64_t)swr_context::RING) { int rc = sync_streams(c); if (rc) return rc; harvest(c); }   // ring full: drain it
+    *ev = c->ev[c->seq % swr_context::RING];
+    c->ev_level[c->seq++ % swr_context::RING] = c->timing;
+    return SWR_OK;
+}
+
+// frame_policy (swr_frame_policy.h) on the context's pinned words, into the frame; returns whether k_sort_bins goes onto the raster stream
+bool settle_policy(swr_context* c, Sched sched, DeviceFrame& f) {
+    const int tiles = tiles_of(c->tg);
+    // (words the GPU overwrites while frames are in flight: read them as what they are, relaxed atomics)
+    const uint32_t fullest = __atomic_load_n(&c->h_pairs[swr_context::PAIR_RING], __ATOMIC_RELAXED);
+    const uint32_t redo = __atomic_load_n(&c->h_pairs[2 * swr_context::PAIR_RING + 1], __ATOMIC_RELAXED);
+    FramePolicy p = frame_policy(fullest, redo, tiles, f.ntri, f.flags, f.k32 != 0, sched == Sched::TwoStream);
+    if (p.k32_give_up) c->k32_ok = false;
+    f.k32 = p.k32 ? 1 : 0;
+    policy_insort(p, tiles, frame_uses_k32(f), c->dbg_insort);
+    f.skip_sort = p.skip_sort ? 1 : 0; f.defer_big = p.defer_big ? 1 : 0; f.insort = p.insort ? 1 : 0;
+    return p.sort_on_raster_stream;
+}
+
+// Fixed-stride bins: the frame's fill block must be zero when k_bin starts (the k_bin before it did that, unless that frame took
+// another path); k_bin leaves it dirty and zeroes the next frame's.  Returns whether the frame has to memset its block first.
+bool claim_fill_block(swr_context* c, Sched sched, int si, uint64_t frame) {
+    const int k = sched == Sched::Lanes ? (int)((frame / (uint64_t)swr_context::NSLOT) & 1u) : (int)(frame % TS::NFILL);
+    bool* dirty = sched == Sched::Lanes ? c->lanefill_dirty[si] : c->ts.fill_dirty;
+    const bool was = dirty[k];
+    dirty[k] = true;
+    dirty[sched == Sched::Lanes ? k ^ 1 : (k + 1) % TS::NFILL] = false;
+    return was;
+}
+
+// ---- FRAME LANES: the whole frame, binning and raster, back to back on the lane's stream (see swr_context::lane_stream) ----------
+// nothing was enqueued for the frame: the context has failed (fatal) or the call reports
+int abandon_frame(swr_context* c, uint64_t frame, int rc) { mark_posted(c, frame + 1); return rc; }
+// an un-waited burst is paced by markers: at most ~4 * PACE_EVERY frames in flight
+int pace_burst(swr_context* c, uint64_t frame) {
+    constexpr uint64_t E = swr_context::PACE_EVERY;
+    if (frame % E != 0 || frame < 3 * E) return SWR_OK;
+    const uint64_t old = frame - 3 * E;
+    const int ko = (int)((frame / E + 1) % 4);          // the marker of `old`: (k - 3) mod 4
+    if (c->pace_frame[ko] != old || old < c->synced_upto) return SWR_OK;
+    return poll_event(c, c->pace_ev[ko], "an earlier frame of the burst", old);
+}
+
+// what the frame puts on its lane S: the binning chain, k_sort_bins, the raster, and the markers behind it
+int enqueue_lane_chain(swr_context* c, const DeviceFrame& f, int si, uint64_t frame, hipStream_t S, const BinChain& bc, hipEvent_t* ev, bool src_wait) {
+    bool bound;
+    { const int rb = enqueue_binning(c, f, si, S, bc, nullptr, &bound); if (rb) return rb; }
+    if (!f.skip_sort) launch_sort_bins(f, S, nullptr);
+    if (src_wait) HIP_TRY(c, hipStreamWaitEvent(S, c->src_ready, 0));
+    if (ev) HIP_TRY(c, hipEventRecord(ev[3], S));
+    launch_raster(f, S, nullptr);
+    if (ev) HIP_TRY(c, hipEventRecord(ev[4], S));
+    if (f.flags & SWR_FLAG_LOAD) {
+        HIP_TRY(c, hipEventRecord(c->read_done[c->load_src], S));
+        c->read_recorded[c->load_src] = true;
+    }
+    if (frame % (uint64_t)swr_context::PACE_EVERY == 0) {
+        const int k = (int)((frame / (uint64_t)swr_context::PACE_EVERY) % 4);
+        HIP_TRY(c, hipEventRecord(c->pace_ev[k], S));
+        c->pace_frame[k] = frame;
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SWR_OK;
+}
+
+int enqueue_lane_frame(swr_context* c, const DeviceFrame& f, int si, uint64_t frame, const BinChain& bc, hipEvent_t* ev) {
+    hipStream_t S = c->lane_stream[si];
+    const int inj = c->inject.exchange(0, std::memory_order_relaxed);      // swr_debug_fault
+    if (inj == SWR_FAULT_ENQUEUE) return abandon_frame(c, frame, fatal(c, SWR_ERR_HIP, "frame %llu: injected enqueue failure (swr_debug_fault)", (unsigned long long)frame));
+    int rc = inj != SWR_FAULT_LOST_EVENT ? SWR_OK : poll_event(c, c->slot[si].bin_done, "the lane's previous frame (injected: a completion that never arrives)", frame, true);
+    if (!rc) rc = pace_burst(c, frame);
+    if (!rc) rc = wait_for_copies_of(c, c->fb_cur, S);
+    if (rc) return abandon_frame(c, frame, rc);
+    // a load frame: its raster starts after the raster of the frame it loads (the previous one, on another lane); its binning
+    // still overlaps that raster
+    const bool src_wait = (f.flags & SWR_FLAG_LOAD) && c->last_stream && c->last_stream != S;
+    if (src_wait && hipEventRecord(c->src_ready, c->last_stream) != hipSuccess)
+        return abandon_frame(c, frame, fatal(c, SWR_ERR_HIP, "frame %llu: recording the source frame's completion failed", (unsigned long long)frame));
+    if ((rc = enqueue_lane_chain(c, f, si, frame, S, bc, ev, src_wait)))
+        return abandon_frame(c, frame, fatal(c, rc, "enqueueing frame %llu failed: %s", (unsigned long long)frame, c->err.c_str()));
+    c->draw_pending = true;
+    mark_posted(c, frame + 1);
+    c->last_stream = S;
+    c->fb_cur = (c->fb_last + 1) % swr_context::NFB;      // the next frame (another lane) renders into its own buffer
+    return SWR_OK;
+}
+
+// ---- THE TWO-STREAM PIPELINE, and one stream (swr_context::TwoStream) -------------------------------------------------------------
+// What the binning stream's share of a frame needs, by value: a helper thread may enqueue it later.
+struct BinShare {
+    DeviceFrame f; BinChain bc; uint64_t frame; int si;
+    hipStream_t sb;                     // the binning stream
+    bool two_streams, sort_on_raster_stream, slot_wait, paced;
+};
+
+// The binning stream's share of frame b.frame (caller's thread or bin_worker).
+int bin_share(swr_context* c, const BinShare& b) {
+    swr_context::Slot& sl = c->slot[b.si];
+    if (b.slot_wait) {
+        // the first event-carrying raster at or after that frame (RAS_EVERY); its event must have been bound /
+        // recorded (by ras_worker or the caller's thread) before it is polled / waited for
+        const uint64_t prev = b.frame - (uint64_t)swr_context::NSLOT;
+        const uint64_t ef = prev + (uint64_t)(TS::RAS_EVERY - 1) - prev % (uint64_t)TS::RAS_EVERY;
+        { const int rc = wait_counter(c, c->ras_enqueued, ef, "the raster of an earlier frame"); if (rc) return rc; }
+        const TS::RasDone& rd = c->ts.ras_done[ef % (uint64_t)swr_context::NSLOT];
+        if (rd.frame == ef) {
+            if (b.paced) { const int rc = poll_event(c, rd.ev, "k_raster (its working set is needed again)", ef); if (rc) return rc; }
+            else HIP_TRY(c, hipStreamWaitEvent(b.sb, rd.ev, 0));
+        }
+    }
+    // bin_done = the completion of the chain's last kernel itself (bound at launch) where there is one
+    hipEvent_t stop = (b.two_streams && c->ts.bind_events) ? sl.bin_done : nullptr;
+    bool bound;
+    { const int rb = enqueue_binning(c, b.f, b.si, b.sb, b.bc, (b.sort_on_raster_stream || b.f.skip_sort) ? stop : nullptr, &bound); if (rb) return rb; }
+    if (!b.sort_on_raster_stream && !b.f.skip_sort) bound = launch_sort_bins(b.f, b.sb, stop);
+    if (b.two_streams && !bound) HIP_TRY(c, hipEventRecord(sl.bin_done, b.sb));
+    HIP_TRY(c, hipGetLastError());
+    return SWR_OK;
+}
+
+// bin_share as the helpers' job: ANY failure fails the context, and bin_enqueued still advances (the raster share waits on it)
+int bin_job(swr_context* c, const BinShare& b) {
+    int rc = c->failed.load(std::memory_order_acquire);
+    if (!rc) rc = bin_share(c, b);
+    if (rc) {
+        fatal(c, rc, "enqueueing the binning of frame %llu failed: %s", (unsigned long long)b.frame, tl_helper_thread ? "(helper thread)" : c->err.c_str());
+        c->ts.bin_error.store(rc, std::memory_order_relaxed);
+    }
+    c->bin_enqueued.store(b.frame + 1, std::memory_order_release);
+    return rc;
+}
+
+// Binning onto bin_stream, raster onto `stream` (one stream: the same), each share enqueued by a helper thread or by the caller's own.
+int enqueue_two_stream_frame(swr_context* c, Sched sched, const DeviceFrame& f, int si, uint64_t frame, const BinChain& bc, hipEvent_t* ev,
+                             bool sort_on_raster_stream) {
+    TS& ts = c->ts;
+    const bool two = sched == Sched::TwoStream;
+    c->last_stream = c->stream;
+    // this slot's buffers are free again once the raster of NSLOT frames ago has read them (a full sync since then
+    // settles it: every non-pipelined path syncs first)
+    const bool slot_wait = two && frame >= (uint64_t)swr_context::NSLOT && frame - (uint64_t)swr_context::NSLOT >= c->synced_upto;
+    // helpers or the caller's own thread?  (idle context: every earlier frame is complete)
+    const bool streaming = two && (ts.bin_worker || ts.ras_worker) && !(ts.inline_idle && c->synced_upto == c->posted);
+    const bool paced = streaming && ts.ras_worker != nullptr;      // cross-stream order by host polls instead of event waits
+    if (frame >= (uint64_t)TS::RAS_RING) {
+        const int rc = wait_counter(c, c->ras_enqueued, frame - (uint64_t)TS::RAS_RING, "the raster share of an earlier frame");
+        if (rc) { c->frame_no = frame; return or_sticky(c, rc); }     // nothing was posted for this frame
+    }
+    TS::RasJob& rj = ts.ras_job[frame % TS::RAS_RING];
+    rj.f = f; rj.ev3 = ev ? ev[3] : nullptr; rj.ev4 = ev ? ev[4] : nullptr; rj.si = si; rj.sort_here = sort_on_raster_stream;
+    rj.fb = c->fb_cur; rj.paced = paced;
+    c->draw_pending = true;   // the pair total lands in the frame's pinned word (written by the scan)
+    c->posted = frame + 1;
+    const BinShare share{f, bc, frame, si, c->bin_stream, two, sort_on_raster_stream, slot_wait, paced};
+    if (!streaming) {
+        { int rc = bin_share(c, share); if (rc) return rc; }
+        c->bin_enqueued.store(frame + 1, std::memory_order_release);
+        c->hp_lap(2);
+        return flush_raster(c, frame + 1);
+    }
+    // two helpers: one enqueues this frame's binning while the other enqueues the previous frame's raster.  One
+    // helper (sub-contexts of a group: the group's per-device thread is this thread): the binning share runs here.
+    if (ts.bin_worker) ts.bin_worker->post([c, share]() -> int { return bin_job(c, share); });
+    else (void)bin_job(c, share);            // a failure is picked up by the raster share (bin_error) and by the next blocking call
+    c->hp_lap(2);
+    if (ts.ras_worker) {
+        ts.ras_worker->post([c, frame]() -> int { return enqueue_raster_shares(c, frame + 1); });
+        return SWR_OK;
+    }
+    return flush_raster(c, frame);            // frames < frame; this one follows with the next draw / sync / present
+}
+
+// (exact-size bins only: never on the single-launch path) the count matrix of the LDS binning walk, for every lane
+int ensure_bin_matrix(swr_context* c) {
+    const BinPlan plan = plan_binning(c->ni / 3, tiles_of(c->tg), c->dbg_bin_mode == 3);
+    if (!plan.use_lds || c->fixed_mode) return SWR_OK;
+    LaneSizes t;
+    t.add(&swr_context::Slot::bin_matrix, (size_t)plan.G * (size_t)tiles_of(c->tg) * 4);
+    return grow_lanes(c, t);
+}
+
+// Post the frame of the last draw (c->last_draw: swr_draw / swr_draw_list through end_draw, or its redo after an overflow).
 int enqueue_frame(swr_context* c) {
     if (const int f = sticky(c)) return f;      // a failed context posts nothing more
     c->hp_begin();
-    {
-        const BinPlan plan = plan_binning(c->ni / 3, tiles_of(c->tg), c->dbg_bin_mode == 3);
-        if (plan.use_lds && !c->fixed_mode) {      // (exact-size bins only: never on the single-launch path)
-            LaneSizes t;
-            t.add(&swr_context::Slot::bin_matrix, (size_t)plan.G * (size_t)tiles_of(c->tg) * 4);
-            const int rc = grow_lanes(c, t);
-            if (rc) return rc;
-        }
-    }
+    const swr_context::DrawRecord& d = c->last_draw;
+    int rc = ensure_bin_matrix(c);
+    if (rc) return rc;
     c->fb_last = c->fb_cur;
-    if (tiles_of(c->tg) == 0) {
-        // an empty band (a group with more sub-contexts than tile rows hands these out): nothing to bin, raster or copy
-        int rc = flush_raster(c, c->frame_no);
-        if (rc) return rc;
-        fill_word(c, c->frame_no) = 0;
-        c->frame_load[c->frame_no % swr_context::PAIR_RING] = false;     // (no pixels: nothing it could load wrongly)
-        pair_word(c, c->frame_no++) = 0;
-        c->posted = c->frame_no;
-        c->bin_enqueued.store(c->frame_no); c->ras_enqueued.store(c->frame_no);
-        c->draw_pending = true;
-        return SWR_OK;
-    }
-    if (c->last_prim != SWR_PRIMITIVE_TRIANGLE) {
-        // .vertices / .line: three small kernels, no binning; the pair counter reads 0
-        int rc = sync_streams(c);
-        if (rc) return rc;
-        const uint64_t frame = c->frame_no++;
-        DeviceFrame f = make_frame(c, 0, frame, c->last_m, c->last_flags);
-        pair_word(c, frame) = 0;
-        fill_word(c, frame) = 0;
-        c->frame_load[frame % swr_context::PAIR_RING] = (c->last_flags & SWR_FLAG_LOAD) != 0;
-        if ((rc = wait_for_copies_of(c, c->fb_cur, c->stream))) return rc;
-        launch_points_or_lines(f, c->last_prim, c->stream);
-        if ((c->last_flags & SWR_FLAG_LOAD) && lane_mode(c)) {
-            HIP_TRY(c, hipEventRecord(c->read_done[c->load_src], c->stream));
-            c->read_recorded[c->load_src] = true;
-        }
-        HIP_TRY(c, hipGetLastError());
-        c->posted = c->frame_no;
-        c->bin_enqueued.store(c->frame_no); c->ras_enqueued.store(c->frame_no);
-        c->draw_pending = true;
-        c->last_stream = c->stream;
-        if (lane_mode(c)) c->fb_cur = (c->fb_last + 1) % swr_context::NFB;
-        return SWR_OK;
-    }
+    if (tiles_of(c->tg) == 0) return enqueue_empty_frame(c);
+    if (d.prim != SWR_PRIMITIVE_TRIANGLE) return enqueue_points_frame(c, d);
+    const Sched sched = sched_of(c);
     const uint64_t frame = c->frame_no++;
     c->frame_presented[frame % swr_context::PAIR_RING] = false;
-    const bool load = (c->last_flags & SWR_FLAG_LOAD) != 0;
-    c->frame_load[frame % swr_context::PAIR_RING] = load;
-    const int si = (int)(frame % swr_context::NSLOT);
-    c->last_slot = si;
-    DeviceFrame f = make_frame(c, si, frame, c->last_m, c->last_flags);
+    c->frame_load[frame % swr_context::PAIR_RING] = (d.flags & SWR_FLAG_LOAD) != 0;
+    const int si = c->last_slot = (int)(frame % swr_context::NSLOT);
+    DeviceFrame f = make_frame(c, si, frame, d);
     BinChain bc;
-    if (c->last_list) {
-        make_list_frame(c, si, f);
-        const int rc = stage_list(c, si, frame, bc.lp);
-        if (rc) { c->frame_no = frame; return rc; }
+    if (d.is_list) {
+        make_list_frame(c, si, d, f);
+        if ((rc = stage_list(c, si, frame, bc.lp))) { c->frame_no = frame; return rc; }
     }
     c->h_clip[frame % swr_context::PAIR_RING] = 0u;
-    if (c->last_clip) make_clip_frame(c, si, frame, f);
+    if (d.clip) make_clip_frame(c, si, frame, d, f);
     hipEvent_t* ev = nullptr;
-    if (c->timing >= 2 || (c->timing == 1 && (c->frame_no % (uint64_t)c->timing_every) == 0)) {
-        if (c->seq - c->harvested >= (uint64_t)swr_context::RING) {   // ring full: drain it
-            int rc = sync_streams(c);
-            if (rc) return rc;
-            harvest(c);
-        }
-        ev = c->ev[c->seq % swr_context::RING];
-        c->ev_level[c->seq % swr_context::RING] = c->timing;
-        c->seq++;
-    }
-    hipStream_t sb = c->bin_stream, sr = c->stream;
+    if ((rc = claim_timing_events(c, &ev))) return rc;
     c->hp_lap(0);
-    // Where k_sort_bins runs.  On the binning stream it is part of the chain that runs ahead of the raster; on
-    // the raster stream (right before k_raster) the binning stream is free one kernel earlier.  Alternating A/B on
-    // one box (tools/ab_sort_stream.py, tools/bt_bands.sh; untimed frames of cfg4, us per frame):
-    //   whole 4K frame (4 080 tiles): 112 vs 122 -> binning stream;  half / quarter / eighth bands: 83 / 59 / 41
-    //   vs 73 / 49 / 40 -> raster stream;  light frames (cfg2, 6 k triangles): 37 vs 43 -> binning stream.
-    // -DSWR_TUNE_SORT_STREAM=0/1 forces either.
-#ifndef SWR_TUNE_SORT_STREAM
-#define SWR_TUNE_SORT_STREAM (-1)     // 0 / 1: k_sort_bins always on the binning / raster stream (tuning builds)
-#endif
-#ifndef SWR_TUNE_SORT_SPARSE
-#define SWR_TUNE_SORT_SPARSE 0        // 1: launch k_sort_bins on sparse frames too
-#endif
-    constexpr int sort_stream_mode = SWR_TUNE_SORT_STREAM;
-    const bool sort_on_raster_stream = sort_stream_mode >= 0 ? sort_stream_mode == 1
-                                                            : (sb != sr && f.ntri >= 200000 && tiles_of(c->tg) < 3000);
-    // Sparse frames need no k_sort_bins: when the fullest bin of the latest binned frame (a pinned word k_fill_lds
-    // overwrites every frame; 0xFFFFFFFF after a new scene or target) fits two chunks, every tile of THIS frame is
-    // expected to be walked by all four waves together (row-split mode), where the order inside the bin does not
-    // matter — k_raster masks the class tags itself.  A wrong guess costs time, never pixels.  (cfg5: 0.321 -> 0.313 ms,
-    // the app's sphere 18.6 -> 17.1 us; -DSWR_TUNE_SORT_SPARSE=1 sorts always.)
-    constexpr bool sort_sparse = SWR_TUNE_SORT_SPARSE != 0;
-    // (a word the GPU overwrites while frames are in flight: read it as what it is, a relaxed atomic)
-    const uint32_t fullest = __atomic_load_n(&c->h_pairs[swr_context::PAIR_RING], __ATOMIC_RELAXED);
-    if (!sort_sparse && sort_stream_mode < 0 && fullest <= 128u) f.skip_sort = 1;
-    // bit 31 of that word: the latest rastered frame met triangles that cover hundreds of tiles — this frame's k_bin puts them on
-    // the deferred list and k_sort_bins appends them per tile (swr_kernels.hip, BIN_BIG_TILES); 0xFFFFFFFF = nothing known yet
-    f.defer_big = (fullest != 0xFFFFFFFFu && (fullest & 0x80000000u)) ? 1 : 0;
-    // a blend frame orders its bins itself (k_blend_order strips the class tags): no k_sort_bins, so nothing is deferred to it
-    if (f.flags & SWR_FLAG_BLEND) { f.skip_sort = 1; f.defer_big = 0; }
-    // 32-bit depth keys: one tile in REDO_SAMPLE (8) reports when it had to be rastered again (~6x the time of a tile that did
-    // not); from 2 % of the tiles on the 64-bit kernel is the cheaper one for this scene
-    if (f.k32) {
-        const uint32_t redo = __atomic_load_n(&c->h_pairs[2 * swr_context::PAIR_RING + 1], __ATOMIC_RELAXED);
-        if ((uint64_t)redo * 8u * 50u > (uint64_t)tiles_of(c->tg)) { c->k32_ok = false; f.k32 = 0; }
-    }
-    // ... and on a small grid (a thin band: the frame is bound by its kernel chain, not by the chip) such a frame sorts its bins
-    // inside the raster workgroups, in the LDS the narrow keys leave free: no k_sort_bins launch — unless the frame defers
-    // triangles that cover hundreds of tiles, which k_sort_bins appends to the bins.  On a grid that fills the chip the launch
-    // is the cheaper place for the sort (swr_kernels.hip, raster_tile; profiles/r04/insort_ab.txt).
-    // (swr_debug_set SWR_DEBUG_RASTER_SORT: 0 never, 1 by grid size, 2 always)
-    const bool insort_grid = c->dbg_insort == 2 || (c->dbg_insort == 1 && tiles_of(c->tg) <= 1536);
-    if (insort_grid && frame_uses_k32(f) && !f.defer_big && !f.skip_sort && sort_stream_mode < 0) { f.insort = 1; f.skip_sort = 1; }
-    const bool all = c->timing >= 2;
-    if (f.ntri <= 0) { int rc = sync_streams(c); if (rc) return rc; pair_word(c, frame) = 0; }
+    const bool sort_on_raster_stream = settle_policy(c, sched, f);
+    if (f.ntri <= 0) { if ((rc = sync_streams(c))) return rc; pair_word(c, frame) = 0; }
     if (!f.fixed_bins) fill_word(c, frame) = 0;
-    // fixed-stride bins: this frame's fill block must be zero when k_bin starts (the k_bin before it did that, unless that
-    // frame took another path); k_bin leaves it dirty and zeroes the next frame's
-    const bool lanes = lane_mode(c);
-    if (f.fixed_bins && lanes) {
-        const int par = (int)((frame / (uint64_t)swr_context::NSLOT) & 1u);
-        bc.fill_memset = c->lanefill_dirty[si][par];
-        c->lanefill_dirty[si][par] = true;
-        c->lanefill_dirty[si][par ^ 1] = false;
-    } else if (f.fixed_bins) {
-        const int fbk = (int)(frame % swr_context::NFILL);
-        bc.fill_memset = c->fill_dirty[fbk];
-        c->fill_dirty[fbk] = true;
-        c->fill_dirty[(fbk + 1) % swr_context::NFILL] = false;
-    }
+    else bc.fill_memset = claim_fill_block(c, sched, si, frame);
     bc.zero_tables = !f.fixed_bins && (!f.plan.use_lds || f.ntri <= 0);
     bc.zero_bytes = (size_t)(CNT_WORDS + 3 * tiles_of(c->tg) + 1) * 4;
-    if (ev && all) { bc.e0 = ev[0]; bc.e1 = ev[1]; bc.e2 = ev[2]; }
-    if (lanes) {
-        // ---- FRAME LANES: the whole frame, binning and raster, back to back on the lane's stream (see swr_context::lane_stream)
-        hipStream_t S = c->lane_stream[si];
-        const int inj = c->inject.exchange(0, std::memory_order_relaxed);      // swr_debug_fault
-        auto fail_frame = [&](int rc) {      // nothing was enqueued for this frame: the context has failed (fatal) or the call reports
-            c->posted = frame + 1;
-            c->bin_enqueued.store(frame + 1, std::memory_order_release);
-            c->ras_enqueued.store(frame + 1, std::memory_order_release);
-            return rc;
-        };
-        if (inj == SWR_FAULT_ENQUEUE) return fail_frame(fatal(c, SWR_ERR_HIP, "frame %llu: injected enqueue failure (swr_debug_fault)", (unsigned long long)frame));
-        if (inj == SWR_FAULT_LOST_EVENT) {
-            const int rc = poll_event(c, c->slot[si].bin_done, "the lane's previous frame (injected: a completion that never arrives)", frame, true);
-            if (rc) return fail_frame(rc);
-        }
-        // an un-waited burst is paced by markers: at most ~4 * PACE_EVERY frames in flight
-        if (frame % (uint64_t)swr_context::PACE_EVERY == 0) {
-            const uint64_t old = frame - 3 * (uint64_t)swr_context::PACE_EVERY;
-            const int k = (int)((frame / (uint64_t)swr_context::PACE_EVERY) % 4);
-            const int ko = (k + 1) % 4;          // (k - 3) mod 4
-            if (frame >= 3 * (uint64_t)swr_context::PACE_EVERY && c->pace_frame[ko] == old && old >= c->synced_upto) {
-                const int rc = poll_event(c, c->pace_ev[ko], "an earlier frame of the burst", old);
-                if (rc) return fail_frame(rc);
-            }
-        }
-        int rc = wait_for_copies_of(c, c->fb_cur, S);
-        if (rc) return fail_frame(rc);
-        // a load frame: its raster starts after the raster of the frame it loads (the previous one, on another lane); its binning
-        // still overlaps that raster
-        const bool src_wait = load && c->last_stream && c->last_stream != S;
-        if (src_wait && hipEventRecord(c->src_ready, c->last_stream) != hipSuccess)
-            return fail_frame(fatal(c, SWR_ERR_HIP, "frame %llu: recording the source frame's completion failed", (unsigned long long)frame));
-        auto enq = [&]() -> int {
-            bool bound;
-            { const int rb = enqueue_binning(c, f, si, S, bc, nullptr, &bound); if (rb) return rb; }
-            if (!f.skip_sort) launch_sort_bins(f, S, nullptr);
-            if (src_wait) HIP_TRY(c, hipStreamWaitEvent(S, c->src_ready, 0));
-            if (ev) HIP_TRY(c, hipEventRecord(ev[3], S));
-            launch_raster(f, S, nullptr);
-            if (ev) HIP_TRY(c, hipEventRecord(ev[4], S));
-            if (load) {
-                HIP_TRY(c, hipEventRecord(c->read_done[c->load_src], S));
-                c->read_recorded[c->load_src] = true;
-            }
-            if (frame % (uint64_t)swr_context::PACE_EVERY == 0) {
-                const int k = (int)((frame / (uint64_t)swr_context::PACE_EVERY) % 4);
-                HIP_TRY(c, hipEventRecord(c->pace_ev[k], S));
-                c->pace_frame[k] = frame;
-            }
-            HIP_TRY(c, hipGetLastError());
-            return SWR_OK;
-        };
-        rc = enq();
-        if (rc) return fail_frame(fatal(c, rc, "enqueueing frame %llu failed: %s", (unsigned long long)frame, c->err.c_str()));
-        c->draw_pending = true;
-        c->posted = frame + 1;
-        c->bin_enqueued.store(frame + 1, std::memory_order_release);
-        c->ras_enqueued.store(frame + 1, std::memory_order_release);
-        c->last_stream = S;
-        c->fb_cur = (c->fb_last + 1) % swr_context::NFB;      // the next frame (another lane) renders into its own buffer
-        return SWR_OK;
-    }
-    c->last_stream = sr;
-    // ---- the binning stream's share of the frame ----
-    // this slot's buffers are free again once the raster of NSLOT frames ago has read them (a full sync since then
-    // settles it: every non-pipelined path syncs first)
-    const bool slot_wait = sb != sr && frame >= (uint64_t)swr_context::NSLOT && frame - (uint64_t)swr_context::NSLOT >= c->synced_upto;
-    // helpers or the caller's own thread?  (idle context: every earlier frame is complete)
-    const bool streaming = sb != sr && (c->bin_worker || c->ras_worker) && !(c->inline_idle && c->synced_upto == c->posted);
-    const bool paced = streaming && c->ras_worker != nullptr;      // cross-stream order by host polls instead of event waits
-    auto bin_share = [c, f, si, sb, sr, frame, bc, sort_on_raster_stream, slot_wait, paced]() -> int {
-        swr_context::Slot& sl = c->slot[si];
-        if (slot_wait) {
-            // the first event-carrying raster at or after that frame (RAS_EVERY); its event must have been bound /
-            // recorded (by ras_worker or the caller's thread) before it is polled / waited for
-            const uint64_t prev = frame - (uint64_t)swr_context::NSLOT;
-            const uint64_t ef = prev + (uint64_t)(swr_context::RAS_EVERY - 1) - prev % (uint64_t)swr_context::RAS_EVERY;
-            { const int rc = wait_counter(c, c->ras_enqueued, ef, "the raster of an earlier frame"); if (rc) return rc; }
-            swr_context::Slot& es = c->slot[ef % (uint64_t)swr_context::NSLOT];
-            if (es.ras_event_frame == ef) {
-                if (paced) { const int rc = poll_event(c, es.ras_done, "k_raster (its working set is needed again)", ef); if (rc) return rc; }
-                else HIP_TRY(c, hipStreamWaitEvent(sb, es.ras_done, 0));
-            }
-        }
-        // bin_done = the completion of the chain's last kernel itself (bound at launch) where there is one
-        hipEvent_t stop = (sb != sr && c->bind_events) ? sl.bin_done : nullptr;
-        bool bound;
-        { const int rb = enqueue_binning(c, f, si, sb, bc, (sort_on_raster_stream || f.skip_sort) ? stop : nullptr, &bound); if (rb) return rb; }
-        if (!sort_on_raster_stream && !f.skip_sort) bound = launch_sort_bins(f, sb, stop);
-        if (sb != sr && !bound) HIP_TRY(c, hipEventRecord(sl.bin_done, sb));
-        HIP_TRY(c, hipGetLastError());
-        return SWR_OK;
-    };
-    if (frame >= (uint64_t)swr_context::RAS_RING) {
-        const int rc = wait_counter(c, c->ras_enqueued, frame - (uint64_t)swr_context::RAS_RING, "the raster share of an earlier frame");
-        if (rc) { c->frame_no = frame; return or_sticky(c, rc); }     // nothing was posted for this frame
-    }
-    swr_context::RasJob& rj = c->ras_job[frame % swr_context::RAS_RING];
-    rj.f = f; rj.ev3 = ev ? ev[3] : nullptr; rj.ev4 = ev ? ev[4] : nullptr; rj.si = si; rj.sort_here = sort_on_raster_stream;
-    rj.fb = c->fb_cur;
-    rj.paced = paced;
-    c->draw_pending = true;   // the pair total lands in the frame's pinned word (written by the scan)
-    c->posted = frame + 1;
-    if (streaming) {
-        // two helpers: one enqueues this frame's binning while the other enqueues the previous frame's raster.  One
-        // helper (sub-contexts of a group: the group's per-device thread is this thread): the binning share runs here.
-        auto bin_job = [c, bin_share, frame]() -> int {
-            int rc = c->failed.load(std::memory_order_acquire);
-            if (!rc) rc = bin_share();
-            if (rc) {
-                fatal(c, rc, "enqueueing the binning of frame %llu failed: %s", (unsigned long long)frame, tl_helper_thread ? "(helper thread)" : c->err.c_str());
-                c->bin_error.store(rc, std::memory_order_relaxed);
-            }
-            c->bin_enqueued.store(frame + 1, std::memory_order_release);
-            return rc;
-        };
-        if (c->bin_worker) c->bin_worker->post(bin_job);
-        else (void)bin_job();                    // a failure is picked up by the raster share (bin_error) and by the next blocking call
-        c->hp_lap(2);
-        if (c->ras_worker) {
-            c->ras_worker->post([c, frame]() -> int { return enqueue_raster_shares(c, frame + 1); });
-            return SWR_OK;
-        }
-        return flush_raster(c, frame);            // frames < frame; this one follows with the next draw / sync / present
-    }
-    { int rc = bin_share(); if (rc) return rc; }
-    c->bin_enqueued.store(frame + 1, std::memory_order_release);
-    c->hp_lap(2);
-    return flush_raster(c, frame + 1);
+    if (ev && c->timing >= 2) { bc.e0 = ev[0]; bc.e1 = ev[1]; bc.e2 = ev[2]; }
+    if (sched == Sched::Lanes) return enqueue_lane_frame(c, f, si, frame, bc, ev);
+    return enqueue_two_stream_frame(c, sched, f, si, frame, bc, ev, sort_on_raster_stream);
 }
 
 // Every frame below `upto` has its raster share on the raster stream when this returns.
 int flush_raster(swr_context* c, uint64_t upto) {
-    if (c->ras_worker) {                                  // every posted share (and present) has been enqueued
-        const int rc = c->ras_worker->drain();
+    if (c->ts.ras_worker) {                                  // every posted share (and present) has been enqueued
+        const int rc = c->ts.ras_worker->drain();
         if (rc) return rc;
     }
     return enqueue_raster_shares(c, std::min(upto, c->posted));   // frames of the one-stream path (never posted)
@@ -1311,34 +1309,31 @@ int flush_raster(swr_context* c, uint64_t upto) {
 // The raster stream's share of frame g (caller's thread or ras_worker).
 int raster_share(swr_context* c, uint64_t g) {
     { const int rc = wait_counter(c, c->bin_enqueued, g, "the binning share"); if (rc) return rc; }
-    if (c->bin_error.load(std::memory_order_relaxed)) {
-        const int rc = c->bin_error.exchange(0);
+    if (c->ts.bin_error.load(std::memory_order_relaxed)) {
+        const int rc = c->ts.bin_error.exchange(0);
         return rc ? rc : SWR_ERR_HIP;          // the text was recorded by the thread that failed
     }
-    swr_context::RasJob& rj = c->ras_job[g % swr_context::RAS_RING];
+    TS::RasJob& rj = c->ts.ras_job[g % TS::RAS_RING];
     swr_context::Slot& sl = c->slot[rj.si];
-    hipStream_t sb = c->bin_stream, sr = c->stream;
+    TS::RasDone& rd = c->ts.ras_done[rj.si];
+    hipStream_t sr = c->stream;
+    const bool two = sched_of(c) != Sched::OneStream;      // (never Lanes: a lane frame has no raster share)
     const int inj = c->inject.exchange(0, std::memory_order_relaxed);      // swr_debug_fault
     if (inj == SWR_FAULT_ENQUEUE) return fatal(c, SWR_ERR_HIP, "frame %llu: injected enqueue failure (swr_debug_fault)", (unsigned long long)g);
     c->hp_begin_r();
-    if (sb != sr) {
-        if (rj.paced || inj == SWR_FAULT_LOST_EVENT) {
-            const int rc = poll_event(c, sl.bin_done, "the binning (k_bin / k_sort_bins)", g, inj == SWR_FAULT_LOST_EVENT);
-            if (rc) return rc;
-        } else HIP_TRY(c, hipStreamWaitEvent(sr, sl.bin_done, 0));
-    } else if (inj == SWR_FAULT_LOST_EVENT) {
-        const int rc = poll_event(c, sl.bin_done, "the binning (k_bin / k_sort_bins)", g, true);
+    if ((two && rj.paced) || inj == SWR_FAULT_LOST_EVENT) {
+        const int rc = poll_event(c, sl.bin_done, "the binning (k_bin / k_sort_bins)", g, inj == SWR_FAULT_LOST_EVENT);
         if (rc) return rc;
-    }
+    } else if (two) HIP_TRY(c, hipStreamWaitEvent(sr, sl.bin_done, 0));
     c->hp_lap_r(3);
     { int rc = wait_for_copies_of(c, rj.fb, sr); if (rc) return rc; }
     if (rj.sort_here) launch_sort_bins(rj.f, sr);
     if (rj.ev3) HIP_TRY(c, hipEventRecord(rj.ev3, sr));
-    const bool carries = sb != sr && g % (uint64_t)swr_context::RAS_EVERY == (uint64_t)(swr_context::RAS_EVERY - 1);
-    const bool bound = launch_raster(rj.f, sr, (carries && c->bind_events) ? sl.ras_done : nullptr);
+    const bool carries = two && g % (uint64_t)TS::RAS_EVERY == (uint64_t)(TS::RAS_EVERY - 1);
+    const bool bound = launch_raster(rj.f, sr, (carries && c->ts.bind_events) ? rd.ev : nullptr);
     if (rj.ev4) HIP_TRY(c, hipEventRecord(rj.ev4, sr));
     c->hp_lap_r(4);
-    if (carries) { if (!bound) HIP_TRY(c, hipEventRecord(sl.ras_done, sr)); sl.ras_event_frame = g; }
+    if (carries) { if (!bound) HIP_TRY(c, hipEventRecord(rd.ev, sr)); rd.frame = g; }
     c->hp_lap_r(5);
     c->hp_frames++;
     HIP_TRY(c, hipGetLastError());
@@ -1430,6 +1425,9 @@ int copy_band(swr_context* c, int fb, int img, const void* src_band, size_t row,
 int check_frames(swr_context* c);
 int enqueue_present(swr_context* c, void* color_full, float* depth_full);
 
+#ifndef SWR_TUNE_ONESHOT_CUTS
+#define SWR_TUNE_ONESHOT_CUTS {70, 100}   // single_scene_upload: where a one-shot scene's index array is cut, per cent of the primitives
+#endif
 // oneshot: the scene is uploaded for ONE frame (swr_render without a scene identity, the reference's calling pattern):
 // the triangle stream keeps index order — the Morton sort costs more than it saves a single frame (cfg4: build 0.49 ->
 // 0.23 ms, the frame 0.154 -> 0.177 ms) — and it is built chunk by chunk behind the copy of the index array.
@@ -1445,7 +1443,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     c->has_scene = false;
     c->has_attrs = false;
     c->draw_pending = false;
-    c->last_list = false;
+    c->last_draw.is_list = false;
     c->cuts.clear();                 // a new stream is one segment
     c->list_plan_max = 0;
     c->present_pending = false;
@@ -1495,9 +1493,6 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     if (chunked) {
         // two chunks, the second one small: every extra copy call from pageable memory costs the link ~30 us, the last
         // chunk's build is the tail (cfg4, whole call: {100} 3.10 ms, {70,100} 3.06, {50,82,100} 3.07, four quarters 3.12)
-#ifndef SWR_TUNE_ONESHOT_CUTS
-#define SWR_TUNE_ONESHOT_CUTS {70, 100}
-#endif
         constexpr int cuts[] = SWR_TUNE_ONESHOT_CUTS;          // per cent of the primitives
         if (!c->up_chunk_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->up_chunk_ev, hipEventDisableTiming));
         HIP_TRY(c, hipEventRecord(c->up_chunk_ev, c->stream));           // (vertices resident, counter words zero)
@@ -1726,13 +1721,10 @@ int end_draw(swr_context* c, uint32_t flags, int32_t primitive_type, bool list, 
         }
     }
     c->src_clear = false;
-    c->last_flags = flags;
-    c->last_blend = c->blend;
     c->ids_valid = (flags & SWR_FLAG_PRIMITIVE_IDS) != 0;
-    c->last_prim = primitive_type;
-    c->last_list = list;
-    c->last_clip = (flags & SWR_FLAG_DEPTH_CLIP) != 0;
-    c->last_persp = persp;
+    swr_context::DrawRecord& d = c->last_draw;
+    d.flags = flags; d.blend = c->blend; d.prim = primitive_type;
+    d.is_list = list; d.clip = (flags & SWR_FLAG_DEPTH_CLIP) != 0; d.persp = persp;
     return enqueue_frame(c);
 }
 
@@ -1752,7 +1744,7 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
     if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, c->ni / 3, flags, transform))) return rc;
     const bool persp = persp_frame(flags, primitive_type, affine_transform(transform));
     if (persp && (rc = ensure_persp(c, (flags & SWR_FLAG_DEPTH_CLIP) ? clip_slots(c) : c->ni / 3))) return rc;
-    memcpy(c->last_m, transform, sizeof c->last_m);
+    memcpy(c->last_draw.m, transform, sizeof c->last_draw.m);
     return end_draw(c, flags, primitive_type, false, persp);
 }
 
@@ -1866,11 +1858,9 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
     if ((flags & SWR_FLAG_DEPTH_CLIP) && (rc = prepare_clip(c, tris, flags, nullptr))) return rc;
     const bool persp = persp_frame(flags, SWR_PRIMITIVE_TRIANGLE, affine);
     if (persp && (rc = ensure_persp(c, (flags & SWR_FLAG_DEPTH_CLIP) ? clip_slots(c) : tris))) return rc;
-    c->list.swap(list);
-    c->list_tris = tris;
-    c->list_units = units;
-    c->list_affine = affine;
-    c->list_identity = identity;
+    c->last_draw.list.swap(list);
+    c->last_draw.list_tris = tris; c->last_draw.list_units = units;
+    c->last_draw.list_affine = affine; c->last_draw.list_identity = identity;
     return end_draw(c, flags, SWR_PRIMITIVE_TRIANGLE, true, persp);
 }
 
@@ -1878,7 +1868,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
 int enqueue_present(swr_context* c, void* color_full, float* depth_full) {
     const int fb = c->fb_last;
     if (tiles_of(c->tg) == 0) return SWR_OK;
-    const bool want_color = color_full && !(c->last_flags & SWR_FLAG_NO_COLOR);
+    const bool want_color = color_full && !(c->last_draw.flags & SWR_FLAG_NO_COLOR);
     const uint64_t frame = c->frame_no ? c->frame_no - 1 : 0;      // the frame being presented (for messages)
     hipStream_t fs = c->last_stream ? c->last_stream : c->stream;        // the stream that carries the frame's raster
     auto copies = [c, fb, want_color, color_full, depth_full, frame, fs]() -> int {
@@ -1889,19 +1879,14 @@ int enqueue_present(swr_context* c, void* color_full, float* depth_full) {
         if (depth_full && (rc = copy_band(c, fb, 1, fb_image(c, fb, 1), row, c->tg.row_begin, c->tg.row_end, depth_full, frame))) return rc;
         return SWR_OK;
     };
-    if (lane_mode(c)) {
-        // frame lanes: the frame is on its stream already, and the next draw went (or goes) to another buffer anyway
-        int rc = flush_raster(c, c->frame_no);
-        if (rc || (rc = copies())) return rc;
-        if (c->frame_no) c->frame_presented[(c->frame_no - 1) % swr_context::PAIR_RING] = true;
-        return SWR_OK;
-    }
-    if (c->ras_worker) c->ras_worker->post(copies);   // behind the frame's raster share, in order
+    // frame lanes: the frame is on its stream already, and the next draw went (or goes) to another buffer anyway
+    const bool lanes = sched_of(c) == Sched::Lanes;
+    if (!lanes && c->ts.ras_worker) c->ts.ras_worker->post(copies);   // behind the frame's raster share, in order
     else {
         int rc = flush_raster(c, c->frame_no);        // the frame being presented must be on the raster stream
         if (rc || (rc = copies())) return rc;
     }
-    c->fb_cur = fb == 0 ? 1 : 0;     // the next frame renders into the other framebuffer while this one is being copied
+    if (!lanes) c->fb_cur = fb == 0 ? 1 : 0;     // the next frame renders into the other framebuffer while this one is being copied
     if (c->frame_no) c->frame_presented[(c->frame_no - 1) % swr_context::PAIR_RING] = true;
     return SWR_OK;
 }
@@ -1988,10 +1973,10 @@ int check_frames(swr_context* c) {
         if (clip_need) {
             // more crossing triangles than the fan capacity: grow it (every stream is idle), the redraw below takes the new slots
             if ((rc = sync_copies(c))) return rc;
-            const int64_t extra = (int64_t)clip_need - c->clip_n;
+            const int64_t extra = (int64_t)clip_need - c->last_draw.clip_n;
             c->clip_fan = std::max<int64_t>(2 * c->clip_fan, (extra + 1) / 2 + extra / 8 + 64);
-            if (c->last_clip && (rc = prepare_clip(c, c->clip_n, c->last_flags, nullptr))) return rc;
-            if (c->last_clip && c->last_persp && (rc = ensure_persp(c, clip_slots(c)))) return rc;
+            if (c->last_draw.clip && (rc = prepare_clip(c, c->last_draw.clip_n, c->last_draw.flags, nullptr))) return rc;
+            if (c->last_draw.clip && c->last_draw.persp && (rc = ensure_persp(c, clip_slots(c)))) return rc;
         }
         if (c->frame_load[L % swr_context::PAIR_RING] && c->src_bad) {
             // the last frame loaded a wrong image: a redraw cannot repair it — reported (whether it was copied or not: it is what the
@@ -2011,7 +1996,7 @@ int check_frames(swr_context* c) {
             c->frames_checked = c->frame_no;
             c->last.tile_pairs = pair_word(c, L);
             c->last.tiles = tiles_of(c->tg);
-            c->last.triangles = c->last_list ? c->list_tris : c->ni / 3;
+            c->last.triangles = c->last_draw.is_list ? c->last_draw.list_tris : c->ni / 3;
             return finish();
         }
         // the last frame overflowed: redraw it into the same framebuffer, copy it again
@@ -2172,7 +2157,7 @@ int single_count_ids(swr_context* c, swr_id_count q, const uint32_t* counts, int
         return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: the last frame was drawn without SWR_FLAG_PRIMITIVE_IDS, or swr_target_set / "
                     "swr_target_write came after it");
     const bool per_item = q.group == SWR_COUNT_PER_ITEM;
-    const int64_t need = per_item ? (c->last_list ? (int64_t)c->list.size() : 1) : (c->last_list ? c->list_tris : c->ni / 3);
+    const int64_t need = per_item ? (c->last_draw.is_list ? (int64_t)c->last_draw.list.size() : 1) : (c->last_draw.is_list ? c->last_draw.list_tris : c->ni / 3);
     if (n != need)
         return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: n is %lld, but the last frame has %lld %s", (long long)n, (long long)need,
                     per_item ? "draw items" : "primitives");
@@ -2190,7 +2175,7 @@ int single_count_ids(swr_context* c, swr_id_count q, const uint32_t* counts, int
     if ((rc = ensure(c, c->count_dev, words * 4))) return rc;
     if (!launch_count_ids) return fail(c, SWR_ERR_HIP, "this build has no k_count_ids: there is no fallback for the visibility counts");
     HIP_TRY(c, hipMemsetAsync(c->count_dev.p, 0, words * 4, c->stream));
-    const ListItem* items = (per_item && c->last_list) ? (const ListItem*)c->slot[c->last_slot].items.p : nullptr;
+    const ListItem* items = (per_item && c->last_draw.is_list) ? (const ListItem*)c->slot[c->last_slot].items.p : nullptr;
     launch_count_ids((const uint32_t*)c->ids[c->fb_last].p, c->tg.width, q.x0, q.x1, y0 - c->tg.row_begin, y1 - c->tg.row_begin,
                      per_item ? 1 : 0, items, (uint32_t*)c->count_dev.p, n, c->stream);
     HIP_TRY(c, hipGetLastError());
@@ -2275,8 +2260,8 @@ int single_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, co
 void destroy_single(swr_context* c) {
     hipSetDevice(c->device);
     // helper jobs are bounded (every wait in them is) and give up at once on a failed context: the drains return
-    if (c->ras_worker) { c->ras_worker->drain(); c->ras_worker->stop(); delete c->ras_worker; c->ras_worker = nullptr; }
-    if (c->bin_worker) { c->bin_worker->drain(); c->bin_worker->stop(); delete c->bin_worker; c->bin_worker = nullptr; }
+    if (c->ts.ras_worker) { c->ts.ras_worker->drain(); c->ts.ras_worker->stop(); delete c->ts.ras_worker; c->ts.ras_worker = nullptr; }
+    if (c->ts.bin_worker) { c->ts.bin_worker->drain(); c->ts.bin_worker->stop(); delete c->ts.bin_worker; c->ts.bin_worker = nullptr; }
     // bounded too: a GPU that never finishes must not hang the destructor (what it still owns is then leaked)
     c->wait_budget_ms = std::min<uint32_t>(c->wait_budget_ms, 5000u);
     auto drain = [c](hipStream_t st) {           // (looks at the stream, not at the failed flag: the GPU may be fine)
@@ -2310,10 +2295,11 @@ void destroy_single(swr_context* c) {
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->ids) if (b.p) hipFree(b.p);
-    for (DevBuf& b : c->fillbuf) if (b.p) hipFree(b.p);
+    for (DevBuf& b : c->ts.fillbuf) if (b.p) hipFree(b.p);
     for (auto& lf : c->lanefill) for (DevBuf& b : lf) if (b.p) hipFree(b.p);
     for (hipStream_t ls : c->lane_stream) if (ls) hipStreamDestroy(ls);
     for (hipEvent_t e : c->pace_ev) if (e) hipEventDestroy(e);
+    for (auto& rd : c->ts.ras_done) if (rd.ev) hipEventDestroy(rd.ev);
     for (auto& sl : c->slot) {
         DevBuf* sb[] = {&sl.geo, &sl.geo_full, &sl.ranges, &sl.bins, &sl.bin_matrix, &sl.live, &sl.tilebuf, &sl.biglist,
                         &sl.items, &sl.lrgb, &sl.lnrm, &sl.linv, &sl.cxyz, &sl.crgb, &sl.cnrm, &sl.cmap, &sl.cbox,
@@ -2322,7 +2308,6 @@ void destroy_single(swr_context* c) {
         if (sl.items_host) hipHostFree(sl.items_host);
         if (sl.items_copied) hipEventDestroy(sl.items_copied);
         if (sl.bin_done) hipEventDestroy(sl.bin_done);
-        if (sl.ras_done) hipEventDestroy(sl.ras_done);
     }
     for (int i = 0; i < swr_context::NFB; i++) {
         if (c->frame_done[i]) hipEventDestroy(c->frame_done[i]);
@@ -2390,15 +2375,15 @@ int create_single(int dev, swr_context** out, int helpers, uint32_t wait_budget_
             // SWR_HOST_THREADS=1: enqueue everything from the caller's thread (no helper)
             const char* ht = getenv("SWR_HOST_THREADS");
             if (ht && ht[0] == '1') helpers = 0;
-            { const char* be = getenv("SWR_BIND_EVENTS"); c->bind_events = !(be && be[0] == '0'); }
-            { const char* ii = getenv("SWR_INLINE_IDLE"); c->inline_idle = !(ii && ii[0] == '0'); }
+            { const char* be = getenv("SWR_BIND_EVENTS"); c->ts.bind_events = !(be && be[0] == '0'); }
+            { const char* ii = getenv("SWR_INLINE_IDLE"); c->ts.inline_idle = !(ii && ii[0] == '0'); }
             const char* ew = getenv("SWR_EVENT_WAITS");     // =1: no raster helper; the caller's thread orders the streams by event waits
-            if (c->bin_stream_own && helpers >= 2) { c->bin_worker = new Worker(); c->bin_worker->start(dev, true); }
-            if (c->bin_stream_own && helpers >= 1 && !(ew && ew[0] == '1')) { c->ras_worker = new Worker(); c->ras_worker->start(dev, true); }
+            if (c->bin_stream_own && helpers >= 2) { c->ts.bin_worker = new Worker(); c->ts.bin_worker->start(dev, true); }
+            if (c->bin_stream_own && helpers >= 1 && !(ew && ew[0] == '1')) { c->ts.ras_worker = new Worker(); c->ts.ras_worker->start(dev, true); }
         }
-        for (auto& sl : c->slot) {
-            hipEventCreateWithFlags(&sl.bin_done, hipEventDisableTiming);
-            hipEventCreateWithFlags(&sl.ras_done, hipEventDisableTiming);
+        for (int k = 0; k < swr_context::NSLOT; k++) {
+            hipEventCreateWithFlags(&c->slot[k].bin_done, hipEventDisableTiming);
+            hipEventCreateWithFlags(&c->ts.ras_done[k].ev, hipEventDisableTiming);
         }
         for (int i = 0; i < swr_context::NFB; i++) {
             hipEventCreateWithFlags(&c->frame_done[i], hipEventDisableTiming);
