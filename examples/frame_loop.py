@@ -7,7 +7,7 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion] [--delta]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
@@ -18,6 +18,9 @@ pixels every copy covers, counted on the device (swr_count_ids: only the counts 
 --occlusion (with --objects N and --depth-test) tests every copy's screen rectangle and nearest depth against the depth image of the
 previous frame before the next one is drawn, on the device (swr_query_depth: only one count per copy crosses to the host, not the
 depth image), and prints how many copies could be skipped because nothing of them would pass the z-test.
+--delta runs the host-visible loop the way the app calls it — one swr_render per frame, the same mesh, a new transform, the same two host
+images — through swr_render_delta: the device compares every frame with what the host images already hold, tile by tile, and only the
+rectangle around the tiles that changed crosses to the host.  It prints the tiles that changed per frame.
 --cull {none,back,front} [--front-ccw] turns on face culling (Metal's setCullMode / setFrontFacingWinding): triangles that face
 away (back) or towards the viewer (front) are not drawn; front is clockwise as displayed unless --front-ccw.
 
@@ -382,6 +385,32 @@ def run_streamed(frames: int, size: int, obj: str | None = None, depth_test: boo
     return results
 
 
+def run_delta(frames: int, size: int, obj: str | None = None, depth_test: bool = False, time0: float = 0.0,
+              device_count: int = 1, out: str | None = None):
+    """The host-visible loop through swr_render_delta: the mesh is cached on the device by its scene identity, every frame carries a
+    new transform, and the two page-locked host images keep what the last frame delivered, so only the rectangle around the tiles
+    that changed is copied.  Prints the tiles changed per frame; returns the frames (copies) and the (colour, depth) stats of each."""
+    vertices, indices = load_mesh(obj) if obj else sphere_mesh()
+    flags = S.FLAG_DEPTH_TEST if depth_test else 0
+    color, depth = swr_amd.HostImage((size, size, 4), np.uint8), swr_amd.HostImage((size, size), np.float32)
+    results, stats = [], []
+    with swr_amd.Context(0, device_count=device_count) as ctx:
+        time = time0
+        for k in range(frames):
+            sc, sd = ctx.render_delta(vertices, indices, S.app_transform(time), size, size, color, depth, flags, scene_id=1)
+            print(f"delta: frame {k}: colour {sc.tiles_changed} of {sc.tiles} tiles changed, {sc.bytes_copied} bytes copied"
+                  f"{' (full)' if sc.full else ''}; depth {sd.tiles_changed} of {sd.tiles} tiles, {sd.bytes_copied} bytes"
+                  f"{' (full)' if sd.full else ''}")
+            results.append((color.array.copy(), depth.array.copy()))
+            stats.append((sc, sd))
+            if out:
+                os.makedirs(out, exist_ok=True)
+                write_ppm(os.path.join(out, f"frame_{k:04d}.ppm"), color.array)
+            time += 1.0 / 60.0
+    color.free(); depth.free()
+    return results, stats
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4)
@@ -399,6 +428,8 @@ if __name__ == "__main__":
     ap.add_argument("--occlusion", action="store_true",
                     help="with --objects N: test every copy's screen rectangle and nearest depth against the previous frame's depth "
                          "image on the device and print how many copies could be skipped (swr_query_depth)")
+    ap.add_argument("--delta", action="store_true",
+                    help="the host-visible loop through swr_render_delta: only the tiles that changed cross to the host; prints them per frame")
     ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
     ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
     ap.add_argument("--clip", action="store_true", help="depth clipping: triangles clipped against the near and far planes")
@@ -417,6 +448,12 @@ if __name__ == "__main__":
             ap.error("--glass does not combine with --pick, --ids or --perspective (blend frames write no IDs and interpolate screen-linearly)")
         if a.stream:
             ap.error("--glass is not part of the --stream loop")
+    if a.delta:
+        if a.stream or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion:
+            ap.error("--delta is the plain swr_render loop: not with --stream, --ssaa, --glass, --objects, --pick, --ids or --occlusion")
+        res, _ = run_delta(a.frames, a.size, a.ply or a.obj, a.depth_test, device_count=a.gpus, out=a.out)
+        print(f"{a.frames} frames through delta reads, coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
+        sys.exit(0)
     if a.stream:
         res = run_streamed(a.frames, a.size, a.ply or a.obj, a.depth_test, device_count=a.gpus, cull=a.cull, front_ccw=a.front_ccw,
                            clip=a.clip, perspective=a.perspective)

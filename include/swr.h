@@ -333,6 +333,51 @@ typedef struct swr_depth_box {
 } swr_depth_box;              /* 32 bytes */
 #define SWR_DEPTH_QUERY_MAX (1 << 16)
 
+/* ---- Delta reads (swr_read_color_delta, swr_read_depth_delta, swr_render_delta) — DESIGN.md §22 -----------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_read_color_delta symbol is the feature test.  Nothing
+ * existing changes.  A frame costs little on the device; what a caller waits for is the copy of two full images that mostly hold what
+ * they held a frame ago.  A delta read compares the image with what the host already holds, tile by tile, on the device, and only
+ * the changed part crosses.  Everything below is integer and exact.
+ *   Tiles.  A tile is swr_tile_cols() x swr_tile_rows() pixels (64 x 32), anchored at pixel (0, 0) of the full target.  Bands start
+ *     at multiples of 32 rows, so a band's tiles are tiles of the target.  The right and bottom tiles may be partial.
+ *   Baseline.  Every band keeps one baseline image on the device per image kind (colour, depth): the image the last delta read of
+ *     that kind delivered.  Baselines are allocated on first use.
+ *   The caller's promise.  The band's rows of dst still hold what the previous delta read of that kind delivered.  The pointer may
+ *     differ from call to call; the content may not.
+ *   No baseline.  The band is delivered whole, exactly as swr_read_color / swr_read_depth deliver it: full = 1, and every tile counts
+ *     as changed.
+ *   With a baseline.  A tile is changed iff any of its 32-bit words differs from the baseline, compared as bits: a NaN with another
+ *     payload, and -0 against +0, are therefore changes; equal NaN bits are not.  tiles_changed is the exact number of changed tiles.
+ *     Let R be the bounding box of the band's changed tiles, clipped to the band and the width.  dst is written only inside R (a
+ *     multi-device context: only inside each band's own R); nothing outside is touched.  An implementation may write less than R,
+ *     but never a pixel of an unchanged tile outside R; bytes_copied says what it did.
+ *   After the call.  Under the promise, the band's rows of dst are byte for byte what swr_read_color / swr_read_depth would deliver
+ *     now, and the baseline is that image.
+ *   Completion.  As swr_read_*: everything is completed first, an overflowed last frame is repaired, and no framebuffer image is
+ *     modified.  After a SWR_FLAG_NO_COLOR frame the colour is as unspecified as swr_read_color's, but the baseline still tracks what
+ *     was delivered.
+ *   What drops a baseline.  swr_delta_reset; a swr_target_set that changes the width, the height or the rows; destroying the
+ *     context.  The same target again keeps it (swr_render sets its target every frame).
+ *   What keeps a baseline.  Frames, swr_target_write, swr_present, the other reads and the queries: none of them changes what the
+ *     host holds.
+ *   Bands.  Every band handles its own rows; the stats are summed and the rectangle is the bounding box of the bands' rectangles.  A
+ *     context that owns rows [a, b) of a larger target handles only those rows.  A group writes stats once, after every band succeeded.
+ *   swr_render_delta is swr_render whose gather is the two delta reads (the colour's is skipped under SWR_FLAG_NO_COLOR, and stats[0]
+ *     is then all 0): pass->color and pass->depth carry the promise, swr_render_times.gather_ms covers the delta, scene_id caching
+ *     works as in swr_render.  SWR_FLAG_LOAD returns SWR_ERR_UNSUPPORTED: its starting image is uploaded whole anyway.
+ *   Errors.  SWR_ERR_BAD_ARG: a NULL ctx or dst; zero or unknown swr_delta_reset bits.  SWR_ERR_NO_SCENE: no target.  A failed context
+ *     returns its sticky error.  After an error dst, stats and the baselines are untouched.
+ *   Not covered: the ID image, an asynchronous present, and the C++ and Swift mirrors. */
+typedef struct swr_delta_stats {
+    int32_t x0, y0, x1, y1;   /* bounding box of everything written to dst, pixels of the full target; all 0 when nothing was */
+    int64_t tiles;            /* tiles in the context's band(s) */
+    int64_t tiles_changed;    /* tiles that differed from the baseline (== tiles on a full delivery) */
+    int64_t bytes_copied;     /* bytes written to dst */
+    int32_t full;             /* 1: there was no baseline, the whole band was delivered */
+    int32_t reserved;         /* 0 on return */
+} swr_delta_stats;            /* 48 bytes */
+enum { SWR_DELTA_COLOR = 1, SWR_DELTA_DEPTH = 2 };
+
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
  * continues from the image already there.
@@ -638,12 +683,20 @@ int swr_count_ids(swr_context* ctx, const swr_id_count* q, uint32_t* counts, int
 /* Depth queries (see "Depth queries" above): swr_sync + the copy of the n boxes + a reduction of the depth image on the device + the
  * copy of the n counts + wait.  boxes and passed have n elements. */
 int swr_query_depth(swr_context* ctx, const swr_depth_box* boxes, int64_t n, uint32_t* passed);
+/* Delta reads (see "Delta reads" above): swr_sync + the compare against the band's baseline on the device + the copy of the tile
+ * flags + the copy of the changed rectangle + wait.  dst is the full W x H image, as for swr_read_*; stats may be NULL. */
+int swr_read_color_delta(swr_context* ctx, void*  dst_full_image, swr_delta_stats* stats);
+int swr_read_depth_delta(swr_context* ctx, float* dst_full_image, swr_delta_stats* stats);
+int swr_delta_reset(swr_context* ctx, uint32_t images);     /* SWR_DELTA_* bits, non-zero, no others: the next delta read is full */
 /* Supersampled resolve (see "Supersampled resolve" above): swr_sync + the S x S box filter on the device + the copy of the small
  * image + wait.  The destination has (W/S) x (H/S) elements; page-locked and pageable destinations both work, as for swr_read_*. */
 int swr_read_color_resolved(swr_context* ctx, const swr_resolve* resolve, void*  dst);  /* (W/S) x (H/S) BGRA8 */
 int swr_read_depth_resolved(swr_context* ctx, const swr_resolve* resolve, float* dst);  /* (W/S) x (H/S) floats */
 /* swr_render at S·width x S·height, resolved into the pass's width x height images (both images in one launch per band). */
 int swr_render_resolved(swr_context* ctx, const swr_render_pass* pass, const swr_resolve* resolve);
+/* swr_render whose gather is the two delta reads into pass->color and pass->depth (see "Delta reads" above).  stats[0] is the colour's,
+ * stats[1] the depth's; stats may be NULL. */
+int swr_render_delta(swr_context* ctx, const swr_render_pass* pass, swr_delta_stats stats[2]);
 
 /* Timing instrumentation: hipEvents on the context stream.  level 0 = off, 1 = two events around
  * the dominant kernel (k_raster) only, 2 = around every stage (each event costs a few us of

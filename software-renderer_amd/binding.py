@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     "swr_host_register", "swr_host_unregister", "swr_present", "swr_present_wait", "swr_device_count",
     "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list", "swr_read_ids",
     "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
-    "swr_query_depth",
+    "swr_query_depth", "swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -108,6 +108,21 @@ DEPTH_QUERY_MAX = 1 << 16    # SWR_DEPTH_QUERY_MAX: boxes per swr_query_depth ca
 # swr_depth_box as a numpy record
 DEPTH_BOX_DTYPE = np.dtype([("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32), ("z", np.float32),
                             ("reserved", np.int32, (3,))])
+
+
+class DeltaStats(ctypes.Structure):
+    """swr_delta_stats (include/swr.h "Delta reads"): what a delta read did."""
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32), ("y1", ctypes.c_int32),
+                ("tiles", ctypes.c_int64), ("tiles_changed", ctypes.c_int64), ("bytes_copied", ctypes.c_int64),
+                ("full", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    @property
+    def rect(self):
+        """(x0, y0, x1, y1): the bounding box of everything written, pixels of the full target; all 0 when nothing was."""
+        return (self.x0, self.y0, self.x1, self.y1)
+
+
+DELTA_COLOR, DELTA_DEPTH = 1, 2     # SWR_DELTA_*: the bits of swr_delta_reset
 
 
 class Config(ctypes.Structure):
@@ -259,6 +274,16 @@ def load_library():
         L.swr_query_depth.restype = ctypes.c_int
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
+    try:
+        L.swr_read_color_delta.argtypes = [vp, vp, ctypes.POINTER(DeltaStats)]
+        L.swr_read_depth_delta.argtypes = [vp, vp, ctypes.POINTER(DeltaStats)]
+        L.swr_delta_reset.argtypes = [vp, ctypes.c_uint32]
+        L.swr_render_delta.argtypes = [vp, ctypes.POINTER(RenderPass), ctypes.POINTER(DeltaStats)]
+        for name in ("swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta"):
+            getattr(L, name).restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
             raise
     L.swr_target_write.argtypes = [vp, vp, vp]
     L.swr_target_write.restype = ctypes.c_int
@@ -610,6 +635,27 @@ class Context:
     def _dst_ptr(x):
         return x.ptr if isinstance(x, HostImage) else x.ctypes.data
 
+    def _read_delta(self, fn, out) -> DeltaStats:
+        arr = out.array if isinstance(out, HostImage) else out
+        assert arr.flags.c_contiguous and arr.nbytes == self.width * self.height * 4
+        st = DeltaStats()
+        self._check(fn(self._h, self._dst_ptr(out), ctypes.byref(st)))
+        return st
+
+    def read_color_delta(self, out) -> DeltaStats:
+        """swr_read_color_delta: `out` — a (height, width, 4) uint8 NumPy array or HostImage that still holds what the last
+        read_color_delta delivered — becomes what read_color would deliver now; only the rectangle around the tiles that changed is
+        written (the whole band the first time).  Returns what was done."""
+        return self._read_delta(self._L.swr_read_color_delta, out)
+
+    def read_depth_delta(self, out) -> DeltaStats:
+        """swr_read_depth_delta: read_color_delta for the (height, width) float32 depth image; its baseline is its own."""
+        return self._read_delta(self._L.swr_read_depth_delta, out)
+
+    def delta_reset(self, images: int = DELTA_COLOR | DELTA_DEPTH):
+        """swr_delta_reset: drop the baselines named by the DELTA_* bits; the next delta read of those kinds delivers the whole band."""
+        self._check(self._L.swr_delta_reset(self._h, int(images)))
+
     def read_color_resolved(self, factor: int, out=None, resolve: "Resolve | None" = None) -> np.ndarray:
         """swr_read_color_resolved: the last frame's colour image through the factor x factor box filter, computed on the device —
         (height / factor, width / factor, 4) uint8; alpha is the coverage of the pixel.  `out`: a NumPy array or a HostImage of that
@@ -675,19 +721,31 @@ class Context:
         r = Resolve(int(factor), int(depth_filter), (ctypes.c_int32 * 2)(0, 0))
         return self._render(r, vertices, indices, transform, width, height, flags, primitive_type, color, depth, shading, scene_id)
 
-    def _render(self, resolve, vertices, indices, transform, width, height, flags, primitive_type, color, depth, shading, scene_id):
+    def render_delta(self, vertices, indices, transform, width, height, color, depth, flags=0, primitive_type=0,
+                     shading=None, scene_id=0):
+        """swr_render_delta: Context.render whose gather is the two delta reads.  `color` (None under FLAG_NO_COLOR) and `depth` — NumPy
+        arrays or HostImages — still hold what the last render_delta into them delivered.  FLAG_LOAD is refused.  Returns
+        (colour DeltaStats, depth DeltaStats)."""
+        stats = (DeltaStats * 2)()
+        self._render(None, vertices, indices, transform, width, height, flags, primitive_type, color, depth, shading, scene_id, delta=stats)
+        return stats[0], stats[1]
+
+    def _render(self, resolve, vertices, indices, transform, width, height, flags, primitive_type, color, depth, shading, scene_id,
+                delta=None):
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 8)
         i = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
         m = np.ascontiguousarray(transform, dtype=np.float32).reshape(16)
         if resolve is None and (flags & FLAG_LOAD) and (depth is None or (color is None and not (flags & FLAG_NO_COLOR))):
             raise ValueError("render with FLAG_LOAD: color / depth are the starting image and must be given")
+        if delta is not None and (depth is None or (color is None and not (flags & FLAG_NO_COLOR))):
+            raise ValueError("render_delta: color / depth hold what the last call delivered and must be given")
         if color is None and not (flags & FLAG_NO_COLOR):
             color = np.full((height, width, 4), 0xCD, dtype=np.uint8)
         if depth is None:
             depth = np.full((height, width), -123.0, dtype=np.float32)
         rp = RenderPass()
-        rp.color = color.ctypes.data if color is not None else None
-        rp.depth = depth.ctypes.data
+        rp.color = self._dst_ptr(color) if color is not None else None
+        rp.depth = self._dst_ptr(depth)
         rp.width, rp.height = width, height
         rp.color_bytes_per_row = width * 4
         rp.depth_bytes_per_row = width * 4
@@ -704,7 +762,10 @@ class Context:
             if shading.texture is not None:
                 t = np.ascontiguousarray(shading.texture, dtype=np.uint8)
                 rp.texture, rp.tex_width, rp.tex_height = t.ctypes.data, t.shape[1], t.shape[0]
-        if resolve is None:
+        if delta is not None:
+            self._check(self._L.swr_render_delta(self._h, ctypes.byref(rp), delta))
+            S = 1
+        elif resolve is None:
             self._check(self._L.swr_render(self._h, ctypes.byref(rp)))
             S = 1
         else:

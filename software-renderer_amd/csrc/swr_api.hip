@@ -49,6 +49,10 @@ __attribute__((weak)) void launch_count_ids(const uint32_t* ids, int width, int 
 __attribute__((weak)) void launch_depth_query(const float* depth, int width, int rows, int row_begin, const swr_depth_box* boxes, int64_t n,
                                               const uint32_t* large, int64_t nlarge, uint64_t total_area, void* scratch, uint32_t* passed,
                                               hipStream_t s);
+// (and for the delta reads: without swr_delta.hip swr_read_*_delta fails loudly)
+__attribute__((weak)) void launch_delta(const uint32_t* cur, uint32_t* base, int have_base, int width, int rows, uint32_t* flags,
+                                        uint32_t* direct, hipStream_t s);
+__attribute__((weak)) void launch_delta_pack(const uint32_t* src, int width, int x0, int x1, int y0, int y1, uint32_t* out, hipStream_t s);
 }
 
 using namespace swr;
@@ -138,7 +142,7 @@ struct Worker {
 
 static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && sizeof(swr_vertex_attr) == 32 &&
               sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16 &&
-              sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32 && sizeof(swr_depth_box) == 32,
+              sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32 && sizeof(swr_depth_box) == 32 && sizeof(swr_delta_stats) == 48,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -220,6 +224,14 @@ struct swr_context {
     uint32_t* query_host = nullptr;
     size_t query_host_words = 0;
     const uint32_t* query_passed = nullptr;     // the counts of the last query inside query_host
+    // delta reads: per image kind (0 colour, 1 depth) the band's baseline — the image the last delta read delivered —
+    // and whether it holds one; the tile flags k_delta_tiles writes, on the device and in the band's own page-locked copy; the rows of
+    // a changed rectangle gathered for one linear copy; what the band's last delta read did (a group adds the bands up)
+    DevBuf delta_base[2], delta_flags, delta_pack;
+    bool delta_valid[2] = {false, false};
+    uint32_t* delta_host = nullptr;
+    size_t delta_host_words = 0;
+    swr_delta_stats delta_stats{};
     int fb_cur = 0;                    // the next swr_draw renders into this buffer
     int fb_last = 0;                    // the buffer of the last swr_draw (what swr_present / swr_read_* copy)
     hipStream_t last_stream = nullptr;  // the stream that carries the last frame's raster (swr_present records frame_done behind it)
@@ -1641,6 +1653,7 @@ int single_target_set(swr_context* c, int64_t width, int64_t height, int64_t row
         c->read_recorded[fb] = false;
     }
     c->fb_cur = c->fb_last = 0;
+    c->delta_valid[0] = c->delta_valid[1] = false;          // another target: the host holds nothing of it (delta reads start over)
     for (auto& sl : c->slot)
         if ((rc = ensure(c, sl.tilebuf, (size_t)(CNT_WORDS + 3 * std::max(1, tiles_of(t)) + 1) * 4))) return rc;
     c->tg = t;
@@ -2257,6 +2270,125 @@ int single_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, co
     return SWR_OK;
 }
 
+#ifndef SWR_TUNE_DELTA_DIRECT
+#define SWR_TUNE_DELTA_DIRECT 1     // how the changed part reaches a page-locked destination, chosen by measurement:
+                                    // 1 = k_delta_tiles stores the changed tiles straight into the caller's image through its
+                                    // device address (the product: 0.05 against 0.13 ms on the app's scene at 4K); 0 = R gathered
+                                    // on the device, one linear copy into page-locked staging, rows copied by the host — what a
+                                    // pageable destination always takes (A/B builds)
+#endif
+
+// swr_read_color_delta / swr_read_depth_delta on one band (img: 0 colour, 1 depth): the band's rows of `dst`, which hold what the last
+// delta read of this kind delivered, become what single_read would deliver now; only the bounding box of the tiles that differ from
+// the band's baseline is written.  What was done is left in c->delta_stats.
+int single_read_delta(swr_context* c, int img, void* dst) {
+    if (const int f = sticky(c)) return f;
+    if (!dst) return fail(c, SWR_ERR_BAD_ARG, "swr_read_*_delta: the destination is NULL");
+    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_*_delta needs swr_target_set first");
+    int rc = single_sync(c);        // (an overflowed last frame is repaired here)
+    if (rc) return rc;
+    swr_delta_stats st{};
+    c->delta_stats = st;
+    const int tiles = tiles_of(c->tg);
+    if (tiles == 0) return SWR_OK;
+    const int W = c->tg.width, rows = c->tg.row_end - c->tg.row_begin, fb = c->fb_last;
+    const size_t row = (size_t)W * 4, bytes = row * (size_t)rows;
+    DevBuf& base = c->delta_base[img];
+    if (base.bytes < bytes) c->delta_valid[img] = false;        // (never: a target of another size has dropped the baseline already)
+    if ((rc = ensure(c, base, bytes))) return rc;
+    if ((rc = ensure(c, c->delta_flags, (size_t)tiles * 4))) return rc;
+    if (c->delta_host_words < (size_t)tiles) {
+        if (c->delta_host) { HIP_TRY(c, hipHostFree(c->delta_host)); c->delta_host = nullptr; c->delta_host_words = 0; }
+        const size_t want = (size_t)tiles + (size_t)tiles / 8;
+        HIP_TRY(c, hipHostMalloc((void**)&c->delta_host, want * 4, hipHostMallocDefault));
+        c->delta_host_words = want;
+    }
+    if (!launch_delta || !launch_delta_pack)
+        return fail(c, SWR_ERR_HIP, "this build has no k_delta_tiles: there is no fallback for the delta reads");
+    const uint32_t* cur = (const uint32_t*)fb_image(c, fb, img);
+    uint8_t* band_dst = (uint8_t*)dst + (size_t)c->tg.row_begin * row;
+    const uint64_t frame = c->frame_no ? c->frame_no - 1 : 0;
+    st.tiles = tiles;
+    // the whole band, as single_read delivers it (no baseline, or every tile row and column changed)
+    auto whole_band = [&]() -> int {
+        HIP_TRY(c, hipEventRecord(c->frame_done[fb], c->stream));
+        int rcw = copy_band(c, fb, img, cur, row, c->tg.row_begin, c->tg.row_end, dst, frame);
+        if (rcw) return rcw;
+        if ((rcw = wait_stream(c, c->copy_stream[img], "copy stream (delta read)"))) return or_sticky(c, rcw);
+        st.x0 = 0; st.y0 = c->tg.row_begin; st.x1 = W; st.y1 = c->tg.row_end;
+        st.bytes_copied = (int64_t)bytes;
+        return SWR_OK;
+    };
+    if (!c->delta_valid[img]) {
+        launch_delta(cur, (uint32_t*)base.p, 0, W, rows, (uint32_t*)c->delta_flags.p, nullptr, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        if ((rc = whole_band())) return rc;
+        if ((rc = wait_stream(c, c->stream, "raster stream (delta read)"))) return or_sticky(c, rc);
+        c->delta_valid[img] = true;
+        st.tiles_changed = tiles;
+        st.full = 1;
+        c->delta_stats = st;
+        return SWR_OK;
+    }
+    uint32_t* direct = nullptr;
+    if (SWR_TUNE_DELTA_DIRECT && is_pinned(band_dst)) {
+        if (hipHostGetDevicePointer((void**)&direct, band_dst, 0) != hipSuccess) { (void)hipGetLastError(); direct = nullptr; }
+    }
+    launch_delta(cur, (uint32_t*)base.p, 1, W, rows, (uint32_t*)c->delta_flags.p, direct, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->delta_host, c->delta_flags.p, (size_t)tiles * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_stream(c, c->stream, "raster stream (delta read)"))) return or_sticky(c, rc);
+    // the changed tiles: their number, their bounding box in tiles, and the pixels they hold
+    int tx0 = c->tg.tiles_x, tx1 = -1, ty0 = c->tg.tiles_y, ty1 = -1;
+    int64_t changed = 0, changed_px = 0;
+    for (int ty = 0; ty < c->tg.tiles_y; ty++)
+        for (int tx = 0; tx < c->tg.tiles_x; tx++) {
+            if (!c->delta_host[(size_t)ty * c->tg.tiles_x + tx]) continue;
+            changed++;
+            changed_px += (int64_t)(std::min(W, (tx + 1) * TILE_W) - tx * TILE_W) * (std::min(rows, (ty + 1) * TILE_H) - ty * TILE_H);
+            tx0 = std::min(tx0, tx); tx1 = std::max(tx1, tx);
+            ty0 = std::min(ty0, ty); ty1 = std::max(ty1, ty);
+        }
+    st.tiles_changed = changed;
+    if (changed == 0) { c->delta_stats = st; return SWR_OK; }
+    // R, in columns and band-local rows
+    const int x0 = tx0 * TILE_W, x1 = std::min(W, (tx1 + 1) * TILE_W), y0 = ty0 * TILE_H, y1 = std::min(rows, (ty1 + 1) * TILE_H);
+    if (direct) {       // (the kernel has stored the changed tiles already)
+        st.x0 = x0; st.x1 = x1; st.y0 = c->tg.row_begin + y0; st.y1 = c->tg.row_begin + y1;
+        st.bytes_copied = changed_px * 4;
+    } else if (x0 == 0 && x1 == W && y0 == 0 && y1 == rows) {
+        if ((rc = whole_band())) return rc;
+    } else {
+        // R's rows gathered on the device, moved through the page-locked stage chunks, and copied row by row into the caller's image
+        const size_t rrow = (size_t)(x1 - x0) * 4, rbytes = rrow * (size_t)(y1 - y0);
+        if ((rc = ensure(c, c->delta_pack, rbytes)) || (rc = ensure_stage(c, img))) return rc;
+        launch_delta_pack(cur, W, x0, x1, y0, y1, (uint32_t*)c->delta_pack.p, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        const uint8_t* src = (const uint8_t*)c->delta_pack.p;
+        const size_t CH = swr_context::STAGE_BYTES, n = (rbytes + CH - 1) / CH;
+        for (size_t k = 0; k <= n; k++) {
+            if (k < n) {
+                HIP_TRY(c, hipMemcpyAsync(c->stage[img][k & 1], src + k * CH, std::min(CH, rbytes - k * CH), hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(c, hipEventRecord(c->stage_ev[img][k & 1], c->stream));
+            }
+            if (k > 0) {
+                const size_t j = k - 1;
+                if ((rc = poll_event(c, c->stage_ev[img][j & 1], "a staged copy to the host (delta read)", frame))) return rc;
+                const uint8_t* from = (const uint8_t*)c->stage[img][j & 1];
+                for (size_t off = j * CH, left = std::min(CH, rbytes - j * CH); left;) {       // (a chunk may start and end inside a row)
+                    const size_t r = off / rrow, col = off - r * rrow, len = std::min(left, rrow - col);
+                    memcpy(band_dst + ((size_t)y0 + r) * row + (size_t)x0 * 4 + col, from, len);
+                    off += len; left -= len; from += len;
+                }
+            }
+        }
+        st.x0 = x0; st.x1 = x1; st.y0 = c->tg.row_begin + y0; st.y1 = c->tg.row_begin + y1;
+        st.bytes_copied = (int64_t)rbytes;
+    }
+    c->delta_stats = st;
+    return SWR_OK;
+}
+
 void destroy_single(swr_context* c) {
     hipSetDevice(c->device);
     // helper jobs are bounded (every wait in them is) and give up at once on a failed context: the drains return
@@ -2290,7 +2422,7 @@ void destroy_single(swr_context* c) {
                 c->hp_t[3] / c->hp_frames, c->hp_t[4] / c->hp_frames, c->hp_t[5] / c->hp_frames);
     DevBuf* bufs[] = {&c->redo_cnt, &c->vertices, &c->indices, &c->tri_rgb, &c->tri_xyz, &c->inv, &c->box64, &c->stream_scratch, &c->sort_temp,
                       &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth, &c->count_dev, &c->query_dev,
-                      &c->query_tiles};
+                      &c->query_tiles, &c->delta_base[0], &c->delta_base[1], &c->delta_flags, &c->delta_pack};
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
@@ -2328,6 +2460,7 @@ void destroy_single(swr_context* c) {
     if (c->h_clip) hipHostFree(c->h_clip);
     if (c->count_host) hipHostFree(c->count_host);
     if (c->query_host) hipHostFree(c->query_host);
+    if (c->delta_host) hipHostFree(c->delta_host);
     if (c->ev_ok)
         for (int r = 0; r < swr_context::RING; r++)
             for (int i = 0; i < 5; i++) hipEventDestroy(c->ev[r][i]);
@@ -2721,6 +2854,69 @@ int swr_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, uint3
     return SWR_OK;
 }
 
+// one band's stats added to a total: sums, and the bounding box of the rectangles
+static void delta_add(swr_delta_stats& t, const swr_delta_stats& k, bool first) {
+    if (k.bytes_copied) {
+        if (!t.bytes_copied) { t.x0 = k.x0; t.y0 = k.y0; t.x1 = k.x1; t.y1 = k.y1; }
+        else { t.x0 = std::min(t.x0, k.x0); t.y0 = std::min(t.y0, k.y0); t.x1 = std::max(t.x1, k.x1); t.y1 = std::max(t.y1, k.y1); }
+    }
+    t.tiles += k.tiles; t.tiles_changed += k.tiles_changed; t.bytes_copied += k.bytes_copied;
+    if (k.tiles) t.full = first ? k.full : (t.full & k.full);       // (the bands' baselines come and go together)
+}
+
+// swr_read_color_delta / swr_read_depth_delta and the gather of swr_render_delta; `out` (never NULL) is written after every band succeeded
+static int read_delta(swr_context* c, int img, void* dst, swr_delta_stats* out) {
+    if (!is_group(c)) {
+        const int rc = single_read_delta(c, img, dst);
+        if (rc) return rc;
+        *out = c->delta_stats;
+        return SWR_OK;
+    }
+    if (const int f = sticky(c)) return f;
+    if (!dst) return fail(c, SWR_ERR_BAD_ARG, "swr_read_*_delta: the destination is NULL");
+    if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_*_delta needs swr_target_set first");
+    const int rc = group_run(c, [=](swr_context* k) { return single_read_delta(k, img, dst); });
+    if (rc) return rc;
+    swr_delta_stats t{};
+    bool first = true;
+    for (const swr_context* k : c->kids) {
+        delta_add(t, k->delta_stats, first);
+        if (k->delta_stats.tiles) first = false;
+    }
+    *out = t;
+    return SWR_OK;
+}
+
+int swr_read_color_delta(swr_context* c, void* dst, swr_delta_stats* stats) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    swr_delta_stats st;
+    const int rc = read_delta(c, 0, dst, &st);
+    if (!rc && stats) *stats = st;
+    return rc;
+}
+
+int swr_read_depth_delta(swr_context* c, float* dst, swr_delta_stats* stats) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    swr_delta_stats st;
+    const int rc = read_delta(c, 1, dst, &st);
+    if (!rc && stats) *stats = st;
+    return rc;
+}
+
+int swr_delta_reset(swr_context* c, uint32_t images) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    if (const int f = sticky(c)) return f;
+    if (!images || (images & ~(uint32_t)(SWR_DELTA_COLOR | SWR_DELTA_DEPTH)))
+        return fail(c, SWR_ERR_BAD_ARG, "swr_delta_reset: images 0x%x is zero or holds unknown bits", images);
+    auto reset = [=](swr_context* k) {
+        if (const int f = sticky(k)) return f;
+        if (images & SWR_DELTA_COLOR) k->delta_valid[0] = false;
+        if (images & SWR_DELTA_DEPTH) k->delta_valid[1] = false;
+        return (int)SWR_OK;
+    };
+    return is_group(c) ? group_run(c, reset) : reset(c);
+}
+
 // the resolved read of one or both images (NULL: not wanted); a group checks what it can see before any band is touched
 static int read_resolved(swr_context* c, const swr_resolve* resolve, void* color_dst, float* depth_dst) {
     const swr_resolve rs = *resolve;
@@ -2860,8 +3056,9 @@ int swr_get_timings(swr_context* c, swr_timings* out) {
     return SWR_OK;
 }
 
-// swr_render (resolve == NULL) and swr_render_resolved share this body: only the target's size and the gather differ.
-static int render_pass(swr_context* c, const swr_render_pass* p, const swr_resolve* resolve) {
+// swr_render (resolve == NULL, delta false), swr_render_resolved and swr_render_delta (delta_stats: NULL or where the two stats go)
+// share this body: only the target's size and the gather differ.
+static int render_pass(swr_context* c, const swr_render_pass* p, const swr_resolve* resolve, bool delta = false, swr_delta_stats* delta_stats = nullptr) {
     if (p->primitive_type != SWR_PRIMITIVE_TRIANGLE && p->primitive_type != SWR_PRIMITIVE_LINE &&
         p->primitive_type != SWR_PRIMITIVE_VERTICES)
         return fail(c, SWR_ERR_UNSUPPORTED, "unknown primitive type %d", p->primitive_type);
@@ -2877,6 +3074,8 @@ static int render_pass(swr_context* c, const swr_render_pass* p, const swr_resol
         if (p->flags & SWR_FLAG_LOAD)
             return fail(c, SWR_ERR_UNSUPPORTED, "swr_render_resolved: SWR_FLAG_LOAD is not supported (the starting image would be at the wrong resolution)");
     }
+    if (delta && (p->flags & SWR_FLAG_LOAD))
+        return fail(c, SWR_ERR_UNSUPPORTED, "swr_render_delta: SWR_FLAG_LOAD is not supported (its starting image is uploaded whole anyway)");
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<float, std::milli>(b - a).count(); };
     const auto t0 = clk::now();
@@ -2934,6 +3133,21 @@ static int render_pass(swr_context* c, const swr_render_pass* p, const swr_resol
         c->rt.total_ms = ms(t0, t3);
         return SWR_OK;
     }
+    if (delta) {
+        // the gather of a delta pass: the frame itself (an overflow is repaired), then the changed part of each image
+        if ((rc = swr_sync(c))) return rc;
+        const auto t2 = clk::now();
+        swr_delta_stats st[2] = {};
+        if (!(p->flags & SWR_FLAG_NO_COLOR) && (rc = read_delta(c, 0, p->color, &st[0]))) return rc;
+        if ((rc = read_delta(c, 1, p->depth, &st[1]))) return rc;
+        const auto t3 = clk::now();
+        if (delta_stats) { delta_stats[0] = st[0]; delta_stats[1] = st[1]; }
+        c->rt.draw_ms = ms(t1, t2);
+        c->rt.frames = (int32_t)(kf->frame_no - frames0);
+        c->rt.gather_ms = ms(t2, t3);
+        c->rt.total_ms = ms(t0, t3);
+        return SWR_OK;
+    }
     // colour and depth leave every device together (two copy streams each); synchronous on return like
     // scheduleAndWait (Metal+Extensions.swift:57-67)
     if ((rc = swr_present(c, (p->flags & SWR_FLAG_NO_COLOR) ? nullptr : p->color, p->depth))) return rc;
@@ -2956,6 +3170,11 @@ int swr_render(swr_context* c, const swr_render_pass* p) {
 int swr_render_resolved(swr_context* c, const swr_render_pass* p, const swr_resolve* resolve) {
     if (!c || !p || !resolve) return SWR_ERR_BAD_ARG;
     return render_pass(c, p, resolve);
+}
+
+int swr_render_delta(swr_context* c, const swr_render_pass* p, swr_delta_stats stats[2]) {
+    if (!c || !p) return SWR_ERR_BAD_ARG;
+    return render_pass(c, p, nullptr, true, stats);
 }
 
 int swr_render_timings(swr_context* c, swr_render_times* out) {

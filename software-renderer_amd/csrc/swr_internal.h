@@ -259,4 +259,14 @@ inline size_t depth_query_scratch_bytes(int width, int rows) {      // (16 bytes
 void launch_depth_query(const float* depth, int width, int rows, int row_begin, const swr_depth_box* boxes, int64_t n,
                         const uint32_t* large, int64_t nlarge, uint64_t total_area, void* scratch, uint32_t* passed, hipStream_t s);
 
+// swr_delta.hip: delta reads.  launch_delta compares the band's image `cur` (`width` words per row, `rows` rows) with
+// its baseline `base`, tile by tile (64 x 32, row-major, ceil(width / 64) per row): flags[t] = 1 where tile t differs in any bit, else
+// 0 — every word of the table is written by a plain store, nothing has to be zeroed — and the changed tiles' words are stored into
+// `base`.  have_base == 0: nothing is compared, every tile is stored and flagged (the copy of the band into a fresh baseline).
+// direct: NULL, or the band's rows of a page-locked host image as the device sees them (hipHostGetDevicePointer): the changed tiles'
+// words are stored there too.  launch_delta_pack gathers columns [x0, x1) of the band-local rows [y0, y1) of `src` into `out`, rows of
+// x1 - x0 words.  cur, base, flags, src and out are device memory.
+void launch_delta(const uint32_t* cur, uint32_t* base, int have_base, int width, int rows, uint32_t* flags, uint32_t* direct, hipStream_t s);
+void launch_delta_pack(const uint32_t* src, int width, int x0, int x1, int y0, int y1, uint32_t* out, hipStream_t s);
+
 }  // namespace swr
