@@ -7,7 +7,7 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion] [--delta]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion] [--delta] [--skin]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
@@ -21,6 +21,9 @@ depth image), and prints how many copies could be skipped because nothing of the
 --delta runs the host-visible loop the way the app calls it — one swr_render per frame, the same mesh, a new transform, the same two host
 images — through swr_render_delta: the device compares every frame with what the host images already hold, tile by tile, and only the
 rectangle around the tiles that changed crosses to the host.  It prints the tiles that changed per frame.
+--skin draws a torus that bends between two joints instead: the mesh and its per-vertex joint weights are uploaded once
+(swr_scene_upload, swr_scene_skin), and every frame sets a new pose of two joint matrices (swr_pose_set) — the vertices are posed on
+the device, nothing but 128 bytes of pose crosses per frame — and draws it with the app's transform.
 --cull {none,back,front} [--front-ccw] turns on face culling (Metal's setCullMode / setFrontFacingWinding): triangles that face
 away (back) or towards the viewer (front) are not drawn; front is clockwise as displayed unless --front-ccw.
 
@@ -411,6 +414,50 @@ def run_delta(frames: int, size: int, obj: str | None = None, depth_test: bool =
     return results, stats
 
 
+def bend_skin(vertices: np.ndarray):
+    """(joints, weights) of a mesh that bends along x between joint 0 (weight 1 - t) and joint 1 (weight t), t = x mapped to 0..1
+    across the mesh; all four influences of swr_skin_vertex are given, the last two with weight 0."""
+    x = vertices[:, 0]
+    t = np.clip((x - x.min()) / max(float(x.max() - x.min()), 1e-30), 0.0, 1.0).astype(np.float32)
+    joints = np.zeros((x.shape[0], 4), dtype=np.uint32)
+    joints[:, 1] = 1
+    weights = np.zeros((x.shape[0], 4), dtype=np.float32)
+    weights[:, 0], weights[:, 1] = 1.0 - t, t
+    return joints, weights
+
+
+def bend_pose(time: float) -> np.ndarray:
+    """Two joint matrices (column-major, like a frame's transform): the two ends of the mesh turn about z against each other."""
+    def turn(angle, ty):
+        c, s = math.cos(angle), math.sin(angle)
+        return np.array([c, s, 0, 0, -s, c, 0, 0, 0, 0, 1, 0, 0, ty, 0, 1], dtype=np.float32)
+    a = 0.6 * math.sin(2.0 * time)
+    return np.stack([turn(a, 0.05 * math.sin(3.0 * time)), turn(-a, -0.05 * math.sin(3.0 * time))])
+
+
+def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, device_count: int = 1):
+    """The resident loop with a deforming mesh: a torus skinned to two joints, a new pose every frame (swr_pose_set), the app's
+    transform.  Returns the mesh and the (colour, depth) frames."""
+    xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
+    vertices = S.pack_vertices(xyz, rgb)
+    flags = S.FLAG_DEPTH_TEST if depth_test else 0
+    results = []
+    with swr_amd.Context(0, device_count=device_count) as ctx:
+        ctx.scene_upload(vertices, indices)
+        ctx.scene_skin(*bend_skin(vertices))
+        ctx.target_set(size, size)
+        time = time0
+        for k in range(frames):
+            ctx.pose_set(bend_pose(time))
+            ctx.draw(S.app_transform(time), flags)
+            results.append((ctx.read_color(), ctx.read_depth()))
+            if out:
+                os.makedirs(out, exist_ok=True)
+                write_ppm(os.path.join(out, f"frame_{k:04d}.ppm"), results[-1][0])
+            time += 1.0 / 60.0
+    return vertices, indices, results
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4)
@@ -430,6 +477,8 @@ if __name__ == "__main__":
                          "image on the device and print how many copies could be skipped (swr_query_depth)")
     ap.add_argument("--delta", action="store_true",
                     help="the host-visible loop through swr_render_delta: only the tiles that changed cross to the host; prints them per frame")
+    ap.add_argument("--skin", action="store_true",
+                    help="a torus bending between two joints: skinned once (swr_scene_skin), a new pose every frame (swr_pose_set)")
     ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
     ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
     ap.add_argument("--clip", action="store_true", help="depth clipping: triangles clipped against the near and far planes")
@@ -448,6 +497,12 @@ if __name__ == "__main__":
             ap.error("--glass does not combine with --pick, --ids or --perspective (blend frames write no IDs and interpolate screen-linearly)")
         if a.stream:
             ap.error("--glass is not part of the --stream loop")
+    if a.skin:
+        if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or a.obj or a.ply:
+            ap.error("--skin is its own loop over its own mesh: only --frames, --size, --out, --depth-test and --gpus apply")
+        _, idx, res = run_skin(a.frames, a.size, a.out, a.depth_test, device_count=a.gpus)
+        print(f"{a.frames} posed frames, {idx.size // 3} triangles, coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
+        sys.exit(0)
     if a.delta:
         if a.stream or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion:
             ap.error("--delta is the plain swr_render loop: not with --stream, --ssaa, --glass, --objects, --pick, --ids or --occlusion")

@@ -378,6 +378,43 @@ typedef struct swr_delta_stats {
 } swr_delta_stats;            /* 48 bytes */
 enum { SWR_DELTA_COLOR = 1, SWR_DELTA_DEPTH = 2 };
 
+/* ---- Skinned meshes (swr_scene_skin, swr_pose_set) — DESIGN.md §23 ---------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_pose_set symbol is the feature test.  Nothing
+ * existing changes.  The resident scene can deform without a new swr_scene_upload: every vertex carries four joint influences, and
+ * swr_pose_set rewrites the positions (and normals) of the resident triangle stream on the device from a table of joint matrices.
+ *   swr_scene_skin follows the swr_scene_upload it belongs to, like swr_scene_attributes, before or after it: vertex_count must
+ *     match, and a new swr_scene_upload (the one a swr_render performs included) discards skin and pose.  skin == NULL with vertex_count == 0
+ *     removes the skin and restores the bind pose.  A new skin restores the bind pose too.  The largest joint index is found once, here.
+ *   swr_pose_set puts the scene into the pose.  The pose persists until the next swr_pose_set, swr_scene_skin or swr_scene_upload.
+ *     joints == NULL with joint_count == 0 restores the bind pose: the scene is bit for bit what the upload built.
+ *   Arithmetic (normative): IEEE binary32, one rounding per operation, no FMA.  For the vertex (x, y, z) and every influence
+ *     k = 0..3, in this order, with c0..c3 the columns of joints[joint[k]] (16 floats, column-major like a frame's transform):
+ *         r_k = c0.xyz * x;   r_k = r_k + c1.xyz * y;   r_k = r_k + c2.xyz * z;   r_k = r_k + c3.xyz * 1.0f;
+ *     then   acc = weight[0] * r_0;   acc = acc + weight[1] * r_1;   acc = acc + weight[2] * r_2;   acc = acc + weight[3] * r_3;
+ *     and the posed position is acc.  The fourth row of a joint matrix is ignored: joints are affine, the frame's own transform
+ *     carries the perspective.  Normals (scenes with attributes only) take the same two steps without the c3 term, blended with
+ *     the same weights: no inverse transpose and no renormalisation, the fragment stage normalises per pixel.  Colour and uv never
+ *     change.  There are no special cases: all four influences are always read, zero, negative and non-finite weights follow IEEE
+ *     (a -0 coordinate may come out as +0), and a triangle with a non-finite posed coordinate is skipped exactly as an uploaded one.
+ *   What a pose is.  Every frame, read and query after swr_pose_set is bit for bit that of a context on which swr_scene_upload
+ *     (and swr_scene_attributes) was given the posed vertices (and normals) with the same indices: every entry point, flag, rule
+ *     set, draw list and primitive type.  Primitive IDs, painter's order and tie order keep the numbering of the index array.
+ *   Ordering.  swr_pose_set and swr_scene_skin first complete and check everything drawn before (an overflowed last frame is
+ *     repaired in the pose it was drawn in), then rewrite the scene, and return when the pose is in effect: blocking, like
+ *     swr_scene_attributes.  A frame posted before the call never sees the new pose.  A multi-device context poses every band.
+ *   Errors.  SWR_ERR_NO_SCENE: no scene.  SWR_ERR_BAD_ARG: a NULL ctx; a vertex_count that does not match the scene; skin == NULL
+ *     with vertex_count > 0 on a scene that has vertices; a joint index >= SWR_SKIN_MAX_JOINTS; swr_pose_set without a skin;
+ *     joint_count < 0; joint_count <= the largest joint index the skin uses; NULL joints with joint_count > 0.
+ *     SWR_ERR_UNSUPPORTED: joint_count > SWR_SKIN_MAX_JOINTS.  A failed context returns its sticky error.  After an error the
+ *     scene and the pose are unchanged.
+ *   Not covered: a pose that does not wait (ordered by events), dual-quaternion skinning, morph targets, a partial vertex update
+ *     from the host, and the C++ and Swift mirrors. */
+typedef struct swr_skin_vertex {
+    uint32_t joint[4];   /* indices into the pose; all four are always read */
+    float    weight[4];  /* used as given: not normalised, not sorted, not skipped when 0 */
+} swr_skin_vertex;       /* 32 bytes, parallel to swr_vertex: entry i belongs to vertex i */
+#define SWR_SKIN_MAX_JOINTS 1024
+
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
  * continues from the image already there.
@@ -588,6 +625,9 @@ int swr_scene_upload(swr_context* ctx, const swr_vertex* vertices, int64_t verte
  * reference's passthrough stage.  A draw with a Phong material but no attributes, or a textured material
  * but no texture, returns SWR_ERR_BAD_ARG. */
 int swr_scene_attributes(swr_context* ctx, const swr_vertex_attr* attributes, int64_t vertex_count);
+/* Skinned meshes (see "Skinned meshes" above): the per-vertex influences, and the pose the resident scene is put into. */
+int swr_scene_skin(swr_context* ctx, const swr_skin_vertex* skin, int64_t vertex_count);
+int swr_pose_set(swr_context* ctx, const float* joints /* joint_count x 16, column-major like transform */, int32_t joint_count);
 int swr_material_set(swr_context* ctx, const swr_material* material);
 int swr_texture_upload(swr_context* ctx, const void* bgra8, int32_t width, int32_t height);
 /* The blend state of SWR_FLAG_BLEND frames (see "Alpha blending" above); NULL restores the default, SWR_BLEND_OVER with opacity 255.

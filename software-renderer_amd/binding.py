@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list", "swr_read_ids",
     "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
     "swr_query_depth", "swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta",
+    "swr_scene_skin", "swr_pose_set",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -123,6 +124,16 @@ class DeltaStats(ctypes.Structure):
 
 
 DELTA_COLOR, DELTA_DEPTH = 1, 2     # SWR_DELTA_*: the bits of swr_delta_reset
+
+
+class SkinVertex(ctypes.Structure):
+    """swr_skin_vertex (include/swr.h "Skinned meshes"): the four joint influences of one vertex."""
+    _fields_ = [("joint", ctypes.c_uint32 * 4), ("weight", ctypes.c_float * 4)]
+
+
+SKIN_MAX_JOINTS = 1024       # SWR_SKIN_MAX_JOINTS: joints per pose
+# swr_skin_vertex as a numpy record
+SKIN_VERTEX_DTYPE = np.dtype([("joint", np.uint32, (4,)), ("weight", np.float32, (4,))])
 
 
 class Config(ctypes.Structure):
@@ -285,6 +296,14 @@ def load_library():
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
             raise
+    try:
+        L.swr_scene_skin.argtypes = [vp, vp, i64]
+        L.swr_pose_set.argtypes = [vp, vp, i32]
+        for name in ("swr_scene_skin", "swr_pose_set"):
+            getattr(L, name).restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
+            raise
     L.swr_target_write.argtypes = [vp, vp, vp]
     L.swr_target_write.restype = ctypes.c_int
     L.swr_present_wait.argtypes = [vp]
@@ -417,6 +436,31 @@ class Context:
     def scene_attributes(self, attrs: np.ndarray):
         a = np.ascontiguousarray(attrs, dtype=np.float32).reshape(-1, 8)
         self._check(self._L.swr_scene_attributes(self._h, a.ctypes.data, a.shape[0]))
+
+    def scene_skin(self, joints: "np.ndarray | None", weights: "np.ndarray | None" = None):
+        """swr_scene_skin: per vertex four joint indices (nv x 4, integers) and four weights (nv x 4, float32), or one
+        SKIN_VERTEX_DTYPE record array as `joints`; None removes the skin and restores the bind pose."""
+        if joints is None:
+            self._check(self._L.swr_scene_skin(self._h, None, 0))
+            return
+        if weights is None:
+            sk = np.ascontiguousarray(joints, dtype=SKIN_VERTEX_DTYPE).reshape(-1)
+        else:
+            j = np.asarray(joints).reshape(-1, 4)
+            sk = np.zeros(j.shape[0], dtype=SKIN_VERTEX_DTYPE)
+            sk["joint"] = j
+            sk["weight"] = np.asarray(weights, dtype=np.float32).reshape(-1, 4)
+        self._check(self._L.swr_scene_skin(self._h, sk.ctypes.data, sk.shape[0]))
+
+    def pose_set(self, joints: "np.ndarray | None"):
+        """swr_pose_set: the resident scene in the pose `joints` — joint_count x 16 floats, each matrix column-major like a frame's
+        transform (a (J, 4, 4) array M with M[j] the mathematical matrix is passed as M.transpose(0, 2, 1)); None: the bind pose.
+        Blocking: the pose is in effect when the call returns."""
+        if joints is None:
+            self._check(self._L.swr_pose_set(self._h, None, 0))
+            return
+        m = np.ascontiguousarray(joints, dtype=np.float32).reshape(-1, 16)
+        self._check(self._L.swr_pose_set(self._h, m.ctypes.data, m.shape[0]))
 
     def material_set(self, material: "Material | None"):
         self._check(self._L.swr_material_set(self._h, ctypes.byref(material) if material is not None else None))

@@ -53,6 +53,12 @@ __attribute__((weak)) void launch_depth_query(const float* depth, int width, int
 __attribute__((weak)) void launch_delta(const uint32_t* cur, uint32_t* base, int have_base, int width, int rows, uint32_t* flags,
                                         uint32_t* direct, hipStream_t s);
 __attribute__((weak)) void launch_delta_pack(const uint32_t* src, int width, int x0, int x1, int y0, int y1, uint32_t* out, hipStream_t s);
+// (and for the skinned meshes: without swr_skin.hip swr_pose_set fails loudly)
+__attribute__((weak)) void launch_skin_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, const swr_skin_vertex* skin, int64_t nv,
+                                                const float* joints, int32_t joint_count, swr_vertex* posed, float4* posed_nrm, hipStream_t s);
+__attribute__((weak)) void launch_skin_stream(const float4* pos, int pos_stride, const float4* nrm, int nrm_stride, int64_t nv,
+                                              const int64_t* indices, int64_t ntri, int reordered, float4* tri_xyz, float4* tri_nrm,
+                                              float4* box64, hipStream_t s);
 }
 
 using namespace swr;
@@ -142,7 +148,8 @@ struct Worker {
 
 static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && sizeof(swr_vertex_attr) == 32 &&
               sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16 &&
-              sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32 && sizeof(swr_depth_box) == 32 && sizeof(swr_delta_stats) == 48,
+              sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32 && sizeof(swr_depth_box) == 32 && sizeof(swr_delta_stats) == 48 &&
+              sizeof(swr_skin_vertex) == 32,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -193,6 +200,14 @@ struct swr_context {
     swr_material material{};            // shader 0 = the reference's passthrough stage
     swr_blend blend{SWR_BLEND_OVER, 255, {0, 0}};   // swr_blend_set: the state of SWR_FLAG_BLEND frames
     int32_t tex_w = 0, tex_h = 0;
+    // skinned meshes (swr_scene_skin / swr_pose_set): the influences; the pose in effect, on the host (restream and
+    // swr_scene_attributes rebuild the stream from the bind pose and pose it again) and on the device; the posed vertices (what
+    // .vertices and line frames read while a pose is in effect) and normals k_skin_vertices writes
+    DevBuf skin, pose_dev, posed, posed_nrm;
+    bool has_skin = false;
+    int64_t skin_max_joint = -1;        // the largest joint index of the skin (-1: a scene without vertices)
+    bool pose_active = false;           // the stream is in `pose` (else: as the upload built it)
+    std::vector<float> pose;            // joint_count x 16
 
     // target band (RenderPass.colorBuffer / .depthBuffer), double-buffered in HBM: swr_present copies the frame just
     // drawn to the host while the next swr_draw renders into the other buffer
@@ -747,7 +762,7 @@ BinPlan plan_frame(const swr_context* c, int64_t ntri, int64_t size, int64_t idl
 DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const swr_context::DrawRecord& d) {
     swr_context::Slot& sl = c->slot[si];
     DeviceFrame f{};
-    f.vertices = (const swr_vertex*)c->vertices.p;
+    f.vertices = (const swr_vertex*)(c->pose_active ? c->posed.p : c->vertices.p);   // (k_points / k_lines: the posed vertices)
     f.indices = (const int64_t*)c->indices.p;
     f.tri_rgb = (const float4*)c->tri_rgb.p;
     f.tri_xyz = (const float4*)c->tri_xyz.p;
@@ -1437,6 +1452,34 @@ int copy_band(swr_context* c, int fb, int img, const void* src_band, size_t row,
 int check_frames(swr_context* c);
 int enqueue_present(swr_context* c, void* color_full, float* depth_full);
 
+// Skinned meshes.  Enqueue on c->stream (every stream idle) what puts the triangle stream — positions, the normals
+// when with_nrm, the group boxes — into the context's pose, or without one back into the bind pose, bit for bit what the upload built.
+int enqueue_pose(swr_context* c, bool with_nrm) {
+    if (!launch_skin_vertices || !launch_skin_stream)
+        return fail(c, SWR_ERR_HIP, "this build has no k_skin_vertices: there is no fallback for skinned meshes");
+    const int64_t ntri = c->ni / 3;
+    if (c->pose_active) {
+        int rc;
+        if ((rc = ensure(c, c->posed, (size_t)c->nv * sizeof(swr_vertex)))) return rc;
+        if (with_nrm && (rc = ensure(c, c->posed_nrm, (size_t)c->nv * 16))) return rc;
+        if ((rc = ensure(c, c->pose_dev, c->pose.size() * 4))) return rc;
+        if (!c->pose.empty())
+            HIP_TRY(c, hipMemcpyAsync(c->pose_dev.p, c->pose.data(), c->pose.size() * 4, hipMemcpyHostToDevice, c->stream));
+        launch_skin_vertices((const swr_vertex*)c->vertices.p, with_nrm ? (const swr_vertex_attr*)c->attrs.p : nullptr,
+                             (const swr_skin_vertex*)c->skin.p, c->nv, (const float*)c->pose_dev.p, (int32_t)(c->pose.size() / 16),
+                             (swr_vertex*)c->posed.p, (float4*)c->posed_nrm.p, c->stream);
+        launch_skin_stream((const float4*)c->posed.p, 2, with_nrm ? (const float4*)c->posed_nrm.p : nullptr, 1, c->nv,
+                           (const int64_t*)c->indices.p, ntri, c->reordered ? 1 : 0, (float4*)c->tri_xyz.p,
+                           with_nrm ? (float4*)c->tri_nrm.p : nullptr, (float4*)c->box64.p, c->stream);
+    } else {
+        launch_skin_stream((const float4*)c->vertices.p, 2, with_nrm ? (const float4*)c->attrs.p : nullptr, 2, c->nv,
+                           (const int64_t*)c->indices.p, ntri, c->reordered ? 1 : 0, (float4*)c->tri_xyz.p,
+                           with_nrm ? (float4*)c->tri_nrm.p : nullptr, (float4*)c->box64.p, c->stream);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SWR_OK;
+}
+
 #ifndef SWR_TUNE_ONESHOT_CUTS
 #define SWR_TUNE_ONESHOT_CUTS {70, 100}   // single_scene_upload: where a one-shot scene's index array is cut, per cent of the primitives
 #endif
@@ -1454,6 +1497,8 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     { int rcs = check_frames(c); if (rcs) return rcs; }     // (an overflowed frame presented just before is repaired / reported first)
     c->has_scene = false;
     c->has_attrs = false;
+    c->has_skin = false; c->skin_max_joint = -1;     // (a new scene has neither skin nor pose)
+    c->pose_active = false; c->pose.clear();
     c->draw_pending = false;
     c->last_draw.is_list = false;
     c->cuts.clear();                 // a new stream is one segment
@@ -1577,8 +1622,66 @@ int single_scene_attributes(swr_context* c, const swr_vertex_attr* attributes, i
     launch_gather_attrs((const swr_vertex_attr*)c->attrs.p, vertex_count, (const int64_t*)c->indices.p, c->ni / 3,
                         (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
     HIP_TRY(c, hipGetLastError());
+    if (c->pose_active && (rc = enqueue_pose(c, true))) return rc;      // (the gather wrote the bind normals: pose them)
     if ((rc = wait_stream(c, c->stream, "attribute upload"))) return or_sticky(c, rc);
     c->has_attrs = true;
+    return SWR_OK;
+}
+
+// swr_scene_skin: the influences of the resident scene's vertices (skin == NULL: none).  The stream goes back to the bind pose.
+int single_scene_skin(swr_context* c, const swr_skin_vertex* skin, int64_t vertex_count) {
+    if (const int f = sticky(c)) return f;
+    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "swr_scene_skin needs swr_scene_upload first");
+    if (skin ? vertex_count != c->nv : vertex_count != 0)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_scene_skin: %lld influences%s for %lld vertices", (long long)vertex_count,
+                    skin ? "" : " without a skin", (long long)c->nv);
+    int64_t maxj = -1;
+    for (int64_t i = 0; skin && i < vertex_count; i++)
+        for (int k = 0; k < 4; k++) maxj = std::max<int64_t>(maxj, skin[i].joint[k]);
+    if (maxj >= SWR_SKIN_MAX_JOINTS)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_scene_skin: joint index %lld (at most %d)", (long long)maxj, SWR_SKIN_MAX_JOINTS - 1);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the pose it was drawn in)
+    if (skin) {
+        if ((rc = ensure(c, c->skin, (size_t)vertex_count * sizeof(swr_skin_vertex)))) return rc;
+        if (vertex_count)
+            HIP_TRY(c, hipMemcpyAsync(c->skin.p, skin, (size_t)vertex_count * sizeof(swr_skin_vertex), hipMemcpyHostToDevice, c->stream));
+    }
+    if (c->pose_active) {
+        c->pose_active = false;
+        c->pose.clear();
+        if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
+    }
+    if ((rc = wait_stream(c, c->stream, "skin upload"))) return or_sticky(c, rc);
+    c->has_skin = skin != nullptr;
+    c->skin_max_joint = maxj;
+    return SWR_OK;
+}
+
+// swr_pose_set: the resident scene in the pose `joints` (NULL with joint_count 0: the bind pose), in effect when the call returns.
+int single_pose_set(swr_context* c, const float* joints, int32_t joint_count) {
+    if (const int f = sticky(c)) return f;
+    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "swr_pose_set needs swr_scene_upload first");
+    if (!c->has_skin) return fail(c, SWR_ERR_BAD_ARG, "swr_pose_set needs swr_scene_skin first");
+    if (joint_count < 0) return fail(c, SWR_ERR_BAD_ARG, "swr_pose_set: joint_count %d", joint_count);
+    if (joint_count > SWR_SKIN_MAX_JOINTS)
+        return fail(c, SWR_ERR_UNSUPPORTED, "swr_pose_set: %d joints (at most %d)", joint_count, SWR_SKIN_MAX_JOINTS);
+    if (!joints && joint_count > 0) return fail(c, SWR_ERR_BAD_ARG, "swr_pose_set: %d joints without matrices", joint_count);
+    const bool bind = !joints;
+    if (!bind && (int64_t)joint_count <= c->skin_max_joint)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_pose_set: %d joints, but the skin uses joint index %lld", joint_count,
+                    (long long)c->skin_max_joint);
+    if (!launch_skin_vertices || !launch_skin_stream)
+        return fail(c, SWR_ERR_HIP, "this build has no k_skin_vertices: there is no fallback for skinned meshes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the pose it was drawn in)
+    if (bind && !c->pose_active) return SWR_OK;
+    c->pose_active = !bind;
+    if (bind) c->pose.clear(); else c->pose.assign(joints, joints + (size_t)joint_count * 16);
+    if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
+    if ((rc = wait_stream(c, c->stream, "pose"))) return or_sticky(c, rc);
     return SWR_OK;
 }
 
@@ -1808,6 +1911,7 @@ int restream(swr_context* c, const std::vector<uint32_t>& cuts) {
         launch_gather_attrs((const swr_vertex_attr*)c->attrs.p, c->nv, (const int64_t*)c->indices.p, ntri,
                             (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
     HIP_TRY(c, hipGetLastError());
+    if (c->pose_active && (rc = enqueue_pose(c, c->has_attrs))) return rc;      // (the rebuild gathered the bind pose: pose it again)
     if ((rc = wait_stream(c, c->stream, "stream rebuild (draw list)"))) return or_sticky(c, rc);
     c->cuts = cuts;
     return SWR_OK;
@@ -2422,7 +2526,8 @@ void destroy_single(swr_context* c) {
                 c->hp_t[3] / c->hp_frames, c->hp_t[4] / c->hp_frames, c->hp_t[5] / c->hp_frames);
     DevBuf* bufs[] = {&c->redo_cnt, &c->vertices, &c->indices, &c->tri_rgb, &c->tri_xyz, &c->inv, &c->box64, &c->stream_scratch, &c->sort_temp,
                       &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth, &c->count_dev, &c->query_dev,
-                      &c->query_tiles, &c->delta_base[0], &c->delta_base[1], &c->delta_flags, &c->delta_pack};
+                      &c->query_tiles, &c->delta_base[0], &c->delta_base[1], &c->delta_flags, &c->delta_pack, &c->skin, &c->pose_dev, &c->posed,
+                      &c->posed_nrm};
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
@@ -2679,6 +2784,20 @@ int swr_scene_attributes(swr_context* c, const swr_vertex_attr* attributes, int6
     c->scene_id = 0;      // the resident scene changes: a later swr_render must not take it for its own
     if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_scene_attributes(k, attributes, vertex_count); });
     return single_scene_attributes(c, attributes, vertex_count);
+}
+
+int swr_scene_skin(swr_context* c, const swr_skin_vertex* skin, int64_t vertex_count) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    c->scene_id = 0;      // the resident scene changes: a later swr_render must not take it for its own
+    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_scene_skin(k, skin, vertex_count); });
+    return single_scene_skin(c, skin, vertex_count);
+}
+
+int swr_pose_set(swr_context* c, const float* joints, int32_t joint_count) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    c->scene_id = 0;      // (the same)
+    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_pose_set(k, joints, joint_count); });
+    return single_pose_set(c, joints, joint_count);
 }
 
 int swr_material_set(swr_context* c, const swr_material* m) {

@@ -269,4 +269,18 @@ void launch_depth_query(const float* depth, int width, int rows, int row_begin, 
 void launch_delta(const uint32_t* cur, uint32_t* base, int have_base, int width, int rows, uint32_t* flags, uint32_t* direct, hipStream_t s);
 void launch_delta_pack(const uint32_t* src, int width, int x0, int x1, int y0, int y1, uint32_t* out, hipStream_t s);
 
+// swr_skin.hip: skinned meshes.  launch_skin_vertices poses the nv vertices — posed[i] = the blend of include/swr.h
+// "Skinned meshes" of vertices[i] with its colour copied, posed_nrm[i] = (the blended normal of attrs[i], 0) — from `joints`, the
+// pose on the device: joint_count matrices of 16 floats, column-major.  attrs == NULL: the scene has no attributes and posed_nrm is
+// not written.  Every joint index of `skin` is below joint_count (the host has checked it).
+// launch_skin_stream rewrites the positions of the scene's triangle stream from a vertex array — the xyz lanes of tri_xyz[3s + k] =
+// those of pos[pos_stride * index], in float4 units; the w lanes stay — and, nrm != NULL, the xyz lanes of tri_nrm[3s + k] from
+// nrm[nrm_stride * index], and writes the box of every 64-slot group as k_box64 does.  The primitive of slot s is tri_xyz[3s].w when
+// `reordered`, else s.  Given the posed arrays (strides 2 and 1) the stream is in the pose; given the scene's own vertices and
+// attributes (strides 2 and 2) it is bit for bit the stream the upload built.  All pointers are device memory.
+void launch_skin_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, const swr_skin_vertex* skin, int64_t nv,
+                          const float* joints, int32_t joint_count, swr_vertex* posed, float4* posed_nrm, hipStream_t s);
+void launch_skin_stream(const float4* pos, int pos_stride, const float4* nrm, int nrm_stride, int64_t nv, const int64_t* indices,
+                        int64_t ntri, int reordered, float4* tri_xyz, float4* tri_nrm, float4* box64, hipStream_t s);
+
 }  // namespace swr
