@@ -7,7 +7,7 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion] [--delta] [--skin]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion] [--delta] [--skin] [--morph]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
@@ -24,6 +24,9 @@ rectangle around the tiles that changed crosses to the host.  It prints the tile
 --skin draws a torus that bends between two joints instead: the mesh and its per-vertex joint weights are uploaded once
 (swr_scene_upload, swr_scene_skin), and every frame sets a new pose of two joint matrices (swr_pose_set) — the vertices are posed on
 the device, nothing but 128 bytes of pose crosses per frame — and draws it with the app's transform.
+--morph gives the mesh two procedural morph targets (blend shapes) — a swell along the direction from the mesh's centre and a twist
+about z — uploaded once (swr_scene_morph), and every frame sets two new weights (swr_morph_set): the vertices are morphed on the
+device, nothing but the weights crosses per frame.  With --skin the torus is morphed first and then posed, as glTF orders the two.
 --cull {none,back,front} [--front-ccw] turns on face culling (Metal's setCullMode / setFrontFacingWinding): triangles that face
 away (back) or towards the viewer (front) are not drawn; front is clockwise as displayed unless --front-ccw.
 
@@ -458,6 +461,59 @@ def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = 
     return vertices, indices, results
 
 
+def morph_targets(vertices: np.ndarray) -> np.ndarray:
+    """(2, nv, 3) position deltas of any mesh: a swell away from the mesh's centre by a quarter of each vertex' distance, and a twist
+    about z that grows with height."""
+    p = vertices[:, 0:3].astype(np.float32)
+    centre = ((p.min(axis=0) + p.max(axis=0)) * np.float32(0.5)).astype(np.float32)
+    r = p - centre
+    d = np.zeros((2, p.shape[0], 3), dtype=np.float32)
+    d[0] = r * np.float32(0.25)
+    extent = max(float(np.abs(r[:, 2]).max()), 1e-30)
+    angle = (r[:, 2] / np.float32(extent)) * np.float32(0.8)
+    c, s = np.cos(angle).astype(np.float32), np.sin(angle).astype(np.float32)
+    d[1, :, 0] = (c * r[:, 0] - s * r[:, 1]) - r[:, 0]
+    d[1, :, 1] = (s * r[:, 0] + c * r[:, 1]) - r[:, 1]
+    return d
+
+
+def morph_weights(time: float) -> np.ndarray:
+    """The two weights at `time`: the mesh breathes and twists back and forth (never exactly 0: both targets stay active)."""
+    return np.array([0.5 + 0.45 * math.sin(4.0 * time), 0.05 + math.sin(2.5 * time)], dtype=np.float32)
+
+
+def run_morph(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, skin: bool = False,
+              device_count: int = 1, obj: str | None = None):
+    """The resident loop with a mesh that changes its shape: two morph targets uploaded once (swr_scene_morph), new weights every
+    frame (swr_morph_set), the app's transform.  skin: the torus of run_skin, morphed and then posed (swr_pose_set) every frame.
+    Returns the mesh and the (colour, depth) frames."""
+    if skin:
+        xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
+        vertices = S.pack_vertices(xyz, rgb)
+    else:
+        vertices, indices = load_mesh(obj) if obj else sphere_mesh()
+    flags = S.FLAG_DEPTH_TEST if depth_test else 0
+    results = []
+    with swr_amd.Context(0, device_count=device_count) as ctx:
+        ctx.scene_upload(vertices, indices)
+        ctx.scene_morph(morph_targets(vertices))
+        if skin:
+            ctx.scene_skin(*bend_skin(vertices))
+        ctx.target_set(size, size)
+        time = time0
+        for k in range(frames):
+            ctx.morph_set(morph_weights(time))
+            if skin:
+                ctx.pose_set(bend_pose(time))
+            ctx.draw(S.app_transform(time), flags)
+            results.append((ctx.read_color(), ctx.read_depth()))
+            if out:
+                os.makedirs(out, exist_ok=True)
+                write_ppm(os.path.join(out, f"frame_{k:04d}.ppm"), results[-1][0])
+            time += 1.0 / 60.0
+    return vertices, indices, results
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4)
@@ -479,6 +535,8 @@ if __name__ == "__main__":
                     help="the host-visible loop through swr_render_delta: only the tiles that changed cross to the host; prints them per frame")
     ap.add_argument("--skin", action="store_true",
                     help="a torus bending between two joints: skinned once (swr_scene_skin), a new pose every frame (swr_pose_set)")
+    ap.add_argument("--morph", action="store_true",
+                    help="two procedural morph targets on the mesh (swr_scene_morph), new weights every frame (swr_morph_set); composes with --skin")
     ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
     ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
     ap.add_argument("--clip", action="store_true", help="depth clipping: triangles clipped against the near and far planes")
@@ -497,6 +555,13 @@ if __name__ == "__main__":
             ap.error("--glass does not combine with --pick, --ids or --perspective (blend frames write no IDs and interpolate screen-linearly)")
         if a.stream:
             ap.error("--glass is not part of the --stream loop")
+    if a.morph:
+        if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or (a.skin and (a.obj or a.ply)):
+            ap.error("--morph is its own loop: only --frames, --size, --out, --depth-test, --gpus, --skin and (without --skin) --obj / --ply apply")
+        _, idx, res = run_morph(a.frames, a.size, a.out, a.depth_test, skin=a.skin, device_count=a.gpus, obj=a.ply or a.obj)
+        print(f"{a.frames} morphed{' and posed' if a.skin else ''} frames, {idx.size // 3} triangles, "
+              f"coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
+        sys.exit(0)
     if a.skin:
         if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or a.obj or a.ply:
             ap.error("--skin is its own loop over its own mesh: only --frames, --size, --out, --depth-test and --gpus apply")

@@ -407,13 +407,59 @@ enum { SWR_DELTA_COLOR = 1, SWR_DELTA_DEPTH = 2 };
  *     joint_count < 0; joint_count <= the largest joint index the skin uses; NULL joints with joint_count > 0.
  *     SWR_ERR_UNSUPPORTED: joint_count > SWR_SKIN_MAX_JOINTS.  A failed context returns its sticky error.  After an error the
  *     scene and the pose are unchanged.
- *   Not covered: a pose that does not wait (ordered by events), dual-quaternion skinning, morph targets, a partial vertex update
+ *   Not covered: a pose that does not wait (ordered by events), dual-quaternion skinning, a partial vertex update
  *     from the host, and the C++ and Swift mirrors. */
 typedef struct swr_skin_vertex {
     uint32_t joint[4];   /* indices into the pose; all four are always read */
     float    weight[4];  /* used as given: not normalised, not sorted, not skipped when 0 */
 } swr_skin_vertex;       /* 32 bytes, parallel to swr_vertex: entry i belongs to vertex i */
 #define SWR_SKIN_MAX_JOINTS 1024
+
+/* ---- Morph targets (swr_scene_morph, swr_morph_set) — DESIGN.md §24 ----------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_morph_set symbol is the feature test.  Nothing
+ * existing changes.  The resident scene can change its shape without a new swr_scene_upload: swr_scene_morph gives it up to
+ * SWR_MORPH_MAX_TARGETS morph targets (blend shapes), per-vertex deltas of position and, optionally, normal, and swr_morph_set
+ * rewrites the resident triangle stream on the device from a weight per target.
+ *   Arithmetic (normative): IEEE binary32, one rounding per operation, no FMA.  For vertex i the base position is b, exactly as
+ *     uploaded, d[t][i] is the position delta of target t, and the weights are w[0 .. T).  Start with p = b.  Walk t in ascending
+ *     order.  For every t with w[t] != 0.0f (float compare), p = p + w[t] * d[t][i], componentwise: the product is rounded, then the
+ *     sum is rounded.  The morphed position is p.
+ *     A target whose weight is +0 or -0 is skipped and its deltas are not read: a NaN or infinite delta in a zero-weight target
+ *     changes nothing, and a -0 coordinate stays -0.  A NaN weight compares unequal to 0 and is applied.  The skip is normative: it
+ *     makes a rig of 100 targets with 4 active cost 4, and it is bit-defined where x + 0 * d is not (-0 would become +0, 0 * inf NaN).
+ *     Normals take the same loop with normal_deltas, only when the scene has attributes and normal_deltas was given; otherwise
+ *     normals stay as uploaded.  Normal deltas given before swr_scene_attributes arrives are kept and take effect when it does.
+ *     Colour, uv and the padding lanes never change.
+ *   Order with the skin.  Morph first, then skin: the position and normal that the "Skinned meshes" arithmetic reads are the
+ *     morphed ones.  Without a skin or a pose, the morphed vertices are the scene.
+ *   What a morph is.  Every frame, read and query after the call is bit for bit that of a context on which swr_scene_upload (and
+ *     swr_scene_attributes) was given the morphed-then-posed vertices (and normals) with the same indices: every entry point, flag,
+ *     rule set, draw list and primitive type.  Primitive IDs, painter's order and tie order keep the numbering of the index array.
+ *     When all weights are zero, the scene is bit for bit what the upload built, or what the current pose alone built.
+ *   Lifetime.  swr_scene_morph follows the swr_scene_upload it belongs to, before or after swr_scene_attributes and swr_scene_skin.
+ *     It copies the deltas: the caller's arrays are free on return.  New targets set every weight to 0; they keep the skin and the
+ *     pose, which is re-applied to the unmorphed base.  targets == NULL removes the targets.  A new swr_scene_upload (the one a
+ *     swr_render performs included) discards targets and weights.  swr_morph_set persists until the next swr_morph_set,
+ *     swr_scene_morph or swr_scene_upload.  swr_pose_set and swr_scene_skin keep the weights: the new pose is applied to the
+ *     morphed vertices.
+ *   Ordering.  swr_scene_morph and swr_morph_set first complete and check everything drawn before, exactly as swr_pose_set does
+ *     (an overflowed last frame is repaired in the shape it was drawn in), then rewrite the scene, and return when it is in effect:
+ *     blocking.  A frame posted before the call never sees the new shape.  A multi-device context morphs every band.
+ *   Errors.  SWR_ERR_NO_SCENE: no scene.  SWR_ERR_BAD_ARG: a NULL ctx; a vertex_count that does not match the scene; NULL
+ *     position_deltas; target_count < 1; a non-zero reserved; swr_morph_set without targets; weight_count not equal to the target
+ *     count (except NULL with 0); NULL weights with a positive count.  SWR_ERR_UNSUPPORTED: target_count > SWR_MORPH_MAX_TARGETS.
+ *     SWR_ERR_NOMEM: the delta buffer cannot be allocated.  A failed context returns its sticky error.  After an error the scene,
+ *     the targets and the weights are unchanged.
+ *   Not covered: sparse targets, morphing colours or uv, one call that sets weights and joints together (today swr_morph_set
+ *     followed by swr_pose_set runs the skin and stream passes twice), an un-waited morph, and the C++ and Swift mirrors. */
+#define SWR_MORPH_MAX_TARGETS 256
+typedef struct swr_morph_targets {
+    const float* position_deltas; /* target_count x vertex_count x 3 floats, target-major, tightly packed (glTF VEC3 accessors back to back) */
+    const float* normal_deltas;   /* same shape, or NULL: normals do not morph */
+    int64_t vertex_count;         /* must equal the resident scene's */
+    int32_t target_count;         /* 1 .. SWR_MORPH_MAX_TARGETS */
+    int32_t reserved;             /* 0 */
+} swr_morph_targets;              /* 32 bytes */
 
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
@@ -628,6 +674,9 @@ int swr_scene_attributes(swr_context* ctx, const swr_vertex_attr* attributes, in
 /* Skinned meshes (see "Skinned meshes" above): the per-vertex influences, and the pose the resident scene is put into. */
 int swr_scene_skin(swr_context* ctx, const swr_skin_vertex* skin, int64_t vertex_count);
 int swr_pose_set(swr_context* ctx, const float* joints /* joint_count x 16, column-major like transform */, int32_t joint_count);
+/* Morph targets (see "Morph targets" above): the targets of the resident scene, and the weights it is morphed by. */
+int swr_scene_morph(swr_context* ctx, const swr_morph_targets* targets);                 /* NULL: remove the targets */
+int swr_morph_set(swr_context* ctx, const float* weights, int32_t weight_count);         /* NULL, 0: every weight 0 */
 int swr_material_set(swr_context* ctx, const swr_material* material);
 int swr_texture_upload(swr_context* ctx, const void* bgra8, int32_t width, int32_t height);
 /* The blend state of SWR_FLAG_BLEND frames (see "Alpha blending" above); NULL restores the default, SWR_BLEND_OVER with opacity 255.

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list", "swr_read_ids",
     "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
     "swr_query_depth", "swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta",
-    "swr_scene_skin", "swr_pose_set",
+    "swr_scene_skin", "swr_pose_set", "swr_scene_morph", "swr_morph_set",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -134,6 +134,15 @@ class SkinVertex(ctypes.Structure):
 SKIN_MAX_JOINTS = 1024       # SWR_SKIN_MAX_JOINTS: joints per pose
 # swr_skin_vertex as a numpy record
 SKIN_VERTEX_DTYPE = np.dtype([("joint", np.uint32, (4,)), ("weight", np.float32, (4,))])
+
+
+class MorphTargets(ctypes.Structure):
+    """swr_morph_targets (include/swr.h "Morph targets"): the deltas of target_count targets, target-major, packed float3."""
+    _fields_ = [("position_deltas", ctypes.c_void_p), ("normal_deltas", ctypes.c_void_p), ("vertex_count", ctypes.c_int64),
+                ("target_count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+MORPH_MAX_TARGETS = 256      # SWR_MORPH_MAX_TARGETS: targets per scene
 
 
 class Config(ctypes.Structure):
@@ -304,6 +313,14 @@ def load_library():
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
             raise
+    try:
+        L.swr_scene_morph.argtypes = [vp, ctypes.POINTER(MorphTargets)]
+        L.swr_morph_set.argtypes = [vp, vp, i32]
+        for name in ("swr_scene_morph", "swr_morph_set"):
+            getattr(L, name).restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
+            raise
     L.swr_target_write.argtypes = [vp, vp, vp]
     L.swr_target_write.restype = ctypes.c_int
     L.swr_present_wait.argtypes = [vp]
@@ -461,6 +478,32 @@ class Context:
             return
         m = np.ascontiguousarray(joints, dtype=np.float32).reshape(-1, 16)
         self._check(self._L.swr_pose_set(self._h, m.ctypes.data, m.shape[0]))
+
+    def scene_morph(self, position_deltas: "np.ndarray | None", normal_deltas: "np.ndarray | None" = None):
+        """swr_scene_morph: the morph targets of the resident scene — position deltas of shape (T, nv, 3) and, optionally, normal
+        deltas of the same shape; None removes the targets.  The deltas are copied; every weight is 0 afterwards."""
+        if position_deltas is None:
+            self._check(self._L.swr_scene_morph(self._h, None))
+            return
+        dp = np.ascontiguousarray(position_deltas, dtype=np.float32)
+        if dp.ndim != 3 or dp.shape[2] != 3:
+            raise ValueError(f"position_deltas of shape {dp.shape}, not (T, nv, 3)")
+        dn = None
+        if normal_deltas is not None:
+            dn = np.ascontiguousarray(normal_deltas, dtype=np.float32)
+            if dn.shape != dp.shape:
+                raise ValueError(f"normal_deltas of shape {dn.shape}, not {dp.shape}")
+        t = MorphTargets(dp.ctypes.data, dn.ctypes.data if dn is not None else None, dp.shape[1], dp.shape[0], 0)
+        self._check(self._L.swr_scene_morph(self._h, ctypes.byref(t)))
+
+    def morph_set(self, weights: "np.ndarray | None"):
+        """swr_morph_set: the resident scene morphed by one weight per target (a target with weight 0 is skipped); None: every
+        weight 0.  Blocking: the shape is in effect when the call returns."""
+        if weights is None:
+            self._check(self._L.swr_morph_set(self._h, None, 0))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        self._check(self._L.swr_morph_set(self._h, w.ctypes.data, w.shape[0]))
 
     def material_set(self, material: "Material | None"):
         self._check(self._L.swr_material_set(self._h, ctypes.byref(material) if material is not None else None))

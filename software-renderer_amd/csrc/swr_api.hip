@@ -59,6 +59,10 @@ __attribute__((weak)) void launch_skin_vertices(const swr_vertex* vertices, cons
 __attribute__((weak)) void launch_skin_stream(const float4* pos, int pos_stride, const float4* nrm, int nrm_stride, int64_t nv,
                                               const int64_t* indices, int64_t ntri, int reordered, float4* tri_xyz, float4* tri_nrm,
                                               float4* box64, hipStream_t s);
+// (and for the morph targets: without swr_morph.hip swr_morph_set fails loudly)
+__attribute__((weak)) void launch_morph_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, int64_t nv, const float* dpos,
+                                                 const float* dnrm, const MorphEntry* list, int32_t active, swr_vertex* morphed,
+                                                 swr_vertex_attr* morphed_attrs, hipStream_t s);
 }
 
 using namespace swr;
@@ -149,7 +153,7 @@ struct Worker {
 static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && sizeof(swr_vertex_attr) == 32 &&
               sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16 &&
               sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32 && sizeof(swr_depth_box) == 32 && sizeof(swr_delta_stats) == 48 &&
-              sizeof(swr_skin_vertex) == 32,
+              sizeof(swr_skin_vertex) == 32 && sizeof(swr_morph_targets) == 32,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -208,6 +212,15 @@ struct swr_context {
     int64_t skin_max_joint = -1;        // the largest joint index of the skin (-1: a scene without vertices)
     bool pose_active = false;           // the stream is in `pose` (else: as the upload built it)
     std::vector<float> pose;            // joint_count x 16
+    // morph targets (swr_scene_morph / swr_morph_set): the deltas as swr_internal.h lays them out; the weights on the
+    // host (restream and swr_scene_attributes re-apply them) and their non-zero entries as the list the kernel walks, on the host and
+    // on the device; the morphed vertices (what the skin, .vertices and line frames read while a weight is not zero) and attributes
+    DevBuf morph_dpos, morph_dnrm, morph_list_dev, morphed, morphed_attrs;
+    int32_t morph_targets = 0;          // 0: no targets
+    bool morph_has_nrm = false;         // normal deltas were given (they take effect once the scene has attributes)
+    bool morph_active = false;          // some weight is not zero
+    std::vector<float> morph_w;         // morph_targets weights
+    std::vector<MorphEntry> morph_list;
 
     // target band (RenderPass.colorBuffer / .depthBuffer), double-buffered in HBM: swr_present copies the frame just
     // drawn to the host while the next swr_draw renders into the other buffer
@@ -762,7 +775,8 @@ BinPlan plan_frame(const swr_context* c, int64_t ntri, int64_t size, int64_t idl
 DeviceFrame make_frame(swr_context* c, int si, uint64_t frame, const swr_context::DrawRecord& d) {
     swr_context::Slot& sl = c->slot[si];
     DeviceFrame f{};
-    f.vertices = (const swr_vertex*)(c->pose_active ? c->posed.p : c->vertices.p);   // (k_points / k_lines: the posed vertices)
+    // (k_points / k_lines: the last array of the chain morph, skin)
+    f.vertices = (const swr_vertex*)(c->pose_active ? c->posed.p : c->morph_active ? c->morphed.p : c->vertices.p);
     f.indices = (const int64_t*)c->indices.p;
     f.tri_rgb = (const float4*)c->tri_rgb.p;
     f.tri_xyz = (const float4*)c->tri_xyz.p;
@@ -1452,32 +1466,62 @@ int copy_band(swr_context* c, int fb, int img, const void* src_band, size_t row,
 int check_frames(swr_context* c);
 int enqueue_present(swr_context* c, void* color_full, float* depth_full);
 
-// Skinned meshes.  Enqueue on c->stream (every stream idle) what puts the triangle stream — positions, the normals
-// when with_nrm, the group boxes — into the context's pose, or without one back into the bind pose, bit for bit what the upload built.
+// Skinned meshes and morph targets.  Enqueue on c->stream (every stream idle) what puts the triangle stream —
+// positions, the normals when with_nrm, the group boxes — into the context's shape: the morph when a weight is not zero, then the pose
+// reading the morphed arrays, then the stream from whichever array is last.  With neither, back to what the upload built, bit for bit.
 int enqueue_pose(swr_context* c, bool with_nrm) {
     if (!launch_skin_vertices || !launch_skin_stream)
         return fail(c, SWR_ERR_HIP, "this build has no k_skin_vertices: there is no fallback for skinned meshes");
     const int64_t ntri = c->ni / 3;
+    int rc;
+    const swr_vertex* v = (const swr_vertex*)c->vertices.p;
+    const swr_vertex_attr* at = with_nrm ? (const swr_vertex_attr*)c->attrs.p : nullptr;
+    if (c->morph_active) {
+        if (!launch_morph_vertices)
+            return fail(c, SWR_ERR_HIP, "this build has no k_morph_vertices: there is no fallback for morph targets");
+        const bool mnrm = with_nrm && c->morph_has_nrm;         // (else the normals stay as uploaded)
+        c->morph_list.clear();
+        for (int32_t t = 0; t < c->morph_targets; t++)
+            if (c->morph_w[t] != 0.0f) c->morph_list.push_back(MorphEntry{(uint32_t)t, c->morph_w[t]});
+        if ((rc = ensure(c, c->morphed, (size_t)c->nv * sizeof(swr_vertex)))) return rc;
+        if (mnrm && (rc = ensure(c, c->morphed_attrs, (size_t)c->nv * sizeof(swr_vertex_attr)))) return rc;
+        if ((rc = ensure(c, c->morph_list_dev, c->morph_list.size() * sizeof(MorphEntry)))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->morph_list_dev.p, c->morph_list.data(), c->morph_list.size() * sizeof(MorphEntry),
+                                  hipMemcpyHostToDevice, c->stream));
+        launch_morph_vertices(v, mnrm ? at : nullptr, c->nv, (const float*)c->morph_dpos.p, (const float*)c->morph_dnrm.p,
+                              (const MorphEntry*)c->morph_list_dev.p, (int32_t)c->morph_list.size(), (swr_vertex*)c->morphed.p,
+                              (swr_vertex_attr*)c->morphed_attrs.p, c->stream);
+        v = (const swr_vertex*)c->morphed.p;
+        if (mnrm) at = (const swr_vertex_attr*)c->morphed_attrs.p;
+    }
     if (c->pose_active) {
-        int rc;
         if ((rc = ensure(c, c->posed, (size_t)c->nv * sizeof(swr_vertex)))) return rc;
         if (with_nrm && (rc = ensure(c, c->posed_nrm, (size_t)c->nv * 16))) return rc;
         if ((rc = ensure(c, c->pose_dev, c->pose.size() * 4))) return rc;
         if (!c->pose.empty())
             HIP_TRY(c, hipMemcpyAsync(c->pose_dev.p, c->pose.data(), c->pose.size() * 4, hipMemcpyHostToDevice, c->stream));
-        launch_skin_vertices((const swr_vertex*)c->vertices.p, with_nrm ? (const swr_vertex_attr*)c->attrs.p : nullptr,
-                             (const swr_skin_vertex*)c->skin.p, c->nv, (const float*)c->pose_dev.p, (int32_t)(c->pose.size() / 16),
-                             (swr_vertex*)c->posed.p, (float4*)c->posed_nrm.p, c->stream);
+        launch_skin_vertices(v, at, (const swr_skin_vertex*)c->skin.p, c->nv, (const float*)c->pose_dev.p,
+                             (int32_t)(c->pose.size() / 16), (swr_vertex*)c->posed.p, (float4*)c->posed_nrm.p, c->stream);
         launch_skin_stream((const float4*)c->posed.p, 2, with_nrm ? (const float4*)c->posed_nrm.p : nullptr, 1, c->nv,
                            (const int64_t*)c->indices.p, ntri, c->reordered ? 1 : 0, (float4*)c->tri_xyz.p,
                            with_nrm ? (float4*)c->tri_nrm.p : nullptr, (float4*)c->box64.p, c->stream);
     } else {
-        launch_skin_stream((const float4*)c->vertices.p, 2, with_nrm ? (const float4*)c->attrs.p : nullptr, 2, c->nv,
+        launch_skin_stream((const float4*)v, 2, (const float4*)at, 2, c->nv,
                            (const int64_t*)c->indices.p, ntri, c->reordered ? 1 : 0, (float4*)c->tri_xyz.p,
                            with_nrm ? (float4*)c->tri_nrm.p : nullptr, (float4*)c->box64.p, c->stream);
     }
     HIP_TRY(c, hipGetLastError());
     return SWR_OK;
+}
+
+// swr_scene_morph(NULL), a new scene: no targets, no weights; the delta planes go back to the device
+void drop_morph(swr_context* c) {
+    for (DevBuf* b : {&c->morph_dpos, &c->morph_dnrm})
+        if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->bytes = 0; }
+    c->morph_targets = 0;
+    c->morph_has_nrm = false;
+    c->morph_active = false;
+    c->morph_w.clear();
 }
 
 #ifndef SWR_TUNE_ONESHOT_CUTS
@@ -1499,6 +1543,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     c->has_attrs = false;
     c->has_skin = false; c->skin_max_joint = -1;     // (a new scene has neither skin nor pose)
     c->pose_active = false; c->pose.clear();
+    drop_morph(c);                                   // (nor morph targets)
     c->draw_pending = false;
     c->last_draw.is_list = false;
     c->cuts.clear();                 // a new stream is one segment
@@ -1622,7 +1667,8 @@ int single_scene_attributes(swr_context* c, const swr_vertex_attr* attributes, i
     launch_gather_attrs((const swr_vertex_attr*)c->attrs.p, vertex_count, (const int64_t*)c->indices.p, c->ni / 3,
                         (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
     HIP_TRY(c, hipGetLastError());
-    if (c->pose_active && (rc = enqueue_pose(c, true))) return rc;      // (the gather wrote the bind normals: pose them)
+    // (the gather wrote the uploaded normals: morph and pose them)
+    if ((c->pose_active || c->morph_active) && (rc = enqueue_pose(c, true))) return rc;
     if ((rc = wait_stream(c, c->stream, "attribute upload"))) return or_sticky(c, rc);
     c->has_attrs = true;
     return SWR_OK;
@@ -1682,6 +1728,110 @@ int single_pose_set(swr_context* c, const float* joints, int32_t joint_count) {
     if (bind) c->pose.clear(); else c->pose.assign(joints, joints + (size_t)joint_count * 16);
     if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
     if ((rc = wait_stream(c, c->stream, "pose"))) return or_sticky(c, rc);
+    return SWR_OK;
+}
+
+// One plane of deltas — target_count x nv x 3 floats of the caller's — into `dst` in the device layout, on c->stream (idle).  Packed
+// layout from page-locked memory: one copy straight from the caller's array.  Else through the pinned staging chunks of image 0, two
+// in flight, the host writing (and, SWR_TUNE_MORPH_PAD, padding) chunk k+1 while chunk k is on the link: no second full host copy.
+// `chunks` counts the chunks staged since the stream was last idle (the two planes of one call share the staging).
+int upload_deltas(swr_context* c, void* dst, const float* src, size_t count /* target_count * nv */, size_t& chunks) {
+    if (!count) return SWR_OK;
+    if (!SWR_TUNE_MORPH_PAD && is_pinned(src)) {
+        HIP_TRY(c, hipMemcpyAsync(dst, src, count * 12, hipMemcpyHostToDevice, c->stream));
+        return SWR_OK;
+    }
+    int rc = ensure_stage(c, 0);
+    if (rc) return rc;
+    constexpr size_t F = SWR_TUNE_MORPH_PAD ? 4 : 3;
+    const size_t per = swr_context::STAGE_BYTES / (F * 4);        // vectors per chunk
+    for (size_t at = 0; at < count; at += per) {
+        const size_t n = std::min(per, count - at), k = chunks++;
+        if (k >= 2 && (rc = poll_event(c, c->stage_ev[0][k & 1], "a staged copy of morph deltas", c->frame_no))) return rc;
+        float* st = (float*)c->stage[0][k & 1];
+        if (SWR_TUNE_MORPH_PAD)
+            for (size_t i = 0; i < n; i++) {
+                st[4 * i] = src[3 * (at + i)]; st[4 * i + 1] = src[3 * (at + i) + 1]; st[4 * i + 2] = src[3 * (at + i) + 2]; st[4 * i + 3] = 0.0f;
+            }
+        else memcpy(st, src + 3 * at, n * 12);
+        HIP_TRY(c, hipMemcpyAsync((uint8_t*)dst + at * F * 4, st, n * F * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipEventRecord(c->stage_ev[0][k & 1], c->stream));
+    }
+    return SWR_OK;
+}
+
+// swr_scene_morph: the morph targets of the resident scene (targets == NULL: none).  Every weight is 0 afterwards; skin and pose stay.
+int single_scene_morph(swr_context* c, const swr_morph_targets* t) {
+    if (const int f = sticky(c)) return f;
+    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "swr_scene_morph needs swr_scene_upload first");
+    if (t) {
+        if (t->vertex_count != c->nv)
+            return fail(c, SWR_ERR_BAD_ARG, "swr_scene_morph: targets of %lld vertices for %lld vertices", (long long)t->vertex_count, (long long)c->nv);
+        if (!t->position_deltas) return fail(c, SWR_ERR_BAD_ARG, "swr_scene_morph: position_deltas is NULL");
+        if (t->target_count < 1) return fail(c, SWR_ERR_BAD_ARG, "swr_scene_morph: target_count %d", t->target_count);
+        if (t->reserved != 0) return fail(c, SWR_ERR_BAD_ARG, "swr_scene_morph: reserved must be 0");
+        if (t->target_count > SWR_MORPH_MAX_TARGETS)
+            return fail(c, SWR_ERR_UNSUPPORTED, "swr_scene_morph: %d targets (at most %d)", t->target_count, SWR_MORPH_MAX_TARGETS);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the shape it was drawn in)
+    DevBuf dpos, dnrm;                          // the new planes: the old ones stay until these are filled
+    if (t) {
+        const size_t count = (size_t)t->target_count * (size_t)c->nv;
+        const size_t bytes = std::max<size_t>(16, count * (SWR_TUNE_MORPH_PAD ? 16 : 12));
+        auto undo = [&](int code) { if (dpos.p) (void)hipFree(dpos.p); if (dnrm.p) (void)hipFree(dnrm.p); return code; };
+        for (DevBuf* b : {&dpos, &dnrm}) {
+            if (b == &dnrm && !t->normal_deltas) break;
+            const hipError_t e = hipMalloc(&b->p, bytes);
+            if (e != hipSuccess) {
+                b->p = nullptr;
+                return undo(fail(c, SWR_ERR_NOMEM, "swr_scene_morph: hipMalloc(%zu) for the deltas failed: %s", bytes, hipGetErrorString(e)));
+            }
+            b->bytes = bytes;
+        }
+        size_t chunks = 0;
+        if ((rc = upload_deltas(c, dpos.p, t->position_deltas, count, chunks))) return undo(rc);
+        if (t->normal_deltas && (rc = upload_deltas(c, dnrm.p, t->normal_deltas, count, chunks))) return undo(rc);
+        if ((rc = wait_stream(c, c->stream, "morph target upload"))) return undo(or_sticky(c, rc));
+    }
+    const bool was_active = c->morph_active;
+    drop_morph(c);
+    if (t) {
+        c->morph_dpos = dpos; c->morph_dnrm = dnrm;
+        c->morph_targets = t->target_count;
+        c->morph_has_nrm = t->normal_deltas != nullptr;
+        c->morph_w.assign((size_t)t->target_count, 0.0f);
+    }
+    if (was_active) {                           // every weight is 0 now: the unmorphed scene, in the pose it has
+        if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
+        if ((rc = wait_stream(c, c->stream, "morph targets"))) return or_sticky(c, rc);
+    }
+    return SWR_OK;
+}
+
+// swr_morph_set: the resident scene under `weights` (NULL with weight_count 0: every weight 0), in effect when the call returns.
+int single_morph_set(swr_context* c, const float* weights, int32_t weight_count) {
+    if (const int f = sticky(c)) return f;
+    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "swr_morph_set needs swr_scene_upload first");
+    if (!c->morph_targets) return fail(c, SWR_ERR_BAD_ARG, "swr_morph_set needs swr_scene_morph first");
+    if (weights ? weight_count != c->morph_targets : weight_count != 0)
+        return fail(c, SWR_ERR_BAD_ARG, "swr_morph_set: %d weights%s for %d targets", weight_count, weights ? "" : " without an array",
+                    c->morph_targets);
+    if (!launch_morph_vertices)
+        return fail(c, SWR_ERR_HIP, "this build has no k_morph_vertices: there is no fallback for morph targets");
+    if (!launch_skin_vertices || !launch_skin_stream)
+        return fail(c, SWR_ERR_HIP, "this build has no k_skin_vertices: there is no fallback for skinned meshes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the shape it was drawn in)
+    bool any = false;
+    for (int32_t k = 0; weights && k < weight_count; k++) any = any || weights[k] != 0.0f;
+    if (weights) c->morph_w.assign(weights, weights + weight_count); else c->morph_w.assign((size_t)c->morph_targets, 0.0f);
+    if (!any && !c->morph_active) return SWR_OK;
+    c->morph_active = any;
+    if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
+    if ((rc = wait_stream(c, c->stream, "morph"))) return or_sticky(c, rc);
     return SWR_OK;
 }
 
@@ -1911,7 +2061,8 @@ int restream(swr_context* c, const std::vector<uint32_t>& cuts) {
         launch_gather_attrs((const swr_vertex_attr*)c->attrs.p, c->nv, (const int64_t*)c->indices.p, ntri,
                             (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
     HIP_TRY(c, hipGetLastError());
-    if (c->pose_active && (rc = enqueue_pose(c, c->has_attrs))) return rc;      // (the rebuild gathered the bind pose: pose it again)
+    // (the rebuild gathered the uploaded scene: morph and pose it again)
+    if ((c->pose_active || c->morph_active) && (rc = enqueue_pose(c, c->has_attrs))) return rc;
     if ((rc = wait_stream(c, c->stream, "stream rebuild (draw list)"))) return or_sticky(c, rc);
     c->cuts = cuts;
     return SWR_OK;
@@ -2527,7 +2678,7 @@ void destroy_single(swr_context* c) {
     DevBuf* bufs[] = {&c->redo_cnt, &c->vertices, &c->indices, &c->tri_rgb, &c->tri_xyz, &c->inv, &c->box64, &c->stream_scratch, &c->sort_temp,
                       &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth, &c->count_dev, &c->query_dev,
                       &c->query_tiles, &c->delta_base[0], &c->delta_base[1], &c->delta_flags, &c->delta_pack, &c->skin, &c->pose_dev, &c->posed,
-                      &c->posed_nrm};
+                      &c->posed_nrm, &c->morph_dpos, &c->morph_dnrm, &c->morph_list_dev, &c->morphed, &c->morphed_attrs};
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
@@ -2798,6 +2949,20 @@ int swr_pose_set(swr_context* c, const float* joints, int32_t joint_count) {
     c->scene_id = 0;      // (the same)
     if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_pose_set(k, joints, joint_count); });
     return single_pose_set(c, joints, joint_count);
+}
+
+int swr_scene_morph(swr_context* c, const swr_morph_targets* targets) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    c->scene_id = 0;      // the resident scene changes: a later swr_render must not take it for its own
+    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_scene_morph(k, targets); });
+    return single_scene_morph(c, targets);
+}
+
+int swr_morph_set(swr_context* c, const float* weights, int32_t weight_count) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    c->scene_id = 0;      // (the same)
+    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_morph_set(k, weights, weight_count); });
+    return single_morph_set(c, weights, weight_count);
 }
 
 int swr_material_set(swr_context* c, const swr_material* m) {

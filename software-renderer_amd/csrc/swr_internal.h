@@ -283,4 +283,17 @@ void launch_skin_vertices(const swr_vertex* vertices, const swr_vertex_attr* att
 void launch_skin_stream(const float4* pos, int pos_stride, const float4* nrm, int nrm_stride, int64_t nv, const int64_t* indices,
                         int64_t ntri, int reordered, float4* tri_xyz, float4* tri_nrm, float4* box64, hipStream_t s);
 
+// swr_morph.hip: morph targets.  The deltas live on the device as target-major planes of SWR_TUNE_MORPH_PAD ? 4 : 3
+// floats per vertex (the swr_api.hip upload packs them so): dpos[(target * nv + i) * floats ..], and dnrm the same.  `list` holds the
+// `active` targets whose weight is not zero, ascending, on the device.  launch_morph_vertices writes morphed[i] = vertices[i] with
+// p = p + weight * dpos[target][i] applied per list entry in order (include/swr.h "Morph targets"), colour and padding lanes copied,
+// and, attrs != NULL (then dnrm != NULL), morphed_attrs[i] = attrs[i] with the normal taken through the same loop over dnrm, uv
+// copied.  Every target of the list is below the resident target count (the host built the list).  All pointers are device memory.
+#ifndef SWR_TUNE_MORPH_PAD
+#define SWR_TUNE_MORPH_PAD 0       // deltas as 12 bytes per vertex and target (0) or as padded float4 (1): DESIGN.md §24 has the measurement
+#endif
+struct MorphEntry { uint32_t target; float weight; };
+void launch_morph_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, int64_t nv, const float* dpos, const float* dnrm,
+                           const MorphEntry* list, int32_t active, swr_vertex* morphed, swr_vertex_attr* morphed_attrs, hipStream_t s);
+
 }  // namespace swr
