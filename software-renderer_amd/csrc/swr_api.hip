@@ -36,35 +36,6 @@
 #include "swr_internal.h"
 #include "swr_frame_policy.h"
 
-// The host layer is also built without the kernels, against stand-in launch functions (tests/host/hip_stub); a stand-in set that
-// predates the supersampled resolve does not define its launch.  The reference is weak so that such a program still links; the library
-// always carries k_resolve, and a resolved read without it fails loudly (single_read_resolved).
-namespace swr {
-__attribute__((weak)) void launch_resolve(const void* color, const void* depth, void* color_out, void* depth_out, int width, int rows,
-                                          int factor, int depth_filter, hipStream_t s);
-// (the same for the visibility counts: a stand-in set without swr_count.hip still links, and swr_count_ids then fails loudly)
-__attribute__((weak)) void launch_count_ids(const uint32_t* ids, int width, int x0, int x1, int y0, int y1, int per_item,
-                                            const ListItem* items, uint32_t* counters, int64_t n, hipStream_t s);
-// (and for the depth queries: without swr_depth_query.hip swr_query_depth fails loudly)
-__attribute__((weak)) void launch_depth_query(const float* depth, int width, int rows, int row_begin, const swr_depth_box* boxes, int64_t n,
-                                              const uint32_t* large, int64_t nlarge, uint64_t total_area, void* scratch, uint32_t* passed,
-                                              hipStream_t s);
-// (and for the delta reads: without swr_delta.hip swr_read_*_delta fails loudly)
-__attribute__((weak)) void launch_delta(const uint32_t* cur, uint32_t* base, int have_base, int width, int rows, uint32_t* flags,
-                                        uint32_t* direct, hipStream_t s);
-__attribute__((weak)) void launch_delta_pack(const uint32_t* src, int width, int x0, int x1, int y0, int y1, uint32_t* out, hipStream_t s);
-// (and for the skinned meshes: without swr_skin.hip swr_pose_set fails loudly)
-__attribute__((weak)) void launch_skin_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, const swr_skin_vertex* skin, int64_t nv,
-                                                const float* joints, int32_t joint_count, swr_vertex* posed, float4* posed_nrm, hipStream_t s);
-__attribute__((weak)) void launch_skin_stream(const float4* pos, int pos_stride, const float4* nrm, int nrm_stride, int64_t nv,
-                                              const int64_t* indices, int64_t ntri, int reordered, float4* tri_xyz, float4* tri_nrm,
-                                              float4* box64, hipStream_t s);
-// (and for the morph targets: without swr_morph.hip swr_morph_set fails loudly)
-__attribute__((weak)) void launch_morph_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, int64_t nv, const float* dpos,
-                                                 const float* dnrm, const MorphEntry* list, int32_t active, swr_vertex* morphed,
-                                                 swr_vertex_attr* morphed_attrs, hipStream_t s);
-}
-
 using namespace swr;
 
 namespace {
@@ -76,6 +47,11 @@ thread_local bool tl_helper_thread = false;
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+};
+// page-locked host words one band keeps for itself (what a query's answer or a flag table is copied into)
+struct HostBuf {
+    uint32_t* p = nullptr;
+    size_t words = 0;
 };
 
 #ifndef SWR_TUNE_HELPER_SPIN
@@ -244,21 +220,18 @@ struct swr_context {
     // visibility counts: the n + 1 counters of a query on the device (zeroed before every query, k_count_ids adds) and
     // the band's own page-locked copy of them, both sized by the largest query so far
     DevBuf count_dev;
-    uint32_t* count_host = nullptr;
-    size_t count_host_words = 0;
+    HostBuf count_host;
     // depth queries: the n boxes, the list of the large ones and the n counts of a query, in this order, on the device and
     // in the band's own page-locked staging (words), both sized by the largest query so far; the tile summary k_depth_tiles writes
     DevBuf query_dev, query_tiles;
-    uint32_t* query_host = nullptr;
-    size_t query_host_words = 0;
+    HostBuf query_host;
     const uint32_t* query_passed = nullptr;     // the counts of the last query inside query_host
     // delta reads: per image kind (0 colour, 1 depth) the band's baseline — the image the last delta read delivered —
     // and whether it holds one; the tile flags k_delta_tiles writes, on the device and in the band's own page-locked copy; the rows of
     // a changed rectangle gathered for one linear copy; what the band's last delta read did (a group adds the bands up)
     DevBuf delta_base[2], delta_flags, delta_pack;
     bool delta_valid[2] = {false, false};
-    uint32_t* delta_host = nullptr;
-    size_t delta_host_words = 0;
+    HostBuf delta_host;
     swr_delta_stats delta_stats{};
     int fb_cur = 0;                    // the next swr_draw renders into this buffer
     int fb_last = 0;                    // the buffer of the last swr_draw (what swr_present / swr_read_* copy)
@@ -543,6 +516,15 @@ int ensure(swr_context* c, DevBuf& b, size_t bytes) {
         return fail(c, SWR_ERR_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
     }
     b.bytes = want;
+    return SWR_OK;
+}
+
+int ensure_host(swr_context* c, HostBuf& b, size_t words) {
+    if (b.words >= words) return SWR_OK;
+    if (b.p) { HIP_TRY(c, hipHostFree(b.p)); b.p = nullptr; b.words = 0; }
+    const size_t want = words + words / 8;
+    HIP_TRY(c, hipHostMalloc((void**)&b.p, want * 4, hipHostMallocDefault));
+    b.words = want;
     return SWR_OK;
 }
 
@@ -1470,15 +1452,11 @@ int enqueue_present(swr_context* c, void* color_full, float* depth_full);
 // positions, the normals when with_nrm, the group boxes — into the context's shape: the morph when a weight is not zero, then the pose
 // reading the morphed arrays, then the stream from whichever array is last.  With neither, back to what the upload built, bit for bit.
 int enqueue_pose(swr_context* c, bool with_nrm) {
-    if (!launch_skin_vertices || !launch_skin_stream)
-        return fail(c, SWR_ERR_HIP, "this build has no k_skin_vertices: there is no fallback for skinned meshes");
     const int64_t ntri = c->ni / 3;
     int rc;
     const swr_vertex* v = (const swr_vertex*)c->vertices.p;
     const swr_vertex_attr* at = with_nrm ? (const swr_vertex_attr*)c->attrs.p : nullptr;
     if (c->morph_active) {
-        if (!launch_morph_vertices)
-            return fail(c, SWR_ERR_HIP, "this build has no k_morph_vertices: there is no fallback for morph targets");
         const bool mnrm = with_nrm && c->morph_has_nrm;         // (else the normals stay as uploaded)
         c->morph_list.clear();
         for (int32_t t = 0; t < c->morph_targets; t++)
@@ -1718,8 +1696,6 @@ int single_pose_set(swr_context* c, const float* joints, int32_t joint_count) {
     if (!bind && (int64_t)joint_count <= c->skin_max_joint)
         return fail(c, SWR_ERR_BAD_ARG, "swr_pose_set: %d joints, but the skin uses joint index %lld", joint_count,
                     (long long)c->skin_max_joint);
-    if (!launch_skin_vertices || !launch_skin_stream)
-        return fail(c, SWR_ERR_HIP, "this build has no k_skin_vertices: there is no fallback for skinned meshes");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
     if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the pose it was drawn in)
@@ -1818,10 +1794,6 @@ int single_morph_set(swr_context* c, const float* weights, int32_t weight_count)
     if (weights ? weight_count != c->morph_targets : weight_count != 0)
         return fail(c, SWR_ERR_BAD_ARG, "swr_morph_set: %d weights%s for %d targets", weight_count, weights ? "" : " without an array",
                     c->morph_targets);
-    if (!launch_morph_vertices)
-        return fail(c, SWR_ERR_HIP, "this build has no k_morph_vertices: there is no fallback for morph targets");
-    if (!launch_skin_vertices || !launch_skin_stream)
-        return fail(c, SWR_ERR_HIP, "this build has no k_skin_vertices: there is no fallback for skinned meshes");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
     if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the shape it was drawn in)
@@ -2383,7 +2355,6 @@ int single_read_resolved(swr_context* c, swr_resolve rs, void* color_dst, float*
     const size_t row = (size_t)(c->tg.width / S) * 4, bytes = row * (size_t)(rows / S);
     if (color_dst && (rc = ensure(c, c->rs_color, bytes))) return rc;
     if (depth_dst && (rc = ensure(c, c->rs_depth, bytes))) return rc;
-    if (!launch_resolve) return fail(c, SWR_ERR_HIP, "this build has no k_resolve: there is no fallback for the supersampled resolve");
     launch_resolve(color_dst ? c->color[fb].p : nullptr, depth_dst ? c->depth[fb].p : nullptr, c->rs_color.p, c->rs_depth.p,
                    c->tg.width, rows, S, rs.depth_filter, c->stream);
     HIP_TRY(c, hipGetLastError());
@@ -2413,7 +2384,7 @@ int check_count_rect(swr_context* c, const swr_id_count& q, const Target& t) {
     return SWR_OK;
 }
 
-// swr_count_ids on one band: the part of the rectangle in the band's rows, counted into c->count_host[0 .. n] (word n: SWR_ID_NONE).
+// swr_count_ids on one band: the part of the rectangle in the band's rows, counted into c->count_host.p[0 .. n] (word n: SWR_ID_NONE).
 // A band the rectangle misses, or one without tiles, launches nothing and leaves zeros there.
 int single_count_ids(swr_context* c, swr_id_count q, const uint32_t* counts, int64_t n) {
     if (const int f = sticky(c)) return f;
@@ -2431,23 +2402,17 @@ int single_count_ids(swr_context* c, swr_id_count q, const uint32_t* counts, int
                     per_item ? "draw items" : "primitives");
     if ((rc = single_sync(c))) return rc;       // (an overflowed last frame is repaired here)
     const size_t words = (size_t)n + 1;
-    if (c->count_host_words < words) {
-        if (c->count_host) { HIP_TRY(c, hipHostFree(c->count_host)); c->count_host = nullptr; c->count_host_words = 0; }
-        const size_t want = words + words / 8;
-        HIP_TRY(c, hipHostMalloc((void**)&c->count_host, want * 4, hipHostMallocDefault));
-        c->count_host_words = want;
-    }
-    memset(c->count_host, 0, words * 4);
+    if ((rc = ensure_host(c, c->count_host, words))) return rc;
+    memset(c->count_host.p, 0, words * 4);
     const int y0 = std::max<int>(q.y0, c->tg.row_begin), y1 = std::min<int>(q.y1, c->tg.row_end);
     if (tiles_of(c->tg) == 0 || y0 >= y1 || q.x0 >= q.x1) return SWR_OK;
     if ((rc = ensure(c, c->count_dev, words * 4))) return rc;
-    if (!launch_count_ids) return fail(c, SWR_ERR_HIP, "this build has no k_count_ids: there is no fallback for the visibility counts");
     HIP_TRY(c, hipMemsetAsync(c->count_dev.p, 0, words * 4, c->stream));
     const ListItem* items = (per_item && c->last_draw.is_list) ? (const ListItem*)c->slot[c->last_slot].items.p : nullptr;
     launch_count_ids((const uint32_t*)c->ids[c->fb_last].p, c->tg.width, q.x0, q.x1, y0 - c->tg.row_begin, y1 - c->tg.row_begin,
                      per_item ? 1 : 0, items, (uint32_t*)c->count_dev.p, n, c->stream);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->count_host, c->count_dev.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->count_host.p, c->count_dev.p, words * 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = wait_stream(c, c->stream, "raster stream (visibility counts)"))) return or_sticky(c, rc);
     return SWR_OK;
 }
@@ -2486,15 +2451,10 @@ int single_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, co
     c->query_passed = nullptr;
     if (n == 0) return SWR_OK;
     const size_t nn = (size_t)n, words = nn * 8 + nn + nn;      // boxes | large | passed
-    if (c->query_host_words < words) {
-        if (c->query_host) { HIP_TRY(c, hipHostFree(c->query_host)); c->query_host = nullptr; c->query_host_words = 0; }
-        const size_t want = words + words / 8;
-        HIP_TRY(c, hipHostMalloc((void**)&c->query_host, want * 4, hipHostMallocDefault));
-        c->query_host_words = want;
-    }
-    uint32_t* large = c->query_host + nn * 8;
-    uint32_t* out = c->query_host + nn * 9;
-    memcpy(c->query_host, boxes, nn * 32);
+    if ((rc = ensure_host(c, c->query_host, words))) return rc;
+    uint32_t* large = c->query_host.p + nn * 8;
+    uint32_t* out = c->query_host.p + nn * 9;
+    memcpy(c->query_host.p, boxes, nn * 32);
     memset(out, 0, nn * 4);
     c->query_passed = out;
     // the boxes' parts in this band: their total area, and the ones large enough to be split across workgroups
@@ -2514,9 +2474,8 @@ int single_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, co
     if (tiles_of(c->tg) == 0 || total_area == 0 || c->src_clear) return SWR_OK;
     if ((rc = ensure(c, c->query_dev, words * 4))) return rc;
     if ((rc = ensure(c, c->query_tiles, depth_query_scratch_bytes(c->tg.width, c->tg.row_end - c->tg.row_begin)))) return rc;
-    if (!launch_depth_query) return fail(c, SWR_ERR_HIP, "this build has no k_depth_boxes: there is no fallback for the depth queries");
     uint32_t* dev = (uint32_t*)c->query_dev.p;
-    HIP_TRY(c, hipMemcpyAsync(dev, c->query_host, (nn * 8 + nlarge) * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dev, c->query_host.p, (nn * 8 + nlarge) * 4, hipMemcpyHostToDevice, c->stream));
     launch_depth_query((const float*)c->depth[c->fb_last].p, c->tg.width, c->tg.row_end - c->tg.row_begin, c->tg.row_begin,
                        (const swr_depth_box*)dev, n, dev + nn * 8, (int64_t)nlarge, total_area, c->query_tiles.p, dev + nn * 9, c->stream);
     HIP_TRY(c, hipGetLastError());
@@ -2552,14 +2511,7 @@ int single_read_delta(swr_context* c, int img, void* dst) {
     if (base.bytes < bytes) c->delta_valid[img] = false;        // (never: a target of another size has dropped the baseline already)
     if ((rc = ensure(c, base, bytes))) return rc;
     if ((rc = ensure(c, c->delta_flags, (size_t)tiles * 4))) return rc;
-    if (c->delta_host_words < (size_t)tiles) {
-        if (c->delta_host) { HIP_TRY(c, hipHostFree(c->delta_host)); c->delta_host = nullptr; c->delta_host_words = 0; }
-        const size_t want = (size_t)tiles + (size_t)tiles / 8;
-        HIP_TRY(c, hipHostMalloc((void**)&c->delta_host, want * 4, hipHostMallocDefault));
-        c->delta_host_words = want;
-    }
-    if (!launch_delta || !launch_delta_pack)
-        return fail(c, SWR_ERR_HIP, "this build has no k_delta_tiles: there is no fallback for the delta reads");
+    if ((rc = ensure_host(c, c->delta_host, (size_t)tiles))) return rc;
     const uint32_t* cur = (const uint32_t*)fb_image(c, fb, img);
     uint8_t* band_dst = (uint8_t*)dst + (size_t)c->tg.row_begin * row;
     const uint64_t frame = c->frame_no ? c->frame_no - 1 : 0;
@@ -2591,14 +2543,14 @@ int single_read_delta(swr_context* c, int img, void* dst) {
     }
     launch_delta(cur, (uint32_t*)base.p, 1, W, rows, (uint32_t*)c->delta_flags.p, direct, c->stream);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->delta_host, c->delta_flags.p, (size_t)tiles * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->delta_host.p, c->delta_flags.p, (size_t)tiles * 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = wait_stream(c, c->stream, "raster stream (delta read)"))) return or_sticky(c, rc);
     // the changed tiles: their number, their bounding box in tiles, and the pixels they hold
     int tx0 = c->tg.tiles_x, tx1 = -1, ty0 = c->tg.tiles_y, ty1 = -1;
     int64_t changed = 0, changed_px = 0;
     for (int ty = 0; ty < c->tg.tiles_y; ty++)
         for (int tx = 0; tx < c->tg.tiles_x; tx++) {
-            if (!c->delta_host[(size_t)ty * c->tg.tiles_x + tx]) continue;
+            if (!c->delta_host.p[(size_t)ty * c->tg.tiles_x + tx]) continue;
             changed++;
             changed_px += (int64_t)(std::min(W, (tx + 1) * TILE_W) - tx * TILE_W) * (std::min(rows, (ty + 1) * TILE_H) - ty * TILE_H);
             tx0 = std::min(tx0, tx); tx1 = std::max(tx1, tx);
@@ -2714,9 +2666,7 @@ void destroy_single(swr_context* c) {
     if (c->h_pairs) hipHostFree(c->h_pairs);
     if (c->h_misc) hipHostFree(c->h_misc);
     if (c->h_clip) hipHostFree(c->h_clip);
-    if (c->count_host) hipHostFree(c->count_host);
-    if (c->query_host) hipHostFree(c->query_host);
-    if (c->delta_host) hipHostFree(c->delta_host);
+    for (HostBuf* b : {&c->count_host, &c->query_host, &c->delta_host}) if (b->p) hipHostFree(b->p);
     if (c->ev_ok)
         for (int r = 0; r < swr_context::RING; r++)
             for (int i = 0; i < 5; i++) hipEventDestroy(c->ev[r][i]);
@@ -2817,6 +2767,10 @@ int group_run(swr_context* g, F fn) {
     }
     return first;
 }
+
+// an entry point that waits: fn on every band of a group, or on the one context
+template <class F>
+int fan(swr_context* c, F fn) { return is_group(c) ? group_run(c, fn) : fn(c); }
 
 // fire and forget (swr_draw / swr_present on a group): errors surface at the next group_run
 template <class F>
@@ -2925,44 +2879,38 @@ int swr_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vertex_
                      const int64_t* indices, int64_t index_count) {
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // the resident scene changes: a later swr_render must not take it for its own
-    if (is_group(c))   // replicated: every device reads the caller's arrays itself, over its own PCIe link
-        return group_run(c, [=](swr_context* k) { return single_scene_upload(k, vertices, vertex_count, indices, index_count); });
-    return single_scene_upload(c, vertices, vertex_count, indices, index_count);
+    // (a group replicates the scene: every device reads the caller's arrays itself, over its own PCIe link)
+    return fan(c, [=](swr_context* k) { return single_scene_upload(k, vertices, vertex_count, indices, index_count); });
 }
 
 int swr_scene_attributes(swr_context* c, const swr_vertex_attr* attributes, int64_t vertex_count) {
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // the resident scene changes: a later swr_render must not take it for its own
-    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_scene_attributes(k, attributes, vertex_count); });
-    return single_scene_attributes(c, attributes, vertex_count);
+    return fan(c, [=](swr_context* k) { return single_scene_attributes(k, attributes, vertex_count); });
 }
 
 int swr_scene_skin(swr_context* c, const swr_skin_vertex* skin, int64_t vertex_count) {
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // the resident scene changes: a later swr_render must not take it for its own
-    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_scene_skin(k, skin, vertex_count); });
-    return single_scene_skin(c, skin, vertex_count);
+    return fan(c, [=](swr_context* k) { return single_scene_skin(k, skin, vertex_count); });
 }
 
 int swr_pose_set(swr_context* c, const float* joints, int32_t joint_count) {
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // (the same)
-    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_pose_set(k, joints, joint_count); });
-    return single_pose_set(c, joints, joint_count);
+    return fan(c, [=](swr_context* k) { return single_pose_set(k, joints, joint_count); });
 }
 
 int swr_scene_morph(swr_context* c, const swr_morph_targets* targets) {
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // the resident scene changes: a later swr_render must not take it for its own
-    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_scene_morph(k, targets); });
-    return single_scene_morph(c, targets);
+    return fan(c, [=](swr_context* k) { return single_scene_morph(k, targets); });
 }
 
 int swr_morph_set(swr_context* c, const float* weights, int32_t weight_count) {
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // (the same)
-    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_morph_set(k, weights, weight_count); });
-    return single_morph_set(c, weights, weight_count);
+    return fan(c, [=](swr_context* k) { return single_morph_set(k, weights, weight_count); });
 }
 
 int swr_material_set(swr_context* c, const swr_material* m) {
@@ -2990,8 +2938,7 @@ int swr_blend_set(swr_context* c, const swr_blend* b) {
 int swr_texture_upload(swr_context* c, const void* bgra8, int32_t width, int32_t height) {
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // the resident scene changes: a later swr_render must not take it for its own
-    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_texture_upload(k, bgra8, width, height); });
-    return single_texture_upload(c, bgra8, width, height);
+    return fan(c, [=](swr_context* k) { return single_texture_upload(k, bgra8, width, height); });
 }
 
 int swr_target_set(swr_context* c, int64_t width, int64_t height, int64_t row_begin, int64_t row_end) {
@@ -3043,17 +2990,13 @@ int swr_draw_list(swr_context* c, const swr_draw_item* items, int32_t item_count
 
 int swr_target_write(swr_context* c, const void* color_full, const float* depth_full) {
     if (!c) return SWR_ERR_BAD_ARG;
-    if (is_group(c)) {
-        if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_target_write needs swr_target_set first");
-        return group_run(c, [=](swr_context* k) { return single_target_write(k, color_full, depth_full); });
-    }
-    return single_target_write(c, color_full, depth_full);
+    if (is_group(c) && !c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_target_write needs swr_target_set first");
+    return fan(c, [=](swr_context* k) { return single_target_write(k, color_full, depth_full); });
 }
 
 int swr_sync(swr_context* c) {
     if (!c) return SWR_ERR_BAD_ARG;
-    if (is_group(c)) return group_run(c, [](swr_context* k) { return single_sync(k); });
-    return single_sync(c);
+    return fan(c, [](swr_context* k) { return single_sync(k); });
 }
 
 int swr_present(swr_context* c, void* color_full, float* depth_full) {
@@ -3066,26 +3009,22 @@ int swr_present(swr_context* c, void* color_full, float* depth_full) {
 
 int swr_present_wait(swr_context* c) {
     if (!c) return SWR_ERR_BAD_ARG;
-    if (is_group(c)) return group_run(c, [](swr_context* k) { return single_present_wait(k); });
-    return single_present_wait(c);
+    return fan(c, [](swr_context* k) { return single_present_wait(k); });
 }
 
 int swr_read_color(swr_context* c, void* dst) {
     if (!c || !dst) return SWR_ERR_BAD_ARG;
-    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_read(k, 0, dst); });
-    return single_read(c, 0, dst);
+    return fan(c, [=](swr_context* k) { return single_read(k, 0, dst); });
 }
 
 int swr_read_depth(swr_context* c, float* dst) {
     if (!c || !dst) return SWR_ERR_BAD_ARG;
-    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_read(k, 1, dst); });
-    return single_read(c, 1, dst);
+    return fan(c, [=](swr_context* k) { return single_read(k, 1, dst); });
 }
 
 int swr_read_ids(swr_context* c, uint32_t* dst) {
     if (!c || !dst) return SWR_ERR_BAD_ARG;
-    if (is_group(c)) return group_run(c, [=](swr_context* k) { return single_read(k, 2, dst); });
-    return single_read(c, 2, dst);
+    return fan(c, [=](swr_context* k) { return single_read(k, 2, dst); });
 }
 
 int swr_count_ids(swr_context* c, const swr_id_count* query, uint32_t* counts, int64_t n, uint32_t* none) {
@@ -3094,8 +3033,8 @@ int swr_count_ids(swr_context* c, const swr_id_count* query, uint32_t* counts, i
     if (!is_group(c)) {
         const int rc = single_count_ids(c, q, counts, n);
         if (rc) return rc;
-        if (n) memcpy(counts, c->count_host, (size_t)n * 4);
-        if (none) *none = c->count_host[n];
+        if (n) memcpy(counts, c->count_host.p, (size_t)n * 4);
+        if (none) *none = c->count_host.p[n];
         return SWR_OK;
     }
     // a group checks what it can see before any band is touched; every band counts into staging of its own, and the caller's array is
@@ -3109,8 +3048,8 @@ int swr_count_ids(swr_context* c, const swr_id_count* query, uint32_t* counts, i
     if (n) memset(counts, 0, (size_t)n * 4);
     uint32_t nn = 0;
     for (const swr_context* k : c->kids) {
-        for (int64_t i = 0; i < n; i++) counts[i] += k->count_host[i];
-        nn += k->count_host[n];
+        for (int64_t i = 0; i < n; i++) counts[i] += k->count_host.p[i];
+        nn += k->count_host.p[n];
     }
     if (none) *none = nn;
     return SWR_OK;
@@ -3198,7 +3137,7 @@ int swr_delta_reset(swr_context* c, uint32_t images) {
         if (images & SWR_DELTA_DEPTH) k->delta_valid[1] = false;
         return (int)SWR_OK;
     };
-    return is_group(c) ? group_run(c, reset) : reset(c);
+    return fan(c, reset);
 }
 
 // the resolved read of one or both images (NULL: not wanted); a group checks what it can see before any band is touched

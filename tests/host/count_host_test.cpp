@@ -1,67 +1,16 @@
 // The host side of the visibility counts (software-renderer_amd/csrc/swr_api.hip: single_count_ids, the group fan-out and sum,
 // swr_count_ids) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The stand-in
-// set of stub_launch.cpp has no count launch: this program defines swr::launch_count_ids itself, as a plain CPU loop over the header's
-// definition run as a "kernel" of the fake stream.  The stand-in raster leaves the ID image at zero, so the loop ADDS a pattern of
+// of swr::launch_count_ids (stub_launch.cpp) is a plain CPU loop over the header's definition run as a "kernel" of the fake stream.  The stand-in raster leaves the ID image at zero, so the loop ADDS a pattern of
 // its own to what it reads: the ID of band-local pixel (x, y) is ids[y][x] + pattern(x, y).  The band's rows are read (a rectangle
 // clipped wrongly is an out-of-bounds read the address sanitizer reports, or a wrong count), the counters are added to, never
 // assigned (a buffer that was not zeroed shows), and counters[n] is written (a buffer sized too small is reported).
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ software-renderer_amd/csrc/swr_api.hip \
 //       tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp tests/host/count_host_test.cpp -lpthread
-#include <atomic>
-#include <cstdio>
-#include <cstring>
+#include <algorithm>
 #include <string>
 #include <vector>
 
-#include "../../include/swr.h"
-#include <hip/hip_runtime.h>
-#include "../../software-renderer_amd/csrc/swr_internal.h"
-
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); fails++; } } while (0)
-
-static std::atomic<uint32_t> g_total{0};      // primitives of the frame being counted: the pattern's IDs are below it
-static std::atomic<int> g_launches{0};
-
-// the ID the pattern gives band-local pixel (x, y): 0 .. total - 1, or SWR_ID_NONE
-static uint32_t pattern(uint32_t x, uint32_t y, uint32_t total) {
-    const uint32_t v = (x * 7u + y * 13u + (x >> 3) * (y >> 2)) % (total + 1u);
-    return v == total ? SWR_ID_NONE : v;
-}
-
-#ifndef COUNT_HOST_NO_LAUNCH
-namespace swr {
-void launch_count_ids(const uint32_t* ids, int width, int x0, int x1, int y0, int y1, int per_item, const ListItem* items,
-                      uint32_t* counters, int64_t n, hipStream_t s) {
-    g_launches++;
-    fake_enqueue(s, [=] {
-        const uint32_t total = g_total.load();
-        for (int y = y0; y < y1; y++)
-            for (int x = x0; x < x1; x++) {
-                uint32_t id = ids[(size_t)y * width + x] + pattern((uint32_t)x, (uint32_t)y, total);
-                int64_t slot = n;
-                if (id != SWR_ID_NONE) {
-                    if (!per_item) slot = id;
-                    else if (!items) slot = 0;
-                    else { slot = 0; for (int64_t k = 0; k < n; k++) if (items[k].vbase <= id) slot = k; }
-                }
-                counters[slot] += 1;
-            }
-    }, nullptr, "k_count_ids");
-}
-}  // namespace swr
-#endif
-
-struct Bands { std::vector<int64_t> r0, r1; };
-static Bands bands_of(swr_context* c) {
-    Bands b;
-    for (int k = 0; k < swr_context_bands(c); k++) {
-        int64_t a = 0, e = 0;
-        CHECK(swr_context_band_info(c, k, nullptr, &a, &e) == SWR_OK);
-        b.r0.push_back(a); b.r1.push_back(e);
-    }
-    return b;
-}
+#include "host_test.h"
 
 // what the header defines, over the pattern: per band, the band-local rows of the rectangle
 static void expect(const Bands& b, const swr_id_count& q, uint32_t total, const std::vector<uint32_t>& vbase /* per item; empty: per primitive */,
@@ -71,7 +20,7 @@ static void expect(const Bands& b, const swr_id_count& q, uint32_t total, const 
     for (size_t k = 0; k < b.r0.size(); k++)
         for (int64_t y = std::max<int64_t>(q.y0, b.r0[k]); y < std::min<int64_t>(q.y1, b.r1[k]); y++)
             for (int x = q.x0; x < q.x1; x++) {
-                const uint32_t id = pattern((uint32_t)x, (uint32_t)(y - b.r0[k]), total);
+                const uint32_t id = count_pattern((uint32_t)x, (uint32_t)(y - b.r0[k]), total);
                 if (id == SWR_ID_NONE) { none++; continue; }
                 if (q.group == SWR_COUNT_PER_PRIMITIVE) { counts[id]++; continue; }
                 size_t slot = 0;
@@ -126,7 +75,7 @@ static void scenario(uint32_t devices) {
     CHECK(swr_draw(c, m, SWR_FLAG_DEPTH_TEST) == SWR_OK);
     CHECK(swr_count_ids(c, &whole, big.data(), 100, nullptr) == SWR_ERR_BAD_ARG);     // drawn without the flag
     CHECK(swr_draw(c, m, Z) == SWR_OK);
-    g_total = 100;
+    g_count_total = 100;
     const std::vector<uint32_t> none_v;
     // rectangles: the whole target, inside one band, across band borders, missing the last band(s), columns, one pixel, empty ones
     const int rects[][4] = {{0, 0, W, H}, {3, 70, 97, 100}, {1, 50, 66, 150}, {0, 0, W, 40}, {99, 0, 100, H}, {0, 199, W, 200},
@@ -139,15 +88,15 @@ static void scenario(uint32_t devices) {
     }
     // a rectangle that misses every band launches nothing
     {
-        const int before = g_launches.load();
+        const int before = g_count_launches.load();
         swr_id_count q{SWR_COUNT_PER_PRIMITIVE, 5, 7, 5, 90, {0, 0, 0}};
         query(c, b, q, 100, none_v, false, 100);
-        CHECK(g_launches.load() == before);
+        CHECK(g_count_launches.load() == before);
         if (devices == 3) {             // rows of the first band only: one launch per query
             swr_id_count one{SWR_COUNT_PER_PRIMITIVE, 0, 0, W, (int)b.r1[0], {0, 0, 0}};
             uint32_t nn = 0;
             CHECK(swr_count_ids(c, &one, big.data(), 100, &nn) == SWR_OK);
-            CHECK(g_launches.load() == before + 1);
+            CHECK(g_count_launches.load() == before + 1);
         }
     }
     // every refusal of the header; nothing is written, and the context goes on working
@@ -187,7 +136,7 @@ static void scenario(uint32_t devices) {
             vbase.push_back(total); total += (uint32_t)count[k];
         }
         CHECK(swr_draw_list(c, it, 7, Z) == SWR_OK);
-        g_total = total;
+        g_count_total = total;
         for (const auto& r : rects) {
             swr_id_count q{SWR_COUNT_PER_ITEM, r[0], r[1], r[2], r[3], {0, 0, 0}};
             query(c, b, q, total, vbase, true, 7);
@@ -204,7 +153,7 @@ static void scenario(uint32_t devices) {
         CHECK(std::string(swr_last_error(c)).find("75 primitives") != std::string::npos);
         // a list without items: n == 0 in both groups, counts may be NULL
         CHECK(swr_draw_list(c, nullptr, 0, Z) == SWR_OK);
-        g_total = 0;
+        g_count_total = 0;
         for (int group : {SWR_COUNT_PER_PRIMITIVE, SWR_COUNT_PER_ITEM}) {
             swr_id_count e{group, 2, 3, 71, 181, {0, 0, 0}};
             uint32_t nn = 0;
@@ -217,7 +166,7 @@ static void scenario(uint32_t devices) {
     for (int prims : {10, 5000, 100}) {
         upload(c, prims);
         CHECK(swr_draw(c, m, Z) == SWR_OK);
-        g_total = (uint32_t)prims;
+        g_count_total = (uint32_t)prims;
         query(c, b, whole, (uint32_t)prims, none_v, false, prims);
         swr_id_count q{SWR_COUNT_PER_ITEM, 1, 1, W - 1, H - 1, {0, 0, 0}};
         query(c, b, q, (uint32_t)prims, none_v, false, 1);
@@ -250,7 +199,7 @@ static void one_band_of_a_target() {
     float m[16];
     ident(m);
     CHECK(swr_draw(c, m, Z) == SWR_OK);
-    g_total = 40;
+    g_count_total = 40;
     const Bands b = bands_of(c);
     const std::vector<uint32_t> none_v;
     const int rects[][4] = {{0, 0, 80, 160}, {5, 40, 70, 90}, {5, 0, 70, 32}, {5, 96, 70, 160}, {79, 95, 80, 96}};
@@ -289,37 +238,12 @@ static void failed_context(uint32_t devices) {
     swr_context_destroy(c);
 }
 
-// -DCOUNT_HOST_NO_LAUNCH: the program links without a count launch, as the older stand-alone programs do, and a query that would
-// need the kernel fails loudly instead of answering
-static void without_the_kernel() {
-    swr_config cfg{0, 1, 5000, 0};
-    swr_context* c = nullptr;
-    CHECK(swr_context_create(&cfg, &c) == SWR_OK);
-    upload(c, 100);
-    CHECK(swr_target_set(c, 64, 64, 0, 64) == SWR_OK);
-    float m[16];
-    ident(m);
-    CHECK(swr_draw(c, m, Z) == SWR_OK);
-    swr_id_count q{SWR_COUNT_PER_PRIMITIVE, 0, 0, 64, 64, {0, 0, 0}};
-    std::vector<uint32_t> got(100);
-    CHECK(swr_count_ids(c, &q, got.data(), 100, nullptr) == SWR_ERR_HIP);
-    CHECK(std::string(swr_last_error(c)).find("k_count_ids") != std::string::npos);
-    CHECK(swr_sync(c) == SWR_OK);       // (not a failed context: only this call cannot be answered)
-    swr_context_destroy(c);
-}
-
 int main() {
     fake_kernel_delay_us(0);
-#ifdef COUNT_HOST_NO_LAUNCH
-    without_the_kernel();
-    std::printf(fails ? "count host test: %d failures\n" : "count host test: ok\n", fails);
-    return fails ? 1 : 0;
-#endif
     scenario(1);
     scenario(3);
     one_band_of_a_target();
     failed_context(1);
     failed_context(2);
-    std::printf(fails ? "count host test: %d failures\n" : "count host test: ok\n", fails);
-    return fails ? 1 : 0;
+    return report("count host test");
 }

@@ -1,25 +1,16 @@
 // The host side of the delta reads (software-renderer_amd/csrc/swr_api.hip: single_read_delta, the group fan-out and sum,
 // swr_read_color_delta / swr_read_depth_delta / swr_delta_reset / swr_render_delta) on the fake HIP runtime of tests/host/hip_stub,
-// under the address and undefined-behaviour sanitizers.  The stand-in set of stub_launch.cpp has no delta launch: this program defines
-// swr::launch_delta and swr::launch_delta_pack itself, as plain CPU loops over the header's definition run as "kernels" of the fake
-// stream.  The images are patterns written with swr_target_write, so the loops read the band's own rows, and a baseline, a flag table
+// under the address and undefined-behaviour sanitizers.  The stand-ins of swr::launch_delta and swr::launch_delta_pack
+// (stub_launch.cpp) are plain CPU loops over the header's definition run as "kernels" of the fake stream.  The images are patterns written with swr_target_write, so the loops read the band's own rows, and a baseline, a flag table
 // or a staging buffer sized too small is an out-of-bounds access the address sanitizer reports.  What is checked is the host side:
 // the rectangle and the counts it derives from the flag table, the rows it moves into the caller's image, and what it leaves alone.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ software-renderer_amd/csrc/swr_api.hip \
 //       tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp tests/host/delta_host_test.cpp -lpthread
 #include <algorithm>
-#include <atomic>
-#include <cstdio>
-#include <cstring>
 #include <string>
 #include <vector>
 
-#include "../../include/swr.h"
-#include <hip/hip_runtime.h>
-#include "../../software-renderer_amd/csrc/swr_internal.h"
-
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); fails++; } } while (0)
+#include "host_test.h"
 
 // (the library stores the changed tiles of a page-locked destination from the compare itself; built with -DSWR_TUNE_DELTA_DIRECT=0 it
 // gathers the rectangle and copies it through the stage chunks, as it always does for a pageable destination)
@@ -28,50 +19,6 @@ static int fails = 0;
 #else
 #define SWR_TUNE_DELTA_DIRECT_TEST SWR_TUNE_DELTA_DIRECT
 #endif
-
-static std::atomic<int> g_compares{0}, g_packs{0}, g_directs{0};
-
-#ifndef DELTA_HOST_NO_LAUNCH
-namespace swr {
-void launch_delta(const uint32_t* cur, uint32_t* base, int have_base, int width, int rows, uint32_t* flags, uint32_t* direct, hipStream_t s) {
-    g_compares++;
-    if (direct) g_directs++;
-    fake_enqueue(s, [=] {
-        const int tx_n = (width + 63) / 64, ty_n = (rows + 31) / 32;
-        for (int ty = 0; ty < ty_n; ty++)
-            for (int tx = 0; tx < tx_n; tx++) {
-                const int x0 = tx * 64, x1 = std::min(width, x0 + 64), y0 = ty * 32, y1 = std::min(rows, y0 + 32);
-                bool changed = !have_base;
-                for (int y = y0; y < y1 && !changed; y++)
-                    changed = memcmp(cur + (size_t)y * width + x0, base + (size_t)y * width + x0, (size_t)(x1 - x0) * 4) != 0;
-                flags[(size_t)ty * tx_n + tx] = changed ? 1u : 0u;
-                if (!changed) continue;
-                for (int y = y0; y < y1; y++) {
-                    memcpy(base + (size_t)y * width + x0, cur + (size_t)y * width + x0, (size_t)(x1 - x0) * 4);
-                    if (direct) memcpy(direct + (size_t)y * width + x0, cur + (size_t)y * width + x0, (size_t)(x1 - x0) * 4);
-                }
-            }
-    }, nullptr, "k_delta_tiles");
-}
-void launch_delta_pack(const uint32_t* src, int width, int x0, int x1, int y0, int y1, uint32_t* out, hipStream_t s) {
-    g_packs++;
-    fake_enqueue(s, [=] {
-        for (int y = y0; y < y1; y++) memcpy(out + (size_t)(y - y0) * (x1 - x0), src + (size_t)y * width + x0, (size_t)(x1 - x0) * 4);
-    }, nullptr, "k_delta_pack");
-}
-}  // namespace swr
-#endif
-
-struct Bands { std::vector<int64_t> r0, r1; };
-static Bands bands_of(swr_context* c) {
-    Bands b;
-    for (int k = 0; k < swr_context_bands(c); k++) {
-        int64_t a = 0, e = 0;
-        CHECK(swr_context_band_info(c, k, nullptr, &a, &e) == SWR_OK);
-        b.r0.push_back(a); b.r1.push_back(e);
-    }
-    return b;
-}
 
 using Image = std::vector<uint32_t>;
 
@@ -319,34 +266,8 @@ static void failed_context(uint32_t devices) {
     swr_context_destroy(c);
 }
 
-// -DDELTA_HOST_NO_LAUNCH: the program links without the delta launches, as the older stand-alone programs do, and a delta read fails
-// loudly instead of answering
-static void without_the_kernel() {
-    swr_config cfg{0, 1, 5000, 0};
-    swr_context* c = nullptr;
-    CHECK(swr_context_create(&cfg, &c) == SWR_OK);
-    CHECK(swr_target_set(c, 64, 64, 0, 64) == SWR_OK);
-    Image dst(64 * 64, 0xA5A5A5A5u);
-    swr_delta_stats st;
-    memset(&st, 0x7F, sizeof st);
-    const swr_delta_stats untouched = st;
-    CHECK(swr_read_color_delta(c, dst.data(), &st) == SWR_ERR_HIP);
-    CHECK(std::string(swr_last_error(c)).find("k_delta_tiles") != std::string::npos);
-    CHECK(swr_read_depth_delta(c, (float*)dst.data(), &st) == SWR_ERR_HIP);
-    CHECK(same(st, untouched) && dst[0] == 0xA5A5A5A5u && dst.back() == 0xA5A5A5A5u);
-    CHECK(swr_delta_reset(c, SWR_DELTA_COLOR | SWR_DELTA_DEPTH) == SWR_OK);
-    CHECK(swr_sync(c) == SWR_OK);       // (not a failed context: only these calls cannot be answered)
-    CHECK(swr_read_color(c, dst.data()) == SWR_OK);
-    swr_context_destroy(c);
-}
-
 int main() {
     fake_kernel_delay_us(0);
-#ifdef DELTA_HOST_NO_LAUNCH
-    without_the_kernel();
-    std::printf(fails ? "delta host test: %d failures\n" : "delta host test: ok\n", fails);
-    return fails ? 1 : 0;
-#endif
     for (int img = 0; img < 2; img++)
         for (int pinned = 0; pinned < 2; pinned++) {
             scenario(1, 200, 100, 0, 100, img, pinned != 0);
@@ -363,6 +284,5 @@ int main() {
     failed_context(2);
     CHECK(g_compares.load() > 0 && g_packs.load() > 0);
     CHECK(SWR_TUNE_DELTA_DIRECT_TEST ? g_directs.load() > 0 : g_directs.load() == 0);
-    std::printf(fails ? "delta host test: %d failures\n" : "delta host test: ok\n", fails);
-    return fails ? 1 : 0;
+    return report("delta host test");
 }

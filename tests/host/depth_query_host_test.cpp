@@ -1,28 +1,17 @@
 // The host side of the depth queries (software-renderer_amd/csrc/swr_api.hip: single_query_depth, the group fan-out and sum,
 // swr_query_depth) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The stand-in
-// set of stub_launch.cpp has no depth-query launch: this program defines swr::launch_depth_query itself, as a plain CPU loop over
-// the header's definition run as a "kernel" of the fake stream.  The depth image is a pattern written with swr_target_write, so the
+// of swr::launch_depth_query (stub_launch.cpp) is a plain CPU loop over the header's definition run as a "kernel" of the fake stream.  The depth image is a pattern written with swr_target_write, so the
 // loop reads the band's own rows (a box clipped wrongly is an out-of-bounds read the address sanitizer reports, or a wrong count).
 // The loop also checks what the host hands it next to the boxes: the list of large boxes and the total area of the band's parts.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ software-renderer_amd/csrc/swr_api.hip \
 //       tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp tests/host/depth_query_host_test.cpp -lpthread
-#include <atomic>
+#include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
 
-#include "../../include/swr.h"
-#include <hip/hip_runtime.h>
-#include "../../software-renderer_amd/csrc/swr_internal.h"
-
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); fails++; } } while (0)
-
-static std::atomic<int> g_launches{0};
-static std::atomic<int> g_launch_fails{0};      // (the stand-in kernel runs on the fake stream's thread)
+#include "host_test.h"
 
 // the depth of pixel (x, y) of the full target: ordinary depths, +inf, NaN and -inf
 static float pattern(int x, int y) {
@@ -31,46 +20,6 @@ static float pattern(int x, int y) {
     if (v == 21u) return std::numeric_limits<float>::quiet_NaN();
     if (v == 22u) return -std::numeric_limits<float>::infinity();
     return (float)v / 20.0f;
-}
-
-#ifndef DEPTH_QUERY_HOST_NO_LAUNCH
-namespace swr {
-void launch_depth_query(const float* depth, int width, int rows, int row_begin, const swr_depth_box* boxes, int64_t n,
-                        const uint32_t* large, int64_t nlarge, uint64_t total_area, void* scratch, uint32_t* passed, hipStream_t s) {
-    g_launches++;
-    fake_enqueue(s, [=] {
-        uint64_t area = 0;
-        int64_t seen_large = 0;
-        memset(scratch, 0x5A, depth_query_scratch_bytes(width, rows));      // (a summary sized too small is reported)
-        for (int64_t k = 0; k < n; k++) {
-            const swr_depth_box b = boxes[k];
-            const int y0 = std::max(b.y0, row_begin) - row_begin, y1 = std::min(b.y1, row_begin + rows) - row_begin;
-            uint32_t cnt = 0;
-            for (int y = y0; y < y1; y++)
-                for (int x = b.x0; x < b.x1; x++) cnt += b.z < depth[(size_t)y * width + x] ? 1u : 0u;
-            passed[k] = cnt;
-            const uint64_t part = (y1 > y0 && b.x1 > b.x0) ? (uint64_t)(y1 - y0) * (uint64_t)(b.x1 - b.x0) : 0;
-            area += part;
-            if (part >= swr::DEPTH_QUERY_SPLIT_AREA) {
-                if (seen_large >= nlarge || large[seen_large] != (uint32_t)k) g_launch_fails++;
-                seen_large++;
-            }
-        }
-        if (area != total_area || seen_large != nlarge) g_launch_fails++;
-    }, nullptr, "k_depth_boxes");
-}
-}  // namespace swr
-#endif
-
-struct Bands { std::vector<int64_t> r0, r1; };
-static Bands bands_of(swr_context* c) {
-    Bands b;
-    for (int k = 0; k < swr_context_bands(c); k++) {
-        int64_t a = 0, e = 0;
-        CHECK(swr_context_band_info(c, k, nullptr, &a, &e) == SWR_OK);
-        b.r0.push_back(a); b.r1.push_back(e);
-    }
-    return b;
 }
 
 static swr_depth_box box(int x0, int y0, int x1, int y1, float z) { return swr_depth_box{x0, y0, x1, y1, z, {0, 0, 0}}; }
@@ -131,19 +80,19 @@ static void scenario(uint32_t devices, int W, int H) {
     query(c, b, boxes);
     // n == 0: legal with NULL pointers, launches nothing
     {
-        const int before = g_launches.load();
+        const int before = g_query_launches.load();
         CHECK(swr_query_depth(c, nullptr, 0, nullptr) == SWR_OK);
         CHECK(swr_query_depth(c, boxes.data(), 0, out) == SWR_OK);
         CHECK(out[0] == 7);
         // boxes that miss every band's rows, or are empty, launch nothing and give zeros
         std::vector<swr_depth_box> miss = {box(5, 7, 5, 90, 0.5f), box(0, 0, W, 0, 0.5f)};
         query(c, b, miss);
-        CHECK(g_launches.load() == before);
+        CHECK(g_query_launches.load() == before);
         if (devices == 3) {             // rows of the first band only: one launch per query
             std::vector<swr_depth_box> first = {box(0, 0, W, (int)b.r1[0], 0.5f)};
             std::vector<uint32_t> got(1);
             CHECK(swr_query_depth(c, first.data(), 1, got.data()) == SWR_OK);
-            CHECK(g_launches.load() == before + 1);
+            CHECK(g_query_launches.load() == before + 1);
             CHECK(got == expect(b, first));
         }
     }
@@ -271,31 +220,8 @@ static void failed_context(uint32_t devices) {
     swr_context_destroy(c);
 }
 
-// -DDEPTH_QUERY_HOST_NO_LAUNCH: the program links without a depth-query launch, as the older stand-alone programs do, and a query
-// that would need the kernels fails loudly instead of answering
-static void without_the_kernel() {
-    swr_config cfg{0, 1, 5000, 0};
-    swr_context* c = nullptr;
-    CHECK(swr_context_create(&cfg, &c) == SWR_OK);
-    CHECK(swr_target_set(c, 64, 64, 0, 64) == SWR_OK);
-    write_pattern(c, 64, 64);           // (the cleared image right after swr_target_set is answered without the device)
-    const swr_depth_box q = box(0, 0, 64, 64, 0.5f);
-    uint32_t got = 7;
-    CHECK(swr_query_depth(c, &q, 1, &got) == SWR_ERR_HIP);
-    CHECK(got == 7);
-    CHECK(std::string(swr_last_error(c)).find("k_depth_boxes") != std::string::npos);
-    CHECK(swr_query_depth(c, nullptr, 0, nullptr) == SWR_OK);       // (nothing to launch)
-    CHECK(swr_sync(c) == SWR_OK);       // (not a failed context: only this call cannot be answered)
-    swr_context_destroy(c);
-}
-
 int main() {
     fake_kernel_delay_us(0);
-#ifdef DEPTH_QUERY_HOST_NO_LAUNCH
-    without_the_kernel();
-    std::printf(fails ? "depth query host test: %d failures\n" : "depth query host test: ok\n", fails);
-    return fails ? 1 : 0;
-#endif
     scenario(1, 100, 200);
     scenario(3, 100, 200);
     one_band_of_a_target();
@@ -304,6 +230,5 @@ int main() {
     failed_context(1);
     failed_context(2);
     CHECK(g_launch_fails.load() == 0);
-    std::printf(fails ? "depth query host test: %d failures\n" : "depth query host test: ok\n", fails);
-    return fails ? 1 : 0;
+    return report("depth query host test");
 }

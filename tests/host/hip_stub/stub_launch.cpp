@@ -1,13 +1,32 @@
-// Stand-ins for the kernel launch wrappers of swr_kernels.hip / swr_upload.hip on the fake HIP runtime: they enqueue host
-// lambdas that leave what the host layer looks at afterwards (pair totals, largest fill, a frame tag in the framebuffer)
-// and touch both ends of every table their DeviceFrame names, at the sizes swr_internal.h gives: a buffer the host layer
-// sized too small is an out-of-bounds access the address sanitizer reports.
-// Test infrastructure of tests/host/tsan_host_test.cpp only.
+// Stand-ins for every kernel launch wrapper of swr_internal.h on the fake HIP runtime: the one set every host test program links.
+// The frame launches (swr_kernels.hip / swr_upload.hip) enqueue host lambdas that leave what the host layer looks at afterwards
+// (pair totals, largest fill, a frame tag in the framebuffer) and touch both ends of every table their DeviceFrame names, at the sizes
+// swr_internal.h gives.  The feature launches (resolve, visibility counts, depth queries, delta reads, skin, morph) are plain CPU loops
+// over the header's arithmetic that read and write every element of every array they are handed.  Either way a buffer the host layer
+// sized too small is an out-of-bounds access the address sanitizer reports.  stub_launch.h holds what the programs observe.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
+#include <cstdio>
 #include <cstring>
+#include <mutex>
 
+#include "stub_launch.h"
 #include "../../../software-renderer_amd/csrc/swr_internal.h"
+
+std::atomic<uint32_t> g_count_total{0};
+std::atomic<int> g_count_launches{0}, g_query_launches{0}, g_compares{0}, g_directs{0}, g_packs{0};
+std::atomic<int> g_vertex_launches{0}, g_stream_launches{0}, g_morph_launches{0}, g_morph_nrm_launches{0};
+std::atomic<int> g_launch_fails{0};
+
+static std::mutex g_records_m;
+static std::vector<Record> g_records;
+std::vector<Record> take_records() {
+    std::lock_guard<std::mutex> lk(g_records_m);
+    std::vector<Record> r;
+    r.swap(g_records);
+    return r;
+}
 
 namespace swr {
 std::atomic<uint32_t> g_fake_fill{7};        // largest tile fill the fake k_bin reports (tests raise it to force a regrow)
@@ -123,5 +142,159 @@ void launch_points_or_lines(const DeviceFrame& f, int, hipStream_t s) {
         const size_t n = (size_t)ff.tg.width * (size_t)(ff.tg.row_end - ff.tg.row_begin);
         for (size_t i = 0; i < n; i++) ff.depth[i] = ff.m[0];
     }, nullptr, "k_points_or_lines");
+}
+
+// ---- the feature launches ------------------------------------------------------------------------------------------------------
+
+void launch_resolve(const void* color, const void* depth, void* color_out, void* depth_out, int width, int rows, int factor,
+                    int depth_filter, hipStream_t s) {
+    fake_enqueue(s, [=] {
+        const int S = factor, w = width / S, h = rows / S;
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++) {
+                const size_t at = (size_t)y * S * width + (size_t)x * S;
+                if (color) ((uint32_t*)color_out)[(size_t)y * w + x] = resolve_box((const uint32_t*)color + at, width, S);
+                if (depth) ((float*)depth_out)[(size_t)y * w + x] = depth_filter == SWR_RESOLVE_DEPTH_MIN ? resolve_minimum((const float*)depth + at, width, S)
+                                                                                                              : ((const float*)depth)[at];
+            }
+    }, nullptr, "k_resolve");
+}
+
+// The stand-in raster leaves the ID image at zero, so the loop ADDS a pattern of its own to what it reads.  The band's rows are read,
+// the counters are added to, never assigned (a buffer that was not zeroed shows), and counters[n] is written.
+void launch_count_ids(const uint32_t* ids, int width, int x0, int x1, int y0, int y1, int per_item, const ListItem* items,
+                      uint32_t* counters, int64_t n, hipStream_t s) {
+    g_count_launches++;
+    fake_enqueue(s, [=] {
+        const uint32_t total = g_count_total.load();
+        for (int y = y0; y < y1; y++)
+            for (int x = x0; x < x1; x++) {
+                uint32_t id = ids[(size_t)y * width + x] + count_pattern((uint32_t)x, (uint32_t)y, total);
+                int64_t slot = n;
+                if (id != SWR_ID_NONE) {
+                    if (!per_item) slot = id;
+                    else if (!items) slot = 0;
+                    else { slot = 0; for (int64_t k = 0; k < n; k++) if (items[k].vbase <= id) slot = k; }
+                }
+                counters[slot] += 1;
+            }
+    }, nullptr, "k_count_ids");
+}
+
+// (the loop also checks what the host hands it next to the boxes: the list of large boxes and the total area of the band's parts)
+void launch_depth_query(const float* depth, int width, int rows, int row_begin, const swr_depth_box* boxes, int64_t n,
+                        const uint32_t* large, int64_t nlarge, uint64_t total_area, void* scratch, uint32_t* passed, hipStream_t s) {
+    g_query_launches++;
+    fake_enqueue(s, [=] {
+        uint64_t area = 0;
+        int64_t seen_large = 0;
+        memset(scratch, 0x5A, depth_query_scratch_bytes(width, rows));      // (a summary sized too small is reported)
+        for (int64_t k = 0; k < n; k++) {
+            const swr_depth_box b = boxes[k];
+            const int y0 = std::max(b.y0, row_begin) - row_begin, y1 = std::min(b.y1, row_begin + rows) - row_begin;
+            uint32_t cnt = 0;
+            for (int y = y0; y < y1; y++)
+                for (int x = b.x0; x < b.x1; x++) cnt += b.z < depth[(size_t)y * width + x] ? 1u : 0u;
+            passed[k] = cnt;
+            const uint64_t part = (y1 > y0 && b.x1 > b.x0) ? (uint64_t)(y1 - y0) * (uint64_t)(b.x1 - b.x0) : 0;
+            area += part;
+            if (part >= swr::DEPTH_QUERY_SPLIT_AREA) {
+                if (seen_large >= nlarge || large[seen_large] != (uint32_t)k) g_launch_fails++;
+                seen_large++;
+            }
+        }
+        if (area != total_area || seen_large != nlarge) g_launch_fails++;
+    }, nullptr, "k_depth_boxes");
+}
+
+void launch_delta(const uint32_t* cur, uint32_t* base, int have_base, int width, int rows, uint32_t* flags, uint32_t* direct, hipStream_t s) {
+    g_compares++;
+    if (direct) g_directs++;
+    fake_enqueue(s, [=] {
+        const int tx_n = (width + 63) / 64, ty_n = (rows + 31) / 32;
+        for (int ty = 0; ty < ty_n; ty++)
+            for (int tx = 0; tx < tx_n; tx++) {
+                const int x0 = tx * 64, x1 = std::min(width, x0 + 64), y0 = ty * 32, y1 = std::min(rows, y0 + 32);
+                bool changed = !have_base;
+                for (int y = y0; y < y1 && !changed; y++)
+                    changed = memcmp(cur + (size_t)y * width + x0, base + (size_t)y * width + x0, (size_t)(x1 - x0) * 4) != 0;
+                flags[(size_t)ty * tx_n + tx] = changed ? 1u : 0u;
+                if (!changed) continue;
+                for (int y = y0; y < y1; y++) {
+                    memcpy(base + (size_t)y * width + x0, cur + (size_t)y * width + x0, (size_t)(x1 - x0) * 4);
+                    if (direct) memcpy(direct + (size_t)y * width + x0, cur + (size_t)y * width + x0, (size_t)(x1 - x0) * 4);
+                }
+            }
+    }, nullptr, "k_delta_tiles");
+}
+void launch_delta_pack(const uint32_t* src, int width, int x0, int x1, int y0, int y1, uint32_t* out, hipStream_t s) {
+    g_packs++;
+    fake_enqueue(s, [=] {
+        for (int y = y0; y < y1; y++) memcpy(out + (size_t)(y - y0) * (x1 - x0), src + (size_t)y * width + x0, (size_t)(x1 - x0) * 4);
+    }, nullptr, "k_delta_pack");
+}
+
+void launch_morph_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, int64_t nv, const float* dpos, const float* dnrm,
+                           const MorphEntry* list, int32_t active, swr_vertex* morphed, swr_vertex_attr* morphed_attrs, hipStream_t s) {
+    g_morph_launches++;
+    if (attrs) g_morph_nrm_launches++;
+    fake_enqueue(s, [=] {
+        const size_t F = SWR_TUNE_MORPH_PAD ? 4 : 3;
+        if (active < 1 || active > SWR_MORPH_MAX_TARGETS) { std::printf("FAIL %d active targets\n", active); g_launch_fails++; return; }
+        for (int k = 0; k < active; k++)
+            if (list[k].weight == 0.0f || (k && list[k].target <= list[k - 1].target) || list[k].target >= SWR_MORPH_MAX_TARGETS) {
+                std::printf("FAIL active list entry %d: target %u weight %g\n", k, list[k].target, list[k].weight); g_launch_fails++; return;
+            }
+        for (int64_t i = 0; i < nv; i++) {
+            morphed[i] = vertices[i];
+            if (attrs) morphed_attrs[i] = attrs[i];
+            for (int k = 0; k < active; k++) {
+                const float w = list[k].weight;
+                const float* d = dpos + ((size_t)list[k].target * (size_t)nv + (size_t)i) * F;
+                for (int c = 0; c < 3; c++) { const float m = w * d[c]; morphed[i].xyz[c] = morphed[i].xyz[c] + m; }
+                if (attrs) {
+                    const float* e = dnrm + ((size_t)list[k].target * (size_t)nv + (size_t)i) * F;
+                    for (int c = 0; c < 3; c++) { const float m = w * e[c]; morphed_attrs[i].normal[c] = morphed_attrs[i].normal[c] + m; }
+                }
+            }
+        }
+    }, nullptr, "k_morph_vertices", (size_t)nv);
+}
+void launch_skin_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, const swr_skin_vertex* skin, int64_t nv,
+                          const float* joints, int32_t joint_count, swr_vertex* posed, float4* posed_nrm, hipStream_t s) {
+    g_vertex_launches++;
+    fake_enqueue(s, [=] {
+        for (int64_t i = 0; i < nv; i++) {
+            for (int k = 0; k < 4; k++) if ((int64_t)skin[i].joint[k] >= joint_count) { std::printf("FAIL joint %u of %d\n", skin[i].joint[k], joint_count); g_launch_fails++; return; }
+            posed[i] = vertices[i];
+            blend(vertices[i].xyz, skin[i], joints, true, posed[i].xyz);
+            if (attrs) { float n[3]; blend(attrs[i].normal, skin[i], joints, false, n); posed_nrm[i] = make_float4(n[0], n[1], n[2], 0.0f); }
+        }
+    }, nullptr, "k_skin_vertices", (size_t)nv);
+}
+void launch_skin_stream(const float4* pos, int pos_stride, const float4* nrm, int nrm_stride, int64_t nv, const int64_t* indices,
+                        int64_t ntri, int reordered, float4* tri_xyz, float4* tri_nrm, float4* box64, hipStream_t s) {
+    g_stream_launches++;
+    fake_enqueue(s, [=] {
+        (void)reordered;                    // (the fake upload builds no stream: slot s holds primitive s)
+        for (int64_t g = 0; g < (ntri + 63) / 64; g++) {
+            float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+            for (int64_t t = g * 64; t < std::min(ntri, g * 64 + 64); t++)
+                for (int k = 0; k < 3; k++) {
+                    const int64_t ix = indices[3 * t + k];
+                    if (ix < 0 || ix >= nv) { std::printf("FAIL index\n"); g_launch_fails++; return; }
+                    const float4 x = pos[(size_t)pos_stride * ix];
+                    float4& o = tri_xyz[3 * t + k];
+                    o.x = x.x; o.y = x.y; o.z = x.z;
+                    if (nrm) { const float4 n = nrm[(size_t)nrm_stride * ix]; float4& q = tri_nrm[3 * t + k]; q.x = n.x; q.y = n.y; q.z = n.z; }
+                    const float c[3] = {x.x, x.y, x.z};
+                    for (int j = 0; j < 3; j++) { lo[j] = std::min(lo[j], c[j]); hi[j] = std::max(hi[j], c[j]); }
+                }
+            box64[2 * g] = make_float4(lo[0], lo[1], lo[2], 0);
+            box64[2 * g + 1] = make_float4(hi[0], hi[1], hi[2], 0);
+        }
+        std::lock_guard<std::mutex> lk(g_records_m);
+        g_records.push_back(Record{tri_xyz, tri_nrm, box64, ntri, nrm != nullptr});
+    }, nullptr, "k_skin_stream", (size_t)ntri);
 }
 }  // namespace swr

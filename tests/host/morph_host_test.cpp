@@ -1,162 +1,21 @@
 // The host side of the morph targets (software-renderer_amd/csrc/swr_api.hip: single_scene_morph, single_morph_set, the upload of the
 // deltas, enqueue_pose as the chain morph, skin, stream, and its callers in restream, single_scene_attributes, single_scene_skin and
 // single_pose_set, the group fan-out) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour
-// sanitizers.  The stand-in set of stub_launch.cpp has neither a morph nor a skin launch: this program defines
-// swr::launch_morph_vertices, swr::launch_skin_vertices and swr::launch_skin_stream itself, as plain CPU loops over the header's
-// arithmetic run as "kernels" of the fake stream.  The fake stream build writes no stream, so the loops take slot s for primitive s;
-// they read and write every element of every array they are given, at the sizes swr_internal.h states: an array the host layer sized
-// too small, or the wrong array, is an out-of-bounds access the address sanitizer reports or a stream that differs from the model's.
+// sanitizers.  The stand-ins of swr::launch_morph_vertices, swr::launch_skin_vertices and swr::launch_skin_stream (stub_launch.cpp) are
+// plain CPU loops over the header's arithmetic run as "kernels" of the fake stream.  The fake stream build writes no stream, so the
+// loops take slot s for primitive s; they read and write every element of every array they are given, at the sizes swr_internal.h
+// states: an array the host layer sized too small, or the wrong array, is an out-of-bounds access the address sanitizer reports or a
+// stream that differs from the model's.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ software-renderer_amd/csrc/swr_api.hip \
 //       tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp tests/host/morph_host_test.cpp -lpthread
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
-#include "../../include/swr.h"
-#include <hip/hip_runtime.h>
-#include "../../software-renderer_amd/csrc/swr_internal.h"
+#include "host_test.h"
 
-namespace swr { extern std::atomic<uint32_t> g_fake_fill; }
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); fails++; } } while (0)
-
-// "Skinned meshes": translate = the c3 term (positions), else not (normals)
-static void blend(const float* v, const swr_skin_vertex& sk, const float* joints, bool translate, float* out) {
-    float acc[3] = {0, 0, 0};
-    for (int k = 0; k < 4; k++) {
-        const float* m = joints + 16 * (size_t)sk.joint[k];
-        for (int c = 0; c < 3; c++) {
-            float r = m[c] * v[0];
-            r = r + m[4 + c] * v[1];
-            r = r + m[8 + c] * v[2];
-            if (translate) r = r + m[12 + c] * 1.0f;
-            acc[c] = k == 0 ? sk.weight[k] * r : acc[c] + sk.weight[k] * r;
-        }
-    }
-    memcpy(out, acc, sizeof acc);
-}
-
-// "Morph targets", on the caller's packed arrays: p = b; for t ascending with w[t] != 0: p = p + w[t] * d[t][i]
-static void morph(const float* b, const float* deltas, const float* w, int targets, int64_t nv, int64_t i, float* out) {
-    float p[3] = {b[0], b[1], b[2]};
-    for (int t = 0; t < targets; t++) {
-        if (!(w[t] != 0.0f)) continue;
-        const float* d = deltas + ((size_t)t * (size_t)nv + (size_t)i) * 3;
-        for (int c = 0; c < 3; c++) { const float m = w[t] * d[c]; p[c] = p[c] + m; }
-    }
-    memcpy(out, p, sizeof p);
-}
-
-// what the last stream launch of every band wrote, and how often each launch ran
-struct Record { const float4* tri_xyz; const float4* tri_nrm; const float4* box; int64_t ntri; bool nrm; };
-static std::mutex g_m;
-static std::vector<Record> g_records;
-static std::atomic<int> g_morph_launches{0}, g_vertex_launches{0}, g_stream_launches{0}, g_morph_nrm_launches{0};
-
-namespace swr {
-#ifndef MORPH_HOST_NO_LAUNCH
-void launch_morph_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, int64_t nv, const float* dpos, const float* dnrm,
-                           const MorphEntry* list, int32_t active, swr_vertex* morphed, swr_vertex_attr* morphed_attrs, hipStream_t s) {
-    g_morph_launches++;
-    if (attrs) g_morph_nrm_launches++;
-    fake_enqueue(s, [=] {
-        const size_t F = SWR_TUNE_MORPH_PAD ? 4 : 3;
-        if (active < 1 || active > SWR_MORPH_MAX_TARGETS) { std::printf("FAIL %d active targets\n", active); fails++; return; }
-        for (int k = 0; k < active; k++)
-            if (list[k].weight == 0.0f || (k && list[k].target <= list[k - 1].target) || list[k].target >= SWR_MORPH_MAX_TARGETS) {
-                std::printf("FAIL active list entry %d: target %u weight %g\n", k, list[k].target, list[k].weight); fails++; return;
-            }
-        for (int64_t i = 0; i < nv; i++) {
-            morphed[i] = vertices[i];
-            if (attrs) morphed_attrs[i] = attrs[i];
-            for (int k = 0; k < active; k++) {
-                const float w = list[k].weight;
-                const float* d = dpos + ((size_t)list[k].target * (size_t)nv + (size_t)i) * F;
-                for (int c = 0; c < 3; c++) { const float m = w * d[c]; morphed[i].xyz[c] = morphed[i].xyz[c] + m; }
-                if (attrs) {
-                    const float* e = dnrm + ((size_t)list[k].target * (size_t)nv + (size_t)i) * F;
-                    for (int c = 0; c < 3; c++) { const float m = w * e[c]; morphed_attrs[i].normal[c] = morphed_attrs[i].normal[c] + m; }
-                }
-            }
-        }
-    }, nullptr, "k_morph_vertices", (size_t)nv);
-}
-#endif
-void launch_skin_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, const swr_skin_vertex* skin, int64_t nv,
-                          const float* joints, int32_t joint_count, swr_vertex* posed, float4* posed_nrm, hipStream_t s) {
-    g_vertex_launches++;
-    fake_enqueue(s, [=] {
-        for (int64_t i = 0; i < nv; i++) {
-            for (int k = 0; k < 4; k++) if ((int64_t)skin[i].joint[k] >= joint_count) { std::printf("FAIL joint %u of %d\n", skin[i].joint[k], joint_count); fails++; return; }
-            posed[i] = vertices[i];
-            blend(vertices[i].xyz, skin[i], joints, true, posed[i].xyz);
-            if (attrs) { float n[3]; blend(attrs[i].normal, skin[i], joints, false, n); posed_nrm[i] = make_float4(n[0], n[1], n[2], 0.0f); }
-        }
-    }, nullptr, "k_skin_vertices", (size_t)nv);
-}
-void launch_skin_stream(const float4* pos, int pos_stride, const float4* nrm, int nrm_stride, int64_t nv, const int64_t* indices,
-                        int64_t ntri, int reordered, float4* tri_xyz, float4* tri_nrm, float4* box64, hipStream_t s) {
-    g_stream_launches++;
-    fake_enqueue(s, [=] {
-        (void)reordered;                    // (the fake upload builds no stream: slot s holds primitive s)
-        for (int64_t g = 0; g < (ntri + 63) / 64; g++) {
-            float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (int64_t t = g * 64; t < std::min(ntri, g * 64 + 64); t++)
-                for (int k = 0; k < 3; k++) {
-                    const int64_t ix = indices[3 * t + k];
-                    if (ix < 0 || ix >= nv) { std::printf("FAIL index\n"); fails++; return; }
-                    const float4 x = pos[(size_t)pos_stride * ix];
-                    float4& o = tri_xyz[3 * t + k];
-                    o.x = x.x; o.y = x.y; o.z = x.z;
-                    if (nrm) { const float4 n = nrm[(size_t)nrm_stride * ix]; float4& q = tri_nrm[3 * t + k]; q.x = n.x; q.y = n.y; q.z = n.z; }
-                    const float c[3] = {x.x, x.y, x.z};
-                    for (int j = 0; j < 3; j++) { lo[j] = std::min(lo[j], c[j]); hi[j] = std::max(hi[j], c[j]); }
-                }
-            box64[2 * g] = make_float4(lo[0], lo[1], lo[2], 0);
-            box64[2 * g + 1] = make_float4(hi[0], hi[1], hi[2], 0);
-        }
-        std::lock_guard<std::mutex> lk(g_m);
-        g_records.push_back(Record{tri_xyz, tri_nrm, box64, ntri, nrm != nullptr});
-    }, nullptr, "k_skin_stream", (size_t)ntri);
-}
-}  // namespace swr
-
-struct Scene {
-    std::vector<swr_vertex> v;
-    std::vector<swr_vertex_attr> a;
-    std::vector<swr_skin_vertex> sk;
-    std::vector<int64_t> idx;
-};
-
-static Scene make_scene(int nv, int ntri, uint32_t top_joint) {
-    Scene s;
-    s.v.resize(nv); s.a.resize(nv); s.sk.resize(nv); s.idx.resize(3 * (size_t)ntri);
-    for (int i = 0; i < nv; i++) {
-        s.v[i] = swr_vertex{{0.01f * (i % 97) - 0.5f, 0.3f - 0.002f * (i % 89), 0.1f + 0.001f * (i % 101), 0}, {0.1f, 0.2f, 0.3f, 0}};
-        s.a[i] = swr_vertex_attr{{0.5f, 0.01f * (i % 83), -0.25f, 0}, {0.1f * (i % 7), 0.2f, 0, 0}};
-        s.sk[i] = swr_skin_vertex{{(uint32_t)(i % 3), (uint32_t)((i + 1) % 3), top_joint, 0}, {0.5f, 0.25f, 0.125f, 0.125f}};
-    }
-    for (size_t k = 0; k < s.idx.size(); k++) s.idx[k] = (int64_t)((k * 7 + k / 3) % (size_t)nv);
-    return s;
-}
-
-static std::vector<float> make_pose(int joints, float salt) {
-    std::vector<float> p(16 * (size_t)joints, 0.0f);
-    for (int j = 0; j < joints; j++) {
-        float* m = &p[16 * (size_t)j];
-        m[0] = 1.0f + 0.1f * j + salt; m[5] = 0.9f - 0.05f * j; m[10] = 1.0f; m[15] = 1.0f;
-        m[1] = 0.1f * salt; m[4] = -0.2f; m[12] = 0.01f * j; m[13] = salt; m[14] = -0.02f * j;
-    }
-    return p;
-}
-
-// targets as the caller holds them: packed float3, target-major; target `poison` (if any) is NaN and infinities
-struct Targets { std::vector<float> dp, dn; int count; bool nrm; };
+// target `poison` (if any) is NaN and infinities
 static Targets make_targets(int count, int nv, bool nrm, float salt, int poison = -1) {
     Targets t;
     t.count = count; t.nrm = nrm;
@@ -176,39 +35,6 @@ static swr_morph_targets desc(const Targets& t, int64_t nv) {
     return swr_morph_targets{t.dp.data(), t.nrm ? t.dn.data() : nullptr, nv, t.count, 0};
 }
 
-// the stream every band must hold: the scene morphed by w over T (either NULL: unmorphed), then in `pose` (NULL: unposed); bands = the
-// stream launches the call must have made
-static void expect_stream(const Scene& s, const Targets* T, const float* w, const float* pose, bool nrm, int bands, const char* what) {
-    std::lock_guard<std::mutex> lk(g_m);
-    if ((int)g_records.size() != bands) { std::printf("FAIL %s: %zu stream launches, not %d\n", what, g_records.size(), bands); fails++; g_records.clear(); return; }
-    const int64_t ntri = (int64_t)s.idx.size() / 3, nv = (int64_t)s.v.size();
-    for (const Record& r : g_records) {
-        bool ok = r.ntri == ntri && r.nrm == nrm;
-        for (int64_t t = 0; ok && t < ntri; t++)
-            for (int k = 0; k < 3; k++) {
-                const int64_t ix = s.idx[3 * t + k];
-                float p[3], n[3];
-                memcpy(p, s.v[ix].xyz, 12); memcpy(n, s.a[ix].normal, 12);
-                if (T && w) {
-                    morph(p, T->dp.data(), w, T->count, nv, ix, p);
-                    if (T->nrm) morph(n, T->dn.data(), w, T->count, nv, ix, n);
-                }
-                if (pose) { float q[3]; blend(p, s.sk[ix], pose, true, q); memcpy(p, q, 12); blend(n, s.sk[ix], pose, false, q); memcpy(n, q, 12); }
-                ok = ok && memcmp(&r.tri_xyz[3 * t + k], p, 12) == 0 && (!nrm || memcmp(&r.tri_nrm[3 * t + k], n, 12) == 0);
-            }
-        if (!ok) { std::printf("FAIL %s: the stream is not the model's (ntri %lld nrm %d)\n", what, (long long)r.ntri, (int)r.nrm); fails++; }
-    }
-    g_records.clear();
-}
-static void expect_no_launch(const char* what) {
-    std::lock_guard<std::mutex> lk(g_m);
-    if (!g_records.empty()) { std::printf("FAIL %s: %zu unexpected stream launches\n", what, g_records.size()); fails++; g_records.clear(); }
-}
-
-static void tagm(float* m, float tag) { for (int k = 0; k < 16; k++) m[k] = (k % 5 == 0) ? 1.0f : 0.0f; m[0] = tag; }
-static bool all_eq(const std::vector<float>& d, float v) { for (float x : d) if (x != v) return false; return true; }
-
-#ifndef MORPH_HOST_NO_LAUNCH
 static void scenario(uint32_t devices, int nv, int ntri) {
     swr_config cfg{0, devices, 5000, 0};
     swr_context* c = nullptr;
@@ -407,39 +233,15 @@ static void failed_context(uint32_t devices) {
     CHECK(swr_debug_fault(c, SWR_FAULT_ENQUEUE) == SWR_OK);
     swr_draw(c, m, SWR_FLAG_DEPTH_TEST);
     CHECK(swr_sync(c) == SWR_ERR_HIP);
-    { std::lock_guard<std::mutex> lk(g_m); g_records.clear(); }
+    (void)take_records();
     CHECK(swr_morph_set(c, w, 2) == SWR_ERR_HIP);
     CHECK(swr_scene_morph(c, &t) == SWR_ERR_HIP);
     CHECK(swr_scene_morph(c, nullptr) == SWR_ERR_HIP);
     expect_no_launch("a failed context");
     swr_context_destroy(c);
 }
-#endif
-
-// -DMORPH_HOST_NO_LAUNCH: the program links without the morph launch, as the older stand-alone programs do, and the weights fail loudly
-static void without_the_kernel() {
-    swr_config cfg{0, 1, 5000, 0};
-    swr_context* c = nullptr;
-    CHECK(swr_context_create(&cfg, &c) == SWR_OK);
-    const Scene s = make_scene(300, 100, 2);
-    const Targets T = make_targets(2, 300, false, 0.0f);
-    const float w[2] = {1.0f, 0.5f};
-    CHECK(swr_scene_upload(c, s.v.data(), 300, s.idx.data(), 300) == SWR_OK);
-    const swr_morph_targets t = desc(T, 300);
-    CHECK(swr_scene_morph(c, &t) == SWR_OK);
-    CHECK(swr_morph_set(c, w, 2) == SWR_ERR_HIP);
-    CHECK(std::string(swr_last_error(c)).find("this build has no k_morph_vertices") != std::string::npos);
-    CHECK(swr_sync(c) == SWR_OK);       // (not a failed context: only this call cannot be answered)
-    expect_no_launch("without the kernel");
-    swr_context_destroy(c);
-}
-
 int main() {
     fake_kernel_delay_us(0);
-#ifdef MORPH_HOST_NO_LAUNCH
-    without_the_kernel();
-#else
-    (void)without_the_kernel;
     scenario(1, 300, 200);
     scenario(3, 300, 200);
     scenario(1, 3, 1);              // one triangle: one ragged group
@@ -450,7 +252,5 @@ int main() {
     failed_context(2);
     CHECK(g_morph_launches.load() > 0 && g_morph_nrm_launches.load() > 0 && g_vertex_launches.load() > 0);
     CHECK(g_stream_launches.load() > g_morph_launches.load());
-#endif
-    std::printf(fails ? "morph host test: %d failures\n" : "morph host test: ok\n", fails);
-    return fails ? 1 : 0;
+    return report("morph host test");
 }

@@ -1,50 +1,14 @@
 // The host side of the supersampled resolve (software-renderer_amd/csrc/swr_api.hip: single_read_resolved, the generalised
 // copy_band, the group fan-out, swr_render_resolved) on the fake HIP runtime of tests/host/hip_stub, under the address and
-// undefined-behaviour sanitizers.  The stand-in set of stub_launch.cpp has no resolve launch: this program defines swr::launch_resolve
-// itself, as a plain CPU loop over the header's formulas run as a "kernel" of the fake stream.  What is checked is the host layer's
+// undefined-behaviour sanitizers.  The stand-in of swr::launch_resolve (stub_launch.cpp) is a plain CPU loop over the header's
+// formulas run as a "kernel" of the fake stream.  What is checked is the host layer's
 // arithmetic: buffer sizes, band offsets, row pitch, destination rows, the pinned path and the staged path across an 8 MiB chunk.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ software-renderer_amd/csrc/swr_api.hip \
 //       tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp tests/host/resolve_host_test.cpp -lpthread
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "../../include/swr.h"
-#include <hip/hip_runtime.h>
-
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); fails++; } } while (0)
-
-static uint32_t box(const uint32_t* src, size_t pitch, int S) {
-    uint32_t out = 0;
-    for (int ch = 0; ch < 4; ch++) {
-        uint32_t sum = 0;
-        for (int j = 0; j < S; j++) for (int i = 0; i < S; i++) sum += (src[j * pitch + i] >> (8 * ch)) & 0xFFu;
-        out |= ((sum + S * S / 2) / (S * S)) << (8 * ch);
-    }
-    return out;
-}
-static float minimum(const float* src, size_t pitch, int S) {
-    float m = src[0];
-    for (int j = 0; j < S; j++) for (int i = 0; i < S; i++) { const float s = src[j * pitch + i]; if (s < m || (m != m && s == s)) m = s; }
-    return m;
-}
-
-namespace swr {
-void launch_resolve(const void* color, const void* depth, void* color_out, void* depth_out, int width, int rows, int factor,
-                    int depth_filter, hipStream_t s) {
-    fake_enqueue(s, [=] {
-        const int S = factor, w = width / S, h = rows / S;
-        for (int y = 0; y < h; y++)
-            for (int x = 0; x < w; x++) {
-                const size_t at = (size_t)y * S * width + (size_t)x * S;
-                if (color) ((uint32_t*)color_out)[(size_t)y * w + x] = box((const uint32_t*)color + at, width, S);
-                if (depth) ((float*)depth_out)[(size_t)y * w + x] = depth_filter == SWR_RESOLVE_DEPTH_MIN ? minimum((const float*)depth + at, width, S)
-                                                                                                              : ((const float*)depth)[at];
-            }
-    }, nullptr, "k_resolve");
-}
-}  // namespace swr
+#include "host_test.h"
 
 static void fill(std::vector<uint32_t>& c, std::vector<float>& d, uint32_t seed) {
     uint32_t x = seed;
@@ -72,8 +36,8 @@ static void scenario(uint32_t devices, int W, int H, int r0, int r1, int S, uint
     for (int y = r0 / S; y < r1 / S; y++)
         for (int x = 0; x < w; x++) {
             const size_t at = (size_t)y * S * W + (size_t)x * S;
-            want_c[(size_t)y * w + x] = S == 1 ? col[at] : box(col.data() + at, W, S);
-            want_d[(size_t)y * w + x] = S == 1 ? dep[at] : minimum(dep.data() + at, W, S);
+            want_c[(size_t)y * w + x] = S == 1 ? col[at] : resolve_box(col.data() + at, W, S);
+            want_d[(size_t)y * w + x] = S == 1 ? dep[at] : resolve_minimum(dep.data() + at, W, S);
         }
     swr_resolve rs{S, SWR_RESOLVE_DEPTH_MIN, {0, 0}};
     CHECK(swr_read_color_resolved(c, &rs, got_c.data()) == SWR_OK);
@@ -156,6 +120,5 @@ int main() {
     scenario(1, 4096, 2560, 0, 2560, 2, 9);      // the resolved image is 10 MiB: the staged path crosses one 8 MiB chunk
     render_resolved(1);
     render_resolved(2);
-    std::printf(fails ? "resolve host test: %d failures\n" : "resolve host test: ok\n", fails);
-    return fails ? 1 : 0;
+    return report("resolve host test");
 }

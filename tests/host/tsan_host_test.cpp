@@ -12,18 +12,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/swr.h"
-#include <hip/hip_runtime.h>
+#include "host_test.h"
 
-namespace swr { extern std::atomic<uint32_t> g_fake_fill, g_fake_pairs, g_fake_clip_over; }
-static int fails = 0;
 static bool no_pipeline = false;      // --no-pipeline: every context runs with swr_pipeline_enable(0), one stream
-#define CHECK(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); fails++; } } while (0)
 
 static const int W = 128, H = 96;
 static std::vector<swr_vertex> verts(300);
 static std::vector<int64_t> idx(300);
-static void tagm(float m[16], float tag) { memset(m, 0, 64); m[0] = tag; m[5] = m[10] = m[15] = 1.0f; }
 static bool all_eq(const float* d, float v, int r0 = 0, int r1 = H) {
     for (int i = r0 * W; i < r1 * W; i++) if (d[i] != v) return false;
     return true;
@@ -216,6 +211,5 @@ int main(int argc, char** argv) {
         for (int bin_mode : {0, 1}) frame_types(bin_mode);      // fixed-stride bins, exact-size bins
         for (int fault = 1; fault <= 2 && !no_failure; fault++) { failure(0, fault); failure(2, fault); }
     }
-    std::printf(fails ? "tsan host test: %d failures\n" : "tsan host test: ok\n", fails);
-    return fails ? 1 : 0;
+    return report("tsan host test");
 }

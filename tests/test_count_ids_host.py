@@ -1,41 +1,12 @@
 """The host layer of the visibility counts on the fake HIP runtime (tests/host/hip_stub, used as it is), as a stand-alone program under
-the address and undefined-behaviour sanitizers: tests/host/count_host_test.cpp.  CPU only; nothing is loaded into Python.  The program
-supplies the count launch itself (a CPU loop over the header's definition), so what is checked is the host side: the rectangle clipped
+the address and undefined-behaviour sanitizers: tests/host/count_host_test.cpp.  CPU only; nothing is loaded into Python.  The count
+launch is the stand-in of tests/host/hip_stub (a CPU loop over the header's definition), so what is checked is the host side: the rectangle clipped
 to every band's rows for 1 and 3 bands and for one band of a larger target, the sum across bands and `none`, the counter buffer growing
-and being zeroed between queries of different n, n == 0, and every error the header names.  Built a second time without the launch, the
-program must still link (as the older stand-alone programs do) and the query must fail loudly."""
-import os
-import shutil
-import subprocess
+and being zeroed between queries of different n, n == 0, and every error the header names."""
+import host_build
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_and_run(tmp_path, name, extra):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = tmp_path / name
-    stub = os.path.join(ROOT, "tests", "host", "hip_stub")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-I" + stub, *extra,
-           "-x", "c++", os.path.join(ROOT, "software-renderer_amd", "csrc", "swr_api.hip"),
-           os.path.join(stub, "stub_runtime.cpp"), os.path.join(stub, "stub_launch.cpp"),
-           os.path.join(ROOT, "tests", "host", "count_host_test.cpp"), "-lpthread", "-o", str(exe)]
-    build = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    if build.returncode != 0 and any(r in build.stderr.lower() for r in ("asan", "ubsan")) and "cannot find" in build.stderr.lower():
-        pytest.skip("libasan is not installed")
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1 exitcode=66", UBSAN_OPTIONS="print_stacktrace=1"))
-    out = run.stdout + run.stderr
-    assert "AddressSanitizer" not in out and "LeakSanitizer" not in out and "runtime error:" not in out, out[-4000:]
-    assert run.returncode == 0 and "count host test: ok" in out, out[-2000:]
+ASAN = "address,undefined"
 
 
 def test_count_host_layer_under_address_sanitizer(tmp_path):
-    build_and_run(tmp_path, "count_host_test", [])
-
-
-def test_a_program_without_the_count_launch_links_and_the_query_fails_loudly(tmp_path):
-    build_and_run(tmp_path, "count_host_test_no_launch", ["-DCOUNT_HOST_NO_LAUNCH"])
+    host_build.run_clean(host_build.build_program(tmp_path, "count_host_test.cpp", ASAN), "count host test: ok", ASAN)
