@@ -7,7 +7,7 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion] [--delta] [--skin] [--morph]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion [--bounds]] [--delta] [--skin] [--morph]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
@@ -18,6 +18,9 @@ pixels every copy covers, counted on the device (swr_count_ids: only the counts 
 --occlusion (with --objects N and --depth-test) tests every copy's screen rectangle and nearest depth against the depth image of the
 previous frame before the next one is drawn, on the device (swr_query_depth: only one count per copy crosses to the host, not the
 depth image), and prints how many copies could be skipped because nothing of them would pass the z-test.
+--bounds (with --occlusion) takes every copy's rectangle and nearest depth from the device instead of projecting the vertices on the
+host (swr_item_bounds: 48 bytes per copy cross, in the arithmetic the frame itself uses).  The posed and morphed vertices exist only on
+the device, so --occlusion --bounds is what combines with --skin and --morph: the copies are then copies of the bending, breathing torus.
 --delta runs the host-visible loop the way the app calls it — one swr_render per frame, the same mesh, a new transform, the same two host
 images — through swr_render_delta: the device compares every frame with what the host images already hold, tile by tile, and only the
 rectangle around the tiles that changed crosses to the host.  It prints the tiles that changed per frame.
@@ -268,6 +271,12 @@ def object_boxes(vertices: np.ndarray, matrices, width: int, height: int) -> np.
     return np.array(rows, dtype=np.float64).reshape(-1, 5)
 
 
+# --bounds: how far in front of an item's nearest vertex its box is tested.  swr_item_bounds gives the nearest VERTEX; a fragment's
+# interpolated depth can lie in front of it by rounding (and, under the CPU rules, by extrapolation at span pixels outside the
+# triangle), so the caller subtracts a margin of their own: generous here, the depths of the app's scene are of order 1.
+BOUNDS_Z_MARGIN = 2.0 ** -12
+
+
 def cull_flags(cull: str = "none", front_ccw: bool = False) -> int:
     """Face culling (Metal's setCullMode / setFrontFacingWinding): none / back / front, front = clockwise as displayed unless
     front_ccw."""
@@ -285,33 +294,57 @@ def view_flags(clip: bool = False, perspective: bool = False) -> int:
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
         time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False,
         clip: bool = False, perspective: bool = False, glass: int | None = None, ssaa: int = 1, ids: bool = False,
-        occlusion: bool = False):
+        occlusion: bool = False, bounds: bool = False, skin: bool = False, morph: bool = False):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
     mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
     frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel.
     ids: the ID image is written, and after the last frame its visibility counts are printed (swr_count_ids).
     occlusion: from the second frame on, every copy's screen rectangle and nearest depth are tested against the previous frame's depth
     image before the frame is drawn (swr_query_depth), and the number of copies nothing of which would pass is printed.
+    bounds (with occlusion): the boxes come from the device (swr_item_bounds) instead of object_boxes; an item with a corner behind
+    the eye is never counted as skippable.  skin / morph (with occlusion and bounds): the mesh is the torus of run_skin, morphed
+    and / or posed anew every frame — its vertices exist only on the device, so only the device can say where a copy lands.
     cull / front_ccw: face culling (cull_flags); clip / perspective: view_flags.
     glass = A (0..255): after the opaque frame a second, shifted and smaller instance of the mesh is drawn over it as a blend load
     frame (SWR_FLAG_BLEND | SWR_FLAG_LOAD, SWR_BLEND_OVER at opacity A): you see the first instance through it; the depth image stays
     the opaque frame's (not with --pick or --perspective).
     ssaa = S (2 or 4): the frames are drawn at S * size and resolved on the device to size x size (the depth is sample (0,0))."""
-    vertices, indices = load_mesh(obj) if obj else sphere_mesh()
+    if (skin or morph) and not (occlusion and bounds):
+        raise ValueError("skin / morph in this loop need occlusion and bounds (run_skin and run_morph are the plain loops)")
+    if bounds and clip:
+        raise ValueError("swr_item_bounds does not take SWR_FLAG_DEPTH_CLIP")
+    if skin or morph:
+        xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
+        vertices = S.pack_vertices(xyz, rgb)
+    else:
+        vertices, indices = load_mesh(obj) if obj else sphere_mesh()
     flags = (S.FLAG_DEPTH_TEST if depth_test else 0) | (swr_amd.binding.FLAG_PRIMITIVE_IDS if pick or ids else 0) | cull_flags(cull, front_ccw)
     flags |= view_flags(clip, perspective)
     results = []
     with swr_amd.Context() as ctx:
         ctx.scene_upload(vertices, indices)            # RenderPass.vertices / .indices, App.swift:163
+        if morph:
+            ctx.scene_morph(morph_targets(vertices))
+        if skin:
+            ctx.scene_skin(*bend_skin(vertices))
         ctx.target_set(ssaa * size, ssaa * size)        # MetalView.Coordinator.width/height, App.swift:52-53 (times the samples per axis)
         time = time0
         for k in range(frames):
+            if morph:
+                ctx.morph_set(morph_weights(time))
+            if skin:
+                ctx.pose_set(bend_pose(time))
             if objects > 1:
                 m = object_transforms(time, objects)
                 items = [(0, indices.size, mj) for mj in m]
                 if occlusion and k > 0:
                     # the occlusion query of this frame's copies against the depth the previous frame left on the device (samples, with --ssaa)
-                    passed = ctx.query_depth(object_boxes(vertices, m, ssaa * size, ssaa * size))
+                    if bounds:
+                        where = ctx.item_bounds(items, flags)       # the scene as it is now: morphed and posed
+                        passed = ctx.query_depth(swr_amd.binding.depth_boxes(where, BOUNDS_Z_MARGIN))
+                        passed[(where["behind"] != 0) & (passed == 0)] = 1      # (drawn mirrored through the eye: never culled on its bounds)
+                    else:
+                        passed = ctx.query_depth(object_boxes(vertices, m, ssaa * size, ssaa * size))
                     print(f"occlusion: frame {k}: {int((passed == 0).sum())} of {objects} objects could be skipped "
                           f"(pixels that pass per object: {passed.tolist()})")
                 ctx.draw_list(items, flags)             # all copies in one frame
@@ -531,6 +564,9 @@ if __name__ == "__main__":
     ap.add_argument("--occlusion", action="store_true",
                     help="with --objects N: test every copy's screen rectangle and nearest depth against the previous frame's depth "
                          "image on the device and print how many copies could be skipped (swr_query_depth)")
+    ap.add_argument("--bounds", action="store_true",
+                    help="with --occlusion: the copies' rectangles and nearest depths come from the device (swr_item_bounds), which "
+                         "also allows --skin and --morph")
     ap.add_argument("--delta", action="store_true",
                     help="the host-visible loop through swr_render_delta: only the tiles that changed cross to the host; prints them per frame")
     ap.add_argument("--skin", action="store_true",
@@ -555,14 +591,21 @@ if __name__ == "__main__":
             ap.error("--glass does not combine with --pick, --ids or --perspective (blend frames write no IDs and interpolate screen-linearly)")
         if a.stream:
             ap.error("--glass is not part of the --stream loop")
-    if a.morph:
+    if a.bounds and not (a.occlusion and a.objects > 1):
+        ap.error("--bounds needs --occlusion and --objects N")
+    if a.bounds and a.clip:
+        ap.error("--bounds does not combine with --clip (swr_item_bounds does not take SWR_FLAG_DEPTH_CLIP)")
+    deforming_bounds = a.occlusion and a.bounds and (a.skin or a.morph)
+    if deforming_bounds and (a.obj or a.ply or a.stream or a.delta or a.glass is not None):
+        ap.error("--occlusion --bounds with --skin / --morph draws copies of the torus: not with --obj, --ply, --stream, --delta or --glass")
+    if a.morph and not deforming_bounds:
         if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or (a.skin and (a.obj or a.ply)):
             ap.error("--morph is its own loop: only --frames, --size, --out, --depth-test, --gpus, --skin and (without --skin) --obj / --ply apply")
         _, idx, res = run_morph(a.frames, a.size, a.out, a.depth_test, skin=a.skin, device_count=a.gpus, obj=a.ply or a.obj)
         print(f"{a.frames} morphed{' and posed' if a.skin else ''} frames, {idx.size // 3} triangles, "
               f"coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
-    if a.skin:
+    if a.skin and not deforming_bounds:
         if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or a.obj or a.ply:
             ap.error("--skin is its own loop over its own mesh: only --frames, --size, --out, --depth-test and --gpus apply")
         _, idx, res = run_skin(a.frames, a.size, a.out, a.depth_test, device_count=a.gpus)
@@ -582,6 +625,6 @@ if __name__ == "__main__":
     pick = tuple(int(t) for t in a.pick.split(",")) if a.pick else None
     _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick, cull=a.cull,
                       front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass, ssaa=a.ssaa, ids=a.ids,
-                      occlusion=a.occlusion)
+                      occlusion=a.occlusion, bounds=a.bounds, skin=deforming_bounds and a.skin, morph=deforming_bounds and a.morph)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

@@ -461,6 +461,58 @@ typedef struct swr_morph_targets {
     int32_t reserved;             /* 0 */
 } swr_morph_targets;              /* 32 bytes */
 
+/* ---- Item bounds (swr_item_bounds) — DESIGN.md §25 ---------------------------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_item_bounds symbol is the feature test.  Nothing
+ * existing changes.  swr_query_depth and swr_count_ids take screen rectangles from the caller; since "Skinned meshes" and "Morph
+ * targets" the vertices an object is drawn from exist only on the device.  swr_item_bounds says where every item of a draw list would
+ * land and how near it is, in the arithmetic the frame itself uses; 48 bytes per item cross to the host.
+ *   Input.  Item k is exactly what swr_draw_list would draw: the triangles indices[first_index, first_index + index_count) of the
+ *     resident scene as it is now (morphed and posed), transformed by items[k].transform, on the target of swr_target_set.
+ *   Per corner (normative): IEEE binary32, one rounding per operation, no FMA.  With c0..c3 the columns of the transform:
+ *         r = c0 * x;   r = r + c1 * y;   r = r + c2 * z;   r = r + c3 * 1.0f;        ndc = r.xyz / r.w;
+ *         sx = (ndc.x * 0.5f + 0.5f) * W;   sy = (ndc.y * -0.5f + 0.5f) * H;   sz = ndc.z;
+ *     and under SWR_FLAG_METAL_RULES sx = roundf(sx), sy = roundf(sy) (half away from zero): what the frame's setup computes.
+ *   Drawable.  A triangle is drawable iff all six of its sx, sy satisfy |v| < 2^30 and, under the Metal rules, v >= 0: the coordinate
+ *     part of the frame's skip rule.  A triangle whose integer vertices are collinear counts as drawable, and so does one a frame
+ *     would cull by its facing (the cull bits are ignored: the bounds cover both facings): the answer is conservative.
+ *     drawable + skipped == index_count / 3.
+ *   The rectangle.  With ix = (int)sx, iy = (int)sy (truncation, the integer vertices of "Face culling") over the corners of the
+ *     drawable triangles: x0 = min ix, x1 = max ix + 1, y0 = min iy, y1 = max iy + 1, then each clamped, x into [0, W] and y into
+ *     [0, H].  Every pixel the item covers lies inside it.  An item wholly off the target gives an empty rectangle (x0 == x1 or
+ *     y0 == y1), which is legal input to swr_query_depth and swr_count_ids.  All 0 when drawable == 0.
+ *   The depth range.  zmin and zmax are folded with s < m ? s : m and s > m ? s : m from +inf and -inf over all three sz of every
+ *     drawable triangle, so a NaN sz is left out by the fold itself; a zero result is returned as +0 (m + 0.0f).  Minimum and maximum
+ *     do not depend on the order: the result is bit-defined.
+ *     zmin is the nearest VERTEX.  A fragment's depth za*w0 + zb*w1 + zc*w2 can leave [zmin, zmax] by rounding, and under the CPU
+ *     rules also by extrapolation at span pixels outside the triangle: a caller who feeds zmin to swr_query_depth subtracts a margin
+ *     of their own.
+ *   behind counts the drawable triangles with a corner whose clip-space w (r.w) is not > 0.  Without SWR_FLAG_DEPTH_CLIP such a
+ *     triangle is drawn mirrored through the eye: the caller should not cull an item on bounds with behind != 0.
+ *   flags.  Every combination swr_draw_list accepts is accepted, and only SWR_FLAG_METAL_RULES changes the result.  SWR_FLAG_DEPTH_CLIP
+ *     returns SWR_ERR_UNSUPPORTED: the rectangle of a clipped fan is not that of its triangle.  Unknown bits: SWR_ERR_BAD_ARG.
+ *   Items.  Checked exactly as swr_draw_list checks them (SWR_ERR_INDEX_COUNT, SWR_ERR_BAD_ARG, SWR_ERR_UNSUPPORTED above
+ *     SWR_DRAW_LIST_MAX items, SWR_ERR_NO_SCENE without a scene or a target).  Ranges may overlap and repeat.  item_count == 0 is legal,
+ *     and items and out may then be NULL; NULL out with item_count > 0 is SWR_ERR_BAD_ARG.  An empty item gives drawable = skipped =
+ *     behind = 0, the all-0 rectangle and zmin / zmax = +inf / -inf.  After an error nothing was written.
+ *   Completion.  Blocking, like swr_query_depth: everything drawn before is completed and checked first (an overflowed last frame is
+ *     repaired).  No image and no delta baseline is modified, what the next frame draws does not change, and the call does not count
+ *     as a frame: swr_read_ids and swr_count_ids after it see the last frame as before.  On a scene uploaded in Morton order the call
+ *     cuts the triangle stream at the items' boundaries, as the first swr_draw_list of these items would; that list then finds the
+ *     cuts in place.
+ *   Bands.  The result does not depend on rows.  A multi-device context computes on its first band (every band holds the whole scene)
+ *     and writes the caller's array once; a context that owns rows [a, b) of a larger target answers for the full W x H.  After
+ *     swr_render_resolved the target is the sample grid, and the rectangles are in samples.
+ *   Not covered: SWR_FLAG_DEPTH_CLIP, a call that does not wait, the bounds of .vertices and .line passes, and the C++ and Swift
+ *     mirrors. */
+typedef struct swr_item_bound {
+    int32_t  x0, y0, x1, y1;  /* half-open pixel rectangle in the full W x H target, clipped to it; all 0 when drawable == 0 */
+    float    zmin, zmax;      /* over the corners' sz of drawable triangles; +inf / -inf when there is none */
+    uint32_t drawable;        /* triangles of the item that setup would not skip for their coordinates */
+    uint32_t skipped;         /* the others: drawable + skipped == index_count / 3 */
+    uint32_t behind;          /* drawable triangles with a corner whose clip-space w is not > 0 */
+    uint32_t reserved[3];     /* 0 on return */
+} swr_item_bound;             /* 48 bytes */
+
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
  * continues from the image already there.
@@ -772,6 +824,9 @@ int swr_count_ids(swr_context* ctx, const swr_id_count* q, uint32_t* counts, int
 /* Depth queries (see "Depth queries" above): swr_sync + the copy of the n boxes + a reduction of the depth image on the device + the
  * copy of the n counts + wait.  boxes and passed have n elements. */
 int swr_query_depth(swr_context* ctx, const swr_depth_box* boxes, int64_t n, uint32_t* passed);
+/* Item bounds (see "Item bounds" above): swr_sync + the copy of the items + a reduction of the resident triangle stream on the device +
+ * the copy of the item_count records + wait.  items and out have item_count elements. */
+int swr_item_bounds(swr_context* ctx, const swr_draw_item* items, int32_t item_count, uint32_t flags, swr_item_bound* out);
 /* Delta reads (see "Delta reads" above): swr_sync + the compare against the band's baseline on the device + the copy of the tile
  * flags + the copy of the changed rectangle + wait.  dst is the full W x H image, as for swr_read_*; stats may be NULL. */
 int swr_read_color_delta(swr_context* ctx, void*  dst_full_image, swr_delta_stats* stats);

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "swr_render_timings", "swr_debug_fault", "swr_debug_set", "swr_target_write", "swr_draw_list", "swr_read_ids",
     "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
     "swr_query_depth", "swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta",
-    "swr_scene_skin", "swr_pose_set", "swr_scene_morph", "swr_morph_set",
+    "swr_scene_skin", "swr_pose_set", "swr_scene_morph", "swr_morph_set", "swr_item_bounds",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -109,6 +109,31 @@ DEPTH_QUERY_MAX = 1 << 16    # SWR_DEPTH_QUERY_MAX: boxes per swr_query_depth ca
 # swr_depth_box as a numpy record
 DEPTH_BOX_DTYPE = np.dtype([("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32), ("z", np.float32),
                             ("reserved", np.int32, (3,))])
+
+
+class ItemBound(ctypes.Structure):
+    """swr_item_bound (include/swr.h "Item bounds"): where a draw item lands on the target, its depth range and its triangle counts."""
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32), ("y1", ctypes.c_int32),
+                ("zmin", ctypes.c_float), ("zmax", ctypes.c_float),
+                ("drawable", ctypes.c_uint32), ("skipped", ctypes.c_uint32), ("behind", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+# swr_item_bound as a numpy record (what Context.item_bounds returns)
+ITEM_BOUND_DTYPE = np.dtype([("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32), ("zmin", np.float32),
+                             ("zmax", np.float32), ("drawable", np.uint32), ("skipped", np.uint32), ("behind", np.uint32),
+                             ("reserved", np.uint32, (3,))])
+
+
+def depth_boxes(bounds, z_margin) -> np.ndarray:
+    """The (n, 5) rows (x0, y0, x1, y1, zmin - z_margin) Context.query_depth takes, from the records of Context.item_bounds.  zmin is
+    the nearest vertex: a fragment's depth can lie in front of it by rounding (include/swr.h "Item bounds"), so the caller chooses
+    the margin.  The subtraction is made in float32, as the box's z is one.  Pure: no context, no device."""
+    b = np.asarray(bounds)
+    rows = np.zeros((b.size, 5), dtype=np.float64)
+    for j, f in enumerate(("x0", "y0", "x1", "y1")):
+        rows[:, j] = b[f].reshape(-1)
+    rows[:, 4] = b["zmin"].reshape(-1).astype(np.float32) - np.float32(z_margin)
+    return rows
 
 
 class DeltaStats(ctypes.Structure):
@@ -292,6 +317,12 @@ def load_library():
     try:
         L.swr_query_depth.argtypes = [vp, vp, i64, vp]
         L.swr_query_depth.restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
+    try:
+        L.swr_item_bounds.argtypes = [vp, vp, i32, u32, vp]
+        L.swr_item_bounds.restype = ctypes.c_int
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
             raise
@@ -717,6 +748,15 @@ class Context:
         passed = np.zeros(a.size, dtype=np.uint32)
         self._check(self._L.swr_query_depth(self._h, a.ctypes.data if a.size else None, a.size, passed.ctypes.data if a.size else None))
         return passed
+
+    def item_bounds(self, items, flags: int = 0) -> np.ndarray:
+        """swr_item_bounds: an ITEM_BOUND_DTYPE array, for every item of `items` (as for draw_list) the rectangle it would land in on
+        the target, the depth range of its vertices and its drawable / skipped / behind triangle counts, computed on the device from
+        the resident scene as it is now (morphed and posed).  Only FLAG_METAL_RULES of `flags` changes the result."""
+        a = self.draw_items(items)
+        out = np.zeros(a.size, dtype=ITEM_BOUND_DTYPE)
+        self._check(self._L.swr_item_bounds(self._h, a.ctypes.data if a.size else None, a.size, flags, out.ctypes.data if a.size else None))
+        return out
 
     @staticmethod
     def _dst_ptr(x):

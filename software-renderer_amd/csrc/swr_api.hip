@@ -129,7 +129,7 @@ struct Worker {
 static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && sizeof(swr_vertex_attr) == 32 &&
               sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16 &&
               sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32 && sizeof(swr_depth_box) == 32 && sizeof(swr_delta_stats) == 48 &&
-              sizeof(swr_skin_vertex) == 32 && sizeof(swr_morph_targets) == 32,
+              sizeof(swr_skin_vertex) == 32 && sizeof(swr_morph_targets) == 32 && sizeof(swr_item_bound) == 48,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -226,6 +226,11 @@ struct swr_context {
     DevBuf query_dev, query_tiles;
     HostBuf query_host;
     const uint32_t* query_passed = nullptr;     // the counts of the last query inside query_host
+    // item bounds: the n items and the n records of a call, in this order, on the device and in the band's own
+    // page-locked staging, both sized by the largest call so far; the partial records k_item_bounds folds into
+    DevBuf bounds_dev, bounds_scratch;
+    HostBuf bounds_host;
+    const swr_item_bound* bounds_out = nullptr; // the records of the last call inside bounds_host
     // delta reads: per image kind (0 colour, 1 depth) the band's baseline — the image the last delta read delivered —
     // and whether it holds one; the tile flags k_delta_tiles writes, on the device and in the band's own page-locked copy; the rows of
     // a changed rectangle gathered for one linear copy; what the band's last delta read did (a group adds the bands up)
@@ -2040,6 +2045,21 @@ int restream(swr_context* c, const std::vector<uint32_t>& cuts) {
     return SWR_OK;
 }
 
+// A Morton-sorted stream scatters an index range over the whole stream: cut it at every boundary of `need` (primitive indices, any
+// order) first — once per new set of boundaries: the cuts made for earlier lists stay while they are few.
+int cut_stream(swr_context* c, std::vector<uint32_t>& need) {
+    if (!c->stream_sorted || need.empty()) return SWR_OK;
+    std::sort(need.begin(), need.end());
+    need.erase(std::unique(need.begin(), need.end()), need.end());
+    if (std::includes(c->cuts.begin(), c->cuts.end(), need.begin(), need.end())) return SWR_OK;
+    std::vector<uint32_t> cuts;
+    std::set_union(c->cuts.begin(), c->cuts.end(), need.begin(), need.end(), std::back_inserter(cuts));
+    if (cuts.size() > (size_t)2 * SWR_DRAW_LIST_MAX) cuts = need;
+    int rc;
+    if ((rc = check_frames(c))) return rc;           // (every stream idle; an overflowed last frame redrawn on the old stream)
+    return restream(c, cuts);
+}
+
 int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags) {
     if (const int f = sticky(c)) return f;
     int64_t tris = 0;
@@ -2068,19 +2088,7 @@ int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint
         }
         vbase += it.count;
     }
-    // A Morton-sorted stream scatters an index range over the whole stream: cut it at every range boundary first (once per new set
-    // of boundaries — the cuts made for earlier lists stay while they are few)
-    if (c->stream_sorted && !need.empty()) {
-        std::sort(need.begin(), need.end());
-        need.erase(std::unique(need.begin(), need.end()), need.end());
-        if (!std::includes(c->cuts.begin(), c->cuts.end(), need.begin(), need.end())) {
-            std::vector<uint32_t> cuts;
-            std::set_union(c->cuts.begin(), c->cuts.end(), need.begin(), need.end(), std::back_inserter(cuts));
-            if (cuts.size() > (size_t)2 * SWR_DRAW_LIST_MAX) cuts = need;
-            if ((rc = check_frames(c))) return rc;           // (every stream idle; an overflowed last frame redrawn on the old stream)
-            if ((rc = restream(c, cuts))) return rc;
-        }
-    }
+    if ((rc = cut_stream(c, need))) return rc;
     // per-slot buffers for V frame slots (grown with every stream idle); the frame's own per-slot tables only where the raster reads them
     {
         using Slot = swr_context::Slot;
@@ -2484,8 +2492,80 @@ int single_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, co
     return SWR_OK;
 }
 
+#ifndef SWR_TUNE_ITEM_BOUNDS
+#define SWR_TUNE_ITEM_BOUNDS (-1)   // -1 = the product: k_item_bounds walks the stream, cut at the items' boundaries, one pass per item;
+                                    // the A/B builds of DESIGN.md §25: 1 = it gathers the items' triangles through the index array
+                                    // instead and the stream is not cut; 2 = instancing: an item over the range of the item before it
+                                    // gets no work units, the workgroups of the first apply every matrix of the run
+#endif
+
+// what swr_item_bounds may be handed: swr_draw_list's own checks (ready / ni as there), then what the call adds to them
+int check_bounds_args(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags, const swr_item_bound* out, bool ready, int64_t ni) {
+    int64_t tris = 0;
+    const int rc = check_list_args(c, items, n, flags, ready, ni, &tris);
+    if (rc) return rc;
+    if (flags & SWR_FLAG_DEPTH_CLIP)
+        return fail(c, SWR_ERR_UNSUPPORTED, "swr_item_bounds: SWR_FLAG_DEPTH_CLIP (the rectangle of a clipped fan is not its triangle's)");
+    if (n > 0 && !out) return fail(c, SWR_ERR_BAD_ARG, "swr_item_bounds: out is NULL");
+    return SWR_OK;
+}
+
+// swr_item_bounds on one band (a group: its first): the n records into c->bounds_out[0 .. n), inside the band's page-locked staging.
+// The items are resolved and the stream is cut as single_draw_list does, so the same list drawn afterwards finds its cuts in place.
+int single_item_bounds(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags, const swr_item_bound* out) {
+    if (const int f = sticky(c)) return f;
+    int rc = check_bounds_args(c, items, n, flags, out, c->has_scene && c->has_target, c->ni);
+    if (rc) return rc;
+    if ((rc = single_sync(c))) return rc;       // (an overflowed last frame is repaired here)
+    c->bounds_out = nullptr;
+    if (n == 0) return SWR_OK;
+    const size_t nn = (size_t)n, item_words = sizeof(ListItem) / 4, rec_words = sizeof(swr_item_bound) / 4;
+    const size_t words = nn * (item_words + rec_words);         // items | records
+    if ((rc = ensure_host(c, c->bounds_host, words))) return rc;
+    ListItem* list = (ListItem*)c->bounds_host.p;
+    swr_item_bound* rec = (swr_item_bound*)(c->bounds_host.p + nn * item_words);
+    memset(rec, 0, nn * sizeof(swr_item_bound));
+    std::vector<uint32_t> need;             // the cuts the stream needs
+    const int64_t ntri = c->ni / 3;
+    int64_t units = 0;
+    for (size_t k = 0; k < nn; k++) {
+        ListItem& it = list[k];
+        it.first = (uint32_t)(items[k].first_index / 3);
+        it.count = (uint32_t)(items[k].index_count / 3);
+        it.vbase = 0;
+        it.ubase = (uint32_t)units;
+        memcpy(it.m, items[k].transform, sizeof it.m);
+        const bool follows = SWR_TUNE_ITEM_BOUNDS == 2 && k > 0 && it.first == list[k - 1].first && it.count == list[k - 1].count;
+        if (!follows) units += item_bounds_units(it.count);
+        if (it.count && it.first > 0) need.push_back(it.first);
+        if (it.count && (int64_t)it.first + it.count < ntri) need.push_back(it.first + it.count);
+    }
+    if (SWR_TUNE_ITEM_BOUNDS != 1 && (rc = cut_stream(c, need))) return rc;
+    if ((rc = ensure(c, c->bounds_dev, words * 4))) return rc;
+    if ((rc = ensure(c, c->bounds_scratch, item_bounds_scratch_bytes(n)))) return rc;
+    uint32_t* dev = (uint32_t*)c->bounds_dev.p;
+    HIP_TRY(c, hipMemcpyAsync(dev, list, nn * sizeof(ListItem), hipMemcpyHostToDevice, c->stream));
+    ItemBoundsArgs a{};
+    a.tri_xyz = (const float4*)c->tri_xyz.p;
+    a.vertices = (const swr_vertex*)(c->pose_active ? c->posed.p : c->morph_active ? c->morphed.p : c->vertices.p);
+    a.indices = (const int64_t*)c->indices.p;
+    a.items = (const ListItem*)dev;
+    a.n = n;
+    a.width = c->tg.width; a.height = c->tg.height;
+    a.metal = (flags & SWR_FLAG_METAL_RULES) ? 1 : 0;
+    a.units = units;
+    a.scratch = c->bounds_scratch.p;
+    a.records = (swr_item_bound*)(dev + nn * item_words);
+    launch_item_bounds(a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(rec, a.records, nn * sizeof(swr_item_bound), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_stream(c, c->stream, "raster stream (item bounds)"))) return or_sticky(c, rc);
+    c->bounds_out = rec;
+    return SWR_OK;
+}
+
 #ifndef SWR_TUNE_DELTA_DIRECT
-#define SWR_TUNE_DELTA_DIRECT 1     // how the changed part reaches a page-locked destination, chosen by measurement:
+#define SWR_TUNE_DELTA_DIRECT 1    // how the changed part reaches a page-locked destination, chosen by measurement:
                                     // 1 = k_delta_tiles stores the changed tiles straight into the caller's image through its
                                     // device address (the product: 0.05 against 0.13 ms on the app's scene at 4K); 0 = R gathered
                                     // on the device, one linear copy into page-locked staging, rows copied by the host — what a
@@ -2630,7 +2710,7 @@ void destroy_single(swr_context* c) {
     DevBuf* bufs[] = {&c->redo_cnt, &c->vertices, &c->indices, &c->tri_rgb, &c->tri_xyz, &c->inv, &c->box64, &c->stream_scratch, &c->sort_temp,
                       &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth, &c->count_dev, &c->query_dev,
                       &c->query_tiles, &c->delta_base[0], &c->delta_base[1], &c->delta_flags, &c->delta_pack, &c->skin, &c->pose_dev, &c->posed,
-                      &c->posed_nrm, &c->morph_dpos, &c->morph_dnrm, &c->morph_list_dev, &c->morphed, &c->morphed_attrs};
+                      &c->posed_nrm, &c->morph_dpos, &c->morph_dnrm, &c->morph_list_dev, &c->morphed, &c->morphed_attrs, &c->bounds_dev, &c->bounds_scratch};
     for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
     for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
@@ -2666,7 +2746,7 @@ void destroy_single(swr_context* c) {
     if (c->h_pairs) hipHostFree(c->h_pairs);
     if (c->h_misc) hipHostFree(c->h_misc);
     if (c->h_clip) hipHostFree(c->h_clip);
-    for (HostBuf* b : {&c->count_host, &c->query_host, &c->delta_host}) if (b->p) hipHostFree(b->p);
+    for (HostBuf* b : {&c->count_host, &c->query_host, &c->delta_host, &c->bounds_host}) if (b->p) hipHostFree(b->p);
     if (c->ev_ok)
         for (int r = 0; r < swr_context::RING; r++)
             for (int i = 0; i < 5; i++) hipEventDestroy(c->ev[r][i]);
@@ -3074,6 +3154,26 @@ int swr_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, uint3
     if (n) memset(passed, 0, (size_t)n * 4);
     for (const swr_context* k : c->kids)
         for (int64_t i = 0; i < n; i++) passed[i] += k->query_passed[i];
+    return SWR_OK;
+}
+
+int swr_item_bounds(swr_context* c, const swr_draw_item* items, int32_t item_count, uint32_t flags, swr_item_bound* out) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    swr_context* k0 = c;
+    if (is_group(c)) {
+        // a group checks what it can see before a band is touched; the result does not depend on rows and every band holds the whole
+        // scene, so the first band answers for the full target
+        if (const int f = sticky(c)) return f;
+        k0 = c->kids[0];
+        int rc = check_bounds_args(c, items, item_count, flags, out, k0->has_scene && c->group_has_target, k0->ni);
+        if (rc) return rc;
+        c->workers[0]->post([=] { return single_item_bounds(k0, items, item_count, flags, out); });
+        if ((rc = group_run(c, [](swr_context* k) { return single_sync(k); }))) return rc;
+    } else {
+        const int rc = single_item_bounds(c, items, item_count, flags, out);
+        if (rc) return rc;
+    }
+    if (item_count) memcpy(out, k0->bounds_out, (size_t)item_count * sizeof(swr_item_bound));
     return SWR_OK;
 }
 

@@ -296,4 +296,42 @@ struct MorphEntry { uint32_t target; float weight; };
 void launch_morph_vertices(const swr_vertex* vertices, const swr_vertex_attr* attrs, int64_t nv, const float* dpos, const float* dnrm,
                            const MorphEntry* list, int32_t active, swr_vertex* morphed, swr_vertex_attr* morphed_attrs, hipStream_t s);
 
+// swr_item_bounds.hip: item bounds.  records[k] = the swr_item_bound of items[k] (include/swr.h "Item bounds") over the
+// stream slots [first, first + count) of tri_xyz — the item's triangles, the stream being cut at the item's boundaries — through the
+// item's own matrix, on a width x height target; metal: the Metal rules.  Item k's work units are [ubase, ubase + ceil(count /
+// ITEM_BOUNDS_CHUNK)), `units` in all (an empty item has none; vbase is not read).  The workgroups of an item fold into
+// ITEM_BOUNDS_SLOTS partial records of 64 bytes in `scratch` (item_bounds_scratch_bytes(n) bytes), which the launch initialises itself
+// and folds into records[k] at its end: nothing has to be zeroed.  tri_xyz, items, scratch and records are device memory.
+// (vertices / indices: the vertex array in effect and the index array, read only by the SWR_TUNE_ITEM_BOUNDS = 1 A/B build, which
+// gathers the item's triangles through them, first and count then being primitive numbers, instead of walking the stream)
+#ifndef SWR_TUNE_ITEM_BOUNDS_CHUNK
+#define SWR_TUNE_ITEM_BOUNDS_CHUNK 2048     // stream slots per work unit, a multiple of 256: DESIGN.md §25 has the measurement
+#endif
+constexpr int ITEM_BOUNDS_CHUNK = SWR_TUNE_ITEM_BOUNDS_CHUNK;
+#ifndef SWR_TUNE_ITEM_BOUNDS_SLOTS
+#define SWR_TUNE_ITEM_BOUNDS_SLOTS 32       // partial records per item the workgroups' atomics are spread over: DESIGN.md §25
+#endif
+constexpr int ITEM_BOUNDS_SLOTS = SWR_TUNE_ITEM_BOUNDS_SLOTS;
+inline size_t item_bounds_scratch_bytes(int64_t n) { return (size_t)n * (size_t)ITEM_BOUNDS_SLOTS * 64; }
+struct ItemBoundsArgs {
+    const float4* tri_xyz;
+    const swr_vertex* vertices;
+    const int64_t* indices;
+    const ListItem* items;
+    int32_t n;
+    int32_t width, height;
+    int32_t metal;
+    int64_t units;
+    void* scratch;
+    swr_item_bound* records;
+};
+inline int64_t item_bounds_units(uint32_t count) { return ((int64_t)count + ITEM_BOUNDS_CHUNK - 1) / ITEM_BOUNDS_CHUNK; }
+#if defined(__HIPCC__) || defined(SWR_ITEM_BOUNDS_STANDIN)
+void launch_item_bounds(const ItemBoundsArgs& a, hipStream_t s);
+#else
+// (host test programs built without SWR_ITEM_BOUNDS_STANDIN link a stand-in launch set that predates this launch and never call
+// swr_item_bounds: nothing is enqueued.  The product is always compiled by hipcc and references the launch plainly.)
+inline void launch_item_bounds(const ItemBoundsArgs&, hipStream_t) {}
+#endif
+
 }  // namespace swr
