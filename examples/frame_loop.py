@@ -7,7 +7,7 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion [--bounds]] [--delta] [--skin] [--morph]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion [--bounds]] [--delta] [--skin [--dq]] [--morph]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
@@ -26,7 +26,9 @@ images — through swr_render_delta: the device compares every frame with what t
 rectangle around the tiles that changed crosses to the host.  It prints the tiles that changed per frame.
 --skin draws a torus that bends between two joints instead: the mesh and its per-vertex joint weights are uploaded once
 (swr_scene_upload, swr_scene_skin), and every frame sets a new pose of two joint matrices (swr_pose_set) — the vertices are posed on
-the device, nothing but 128 bytes of pose crosses per frame — and draws it with the app's transform.
+the device, nothing but 128 bytes of pose crosses per frame — and draws it with the app's transform.  --skin --dq adds a twist of the
+two ends against each other and sets the pose as dual quaternions (swr_pose_set_dq, 64 bytes per frame): the joints are blended as rigid
+motions, so the twisting tube keeps its volume where the blended matrices of swr_pose_set would pinch it.
 --morph gives the mesh two procedural morph targets (blend shapes) — a swell along the direction from the mesh's centre and a twist
 about z — uploaded once (swr_scene_morph), and every frame sets two new weights (swr_morph_set): the vertices are morphed on the
 device, nothing but the weights crosses per frame.  With --skin the torus is morphed first and then posed, as glTF orders the two.
@@ -294,7 +296,7 @@ def view_flags(clip: bool = False, perspective: bool = False) -> int:
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
         time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False,
         clip: bool = False, perspective: bool = False, glass: int | None = None, ssaa: int = 1, ids: bool = False,
-        occlusion: bool = False, bounds: bool = False, skin: bool = False, morph: bool = False):
+        occlusion: bool = False, bounds: bool = False, skin: bool = False, morph: bool = False, dq: bool = False):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
     mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
     frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel.
@@ -304,6 +306,7 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
     bounds (with occlusion): the boxes come from the device (swr_item_bounds) instead of object_boxes; an item with a corner behind
     the eye is never counted as skippable.  skin / morph (with occlusion and bounds): the mesh is the torus of run_skin, morphed
     and / or posed anew every frame — its vertices exist only on the device, so only the device can say where a copy lands.
+    dq (with skin): the pose is the twisting one of twist_pose, set as dual quaternions (swr_pose_set_dq).
     cull / front_ccw: face culling (cull_flags); clip / perspective: view_flags.
     glass = A (0..255): after the opaque frame a second, shifted and smaller instance of the mesh is drawn over it as a blend load
     frame (SWR_FLAG_BLEND | SWR_FLAG_LOAD, SWR_BLEND_OVER at opacity A): you see the first instance through it; the depth image stays
@@ -332,7 +335,9 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
         for k in range(frames):
             if morph:
                 ctx.morph_set(morph_weights(time))
-            if skin:
+            if skin and dq:
+                ctx.pose_set_dq(swr_amd.binding.dual_quats(twist_pose(time)))
+            elif skin:
                 ctx.pose_set(bend_pose(time))
             if objects > 1:
                 m = object_transforms(time, objects)
@@ -471,9 +476,28 @@ def bend_pose(time: float) -> np.ndarray:
     return np.stack([turn(a, 0.05 * math.sin(3.0 * time)), turn(-a, -0.05 * math.sin(3.0 * time))])
 
 
-def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, device_count: int = 1):
+def twist_pose(time: float) -> np.ndarray:
+    """Two rigid joints as (2, 4, 4) mathematical matrices: the bend of bend_pose, and under it a twist of the two ends against each
+    other about x — the ring's tangent where the two joints blend.  Blended as matrices the tube would pinch there; blended as dual
+    quaternions (binding.dual_quats, swr_pose_set_dq) it keeps its volume."""
+    def joint(turn_z, twist_x, ty):
+        c, s = math.cos(turn_z), math.sin(turn_z)
+        ct, st = math.cos(twist_x), math.sin(twist_x)
+        rz = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])
+        rx = np.array([[1, 0, 0], [0, ct, -st], [0, st, ct]])
+        m = np.eye(4)
+        m[:3, :3] = rz @ rx
+        m[1, 3] = ty
+        return m
+    a, b = 0.6 * math.sin(2.0 * time), 1.3 * math.sin(1.5 * time + 0.9)
+    return np.stack([joint(a, -b, 0.05 * math.sin(3.0 * time)), joint(-a, b, -0.05 * math.sin(3.0 * time))])
+
+
+def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, device_count: int = 1,
+             dq: bool = False):
     """The resident loop with a deforming mesh: a torus skinned to two joints, a new pose every frame (swr_pose_set), the app's
-    transform.  Returns the mesh and the (colour, depth) frames."""
+    transform.  dq: the pose is twist_pose, which also twists the torus, set as dual quaternions (swr_pose_set_dq).  Returns the mesh
+    and the (colour, depth) frames."""
     xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
     vertices = S.pack_vertices(xyz, rgb)
     flags = S.FLAG_DEPTH_TEST if depth_test else 0
@@ -484,7 +508,10 @@ def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = 
         ctx.target_set(size, size)
         time = time0
         for k in range(frames):
-            ctx.pose_set(bend_pose(time))
+            if dq:
+                ctx.pose_set_dq(swr_amd.binding.dual_quats(twist_pose(time)))
+            else:
+                ctx.pose_set(bend_pose(time))
             ctx.draw(S.app_transform(time), flags)
             results.append((ctx.read_color(), ctx.read_depth()))
             if out:
@@ -516,9 +543,10 @@ def morph_weights(time: float) -> np.ndarray:
 
 
 def run_morph(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, skin: bool = False,
-              device_count: int = 1, obj: str | None = None):
+              device_count: int = 1, obj: str | None = None, dq: bool = False):
     """The resident loop with a mesh that changes its shape: two morph targets uploaded once (swr_scene_morph), new weights every
-    frame (swr_morph_set), the app's transform.  skin: the torus of run_skin, morphed and then posed (swr_pose_set) every frame.
+    frame (swr_morph_set), the app's transform.  skin: the torus of run_skin, morphed and then posed (swr_pose_set, or with dq
+    swr_pose_set_dq and twist_pose) every frame.
     Returns the mesh and the (colour, depth) frames."""
     if skin:
         xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
@@ -536,7 +564,9 @@ def run_morph(frames: int, size: int, out: str | None = None, depth_test: bool =
         time = time0
         for k in range(frames):
             ctx.morph_set(morph_weights(time))
-            if skin:
+            if skin and dq:
+                ctx.pose_set_dq(swr_amd.binding.dual_quats(twist_pose(time)))
+            elif skin:
                 ctx.pose_set(bend_pose(time))
             ctx.draw(S.app_transform(time), flags)
             results.append((ctx.read_color(), ctx.read_depth()))
@@ -571,6 +601,9 @@ if __name__ == "__main__":
                     help="the host-visible loop through swr_render_delta: only the tiles that changed cross to the host; prints them per frame")
     ap.add_argument("--skin", action="store_true",
                     help="a torus bending between two joints: skinned once (swr_scene_skin), a new pose every frame (swr_pose_set)")
+    ap.add_argument("--dq", action="store_true",
+                    help="with --skin: the torus also twists, and the pose is set as dual quaternions (swr_pose_set_dq): the twist keeps "
+                         "its volume where blended matrices would pinch it")
     ap.add_argument("--morph", action="store_true",
                     help="two procedural morph targets on the mesh (swr_scene_morph), new weights every frame (swr_morph_set); composes with --skin")
     ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
@@ -582,6 +615,8 @@ if __name__ == "__main__":
     ap.add_argument("--ssaa", type=int, choices=[1, 2, 4], default=1,
                     help="supersampling: draw at S x size and resolve S x S samples per pixel on the device")
     a = ap.parse_args()
+    if a.dq and not a.skin:
+        ap.error("--dq is a mode of --skin")
     if a.ssaa != 1 and a.stream:
         ap.error("--ssaa is not part of the --stream loop (there is no asynchronous resolved present)")
     if a.glass is not None:
@@ -601,14 +636,14 @@ if __name__ == "__main__":
     if a.morph and not deforming_bounds:
         if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or (a.skin and (a.obj or a.ply)):
             ap.error("--morph is its own loop: only --frames, --size, --out, --depth-test, --gpus, --skin and (without --skin) --obj / --ply apply")
-        _, idx, res = run_morph(a.frames, a.size, a.out, a.depth_test, skin=a.skin, device_count=a.gpus, obj=a.ply or a.obj)
+        _, idx, res = run_morph(a.frames, a.size, a.out, a.depth_test, skin=a.skin, device_count=a.gpus, obj=a.ply or a.obj, dq=a.dq)
         print(f"{a.frames} morphed{' and posed' if a.skin else ''} frames, {idx.size // 3} triangles, "
               f"coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
     if a.skin and not deforming_bounds:
         if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or a.obj or a.ply:
             ap.error("--skin is its own loop over its own mesh: only --frames, --size, --out, --depth-test and --gpus apply")
-        _, idx, res = run_skin(a.frames, a.size, a.out, a.depth_test, device_count=a.gpus)
+        _, idx, res = run_skin(a.frames, a.size, a.out, a.depth_test, device_count=a.gpus, dq=a.dq)
         print(f"{a.frames} posed frames, {idx.size // 3} triangles, coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
     if a.delta:
@@ -625,6 +660,7 @@ if __name__ == "__main__":
     pick = tuple(int(t) for t in a.pick.split(",")) if a.pick else None
     _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick, cull=a.cull,
                       front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass, ssaa=a.ssaa, ids=a.ids,
-                      occlusion=a.occlusion, bounds=a.bounds, skin=deforming_bounds and a.skin, morph=deforming_bounds and a.morph)
+                      occlusion=a.occlusion, bounds=a.bounds, skin=deforming_bounds and a.skin, morph=deforming_bounds and a.morph,
+                      dq=a.dq)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

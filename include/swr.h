@@ -407,13 +407,53 @@ enum { SWR_DELTA_COLOR = 1, SWR_DELTA_DEPTH = 2 };
  *     joint_count < 0; joint_count <= the largest joint index the skin uses; NULL joints with joint_count > 0.
  *     SWR_ERR_UNSUPPORTED: joint_count > SWR_SKIN_MAX_JOINTS.  A failed context returns its sticky error.  After an error the
  *     scene and the pose are unchanged.
- *   Not covered: a pose that does not wait (ordered by events), dual-quaternion skinning, a partial vertex update
- *     from the host, and the C++ and Swift mirrors. */
+ *   Not covered: a pose that does not wait (ordered by events), a partial vertex update from the host, and the C++ and Swift
+ *     mirrors.  (Dual-quaternion skinning is the next section.) */
 typedef struct swr_skin_vertex {
     uint32_t joint[4];   /* indices into the pose; all four are always read */
     float    weight[4];  /* used as given: not normalised, not sorted, not skipped when 0 */
 } swr_skin_vertex;       /* 32 bytes, parallel to swr_vertex: entry i belongs to vertex i */
 #define SWR_SKIN_MAX_JOINTS 1024
+
+/* ---- Dual-quaternion skinning (swr_pose_set_dq) — DESIGN.md §26 -------------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_pose_set_dq symbol is the feature test.  Nothing
+ * existing changes.  swr_pose_set blends the four joint matrices, and that blend is not a rotation: a vertex weighted half and half
+ * between a joint at rest and one twisted 180 degrees about the bone lands on the bone (the "candy wrapper").  swr_pose_set_dq
+ * blends the joints as unit dual quaternions instead, so the blend stays a rigid motion.
+ *   dual_quats is joint_count x 8 floats: per joint the real quaternion (x, y, z, w), then the dual quaternion (x, y, z, w); w is
+ *     the scalar part.  For a rotation quaternion r and a translation t the dual part is 0.5 * (t, 0) * r.
+ *   One pose state.  It is the pose state of "Skinned meshes": the skin of swr_scene_skin, the limit SWR_SKIN_MAX_JOINTS, one pose in
+ *     effect.  The pose in effect is that of the last call of either kind, swr_pose_set or swr_pose_set_dq.
+ *     swr_pose_set_dq(ctx, NULL, 0) and swr_pose_set(ctx, NULL, 0) both restore the bind pose, whichever kind is in effect.
+ *   Carried over from "Skinned meshes", by reference: its Ordering paragraph (everything drawn before is completed and checked first,
+ *     the call blocks, a frame posted before the call never sees the new pose, a multi-device context poses every band); its lifetime
+ *     (a new swr_scene_skin or swr_scene_upload discards the pose); "Order with the skin" of "Morph targets" (morph first, then skin:
+ *     v and n below are the morphed ones when weights are set); and its Errors paragraph, with swr_pose_set_dq in the messages and
+ *     "NULL dual_quats with joint_count > 0" for the last SWR_ERR_BAD_ARG.  A failed context returns its sticky error.  After an
+ *     error the scene and the pose are unchanged.
+ *   Arithmetic (normative): IEEE binary32, one rounding per operation, no FMA; sqrtf and / are correctly rounded.  For the vertex v
+ *     and every influence k = 0..3, Q_k = dual_quats[joint[k]], with R_k its first four and D_k its last four floats.
+ *     Sign.  u_0 = weight[0].  For k = 1..3:  s_k = ((R_0.x*R_k.x + R_0.y*R_k.y) + R_0.z*R_k.z) + R_0.w*R_k.w;
+ *         u_k = s_k < 0.0f ? -weight[k] : weight[k].  A NaN or zero s_k keeps the weight.  (q and -q are the same rotation; influence
+ *         0 is the pivot.)
+ *     Blend, per component of the eight:  B = u_0*Q_0;   B = B + u_1*Q_1;   B = B + u_2*Q_2;   B = B + u_3*Q_3.
+ *     Normalise.  n = ((B.x*B.x + B.y*B.y) + B.z*B.z) + B.w*B.w over the real part;  l = sqrtf(n);  i = 1.0f / l;  C = B * i (eight
+ *         multiplies).  The dual part is not made orthogonal to the real part: the translation below does not need it.
+ *     Rotate a vector x, with q = C.real.xyz and w = C.real.w, where
+ *         cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), two products and one subtraction each:
+ *         a = cross(q, x);   b = a + w*x;   c = cross(q, b);   rot(x) = x + 2.0f*c.
+ *     Translate.  With d = C.dual.xyz and dw = C.dual.w:  e = cross(q, d);   t = 2.0f * ((w*d - dw*q) + e).
+ *     The posed position is rot(v) + t.  Normals (scenes with attributes only) are rot(n): no translation, no renormalisation.
+ *     Colour, uv and the padding lanes never change.  There are no special cases: all four influences are always read; a zero blend
+ *     (l == 0) gives non-finite coordinates and the triangle is skipped exactly as an uploaded one; a -0 coordinate may come out as
+ *     +0; the payload of a NaN result is unspecified (nothing a frame shows depends on it).
+ *   Input contract.  The call does not normalise its input and does not check that it is a unit dual quaternion.  A non-unit real
+ *     part scales nothing: it only changes that joint's share of the blend.  A joint with scale or shear cannot be expressed as a
+ *     dual quaternion: use swr_pose_set for those.
+ *   What a pose is.  As in "Skinned meshes": every frame, read and query after swr_pose_set_dq is bit for bit that of a context on
+ *     which swr_scene_upload (and swr_scene_attributes) was given the posed vertices (and normals) with the same indices.
+ *   Not covered: a per-vertex choice of the mode, scale carried beside the dual quaternion, a pose that does not wait, converting
+ *     matrices on the device, and the C++ and Swift mirrors. */
 
 /* ---- Morph targets (swr_scene_morph, swr_morph_set) — DESIGN.md §24 ----------------------------------------------------------------
  * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_morph_set symbol is the feature test.  Nothing
@@ -726,6 +766,8 @@ int swr_scene_attributes(swr_context* ctx, const swr_vertex_attr* attributes, in
 /* Skinned meshes (see "Skinned meshes" above): the per-vertex influences, and the pose the resident scene is put into. */
 int swr_scene_skin(swr_context* ctx, const swr_skin_vertex* skin, int64_t vertex_count);
 int swr_pose_set(swr_context* ctx, const float* joints /* joint_count x 16, column-major like transform */, int32_t joint_count);
+/* joint_count x 8 floats: per joint the real quaternion (x, y, z, w), then the dual quaternion (x, y, z, w); w is the scalar part */
+int swr_pose_set_dq(swr_context* ctx, const float* dual_quats, int32_t joint_count);
 /* Morph targets (see "Morph targets" above): the targets of the resident scene, and the weights it is morphed by. */
 int swr_scene_morph(swr_context* ctx, const swr_morph_targets* targets);                 /* NULL: remove the targets */
 int swr_morph_set(swr_context* ctx, const float* weights, int32_t weight_count);         /* NULL, 0: every weight 0 */

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
     "swr_query_depth", "swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta",
     "swr_scene_skin", "swr_pose_set", "swr_scene_morph", "swr_morph_set", "swr_item_bounds",
+    "swr_pose_set_dq",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -159,6 +160,40 @@ class SkinVertex(ctypes.Structure):
 SKIN_MAX_JOINTS = 1024       # SWR_SKIN_MAX_JOINTS: joints per pose
 # swr_skin_vertex as a numpy record
 SKIN_VERTEX_DTYPE = np.dtype([("joint", np.uint32, (4,)), ("weight", np.float32, (4,))])
+
+
+def dual_quats(matrices) -> np.ndarray:
+    """The (J, 8) float32 table swr_pose_set_dq takes, from (J, 4, 4) rigid matrices M (the mathematical matrices: rotation in
+    M[j, :3, :3], translation in M[j, :3, 3]; a pose held column-major as swr_pose_set takes it is passed as
+    P.reshape(-1, 4, 4).transpose(0, 2, 1)).  Computed in float64: the unit quaternion r = (x, y, z, w) of the rotation with w >= 0,
+    the dual part 0.5 * (t, 0) * r, both rounded once to float32.  Scale and shear cannot be expressed: a matrix that has them gives
+    the quaternion of whatever rotation the extraction reads out of it."""
+    M = np.asarray(matrices, dtype=np.float64).reshape(-1, 4, 4)
+    out = np.empty((M.shape[0], 8), dtype=np.float64)
+    for j, m in enumerate(M):
+        R, t = m[:3, :3], m[:3, 3]
+        # the largest of the four squared components first: the extraction never divides by a small number
+        tr = R[0, 0] + R[1, 1] + R[2, 2]
+        c = np.array([1 + R[0, 0] - R[1, 1] - R[2, 2], 1 - R[0, 0] + R[1, 1] - R[2, 2], 1 - R[0, 0] - R[1, 1] + R[2, 2], 1 + tr])
+        k = int(np.argmax(c))
+        if k == 3:
+            q = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1], c[3]])
+        elif k == 0:
+            q = np.array([c[0], R[0, 1] + R[1, 0], R[0, 2] + R[2, 0], R[2, 1] - R[1, 2]])
+        elif k == 1:
+            q = np.array([R[0, 1] + R[1, 0], c[1], R[1, 2] + R[2, 1], R[0, 2] - R[2, 0]])
+        else:
+            q = np.array([R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], c[2], R[1, 0] - R[0, 1]])
+        q = q / np.sqrt((q * q).sum())
+        if q[3] < 0:
+            q = -q
+        x, y, z, w = q
+        out[j, 0:4] = q
+        out[j, 4] = 0.5 * (t[0] * w + t[1] * z - t[2] * y)
+        out[j, 5] = 0.5 * (-t[0] * z + t[1] * w + t[2] * x)
+        out[j, 6] = 0.5 * (t[0] * y - t[1] * x + t[2] * w)
+        out[j, 7] = -0.5 * (t[0] * x + t[1] * y + t[2] * z)
+    return out.astype(np.float32)
 
 
 class MorphTargets(ctypes.Structure):
@@ -345,6 +380,12 @@ def load_library():
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
             raise
     try:
+        L.swr_pose_set_dq.argtypes = [vp, vp, i32]
+        L.swr_pose_set_dq.restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
+    try:
         L.swr_scene_morph.argtypes = [vp, ctypes.POINTER(MorphTargets)]
         L.swr_morph_set.argtypes = [vp, vp, i32]
         for name in ("swr_scene_morph", "swr_morph_set"):
@@ -509,6 +550,16 @@ class Context:
             return
         m = np.ascontiguousarray(joints, dtype=np.float32).reshape(-1, 16)
         self._check(self._L.swr_pose_set(self._h, m.ctypes.data, m.shape[0]))
+
+    def pose_set_dq(self, dual_quats: "np.ndarray | None"):
+        """swr_pose_set_dq: the resident scene in the pose `dual_quats` — a (J, 8) float32 array, per joint the real quaternion
+        (x, y, z, w), then the dual quaternion (dual_quats() makes it from rigid matrices); None: the bind pose.  The joints are
+        blended as dual quaternions, so a twisting limb keeps its volume.  Blocking: the pose is in effect when the call returns."""
+        if dual_quats is None:
+            self._check(self._L.swr_pose_set_dq(self._h, None, 0))
+            return
+        q = np.ascontiguousarray(dual_quats, dtype=np.float32).reshape(-1, 8)
+        self._check(self._L.swr_pose_set_dq(self._h, q.ctypes.data, q.shape[0]))
 
     def scene_morph(self, position_deltas: "np.ndarray | None", normal_deltas: "np.ndarray | None" = None):
         """swr_scene_morph: the morph targets of the resident scene — position deltas of shape (T, nv, 3) and, optionally, normal

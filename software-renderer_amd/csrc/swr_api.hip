@@ -187,7 +187,8 @@ struct swr_context {
     bool has_skin = false;
     int64_t skin_max_joint = -1;        // the largest joint index of the skin (-1: a scene without vertices)
     bool pose_active = false;           // the stream is in `pose` (else: as the upload built it)
-    std::vector<float> pose;            // joint_count x 16
+    std::vector<float> pose;            // joint_count x 16, or (pose_dq) joint_count x 8
+    bool pose_dq = false;               // the pose in effect is a swr_pose_set_dq one: dual quaternions, not matrices
     // morph targets (swr_scene_morph / swr_morph_set): the deltas as swr_internal.h lays them out; the weights on the
     // host (restream and swr_scene_attributes re-apply them) and their non-zero entries as the list the kernel walks, on the host and
     // on the device; the morphed vertices (what the skin, .vertices and line frames read while a weight is not zero) and attributes
@@ -1483,8 +1484,12 @@ int enqueue_pose(swr_context* c, bool with_nrm) {
         if ((rc = ensure(c, c->pose_dev, c->pose.size() * 4))) return rc;
         if (!c->pose.empty())
             HIP_TRY(c, hipMemcpyAsync(c->pose_dev.p, c->pose.data(), c->pose.size() * 4, hipMemcpyHostToDevice, c->stream));
-        launch_skin_vertices(v, at, (const swr_skin_vertex*)c->skin.p, c->nv, (const float*)c->pose_dev.p,
-                             (int32_t)(c->pose.size() / 16), (swr_vertex*)c->posed.p, (float4*)c->posed_nrm.p, c->stream);
+        if (c->pose_dq)
+            launch_skin_vertices_dq(v, at, (const swr_skin_vertex*)c->skin.p, c->nv, (const float*)c->pose_dev.p,
+                                    (int32_t)(c->pose.size() / 8), (swr_vertex*)c->posed.p, (float4*)c->posed_nrm.p, c->stream);
+        else
+            launch_skin_vertices(v, at, (const swr_skin_vertex*)c->skin.p, c->nv, (const float*)c->pose_dev.p,
+                                 (int32_t)(c->pose.size() / 16), (swr_vertex*)c->posed.p, (float4*)c->posed_nrm.p, c->stream);
         launch_skin_stream((const float4*)c->posed.p, 2, with_nrm ? (const float4*)c->posed_nrm.p : nullptr, 1, c->nv,
                            (const int64_t*)c->indices.p, ntri, c->reordered ? 1 : 0, (float4*)c->tri_xyz.p,
                            with_nrm ? (float4*)c->tri_nrm.p : nullptr, (float4*)c->box64.p, c->stream);
@@ -1525,7 +1530,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     c->has_scene = false;
     c->has_attrs = false;
     c->has_skin = false; c->skin_max_joint = -1;     // (a new scene has neither skin nor pose)
-    c->pose_active = false; c->pose.clear();
+    c->pose_active = false; c->pose_dq = false; c->pose.clear();
     drop_morph(c);                                   // (nor morph targets)
     c->draw_pending = false;
     c->last_draw.is_list = false;
@@ -1679,6 +1684,7 @@ int single_scene_skin(swr_context* c, const swr_skin_vertex* skin, int64_t verte
     }
     if (c->pose_active) {
         c->pose_active = false;
+        c->pose_dq = false;
         c->pose.clear();
         if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
     }
@@ -1688,25 +1694,30 @@ int single_scene_skin(swr_context* c, const swr_skin_vertex* skin, int64_t verte
     return SWR_OK;
 }
 
-// swr_pose_set: the resident scene in the pose `joints` (NULL with joint_count 0: the bind pose), in effect when the call returns.
-int single_pose_set(swr_context* c, const float* joints, int32_t joint_count) {
+// swr_pose_set, swr_pose_set_dq (dq): the resident scene in the pose `joints` (NULL with joint_count 0: the bind pose), in effect when
+// the call returns.  One pose state: the pose in effect is that of the last call of either kind, joint_count x 16 floats of matrices
+// or, dq, joint_count x 8 floats of dual quaternions.
+int single_pose_set(swr_context* c, const float* joints, int32_t joint_count, bool dq) {
+    const char* fn = dq ? "swr_pose_set_dq" : "swr_pose_set";
     if (const int f = sticky(c)) return f;
-    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "swr_pose_set needs swr_scene_upload first");
-    if (!c->has_skin) return fail(c, SWR_ERR_BAD_ARG, "swr_pose_set needs swr_scene_skin first");
-    if (joint_count < 0) return fail(c, SWR_ERR_BAD_ARG, "swr_pose_set: joint_count %d", joint_count);
+    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "%s needs swr_scene_upload first", fn);
+    if (!c->has_skin) return fail(c, SWR_ERR_BAD_ARG, "%s needs swr_scene_skin first", fn);
+    if (joint_count < 0) return fail(c, SWR_ERR_BAD_ARG, "%s: joint_count %d", fn, joint_count);
     if (joint_count > SWR_SKIN_MAX_JOINTS)
-        return fail(c, SWR_ERR_UNSUPPORTED, "swr_pose_set: %d joints (at most %d)", joint_count, SWR_SKIN_MAX_JOINTS);
-    if (!joints && joint_count > 0) return fail(c, SWR_ERR_BAD_ARG, "swr_pose_set: %d joints without matrices", joint_count);
+        return fail(c, SWR_ERR_UNSUPPORTED, "%s: %d joints (at most %d)", fn, joint_count, SWR_SKIN_MAX_JOINTS);
+    if (!joints && joint_count > 0)
+        return fail(c, SWR_ERR_BAD_ARG, "%s: %d joints without %s", fn, joint_count, dq ? "dual quaternions" : "matrices");
     const bool bind = !joints;
     if (!bind && (int64_t)joint_count <= c->skin_max_joint)
-        return fail(c, SWR_ERR_BAD_ARG, "swr_pose_set: %d joints, but the skin uses joint index %lld", joint_count,
+        return fail(c, SWR_ERR_BAD_ARG, "%s: %d joints, but the skin uses joint index %lld", fn, joint_count,
                     (long long)c->skin_max_joint);
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
     if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the pose it was drawn in)
     if (bind && !c->pose_active) return SWR_OK;
     c->pose_active = !bind;
-    if (bind) c->pose.clear(); else c->pose.assign(joints, joints + (size_t)joint_count * 16);
+    c->pose_dq = !bind && dq;
+    if (bind) c->pose.clear(); else c->pose.assign(joints, joints + (size_t)joint_count * (dq ? 8 : 16));
     if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
     if ((rc = wait_stream(c, c->stream, "pose"))) return or_sticky(c, rc);
     return SWR_OK;
@@ -2978,7 +2989,13 @@ int swr_scene_skin(swr_context* c, const swr_skin_vertex* skin, int64_t vertex_c
 int swr_pose_set(swr_context* c, const float* joints, int32_t joint_count) {
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // (the same)
-    return fan(c, [=](swr_context* k) { return single_pose_set(k, joints, joint_count); });
+    return fan(c, [=](swr_context* k) { return single_pose_set(k, joints, joint_count, false); });
+}
+
+int swr_pose_set_dq(swr_context* c, const float* dual_quats, int32_t joint_count) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    c->scene_id = 0;      // (the same)
+    return fan(c, [=](swr_context* k) { return single_pose_set(k, dual_quats, joint_count, true); });
 }
 
 int swr_scene_morph(swr_context* c, const swr_morph_targets* targets) {
