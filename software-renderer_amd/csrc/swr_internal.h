@@ -129,7 +129,7 @@ struct DeviceFrame {
     int32_t insort;                // 1: k_raster_depth sorts every bin itself (no k_sort_bins launch for this frame)
     int32_t k32;                   // 1: depth-only z-tested frames take the 32-bit depth keys (k_raster_depth)
     uint32_t* redo_dev;            // device word: tiles k_raster_depth had to raster again (sampled)
-    uint32_t* host_redo;           // pinned host word that receives it one launch later
+    uint32_t* host_redo;           // pinned host word that receives it: at the end of a launch's first workgroup, what was counted up to then
     int32_t defer_big;             // 1: the previous frame had triangles for the deferred list (k_bin<DEFER>)
     int32_t skip_sort;             // 1: no k_sort_bins for this frame (every bin of the previous frames fitted two chunks)
     uint32_t* tile_cursor;         // [tiles] running fill position (starts as tile_start)

@@ -1307,15 +1307,63 @@ struct RasterArgs {
     int insort;         // 32-bit keys: the bins are unsorted and tagged (no k_sort_bins ran): the workgroup sorts its bin in LDS
     int pack_local;     // the scene has at most 2^WTAB_PRIM_BITS primitives: colour frames may carry the bin position in the key's low word (winner table)
     int vs_log;         // 2^vs_log workgroups per tile, each owning TILE_H >> vs_log of its rows (small grids, see launch_raster)
-    uint32_t* redo_dev; // k_raster_depth: tiles (one in REDO_SAMPLE) that had to be rastered again with 64-bit keys, since the last launch
-    uint32_t* host_redo;    // ... handed to the host's pinned word by the next launch (the host then switches the scene to the 64-bit kernel)
+    uint32_t* redo_dev; // k_raster_depth: tiles (one in REDO_SAMPLE) that had to be rastered again with 64-bit keys, since the last hand-over
+    uint32_t* host_redo;    // ... handed to the host's pinned word by the first workgroup of a launch when it is done: what the launches
+                            // before it left and what this one has counted by then; the rest waits for the next launch.  The sum is
+                            // exact, one read is about one launch's worth (the host then switches the scene to the 64-bit kernel)
     const uint8_t* src_color;   // load frames (SWR_FLAG_LOAD): the image the frame starts from, band-local like color / depth and never
     const float* src_depth;     // the same buffers (read-only for the frame)
     uint32_t* ids;              // SWR_FLAG_PRIMITIVE_IDS: the frame's ID image, band-local like depth (IDS instances only)
     const float4* persp;        // SWR_FLAG_PERSPECTIVE colour frames through a non-affine transform: per stream slot (q_a, q_b, q_c, bypass)
                                 // (k_persp_fill); NULL: colour and varyings take the screen weights (wave-uniform)
+    // What depends on the launch alone, decided by the host (launch_raster_keys, from raster_choice) instead of by every workgroup:
+    uint32_t rowsplit_max;      // a bin of at most this many entries has its ROWS split among the waves (raster_tile)
+    uint32_t bin_mask;          // the slot bits of a bin entry (tag_class: below CLASS_SHIFT)
+    int spread;                 // fewer workgroups than the chip holds: bins above rowsplit_max are cut into chunks of < 64 entries
+    int prows, wrows;           // rows of a tile one workgroup owns (TILE_H >> vs_log) and one wave of it when the rows are split
+    int interior_ok;            // vs_log == 0 and width % 4 == 0: tiles wholly inside band and image take the interior clear / resolve
 };
 constexpr int REDO_SAMPLE = 8;
+// Arguments that one thread of one workgroup uses once (the host / redo words), or that only the resolve uses, are read from the
+// kernel-argument segment WHERE they are used: read from the by-value struct, the compiler loads them at the kernel's entry and
+// carries them in scalar registers across the chunk loop, which has none to spare (it parked them in VGPR lanes: v_writelane /
+// v_readlane, 24 + 7 in front of the loop, 45 behind it).  RasterArgs is the first and only argument of every raster kernel.
+#define RASTER_KERNARG(field) \
+    (*reinterpret_cast<const __attribute__((address_space(4))) decltype(RasterArgs::field)*>( \
+        (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(RasterArgs, field)))
+// A frame-uniform device word, written by an earlier kernel of the frame's stream (complete at launch, constant for this kernel):
+// read through the scalar path — no v_mov 0 + global_load + v_readfirstlane per word and workgroup.
+__device__ __forceinline__ uint32_t uniform_word(const uint32_t* p) {
+    return *reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(reinterpret_cast<uintptr_t>(p));
+}
+// The extended fragment stage's uniforms, for the resolve (the only reader): fourteen words that do not wait in scalar registers
+// across the chunk loop.
+__device__ __forceinline__ FragmentUniforms kernarg_fragment_uniforms() {
+    FragmentUniforms u;
+    u.shader = RASTER_KERNARG(fs).shader; u.shininess_log2 = RASTER_KERNARG(fs).shininess_log2;
+    u.light_dir = make_float3(RASTER_KERNARG(fs).light_dir.x, RASTER_KERNARG(fs).light_dir.y, RASTER_KERNARG(fs).light_dir.z);
+    u.half_dir = make_float3(RASTER_KERNARG(fs).half_dir.x, RASTER_KERNARG(fs).half_dir.y, RASTER_KERNARG(fs).half_dir.z);
+    u.ambient = RASTER_KERNARG(fs).ambient; u.diffuse = RASTER_KERNARG(fs).diffuse; u.specular = RASTER_KERNARG(fs).specular;
+    u.texels = RASTER_KERNARG(fs).texels; u.tex_w = RASTER_KERNARG(fs).tex_w; u.tex_h = RASTER_KERNARG(fs).tex_h;
+    return u;
+}
+// The words the host reads after the frame (fixed-stride bins): the pair total, the fullest bin and the sort heuristic's word.  The
+// first workgroup's first thread, at the END of the kernel: nothing of it is live while the tile is rastered.
+// BY_LANE: lane 0 of each of the workgroup's waves stores them (the same values four times) instead of thread 0 alone — the thread
+// number is then dead after the resolve's first lines, where the extended-stage kernels have their register peak; k_raster_depth
+// needs it for the redo hand-over anyway.
+template <bool BY_LANE>
+__device__ __forceinline__ void publish_host_words() {
+    if (blockIdx.x != 0 || blockIdx.y != 0 || RASTER_KERNARG(fixed_cap) == 0u) return;
+    if (BY_LANE ? __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) != 0u : threadIdx.x != 0) return;
+    const uint32_t* const fill = RASTER_KERNARG(fill);
+    const uint32_t max_fill = fill[CNT_MAXFILL];
+    *RASTER_KERNARG(host_pairs) = fill[CNT_PAIRS];
+    *RASTER_KERNARG(host_fill) = max_fill;
+    // (bit 31: the frame had triangles for the deferred list — the host then keeps k_sort_bins running, which is what appends them)
+    uint32_t* const host_max = RASTER_KERNARG(host_max);
+    if (host_max) *host_max = max_fill | ((fill[CNT_BIGLIST] | fill[CNT_BIGSEEN]) ? 0x80000000u : 0u);
+}
 
 // ---- LDS of one raster workgroup -------------------------------------------------------------------------------
 // 64-bit visibility keys (orderable depth << 32 | primitive, or ~primitive without z-test): every frame that needs the
@@ -1620,11 +1668,27 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
     // box — was built twice and measured slower both times: refreshed at every chunk in round 2 (profiles/r02/earlyz_ab.txt),
     // occluder-first with one barrier per tile in round 3 (profiles/r03/earlyz_occluder_first_ab.txt).  Not in the kernel.)
 
-    const int tile = (int)(blockIdx.x >> a.vs_log);
-    const int part = (int)(blockIdx.x & ((1u << a.vs_log) - 1u));     // which slice of the tile's rows this workgroup owns
-    const int PROWS = TILE_H >> a.vs_log;
-    const int tx = tile % a.tg.tiles_x, ty = tile / a.tg.tiles_x;
-    const int tid = threadIdx.x;
+    // The 64-bit pass k_raster_depth runs behind its 32-bit one (VAR_ALLCOOP) works out its tile again, from values the compiler
+    // cannot tell from the first pass's (the workgroup and thread numbers through an empty asm, the launch constants read from the
+    // kernel-argument segment): shared, they would all stay in registers across the first pass's chunk loop, for a pass that almost
+    // no tile runs.
+    constexpr bool SECOND = VAR == VAR_ALLCOOP;
+    auto own_s = [](uint32_t v) {
+        if constexpr (SECOND) asm volatile("" : "+s"(v));
+        return v;
+    };
+    auto own_v = [](uint32_t v) {
+        if constexpr (SECOND) asm volatile("" : "+v"(v));
+        return v;
+    };
+    // grid: (tiles_x << vs_log, tiles_y) — the tile without a division; dispatched row-major, the parts of a tile adjacent
+    const uint32_t bx = own_s(blockIdx.x), vs_log = (uint32_t)(SECOND ? RASTER_KERNARG(vs_log) : a.vs_log);
+    const uint32_t fixed_cap = SECOND ? RASTER_KERNARG(fixed_cap) : a.fixed_cap;
+    const int tx = (int)(bx >> vs_log), ty = (int)own_s(blockIdx.y);
+    const int part = (int)(bx & ((1u << vs_log) - 1u));               // which slice of the tile's rows this workgroup owns
+    const int tile = ty * a.tg.tiles_x + tx;
+    const int PROWS = SECOND ? RASTER_KERNARG(prows) : a.prows;
+    const int tid = (int)own_v(threadIdx.x);
     const int lane = tid & 63;
     // tile rectangle in full-image coordinates (inclusive)
     const int X0 = tx * TILE_W, Y0 = a.tg.row_begin + ty * TILE_H;
@@ -1634,26 +1698,43 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
     const int Yp0 = Y0 + part * PROWS;
     const int Yp1 = min(Yp0 + PROWS - 1, Y1);
     if (Yp0 > Y1) return false;     // the band ends above this slice (workgroup-uniform)
+    // 32-bit keys: the clear of a load frame and the resolve have an interior path, chosen per workgroup — the tile lies wholly
+    // inside the band and the image, the rows are 16-B aligned (width % 4 == 0) and the workgroup owns the whole tile (vs_log == 0;
+    // RasterArgs::interior_ok says the last two).  A thread's two 4-pixel groups then sit at in_off and in_off + in_step elements
+    // behind the tile's first pixel (tile_at): no coordinate test per group, no address rebuilt.  Evaluated where it is used: none of
+    // it is live across the chunk loop.
+    static_assert(TILE_W == 64 && TILE_H == 32 && RASTER_THREADS == 256, "interior path: group i = row i / 16, pixels 4 (i % 16); two per thread");
+    struct Interior { bool on; size_t tile_at; uint32_t off, step; };
+    auto interior_path = [&](int yp0, int yp1) {
+        Interior in;
+        uint32_t ok = (uint32_t)RASTER_KERNARG(interior_ok);
+        // (a load frame asks twice, at the clear and at the resolve: the empty asm keeps the compiler from carrying the answer, and
+        // what it is made of, in scalar registers across the chunk loop)
+        int x0 = X0, x1 = X1;
+        asm volatile("" : "+s"(ok), "+s"(x0), "+s"(x1));
+        in.on = K32 && ok != 0u && x1 - x0 == TILE_W - 1 && yp1 - yp0 == TILE_H - 1;
+        const uint32_t width = (uint32_t)RASTER_KERNARG(tg).width;
+        in.tile_at = (size_t)(Y0 - RASTER_KERNARG(tg).row_begin) * (size_t)width + (size_t)X0;
+        uint32_t t = (uint32_t)tid;
+        asm volatile("" : "+v"(t));
+        in.off = (t >> 4) * width + (t & 15u) * 4u;
+        in.step = 16u * width;
+        return in;
+    };
 
     // an overflowed frame (more pairs than the bins hold / a tile region too small) is rastered empty: the host grows the
     // bins and redraws it
+    // (the words the host reads after such a frame: publish_host_words, at the end of the kernel)
     uint32_t b0 = 0u, b1 = 0u;
-    // the fullest bin of the frame: k_bin's maximum, raised by k_sort_bins if the deferred triangles it appended overfilled a tile
-    const uint32_t max_fill = a.fixed_cap ? a.fill[CNT_MAXFILL] : 0u;
-    if (a.fixed_cap && blockIdx.x == 0 && threadIdx.x == 0) {
-        *a.host_pairs = a.fill[CNT_PAIRS];
-        *a.host_fill = max_fill;
-        // (bit 31: the frame had triangles for the deferred list — the host then keeps k_sort_bins running, which is what appends them)
-        if (a.host_max) *a.host_max = a.fill[CNT_MAXFILL] | ((a.fill[CNT_BIGLIST] | a.fill[CNT_BIGSEEN]) ? 0x80000000u : 0u);
-    }
-    if (a.fixed_cap) {
-        if (max_fill <= a.fixed_cap) { b0 = (uint32_t)tile * a.fixed_cap; b1 = b0 + a.fill[CNT_WORDS + tile]; }
-    } else if (a.counters[CNT_PAIRS] <= a.capacity) {
-        b0 = a.tile_start[tile]; b1 = a.tile_start[tile + 1];
+    if (fixed_cap) {
+        // the fullest bin of the frame: k_bin's maximum, raised by k_sort_bins if the deferred triangles it appended overfilled a tile
+        if (uniform_word(a.fill + CNT_MAXFILL) <= fixed_cap) { b0 = (uint32_t)tile * fixed_cap; b1 = b0 + uniform_word(a.fill + CNT_WORDS + tile); }
+    } else if (uniform_word(a.counters + CNT_PAIRS) <= a.capacity) {
+        b0 = uniform_word(a.tile_start + tile); b1 = uniform_word(a.tile_start + tile + 1);
     }
     const uint32_t m = b1 - b0;   // bin sorted by size class (k_sort_bins), heaviest first — unless the host skipped the sort
     // (sparse frames, launch_sort_bins): the entries then still carry k_fill_lds's class tag
-    const uint32_t bin_mask = a.tag_class ? (1u << CLASS_SHIFT) - 1u : 0xFFFFFFFFu;
+    const uint32_t bin_mask = a.bin_mask;
     // Colour frames with the reference's fragment stage: the key's low word also carries the triangle's position in this bin
     // (below the original index, which still decides ties), so the resolve can set up every WINNER once — see "winner table" there.
     // (PLAIN: the kernels for scenes of more than 2^20 primitives — no room for the bin position in the key: the per-thread resolve)
@@ -1662,9 +1743,10 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
 
     // the gather chain of the first batch (bin entry -> record) is issued before the LDS init so
     // that its latency overlaps the init and the barrier
-    uint32_t prim_pre = 0u;
-    int4 q0_pre = make_int4(0, 0, 0, 0);
-    float4 q1_pre = make_float4(0, 0, 0, 0);
+    // (not zero-filled: a lane reads them only where `have` holds, and there the first chunk's loads, or steal_next's, wrote them)
+    uint32_t prim_pre;
+    int4 q0_pre;
+    float4 q1_pre;
     // The sorted bin is cut into contiguous chunks of `csz` entries (one per lane): 64 when the grid
     // saturates the chip (fewest row steps in total), m/4 when it does not (small scenes: shortest
     // critical path).  The first 4 chunks go to the 4 waves statically (their gathers are issued
@@ -1684,13 +1766,19 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
 #endif
     // (up to 192 on grids that do not fill the chip — 1080p is 1 020 tiles: 20 000 triangles of ~100 px 70 -> 54 us, 300
     // screen-filling ones 97 -> 80; cfg4's 4 080 tiles measured 1 % slower with it: profiles/r03/rowsplit_large_ab.txt)
-    const bool rowsplit = m <= (uint32_t)(gridDim.x <= 1536 ? SWR_ROWSPLIT_MAX_SPREAD : SWR_ROWSPLIT_MAX);
-    const int WROWS = PROWS / (RASTER_THREADS / 64);
+    // (the host's choice between the two, RasterArgs::rowsplit_max)
+    const bool rowsplit = m <= a.rowsplit_max;
+    const int WROWS = SECOND ? RASTER_KERNARG(wrows) : a.wrows;
     const int Yw0 = rowsplit ? Yp0 + (tid >> 6) * WROWS : Yp0;          // this wave's rows of the tile
     const int Yw1 = rowsplit ? min(Yw0 + WROWS - 1, Yp1) : Yp1;
-    const bool spread = !rowsplit && gridDim.x <= 1536;   // fewer tiles than the chip holds workgroups (256 CUs x 6)
-    const uint32_t csz = spread ? min(64u, max(1u, (m + RASTER_THREADS / 64 - 1) / (RASTER_THREADS / 64))) : 64u;
-    const uint32_t nchunks = (m + csz - 1) / csz;
+    const bool spread = !rowsplit && a.spread != 0;       // fewer workgroups than the chip holds (256 CUs x 6)
+    static_assert(RASTER_THREADS / 64 == 4, "spread: a quarter of the bin per wave");
+    const uint32_t csz = spread ? min(64u, max(1u, (m + 3u) >> 2)) : 64u;
+    // ceil(m / csz) without a division: chunks of 64 are a shift; a smaller csz is ceil(m / 4), which m fills at most four times
+    // (readfirstlane: the compiler selects vector instructions for the small-chunk count; the value has to wait in a scalar register,
+    // not in a vector one, across the chunk loop)
+    const uint32_t nchunks = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)(csz == 64u ? (m + 63u) >> 6 : (m > 3u * csz ? 4u : (m > 2u * csz ? 3u : (m > csz ? 2u : (m > 0u ? 1u : 0u))))));
     uint32_t chunk = rowsplit ? 0u : (uint32_t)(tid >> 6);
     if (tid == 0) next_chunk = RASTER_THREADS / 64;
     const uint32_t slot0 = chunk * csz + (uint32_t)lane;
@@ -1728,6 +1816,12 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
     }
 
     // clear fused into the LDS init (Renderer.clear :205-206, :232-236)
+    // (the loops over a thread's pixel groups, here and at the resolve, count their rounds — a constant — instead of testing i against
+    // the tile's size: the compiler kept that test's lane mask in scalar registers from the clear to the resolve)
+    // (... and the clear counts from a copy of the thread number the compiler cannot see through: tid + 256 and what else both sides
+    // compute alike would otherwise wait in a vector register from here to the resolve, one more than the chunk loop has)
+    int ctid = tid;
+    asm volatile("" : "+v"(ctid));
     bool load_nan = false;      // (LOAD, 32-bit keys) a loaded NaN: ds_min_f32 would let any fragment replace it — the 64-bit path decides
     if constexpr (LOAD && ZTEST) {
         // a load frame: the depth already there (pixels outside the band / image stay empty: never resolved).  The 32-bit keys take
@@ -1735,7 +1829,18 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
         // the init must not raise the register peak the raster loop sets (Metal rules: 88 -> 90 unrolled)
         if constexpr (K32) {
             if (tid == 0) L.redo = 0u;
-            for (int i = tid; i < TILE_W * TILE_H / 4; i += RASTER_THREADS) {
+            const Interior in = interior_path(Yp0, Yp1);
+            if (in.on) {
+                // the tile lies wholly inside band and image: two 16-B reads per thread at one base address and a constant stride
+                const float* const sp = RASTER_KERNARG(src_depth) + in.tile_at + in.off;
+#pragma unroll
+                for (int g = 0; g < 2; g++) {
+                    const float4 v = *reinterpret_cast<const float4*>(sp + (size_t)g * in.step);
+                    reinterpret_cast<float4*>(L.keys)[ctid + g * RASTER_THREADS] = v;
+                    load_nan = load_nan || v.x != v.x || v.y != v.y || v.z != v.z || v.w != v.w;
+                }
+            } else
+            for (int g = 0, i = ctid; g < TILE_W * TILE_H / 4 / RASTER_THREADS; g++, i += RASTER_THREADS) {
                 const int ly = (i * 4) / TILE_W, lx = (i * 4) % TILE_W;
                 const int y = Y0 + ly, x = X0 + lx;
                 float d4[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
@@ -1756,7 +1861,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
         } else {
             if constexpr (WTAB_OK) { if (tid < WTAB_WORDS) L.winners[tid] = make_uint2(0u, 0u); }
 #pragma unroll 1
-            for (int i = tid; i < TILE_W * TILE_H; i += RASTER_THREADS) {
+            for (int g = 0, i = ctid; g < TILE_W * TILE_H / RASTER_THREADS; g++, i += RASTER_THREADS) {
                 const int y = Y0 + i / TILE_W, x = X0 + i % TILE_W;
                 keys[i] = (y <= Y1 && x <= X1) ? loaded_key(a.src_depth[(size_t)(y - a.tg.row_begin) * (size_t)a.tg.width + (size_t)x])
                                                : KEY_EMPTY;
@@ -1764,10 +1869,10 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
         }
     } else if constexpr (K32) {
         if (tid == 0) L.redo = 0u;
-        for (int i = tid; i < TILE_W * TILE_H / 4; i += RASTER_THREADS)
+        for (int g = 0, i = ctid; g < TILE_W * TILE_H / 4 / RASTER_THREADS; g++, i += RASTER_THREADS)
             reinterpret_cast<float4*>(L.keys)[i] = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);   // (:206)
     } else {
-        for (int i = tid; i < TILE_W * TILE_H; i += RASTER_THREADS) keys[i] = KEY_EMPTY;
+        for (int g = 0, i = ctid; g < TILE_W * TILE_H / RASTER_THREADS; g++, i += RASTER_THREADS) keys[i] = KEY_EMPTY;
         if constexpr (WTAB_OK) { if (tid < WTAB_WORDS) L.winners[tid] = make_uint2(0u, 0u); }
     }
     __syncthreads();
@@ -1974,6 +2079,8 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
 #endif
         uint32_t chunk_next = nchunks;
         bool have_next = false;
+        // (prim_pre / q0_pre / q1_pre are not initialised: whoever sets have_next for a lane writes prim_pre for it here, and the loop's
+        // end loads its records under the same have_next — as the first chunk's loads do under have0 — so `have` never reads a stale one)
         auto steal_next = [&]() {
             if (rowsplit) {
                 chunk_next = chunk + 1u;
@@ -2243,6 +2350,22 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
     __syncthreads();
 
     // ---- resolve: key -> pixel, one coalesced write per pixel --------------------------------
+    // The workgroup's rows (Yp0, Yp1 above) worked out again, from the workgroup number (through an empty asm: the compiler cannot share
+    // them with the prologue's) and the kernel arguments: scalar instructions only, and two scalar registers fewer across the chunk loop.
+    FragmentUniforms rfs = {};
+    if constexpr (EXT) rfs = kernarg_fragment_uniforms();
+    int Rp0, Rp1;
+    {
+        uint32_t rbx = blockIdx.x;
+        asm volatile("" : "+s"(rbx));
+        const int rprows = RASTER_KERNARG(prows);
+        const int ry1 = min(Y0 + TILE_H, RASTER_KERNARG(tg).row_end) - 1;
+        Rp0 = Y0 + (int)(rbx & ((1u << RASTER_KERNARG(vs_log)) - 1u)) * rprows;
+        Rp1 = min(Rp0 + rprows - 1, ry1);
+        // (named scalar: the compiler otherwise keeps the two in vector registers through the resolve, where the colour kernels peak)
+        Rp0 = __builtin_amdgcn_readfirstlane(Rp0);
+        Rp1 = __builtin_amdgcn_readfirstlane(Rp1);
+    }
     constexpr bool want_color = COLOR;          // a.color != nullptr; depth-only frames (SWR_FLAG_NO_COLOR) have their own kernels
     const int W = a.tg.width;
     const bool vec_ok = (W & 3) == 0;
@@ -2250,10 +2373,23 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
     // 16-B store per four pixels.  A zero of either sign (k32_undecided) is what the 64-bit path has to decide.
     if constexpr (K32) {
         bool undecided = false;
-        for (int i = tid; i < TILE_W * TILE_H / 4; i += RASTER_THREADS) {
+        const Interior in = interior_path(Rp0, Rp1);
+        if (in.on) {
+            // no coordinate tests, one base address per thread, the 16-B store unconditional (4 046 of cfg4's 4 080 tiles)
+            float* const dp = RASTER_KERNARG(depth) + in.tile_at + in.off;
+            typedef float f32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+            for (int g = 0; g < 2; g++) {
+                const float4 v = reinterpret_cast<const float4*>(L.keys)[tid + g * RASTER_THREADS];
+                undecided = undecided || k32_undecided(v.x) || k32_undecided(v.y) || k32_undecided(v.z) || k32_undecided(v.w);
+                f32x4 dv = {v.x, v.y, v.z, v.w};
+                __builtin_nontemporal_store(dv, reinterpret_cast<f32x4*>(dp + (size_t)g * in.step));
+            }
+        } else
+        for (int g = 0, i = tid; g < TILE_W * TILE_H / 4 / RASTER_THREADS; g++, i += RASTER_THREADS) {
             const int ly = (i * 4) / TILE_W, lx = (i * 4) % TILE_W;
             const int y = Y0 + ly, x = X0 + lx;
-            if (y < Yp0 || y > Yp1 || x > X1) continue;
+            if (y < Rp0 || y > Rp1 || x > X1) continue;
             const float4 v = reinterpret_cast<const float4*>(L.keys)[i];
             undecided = undecided || k32_undecided(v.x) || k32_undecided(v.y) || k32_undecided(v.z) || k32_undecided(v.w);
             const size_t at = (size_t)(y - a.tg.row_begin) * (size_t)W + (size_t)x;   // App.swift:351-360
@@ -2364,7 +2500,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                 if constexpr (IDS) {
                     // the IDs leave now, while the keys are still there (the records overwrite them): the same pixels as pass 3's
                     const int y = Y0 + p / TILE_W, x = X0 + p % TILE_W;
-                    if (y >= Yp0 && y <= Yp1 && x <= X1) {
+                    if (y >= Rp0 && y <= Rp1 && x <= X1) {
                         uint32_t id[4];
 #pragma unroll
                         for (int k = 0; k < 4; k++) id[k] = key_id<ZTEST, LOAD>(keys[p + k], WTAB_LOCAL_BITS);
@@ -2448,7 +2584,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                                              v[21] * w0 + v[24] * w1 + v[27] * w2);
                     vin.uv = make_float2(v[28] * w0 + v[30] * w1 + v[32] * w2,
                                          v[29] * w0 + v[31] * w1 + v[33] * w2);
-                    f = fragment_shader(vin, a.fs);
+                    f = fragment_shader(vin, rfs);
                 } else {
                     f = fragment_shader(vin);
                 }
@@ -2482,7 +2618,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                     const int i = tid + g * RASTER_THREADS;
                     const int ly = (i * 4) / TILE_W, lx = (i * 4) % TILE_W;
                     const int y = Y0 + ly, x = X0 + lx;
-                    if (y < Yp0 || y > Yp1 || x > X1) continue;
+                    if (y < Rp0 || y > Rp1 || x > X1) continue;
                     const uint2 pp = *reinterpret_cast<const uint2*>(pix + i * 4);
                     const uint32_t ps[4] = {pp.x & 0xFFFFu, pp.x >> 16, pp.y & 0xFFFFu, pp.y >> 16};
                     uint32_t cpix[4];
@@ -2572,10 +2708,10 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
     // sign its arithmetic produced (:257) — sends the wave through the general path below, which re-evaluates the winner.
     if (ZTEST && !COLOR && (VAR == 0 || VAR == VAR_ALLCOOP)) {
         bool zero_seen = false;
-        for (int i = tid; i < TILE_W * TILE_H / 4; i += RASTER_THREADS) {
+        for (int g = 0, i = tid; g < TILE_W * TILE_H / 4 / RASTER_THREADS; g++, i += RASTER_THREADS) {
             const int ly = (i * 4) / TILE_W, lx = (i * 4) % TILE_W;
             const int y = Y0 + ly, x = X0 + lx;
-            if (y < Yp0 || y > Yp1 || x > X1) continue;
+            if (y < Rp0 || y > Rp1 || x > X1) continue;
             float d4[4];
             const size_t at = (size_t)(y - a.tg.row_begin) * (size_t)W + (size_t)x;   // App.swift:351-360
 #pragma unroll
@@ -2634,7 +2770,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
             const int i = i0 + g * RASTER_THREADS;
             ly[g] = (i * 4) / TILE_W; lx[g] = (i * 4) % TILE_W;
             y[g] = Y0 + ly[g]; x[g] = X0 + lx[g];
-            on[g] = !(y[g] < Yp0 || y[g] > Yp1 || x[g] > X1);
+            on[g] = !(y[g] < Rp0 || y[g] > Rp1 || x[g] > X1);
             cached_prim[g] = 0xFFFFFFFFu; slot[g] = 0u;
             lmask[g] = 0u;
             q2[g] = q3[g] = ca[g] = cb[g] = cc[g] = na[g] = nb[g] = nc[g] = make_float4(0, 0, 0, 0);
@@ -2742,7 +2878,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                                                      na[g].z * w0 + nb[g].z * w1 + nc[g].z * w2);
                             vin.uv = make_float2(na[g].w * w0 + nb[g].w * w1 + nc[g].w * w2,
                                                  ca[g].w * w0 + cb[g].w * w1 + cc[g].w * w2);
-                            f = fragment_shader(vin, a.fs);
+                            f = fragment_shader(vin, rfs);
                         } else {
                             f = fragment_shader(vin);
                         }
@@ -2833,12 +2969,14 @@ __global__ __launch_bounds__(RASTER_THREADS, SWR_RASTER_MIN_WAVES) __attribute__
 void k_raster(RasterArgs a) {
     __shared__ RasterLds64 L;
     raster_tile<ZTEST, VAR, METAL, false, COLOR, PLAIN, false, LOAD, IDS>(a, L);
+    publish_host_words<true>();
 }
 template <bool ZTEST, bool METAL = false, bool PLAIN = false, bool LOAD = false, bool IDS = false>
 __global__ __launch_bounds__(RASTER_THREADS, PLAIN ? 4 : SWR_RASTER_MIN_WAVES_EXT)
 void k_raster_ext(RasterArgs a) {
     __shared__ RasterLds64 L;
     raster_tile<ZTEST, 0, METAL, true, true, PLAIN, false, LOAD, IDS>(a, L);
+    publish_host_words<true>();
 }
 // Depth-only z-tested frames under the CPU rules: 32-bit keys first; the rare tile whose result they cannot vouch for (a
 // zero, whose sign is the first-drawn winner's) is rastered again, by the same workgroup, with the 64-bit keys.  One LDS block for both.
@@ -2849,13 +2987,17 @@ __global__ __launch_bounds__(RASTER_THREADS, SWR_RASTER_MIN_WAVES) __attribute__
 void k_raster_depth(RasterArgs a) {
     constexpr size_t BYTES = sizeof(RasterLds64) > sizeof(RasterLds32) ? sizeof(RasterLds64) : sizeof(RasterLds32);
     __shared__ __attribute__((aligned(16))) unsigned char raw[BYTES];
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.host_redo = atomicExch(a.redo_dev, 0u);     // what the launches before this one counted
     if (raster_tile<true, 0, false, false, false, false, true, LOAD>(a, *reinterpret_cast<RasterLds32*>(raw))) {
         // (load frames are not counted: a starting image full of NaN or zeros says nothing about the scene, and the count decides
-        // whether the scene's clear frames stay on the 32-bit keys)
-        if (!LOAD && threadIdx.x == 0 && blockIdx.x % REDO_SAMPLE == 0) atomicAdd(a.redo_dev, 1u);
+        // whether the scene's clear frames stay on the 32-bit keys; one workgroup in REDO_SAMPLE of the dispatch order counts)
+        if (!LOAD && threadIdx.x == 0 && (blockIdx.y * gridDim.x + blockIdx.x) % REDO_SAMPLE == 0) atomicAdd(RASTER_KERNARG(redo_dev), 1u);
         raster_tile<true, VAR_ALLCOOP, false, false, false, false, false, LOAD>(a, *reinterpret_cast<RasterLds64*>(raw));
     }
+    // The sampled count goes to the host's pinned word, which the host reads after the kernel: handed over by the first workgroup
+    // when it is done, so the word holds what the launches before this one counted and what this one has counted by then; the rest
+    // stays in the device counter for the next launch.  Nothing is lost and nothing is counted twice.
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *RASTER_KERNARG(host_redo) = atomicExch(RASTER_KERNARG(redo_dev), 0u);
+    publish_host_words<false>();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3589,9 +3731,18 @@ static bool launch_raster_keys(const DeviceFrame& f, hipStream_t s, hipEvent_t s
     a.persp = c.color ? f.pq : nullptr;
     a.pack_local = c.plain ? 0 : 1;
     a.vs_log = c.vs_log;
-    const unsigned tiles = ntiles << c.vs_log;
+    // what every workgroup of the launch would decide alike (raster_tile): the grid, tiles_x << vs_log by tiles_y workgroups, fills
+    // the chip above 1 536 of them (256 CUs x 6) — below, bins up to SWR_ROWSPLIT_MAX_SPREAD entries split the rows and fuller ones
+    // are spread over the four waves in chunks of less than 64
+    a.spread = (ntiles << c.vs_log) <= 1536u ? 1 : 0;
+    a.rowsplit_max = a.spread ? SWR_ROWSPLIT_MAX_SPREAD : SWR_ROWSPLIT_MAX;
+    a.bin_mask = a.tag_class ? (1u << CLASS_SHIFT) - 1u : 0xFFFFFFFFu;
+    a.prows = TILE_H >> c.vs_log;
+    a.wrows = a.prows / (RASTER_THREADS / 64);
+    a.interior_ok = (c.vs_log == 0 && (f.tg.width & 3) == 0) ? 1 : 0;
+    const dim3 tiles((unsigned)f.tg.tiles_x << c.vs_log, (unsigned)f.tg.tiles_y);
     return with_bools([&](auto ZTEST, auto PLAIN, auto LOAD, auto IDS) {
-        const auto go = [&](auto kernel) { return launch_on(stop, kernel, dim3(tiles), dim3(RASTER_THREADS), 0, s, a); };
+        const auto go = [&](auto kernel) { return launch_on(stop, kernel, tiles, dim3(RASTER_THREADS), 0, s, a); };
         if (c.metal) {
             if (c.ext) return go(k_raster_ext<true, true, PLAIN, LOAD, IDS>);
             if (c.color) return go(k_raster<true, 0, true, true, PLAIN, LOAD, IDS>);
@@ -3604,7 +3755,7 @@ static bool launch_raster_keys(const DeviceFrame& f, hipStream_t s, hipEvent_t s
         static const int variant = getenv("SWR_DEBUG_VARIANT") ? atoi(getenv("SWR_DEBUG_VARIANT")) : 0;
         if (!LOAD && !IDS && ZTEST && variant > 0 && !c.color) {
             switch (variant) {
-#define SWR_V(N) case N: hipLaunchKernelGGL((k_raster<true, N>), dim3(tiles), dim3(RASTER_THREADS), 0, s, a); return false;
+#define SWR_V(N) case N: hipLaunchKernelGGL((k_raster<true, N>), tiles, dim3(RASTER_THREADS), 0, s, a); return false;
                 SWR_V(1) SWR_V(2) SWR_V(3) SWR_V(4) SWR_V(5) SWR_V(8) SWR_V(9) SWR_V(10) SWR_V(11)
 #undef SWR_V
                 default: break;
