@@ -255,7 +255,9 @@ typedef struct swr_resolve {
  *   The colour and depth images of a frame are bit for bit the same with and without the flag.
  * swr_read_ids(ctx, dst): like swr_read_depth — completes everything, then copies rows [row_begin, row_end) of each band into the
  *   caller's full-size image (width * height words).  SWR_ERR_BAD_ARG when the last frame was drawn without the flag, or when
- *   swr_target_set / swr_target_write has been called since.  An overflowed last frame is redrawn with its flags, IDs included. */
+ *   swr_target_set, swr_target_write or swr_scene_upload has been called since (the IDs number the primitives of the scene the frame
+ *   was drawn from: after a new upload, of whatever size, they name nothing, and swr_count_ids would have no n that fits them; the
+ *   colour and depth images stay).  An overflowed last frame is redrawn with its flags, IDs included. */
 #define SWR_ID_NONE 0xFFFFFFFFu
 
 /* ---- Visibility counts (swr_count_ids) — DESIGN.md §20 ---------------------------------------------------------------------
@@ -286,8 +288,8 @@ typedef struct swr_resolve {
  *     sample resolution, S*w x S*h, after a resolved render.
  *   Errors.  SWR_ERR_BAD_ARG: a NULL ctx or q; a NULL counts with n > 0; an unknown group; a non-zero reserved word; a rectangle
  *     outside the target or inverted; an n that is not the required value (the message names it); the conditions under which
- *     swr_read_ids refuses (the last frame was drawn without SWR_FLAG_PRIMITIVE_IDS, or swr_target_set / swr_target_write came after
- *     it).  SWR_ERR_NO_SCENE: no target.  A failed context returns its sticky error.  After an error nothing was written. */
+ *     swr_read_ids refuses (the last frame was drawn without SWR_FLAG_PRIMITIVE_IDS, or swr_target_set / swr_target_write /
+ *     swr_scene_upload came after it).  SWR_ERR_NO_SCENE: no target.  A failed context returns its sticky error.  After an error nothing was written. */
 enum { SWR_COUNT_PER_PRIMITIVE = 0, SWR_COUNT_PER_ITEM = 1 };
 typedef struct swr_id_count {
     int32_t group;          /* SWR_COUNT_* */

@@ -212,7 +212,7 @@ struct swr_context {
     static_assert(NFB >= 2, "double-buffered at least");
     DevBuf color[NFB], depth[NFB];
     // SWR_FLAG_PRIMITIVE_IDS: the ID image of each framebuffer, sized by the first ID frame on a target (a context
-    // that never asks pays no memory); ids_valid = the last frame wrote one (cleared by swr_target_set / swr_target_write)
+    // that never asks pays no memory); ids_valid = the last frame wrote one (cleared by swr_target_set / swr_target_write / swr_scene_upload)
     DevBuf ids[NFB];
     bool ids_valid = false;
     // supersampled resolve: the band's resolved colour and depth images, (W/S) x (band rows/S), sized by the first
@@ -1534,6 +1534,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     drop_morph(c);                                   // (nor morph targets)
     c->draw_pending = false;
     c->last_draw.is_list = false;
+    c->ids_valid = false;            // the IDs number the primitives of the scene that is going: swr_count_ids has no n for them any more
     c->cuts.clear();                 // a new stream is one segment
     c->list_plan_max = 0;
     c->present_pending = false;
@@ -2322,7 +2323,7 @@ int single_read(swr_context* c, int img, void* dst) {
     if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_* needs swr_target_set first");
     if (img == 2 && !c->ids_valid)
         return fail(c, SWR_ERR_BAD_ARG, "swr_read_ids: the last frame was drawn without SWR_FLAG_PRIMITIVE_IDS, or swr_target_set / "
-                    "swr_target_write came after it");
+                    "swr_target_write / swr_scene_upload came after it");
     int rc = single_sync(c);
     if (rc) return rc;
     if (tiles_of(c->tg) == 0) return SWR_OK;
@@ -2413,7 +2414,7 @@ int single_count_ids(swr_context* c, swr_id_count q, const uint32_t* counts, int
     if ((rc = check_count_rect(c, q, c->tg))) return rc;
     if (!c->ids_valid)
         return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: the last frame was drawn without SWR_FLAG_PRIMITIVE_IDS, or swr_target_set / "
-                    "swr_target_write came after it");
+                    "swr_target_write / swr_scene_upload came after it");
     const bool per_item = q.group == SWR_COUNT_PER_ITEM;
     const int64_t need = per_item ? (c->last_draw.is_list ? (int64_t)c->last_draw.list.size() : 1) : (c->last_draw.is_list ? c->last_draw.list_tris : c->ni / 3);
     if (n != need)
