@@ -44,14 +44,59 @@ thread_local std::string g_create_error;
 // error string — the caller may be reading it (swr_last_error) — and is fatal for the context anyway
 thread_local bool tl_helper_thread = false;
 
+// ---- owners: what the HIP runtime hands out is held by a member that gives it back in its destructor.  A context frees nothing by
+// hand: deleting it frees what it owns, in reverse order of declaration (see swr_context).  Aliases of a handle stay raw.
+// device memory, grown by ensure()
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { (void)reset(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+    ~DevBuf() { (void)reset(); }
+    hipError_t reset() { const hipError_t e = p ? hipFree(p) : hipSuccess; p = nullptr; bytes = 0; return e; }
 };
-// page-locked host words one band keeps for itself (what a query's answer or a flag table is copied into)
+// page-locked host words one band keeps for itself (what a query's answer or a flag table is copied into), grown by ensure_host()
 struct HostBuf {
     uint32_t* p = nullptr;
     size_t words = 0;
+    HostBuf() = default;
+    HostBuf(HostBuf&& o) noexcept : p(o.p), words(o.words) { o.p = nullptr; o.words = 0; }
+    HostBuf& operator=(HostBuf&& o) noexcept { if (this != &o) { (void)reset(); p = o.p; words = o.words; o.p = nullptr; o.words = 0; } return *this; }
+    ~HostBuf() { (void)reset(); }
+    hipError_t reset() { const hipError_t e = p ? hipHostFree(p) : hipSuccess; p = nullptr; words = 0; return e; }
+};
+// a page-locked allocation of a fixed size (the per-frame words, the stage chunks, a lane's item table); reads as the pointer
+template <class T>
+struct Pinned {
+    T* p = nullptr;
+    Pinned() = default;
+    Pinned(const Pinned&) = delete;
+    Pinned& operator=(const Pinned&) = delete;
+    ~Pinned() { (void)reset(); }
+    operator T*() const { return p; }
+    hipError_t alloc(size_t bytes, unsigned flags) { return hipHostMalloc((void**)&p, bytes, flags); }
+    hipError_t reset() { const hipError_t e = p ? hipHostFree(p) : hipSuccess; p = nullptr; return e; }
+};
+// an event and a stream; each reads as its raw handle, so the HIP calls take them as they are
+struct Event {
+    hipEvent_t h = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (h) (void)hipEventDestroy(h); }
+    operator hipEvent_t() const { return h; }
+    hipError_t create() { return hipEventCreate(&h); }
+    hipError_t create(unsigned flags) { return hipEventCreateWithFlags(&h, flags); }
+};
+struct Stream {
+    hipStream_t h = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (h) (void)hipStreamDestroy(h); }
+    operator hipStream_t() const { return h; }
+    hipError_t create() { return hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
 };
 
 #ifndef SWR_TUNE_HELPER_SPIN
@@ -122,6 +167,7 @@ struct Worker {
         cv_job.notify_one();
         if (th.joinable()) th.join();
     }
+    ~Worker() { stop(); }       // (jobs still queued run first: a caller that wants their result drains before)
     std::atomic<bool> pending{false};
 };
 }  // namespace
@@ -134,7 +180,17 @@ static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && si
 
 struct swr_context {
     int device = 0;
-    hipStream_t stream = nullptr;
+#ifndef SWR_NSLOT
+#define SWR_NSLOT 4   // working sets = frame lanes = frames in flight: 3 -> 4 lanes: worst band of 8 16.2 -> 13.5 us, of 2 35.8 -> 33.7, the whole frame the same; 5: slower everywhere (more streams than hardware queues), profiles/r04/lanes_probe.txt
+#endif
+    static constexpr int NSLOT = SWR_NSLOT;
+    // ---- ORDER OF FREEING.  Members are destroyed in reverse order of declaration, and every owner below (DevBuf, HostBuf, Pinned,
+    // Event) is declared after these streams: deleting the context frees buffers, pinned words and events first, then the lane, binning
+    // and copy streams, and `stream` last — the order destroy_single kept by hand.  A new owner goes below this block.
+    Stream stream;
+    Stream copy_stream[2];              // colour, depth: both images in flight together
+    Stream bin_stream_own;
+    Stream lane_stream[NSLOT];          // frame lanes (below)
     std::string err;                    // written and read on the caller's thread only (swr_last_error)
 
     // ---- failure state: a HIP error while a helper thread enqueues, or a wait that outlives the budget, fails the
@@ -159,13 +215,13 @@ struct swr_context {
     const void* scene_tex = nullptr; int32_t scene_tw = 0, scene_th = 0;
     swr_render_times rt{};              // phases of the last swr_render
     float up_h2d_ms = 0.0f, up_build_ms = 0.0f;   // of the last swr_scene_upload (HIP events)
-    hipEvent_t up_ev[3] = {nullptr, nullptr, nullptr};
+    Event up_ev[3];
 
-    // ---- group (device_count > 1): the sub-contexts and their host threads; nothing below is used by a group ----
+    // ---- group (device_count > 1): the sub-contexts (owned: destroy_single) and their host threads.  Of what follows a group uses
+    // tg / has_target alone: the full target its bands share ----
     std::vector<swr_context*> kids;
-    std::vector<Worker*> workers;
-    Target group_tg{};
-    bool group_has_target = false;
+    std::vector<std::unique_ptr<Worker>> workers;
+    int band = 0;                       // a sub-context: which band of its group it is
 
     // scene (RenderPass.vertices / .indices)
     DevBuf vertices, indices, tri_rgb;
@@ -203,10 +259,6 @@ struct swr_context {
     // drawn to the host while the next swr_draw renders into the other buffer
     Target tg{};
     bool has_target = false;
-#ifndef SWR_NSLOT
-#define SWR_NSLOT 4   // working sets = frame lanes = frames in flight: 3 -> 4 lanes: worst band of 8 16.2 -> 13.5 us, of 2 35.8 -> 33.7, the whole frame the same; 5: slower everywhere (more streams than hardware queues), profiles/r04/lanes_probe.txt
-#endif
-    static constexpr int NSLOT = SWR_NSLOT;
     // (one per lane: with frame lanes — below — every frame in flight renders into its own buffer; the two-stream pipeline uses two)
     static constexpr int NFB = NSLOT;
     static_assert(NFB >= 2, "double-buffered at least");
@@ -242,20 +294,19 @@ struct swr_context {
     int fb_cur = 0;                    // the next swr_draw renders into this buffer
     int fb_last = 0;                    // the buffer of the last swr_draw (what swr_present / swr_read_* copy)
     hipStream_t last_stream = nullptr;  // the stream that carries the last frame's raster (swr_present records frame_done behind it)
-    hipStream_t copy_stream[2] = {nullptr, nullptr};   // colour, depth: both images in flight together
-    hipEvent_t frame_done[NFB] = {};     // raster stream -> copy streams, per framebuffer
-    hipEvent_t copy_done[NFB][2] = {};   // [fb][image]: the raster into fb waits for these
+    Event frame_done[NFB];               // raster stream -> copy streams, per framebuffer
+    Event copy_done[NFB][2];             // [fb][image]: the raster into fb waits for these
     bool copy_recorded[NFB][2] = {};
     // ---- load frames (SWR_FLAG_LOAD): a frame that starts from the band's current image instead of the clear
     bool src_clear = true;              // the current image is the cleared one (swr_target_set): a load frame is then a clear frame
     int load_src = 0;                   // the framebuffer the last frame loaded from (its overflow redraw reads it again)
-    hipEvent_t src_ready = nullptr;     // frame lanes: the source frame's raster, waited for by the load frame's raster
-    hipEvent_t read_done[NFB] = {};     // frame lanes: the raster of the load frame that read framebuffer fb; writers of fb wait for it
+    Event src_ready;                    // frame lanes: the source frame's raster, waited for by the load frame's raster
+    Event read_done[NFB];               // frame lanes: the raster of the load frame that read framebuffer fb; writers of fb wait for it
     bool read_recorded[NFB] = {};
     // pinned staging for destinations that are not page-locked (two 8 MiB chunks per image, D2H / memcpy pipelined)
     static constexpr size_t STAGE_BYTES = 8u << 20;
-    void* stage[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    hipEvent_t stage_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    Pinned<uint8_t> stage[2][2];
+    Event stage_ev[2][2];
     // the last swr_present (for the redo of a frame whose pair list overflowed)
     void* present_color = nullptr;
     float* present_depth = nullptr;
@@ -268,7 +319,7 @@ struct swr_context {
         DevBuf biglist;        // fixed-stride bins: the frame's deferred large triangles (k_bin -> k_sort_bins)
         DevBuf live;           // per binning workgroup: count + surviving stream-group ids (k_setup_hist -> k_fill_lds)
         DevBuf tilebuf;        // [CNT_WORDS counters][tiles tile_count][tiles+1 tile_start][tiles cursor]
-        hipEvent_t bin_done = nullptr;     // two-stream: the binning chain's completion; lanes: polled by the injected lost event only
+        Event bin_done;                    // two-stream: the binning chain's completion; lanes: polled by the injected lost event only
         // draw-list frames: the item table (pinned staging -> device, on the frame's own stream, before its binning)
         // and the frame's per-slot colours / attributes / original-index table (k_list_gather)
         DevBuf items, lrgb, lnrm, linv;
@@ -276,15 +327,14 @@ struct swr_context {
         DevBuf cxyz, crgb, cnrm, cmap, cbox, csums;
         // perspective frames: the frame's per-slot (q_a, q_b, q_c, bypass) table (k_persp_fill / k_clip_emit)
         DevBuf pq;
-        ListItem* items_host = nullptr;     // pinned; rewritten only after items_copied (its last copy) has completed
+        Pinned<ListItem> items_host;        // pinned; rewritten only after items_copied (its last copy) has completed
         size_t items_cap = 0;
-        hipEvent_t items_copied = nullptr;
+        Event items_copied;
         bool items_recorded = false;
         uint64_t items_frame = 0;           // the frame whose copy items_copied follows
     } slot[NSLOT];
     hipStream_t bin_stream = nullptr;   // the stream binning is enqueued on (== stream when pipelining is off); every scheduler: sched_of reads it
-    hipStream_t bin_stream_own = nullptr;
-    hipEvent_t up_chunk_ev = nullptr;   // one-shot upload: index chunk k resident / its stream built
+    Event up_chunk_ev;                  // one-shot upload: index chunk k resident / its stream built
     uint64_t frame_no = 0;
     uint64_t synced_upto = 0;           // every frame below this has completed (full stream sync seen by the caller)
     int last_slot = 0;
@@ -299,14 +349,13 @@ struct swr_context {
     // 5 us gap behind every kernel that carries a completion signal, the polls of two helper threads — is gone: cfg4 76 -> 67 us
     // per frame, and a thin band (1/8 of the frame: bound by its kernel chain, not by the chip) 24.5 -> 15.9 us
     // (profiles/r04/lanes_probe.txt).  SWR_LANES=0 keeps the two-stream pipeline.
-    hipStream_t lane_stream[NSLOT] = {};
     bool lanes_ok = false;
     DevBuf lanefill[NSLOT][2];
     bool lanefill_dirty[NSLOT][2] = {};
     // pacing of an un-waited burst: every PACE_EVERY-th frame leaves a marker behind its raster; a draw waits for the marker of
     // 3 * PACE_EVERY frames ago (the per-frame pinned words are a ring of PAIR_RING frames)
     static constexpr int PACE_EVERY = 24;
-    hipEvent_t pace_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event pace_ev[4];
     uint64_t pace_frame[4] = {~0ull, ~0ull, ~0ull, ~0ull};
     uint32_t cap_tile = 0;              // entries per tile region
     bool fixed_mode = false;            // frames are binned by k_bin (else: exact-size bins, four kernels)
@@ -319,12 +368,12 @@ struct swr_context {
     // (Fixed-stride bins: words [PAIR_RING + 1, 2 PAIR_RING + 1) receive the LARGEST tile fill of frame f — the overflow
     // test there is per tile region.)
     static constexpr int PAIR_RING = 256;
-    uint32_t* h_pairs = nullptr;
+    Pinned<uint32_t> h_pairs;
     uint32_t* h_pairs_dev = nullptr;
     bool frame_presented[PAIR_RING] = {};   // was frame f copied to the host (swr_present)?  Only then can an overflow be seen
     bool frame_load[PAIR_RING] = {};        // did frame f start from the image of frame f - 1 (a load frame)?
     bool src_bad = false;                   // the image of frame frames_checked - 1 is wrong: an overflow left it empty, or it loaded one
-    uint32_t* h_misc = nullptr;
+    Pinned<uint32_t> h_misc;
     // Depth-only z-tested frames: 32-bit depth keys (k_raster_depth) until the scene shows that too many of its tiles have
     // to be rastered again with the 64-bit keys (depths that are not > +0: a 2-D scene at z = 0, geometry in front of the
     // near plane); word 2 PAIR_RING + 1 of h_pairs receives the sampled count of such tiles, one launch late.
@@ -363,14 +412,14 @@ struct swr_context {
         // three or four launches, event record) is enqueued by `bin_worker` while the caller's thread enqueues the raster
         // stream's share (event wait, launches, event record) of the PREVIOUS frame — a thin band or a small scene is
         // bound by the host's enqueue rate, not by the GPU.
-        Worker* bin_worker = nullptr;
+        std::unique_ptr<Worker> bin_worker;
         // ... and a third one for the raster stream's share, for a different reason: a cross-stream hipStreamWaitEvent in
         // front of a kernel costs that kernel ~10 us after its predecessor on the queue has ended, even when the event
         // completed long before (profiles/r02/gaps_pipelined_before.txt) — a wait that is never enqueued costs nothing.
         // `ras_worker` polls hipEventQuery(bin_done) of the frame and only then enqueues k_raster, with no wait in front
         // (and `bin_worker` does the same with ras_done before it re-uses a working set).  swr_draw / swr_present only post.
         // SWR_EVENT_WAITS=1: the caller's thread enqueues the raster share behind event waits (round-2 first half).
-        Worker* ras_worker = nullptr;
+        std::unique_ptr<Worker> ras_worker;
         // bin_done / ras_done are bound to the kernels they follow (hipExtLaunchKernelGGL's stop event) instead of being
         // recorded behind them: a marker packet between two kernels of a queue costs the second one ~6.5 us.  SWR_BIND_EVENTS=0: record.
         bool bind_events = true;
@@ -384,7 +433,7 @@ struct swr_context {
         static constexpr int RAS_RING = 64;          // frames whose raster share may be waiting for ras_worker; swr_draw blocks beyond that
         struct RasJob { DeviceFrame f; hipEvent_t ev3 = nullptr, ev4 = nullptr; int si = 0; bool sort_here = false; int fb = 0; bool paced = false; } ras_job[RAS_RING];
         // per working set: the completion of the event-carrying k_raster that read it, and the frame whose k_raster it tracks (none yet)
-        struct RasDone { hipEvent_t ev = nullptr; uint64_t frame = ~0ull; } ras_done[NSLOT];
+        struct RasDone { Event ev; uint64_t frame = ~0ull; } ras_done[NSLOT];
     } ts;
     // ---- draw lists (swr_draw_list)
     bool stream_sorted = false;         // the stream is Morton-sorted: a list's ranges must be runs of slots (cut the stream at them)
@@ -393,7 +442,7 @@ struct swr_context {
     // (clip_fan and clip_total are not in the record: they are how the context sizes a clip frame — check_frames grows the fan — not what was drawn)
     int64_t clip_fan = 0;               // fan capacity F: a clip frame of n triangles has n + 2F slots (each crossing triangle adds <= 2)
     int64_t clip_total = -1;            // the post-clip count of the last clip frame when the host had to know it (else -1)
-    uint32_t* h_clip = nullptr;         // pinned, device-mapped: [PAIR_RING] per frame, the post-clip count of a clip frame whose fans
+    Pinned<uint32_t> h_clip;            // pinned, device-mapped: [PAIR_RING] per frame, the post-clip count of a clip frame whose fans
     uint32_t* h_clip_dev = nullptr;     // overflowed its slots (0: none); [PAIR_RING] the post-clip count the host asked for
     int64_t list_plan_max = 0;          // largest binning size (work units * 64) of a list since the upload (fixed-bin limits)
     // The last draw: what its frame is built from (make_frame, make_list_frame, make_clip_frame) and what its redo after an overflow
@@ -417,9 +466,8 @@ struct swr_context {
     static constexpr int RING = 64;
     int timing = 0;            // 0 off, 1 = events around k_raster only, 2 = around every stage
     int timing_every = 1;      // level 1: bracket only every n-th frame's k_raster (swr_timing_sample)
-    hipEvent_t ev[RING][5]{};
+    Event ev[RING][5];
     int ev_level[RING]{};
-    bool ev_ok = false;
     uint64_t seq = 0;          // frames enqueued with timing on
     uint64_t harvested = 0;    // frames whose events have been read
     swr_timings last{};
@@ -489,6 +537,11 @@ int sticky(swr_context* c) {
 // `rc` of a failed wait — or, when the context has failed for good meanwhile, that failure
 inline int or_sticky(swr_context* c, int rc) { const int f = sticky(c); return f ? f : rc; }
 
+// The bands of c: the sub-contexts of a group, or the context itself.  Band 0 answers for the scene every band holds.
+inline bool is_group(const swr_context* c) { return !c->kids.empty(); }
+inline size_t band_count(const swr_context* c) { return is_group(c) ? c->kids.size() : 1; }
+template <class C> inline C* band(C* c, size_t k) { return is_group(c) ? c->kids[k] : c; }
+
 // Bounded waiting: spin, then yield, never beyond the context's budget; gives up at once when the context has failed.
 struct Deadline {
     std::chrono::steady_clock::time_point end;
@@ -513,7 +566,7 @@ struct Deadline {
 int ensure(swr_context* c, DevBuf& b, size_t bytes) {
     if (bytes == 0) bytes = 16;
     if (b.bytes >= bytes) return SWR_OK;
-    if (b.p) { HIP_TRY(c, hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
+    HIP_TRY(c, b.reset());
     // grow geometrically so a slowly growing scene does not reallocate every frame
     size_t want = bytes + bytes / 8;
     hipError_t e = hipMalloc(&b.p, want);
@@ -527,7 +580,7 @@ int ensure(swr_context* c, DevBuf& b, size_t bytes) {
 
 int ensure_host(swr_context* c, HostBuf& b, size_t words) {
     if (b.words >= words) return SWR_OK;
-    if (b.p) { HIP_TRY(c, hipHostFree(b.p)); b.p = nullptr; b.words = 0; }
+    HIP_TRY(c, b.reset());
     const size_t want = words + words / 8;
     HIP_TRY(c, hipHostMalloc((void**)&b.p, want * 4, hipHostMallocDefault));
     b.words = want;
@@ -974,7 +1027,7 @@ struct ListPrep {
 int stage_list(swr_context* c, int si, uint64_t frame, ListPrep& lp) {
     swr_context::Slot& sl = c->slot[si];
     int rc;
-    if (!sl.items_copied) HIP_TRY(c, hipEventCreateWithFlags(&sl.items_copied, hipEventDisableTiming));
+    if (!sl.items_copied) HIP_TRY(c, sl.items_copied.create(hipEventDisableTiming));
     if (sl.items_recorded && sl.items_frame < frame) {      // (a frame number posted again after a failed post: it never copied)
         if (sched_of(c) != Sched::Lanes && (rc = wait_counter(c, c->bin_enqueued, sl.items_frame, "the binning share of an earlier draw list"))) return rc;
         if ((rc = poll_event(c, sl.items_copied, "the copy of an earlier frame's draw list", sl.items_frame))) return rc;
@@ -982,9 +1035,10 @@ int stage_list(swr_context* c, int si, uint64_t frame, ListPrep& lp) {
     }
     const size_t n = c->last_draw.list.size();
     if (sl.items_cap < n) {
-        if (sl.items_host) { HIP_TRY(c, hipHostFree(sl.items_host)); sl.items_host = nullptr; sl.items_cap = 0; }
+        sl.items_cap = 0;
+        HIP_TRY(c, sl.items_host.reset());
         const size_t want = std::max<size_t>(64, n);
-        HIP_TRY(c, hipHostMalloc((void**)&sl.items_host, want * sizeof(ListItem), hipHostMallocDefault));
+        HIP_TRY(c, sl.items_host.alloc(want * sizeof(ListItem), hipHostMallocDefault));
         sl.items_cap = want;
     }
     if (n) memcpy(sl.items_host, c->last_draw.list.data(), n * sizeof(ListItem));
@@ -1006,7 +1060,7 @@ int enqueue_list_prep(swr_context* c, const ListPrep& lp, hipStream_t s) {
 // read the events of every completed-but-unread frame (caller has synchronised the stream)
 void harvest(swr_context* c) {
     for (; c->harvested < c->seq; c->harvested++) {
-        hipEvent_t* ev = c->ev[c->harvested % swr_context::RING];
+        const Event* ev = c->ev[c->harvested % swr_context::RING];
         float ms[5] = {0, 0, 0, 0, 0};
         if (c->ev_level[c->harvested % swr_context::RING] >= 2) {
             hipEventElapsedTime(&ms[0], ev[0], ev[1]);
@@ -1104,7 +1158,7 @@ int enqueue_points_frame(swr_context* c, const swr_context::DrawRecord& d) {
 }
 
 // *ev = the set of timing events of the frame about to be posted (swr_timing_enable), NULL when it is not timed
-int claim_timing_events(swr_context* c, hipEvent_t** ev) {
+int claim_timing_events(swr_context* c, const Event** ev) {
     *ev = nullptr;
     if (c->timing < 2 && !(c->timing == 1 && (c->frame_no % (uint64_t)c->timing_every) == 0)) return SWR_OK;
     if (c->seq - c->harvested >= (uint64_t)swr_context::RING) { int rc = sync_streams(c); if (rc) return rc; harvest(c); }   // ring full: drain it
@@ -1152,7 +1206,7 @@ int pace_burst(swr_context* c, uint64_t frame) {
 }
 
 // what the frame puts on its lane S: the binning chain, k_sort_bins, the raster, and the markers behind it
-int enqueue_lane_chain(swr_context* c, const DeviceFrame& f, int si, uint64_t frame, hipStream_t S, const BinChain& bc, hipEvent_t* ev, bool src_wait) {
+int enqueue_lane_chain(swr_context* c, const DeviceFrame& f, int si, uint64_t frame, hipStream_t S, const BinChain& bc, const Event* ev, bool src_wait) {
     bool bound;
     { const int rb = enqueue_binning(c, f, si, S, bc, nullptr, &bound); if (rb) return rb; }
     if (!f.skip_sort) launch_sort_bins(f, S, nullptr);
@@ -1173,7 +1227,7 @@ int enqueue_lane_chain(swr_context* c, const DeviceFrame& f, int si, uint64_t fr
     return SWR_OK;
 }
 
-int enqueue_lane_frame(swr_context* c, const DeviceFrame& f, int si, uint64_t frame, const BinChain& bc, hipEvent_t* ev) {
+int enqueue_lane_frame(swr_context* c, const DeviceFrame& f, int si, uint64_t frame, const BinChain& bc, const Event* ev) {
     hipStream_t S = c->lane_stream[si];
     const int inj = c->inject.exchange(0, std::memory_order_relaxed);      // swr_debug_fault
     if (inj == SWR_FAULT_ENQUEUE) return abandon_frame(c, frame, fatal(c, SWR_ERR_HIP, "frame %llu: injected enqueue failure (swr_debug_fault)", (unsigned long long)frame));
@@ -1219,7 +1273,7 @@ int bin_share(swr_context* c, const BinShare& b) {
         }
     }
     // bin_done = the completion of the chain's last kernel itself (bound at launch) where there is one
-    hipEvent_t stop = (b.two_streams && c->ts.bind_events) ? sl.bin_done : nullptr;
+    hipEvent_t stop = (b.two_streams && c->ts.bind_events) ? sl.bin_done.h : nullptr;
     bool bound;
     { const int rb = enqueue_binning(c, b.f, b.si, b.sb, b.bc, (b.sort_on_raster_stream || b.f.skip_sort) ? stop : nullptr, &bound); if (rb) return rb; }
     if (!b.sort_on_raster_stream && !b.f.skip_sort) bound = launch_sort_bins(b.f, b.sb, stop);
@@ -1241,7 +1295,7 @@ int bin_job(swr_context* c, const BinShare& b) {
 }
 
 // Binning onto bin_stream, raster onto `stream` (one stream: the same), each share enqueued by a helper thread or by the caller's own.
-int enqueue_two_stream_frame(swr_context* c, Sched sched, const DeviceFrame& f, int si, uint64_t frame, const BinChain& bc, hipEvent_t* ev,
+int enqueue_two_stream_frame(swr_context* c, Sched sched, const DeviceFrame& f, int si, uint64_t frame, const BinChain& bc, const Event* ev,
                              bool sort_on_raster_stream) {
     TS& ts = c->ts;
     const bool two = sched == Sched::TwoStream;
@@ -1251,13 +1305,13 @@ int enqueue_two_stream_frame(swr_context* c, Sched sched, const DeviceFrame& f, 
     const bool slot_wait = two && frame >= (uint64_t)swr_context::NSLOT && frame - (uint64_t)swr_context::NSLOT >= c->synced_upto;
     // helpers or the caller's own thread?  (idle context: every earlier frame is complete)
     const bool streaming = two && (ts.bin_worker || ts.ras_worker) && !(ts.inline_idle && c->synced_upto == c->posted);
-    const bool paced = streaming && ts.ras_worker != nullptr;      // cross-stream order by host polls instead of event waits
+    const bool paced = streaming && ts.ras_worker;      // cross-stream order by host polls instead of event waits
     if (frame >= (uint64_t)TS::RAS_RING) {
         const int rc = wait_counter(c, c->ras_enqueued, frame - (uint64_t)TS::RAS_RING, "the raster share of an earlier frame");
         if (rc) { c->frame_no = frame; return or_sticky(c, rc); }     // nothing was posted for this frame
     }
     TS::RasJob& rj = ts.ras_job[frame % TS::RAS_RING];
-    rj.f = f; rj.ev3 = ev ? ev[3] : nullptr; rj.ev4 = ev ? ev[4] : nullptr; rj.si = si; rj.sort_here = sort_on_raster_stream;
+    rj.f = f; rj.ev3 = ev ? ev[3].h : nullptr; rj.ev4 = ev ? ev[4].h : nullptr; rj.si = si; rj.sort_here = sort_on_raster_stream;
     rj.fb = c->fb_cur; rj.paced = paced;
     c->draw_pending = true;   // the pair total lands in the frame's pinned word (written by the scan)
     c->posted = frame + 1;
@@ -1312,7 +1366,7 @@ int enqueue_frame(swr_context* c) {
     }
     c->h_clip[frame % swr_context::PAIR_RING] = 0u;
     if (d.clip) make_clip_frame(c, si, frame, d, f);
-    hipEvent_t* ev = nullptr;
+    const Event* ev = nullptr;
     if ((rc = claim_timing_events(c, &ev))) return rc;
     c->hp_lap(0);
     const bool sort_on_raster_stream = settle_policy(c, sched, f);
@@ -1359,7 +1413,7 @@ int raster_share(swr_context* c, uint64_t g) {
     if (rj.sort_here) launch_sort_bins(rj.f, sr);
     if (rj.ev3) HIP_TRY(c, hipEventRecord(rj.ev3, sr));
     const bool carries = two && g % (uint64_t)TS::RAS_EVERY == (uint64_t)(TS::RAS_EVERY - 1);
-    const bool bound = launch_raster(rj.f, sr, (carries && c->ts.bind_events) ? rd.ev : nullptr);
+    const bool bound = launch_raster(rj.f, sr, (carries && c->ts.bind_events) ? rd.ev.h : nullptr);
     if (rj.ev4) HIP_TRY(c, hipEventRecord(rj.ev4, sr));
     c->hp_lap_r(4);
     if (carries) { if (!bound) HIP_TRY(c, hipEventRecord(rd.ev, sr)); rd.frame = g; }
@@ -1401,8 +1455,8 @@ bool is_pinned(const void* p) {
 
 int ensure_stage(swr_context* c, int img) {
     for (int k = 0; k < 2; k++) {
-        if (!c->stage[img][k]) HIP_TRY(c, hipHostMalloc(&c->stage[img][k], swr_context::STAGE_BYTES, hipHostMallocDefault));
-        if (!c->stage_ev[img][k]) HIP_TRY(c, hipEventCreateWithFlags(&c->stage_ev[img][k], hipEventDisableTiming));
+        if (!c->stage[img][k]) HIP_TRY(c, c->stage[img][k].alloc(swr_context::STAGE_BYTES, hipHostMallocDefault));
+        if (!c->stage_ev[img][k]) HIP_TRY(c, c->stage_ev[img][k].create(hipEventDisableTiming));
     }
     return SWR_OK;
 }
@@ -1504,8 +1558,8 @@ int enqueue_pose(swr_context* c, bool with_nrm) {
 
 // swr_scene_morph(NULL), a new scene: no targets, no weights; the delta planes go back to the device
 void drop_morph(swr_context* c) {
-    for (DevBuf* b : {&c->morph_dpos, &c->morph_dnrm})
-        if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->bytes = 0; }
+    (void)c->morph_dpos.reset();
+    (void)c->morph_dnrm.reset();
     c->morph_targets = 0;
     c->morph_has_nrm = false;
     c->morph_active = false;
@@ -1561,7 +1615,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
         if ((rc = ensure(c, sl.live, (size_t)((index_count / 3 + 63) / 64 + 2 * 1024 + 2) * 4))) return rc;   // [G <= 1024][1 + per]
         if ((rc = ensure(c, sl.tilebuf, (size_t)(CNT_WORDS + 3 * std::max(1, tiles_of(c->tg)) + 1) * 4))) return rc;
     }
-    for (auto& e : c->up_ev) if (!e) HIP_TRY(c, hipEventCreate(&e));
+    for (Event& e : c->up_ev) if (!e) HIP_TRY(c, e.create());
     HIP_TRY(c, hipEventRecord(c->up_ev[0], c->stream));
     if (vertex_count)
         HIP_TRY(c, hipMemcpyAsync(c->vertices.p, vertices, (size_t)vertex_count * sizeof(swr_vertex),
@@ -1578,14 +1632,14 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     HIP_TRY(c, hipMemsetAsync(bad, 0, CNT_WORDS * 4, c->stream));
     // One-shot scenes with an index array worth cutting up (>= 4 MiB): the index check and the stream of chunk k run on
     // the binning stream while chunk k+1 is on the link (a copy from pageable memory returns when its bytes are staged)
-    hipStream_t side = c->bin_stream_own && c->bin_stream_own != c->stream ? c->bin_stream_own : nullptr;
+    hipStream_t side = c->bin_stream_own.h;      // (a stream of its own, or none)
     const int64_t chunk_min = c->dbg_oneshot_min_tris;                   // (SWR_DEBUG_ONESHOT_MIN_TRIS: chunk small scenes too)
     const bool chunked = oneshot && side && sort_mode != -1 && ntri >= chunk_min && ntri < SORT_MAX_TRIS;
     if (chunked) {
         // two chunks, the second one small: every extra copy call from pageable memory costs the link ~30 us, the last
         // chunk's build is the tail (cfg4, whole call: {100} 3.10 ms, {70,100} 3.06, {50,82,100} 3.07, four quarters 3.12)
         constexpr int cuts[] = SWR_TUNE_ONESHOT_CUTS;          // per cent of the primitives
-        if (!c->up_chunk_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->up_chunk_ev, hipEventDisableTiming));
+        if (!c->up_chunk_ev) HIP_TRY(c, c->up_chunk_ev.create(hipEventDisableTiming));
         HIP_TRY(c, hipEventRecord(c->up_chunk_ev, c->stream));           // (vertices resident, counter words zero)
         HIP_TRY(c, hipStreamWaitEvent(side, c->up_chunk_ev, 0));
         int64_t t0 = 0;
@@ -1741,7 +1795,7 @@ int upload_deltas(swr_context* c, void* dst, const float* src, size_t count /* t
     for (size_t at = 0; at < count; at += per) {
         const size_t n = std::min(per, count - at), k = chunks++;
         if (k >= 2 && (rc = poll_event(c, c->stage_ev[0][k & 1], "a staged copy of morph deltas", c->frame_no))) return rc;
-        float* st = (float*)c->stage[0][k & 1];
+        float* st = (float*)c->stage[0][k & 1].p;
         if (SWR_TUNE_MORPH_PAD)
             for (size_t i = 0; i < n; i++) {
                 st[4 * i] = src[3 * (at + i)]; st[4 * i + 1] = src[3 * (at + i) + 1]; st[4 * i + 2] = src[3 * (at + i) + 2]; st[4 * i + 3] = 0.0f;
@@ -1769,29 +1823,28 @@ int single_scene_morph(swr_context* c, const swr_morph_targets* t) {
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
     if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the shape it was drawn in)
-    DevBuf dpos, dnrm;                          // the new planes: the old ones stay until these are filled
+    DevBuf dpos, dnrm;                          // the new planes: the old ones stay until these are filled (a failure frees them)
     if (t) {
         const size_t count = (size_t)t->target_count * (size_t)c->nv;
         const size_t bytes = std::max<size_t>(16, count * (SWR_TUNE_MORPH_PAD ? 16 : 12));
-        auto undo = [&](int code) { if (dpos.p) (void)hipFree(dpos.p); if (dnrm.p) (void)hipFree(dnrm.p); return code; };
         for (DevBuf* b : {&dpos, &dnrm}) {
             if (b == &dnrm && !t->normal_deltas) break;
             const hipError_t e = hipMalloc(&b->p, bytes);
             if (e != hipSuccess) {
                 b->p = nullptr;
-                return undo(fail(c, SWR_ERR_NOMEM, "swr_scene_morph: hipMalloc(%zu) for the deltas failed: %s", bytes, hipGetErrorString(e)));
+                return fail(c, SWR_ERR_NOMEM, "swr_scene_morph: hipMalloc(%zu) for the deltas failed: %s", bytes, hipGetErrorString(e));
             }
             b->bytes = bytes;
         }
         size_t chunks = 0;
-        if ((rc = upload_deltas(c, dpos.p, t->position_deltas, count, chunks))) return undo(rc);
-        if (t->normal_deltas && (rc = upload_deltas(c, dnrm.p, t->normal_deltas, count, chunks))) return undo(rc);
-        if ((rc = wait_stream(c, c->stream, "morph target upload"))) return undo(or_sticky(c, rc));
+        if ((rc = upload_deltas(c, dpos.p, t->position_deltas, count, chunks))) return rc;
+        if (t->normal_deltas && (rc = upload_deltas(c, dnrm.p, t->normal_deltas, count, chunks))) return rc;
+        if ((rc = wait_stream(c, c->stream, "morph target upload"))) return or_sticky(c, rc);
     }
     const bool was_active = c->morph_active;
     drop_morph(c);
     if (t) {
-        c->morph_dpos = dpos; c->morph_dnrm = dnrm;
+        c->morph_dpos = std::move(dpos); c->morph_dnrm = std::move(dnrm);
         c->morph_targets = t->target_count;
         c->morph_has_nrm = t->normal_deltas != nullptr;
         c->morph_w.assign((size_t)t->target_count, 0.0f);
@@ -1870,10 +1923,10 @@ int check_target_args(swr_context* c, int64_t width, int64_t height, int64_t row
     return SWR_OK;
 }
 
+// swr_target_set on one band: rows [row_begin, row_end) of the target the entry point has checked
 int single_target_set(swr_context* c, int64_t width, int64_t height, int64_t row_begin, int64_t row_end) {
     if (const int f = sticky(c)) return f;
-    int rc = check_target_args(c, width, height, row_begin, row_end);
-    if (rc) return rc;
+    int rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->src_clear = true;        // the band images are the cleared ones again (what the next load frame starts from)
     c->ids_valid = false;       // (and no frame on them has written IDs)
@@ -2004,8 +2057,10 @@ int single_draw(swr_context* c, const float transform[16], uint32_t flags, int32
 }
 
 // ---- swr_draw_list ----------------------------------------------------------------------------------------------
-// The argument checks of a list against a scene of `ni` indices (ready: a scene and a target are there); *tris = the list's total.
-int check_list_args(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags, bool ready, int64_t ni, int64_t* tris) {
+// The argument checks of a list on a band or a group alike: against c's target and the scene every band holds; *tris = the list's total.
+int check_list_args(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags, int64_t* tris) {
+    const swr_context* scene = band(c, 0);
+    const int64_t ni = scene->ni;
     int rc = check_draw_args(c, flags, SWR_PRIMITIVE_TRIANGLE);
     if (rc) return rc;
     if (n < 0) return fail(c, SWR_ERR_BAD_ARG, "swr_draw_list: item_count %d", (int)n);
@@ -2015,7 +2070,7 @@ int check_list_args(swr_context* c, const swr_draw_item* items, int32_t n, uint3
         if (items[k].first_index % 3 != 0 || items[k].index_count % 3 != 0)
             return fail(c, SWR_ERR_INDEX_COUNT, "swr_draw_list: item %d: first_index %lld / index_count %lld not a multiple of 3", (int)k,
                         (long long)items[k].first_index, (long long)items[k].index_count);
-    if (!ready) return fail(c, SWR_ERR_NO_SCENE, "swr_draw_list needs swr_scene_upload and swr_target_set first");
+    if (!scene->has_scene || !c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_draw_list needs swr_scene_upload and swr_target_set first");
     int64_t total = 0;
     for (int32_t k = 0; k < n; k++) {
         const int64_t a = items[k].first_index, cnt = items[k].index_count;
@@ -2072,11 +2127,10 @@ int cut_stream(swr_context* c, std::vector<uint32_t>& need) {
     return restream(c, cuts);
 }
 
-int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags) {
+// swr_draw_list on one band: a list check_list_args has passed, of `tris` triangles
+int single_draw_list(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags, int64_t tris) {
     if (const int f = sticky(c)) return f;
-    int64_t tris = 0;
-    int rc = check_list_args(c, items, n, flags, c->has_scene && c->has_target, c->ni, &tris);
-    if (rc) return rc;
+    int rc;
     if ((rc = begin_draw(c, flags, SWR_PRIMITIVE_TRIANGLE))) return rc;
     // the items, resolved: primitive ranges, frame bases, work units
     std::vector<ListItem> list((size_t)n);
@@ -2273,7 +2327,6 @@ int check_frames(swr_context* c) {
 // starts from).  Everything drawn before is finished and checked first; NULL keeps that image (the cleared one after swr_target_set).
 int single_target_write(swr_context* c, const void* color_full, const float* depth_full) {
     if (const int f = sticky(c)) return f;
-    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_target_write needs swr_target_set first");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
     if ((rc = check_frames(c)) || (rc = sync_copies(c))) return rc;
@@ -2336,7 +2389,12 @@ int single_read(swr_context* c, int img, void* dst) {
     return SWR_OK;
 }
 
-// what a swr_resolve may hold (the target's size is checked against it where the target is known: check_resolve_target)
+// Every query below comes in two parts.  check_X: what the call may be handed, against c->tg — a band's own target or the full one a
+// group keeps, so it holds for either kind of context and runs once, before any band is touched.  band_X: one band's work — sticky,
+// the state only a band has (ids_valid, the last draw), the launches, the wait — which leaves the band's answer in its own staging for
+// the entry point to gather over the bands of c.
+
+// what a swr_resolve may hold (swr_render_resolved checks it before it has a target)
 int check_resolve_args(swr_context* c, const swr_resolve& rs) {
     if (rs.factor != 1 && rs.factor != 2 && rs.factor != 4)
         return fail(c, SWR_ERR_BAD_ARG, "swr_resolve: factor %d is not 1, 2 or 4", rs.factor);
@@ -2346,7 +2404,11 @@ int check_resolve_args(swr_context* c, const swr_resolve& rs) {
     return SWR_OK;
 }
 
-int check_resolve_target(swr_context* c, const swr_resolve& rs, const Target& t) {
+int check_resolve(swr_context* c, const swr_resolve& rs) {
+    const int rc = check_resolve_args(c, rs);
+    if (rc) return rc;
+    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_*_resolved needs swr_target_set first");
+    const Target& t = c->tg;
     if (t.width % rs.factor || t.height % rs.factor)
         return fail(c, SWR_ERR_BAD_ARG, "supersampled resolve: the target %dx%d is not a multiple of the factor %d", t.width, t.height, rs.factor);
     // (row_begin is a multiple of the tile height; a row_end that is one too, or the height, passes: whole sample blocks per band)
@@ -2357,12 +2419,9 @@ int check_resolve_target(swr_context* c, const swr_resolve& rs, const Target& t)
 
 // swr_read_color_resolved / swr_read_depth_resolved (one image) and the gather of swr_render_resolved (both, one launch): the last
 // frame's band, resolved by rs.factor, into rows [row_begin / S, row_end / S) of the caller's (W/S) x (H/S) images.  NULL: not wanted.
-int single_read_resolved(swr_context* c, swr_resolve rs, void* color_dst, float* depth_dst) {
+int band_read_resolved(swr_context* c, swr_resolve rs, void* color_dst, float* depth_dst) {
     if (const int f = sticky(c)) return f;
-    int rc = check_resolve_args(c, rs);
-    if (rc) return rc;
-    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_*_resolved needs swr_target_set first");
-    if ((rc = check_resolve_target(c, rs, c->tg))) return rc;
+    int rc;
     if (rs.factor == 1) {       // one sample per pixel: the plain read
         if (color_dst && (rc = single_read(c, 0, color_dst))) return rc;
         return depth_dst ? single_read(c, 1, depth_dst) : SWR_OK;
@@ -2389,15 +2448,13 @@ int single_read_resolved(swr_context* c, swr_resolve rs, void* color_dst, float*
 }
 
 // what a swr_id_count may hold, and its rectangle against the full target
-int check_count_args(swr_context* c, const swr_id_count& q, const uint32_t* counts, int64_t n) {
+int check_count(swr_context* c, const swr_id_count& q, const uint32_t* counts, int64_t n) {
     if (q.group != SWR_COUNT_PER_PRIMITIVE && q.group != SWR_COUNT_PER_ITEM)
         return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: unknown group %d", q.group);
     if (q.reserved[0] || q.reserved[1] || q.reserved[2]) return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: reserved words must be 0");
     if (n < 0 || (n > 0 && !counts)) return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: counts is NULL or n is negative (n = %lld)", (long long)n);
-    return SWR_OK;
-}
-
-int check_count_rect(swr_context* c, const swr_id_count& q, const Target& t) {
+    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_count_ids needs swr_target_set first");
+    const Target& t = c->tg;
     if (q.x0 < 0 || q.y0 < 0 || q.x0 > q.x1 || q.y0 > q.y1 || q.x1 > t.width || q.y1 > t.height)
         return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: the rectangle [%d,%d) x [%d,%d) is inverted or outside the target %dx%d",
                     q.x0, q.x1, q.y0, q.y1, t.width, t.height);
@@ -2406,12 +2463,9 @@ int check_count_rect(swr_context* c, const swr_id_count& q, const Target& t) {
 
 // swr_count_ids on one band: the part of the rectangle in the band's rows, counted into c->count_host.p[0 .. n] (word n: SWR_ID_NONE).
 // A band the rectangle misses, or one without tiles, launches nothing and leaves zeros there.
-int single_count_ids(swr_context* c, swr_id_count q, const uint32_t* counts, int64_t n) {
+int band_count_ids(swr_context* c, swr_id_count q, int64_t n) {
     if (const int f = sticky(c)) return f;
-    int rc = check_count_args(c, q, counts, n);
-    if (rc) return rc;
-    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_count_ids needs swr_target_set first");
-    if ((rc = check_count_rect(c, q, c->tg))) return rc;
+    int rc;
     if (!c->ids_valid)
         return fail(c, SWR_ERR_BAD_ARG, "swr_count_ids: the last frame was drawn without SWR_FLAG_PRIMITIVE_IDS, or swr_target_set / "
                     "swr_target_write / swr_scene_upload came after it");
@@ -2438,15 +2492,13 @@ int single_count_ids(swr_context* c, swr_id_count q, const uint32_t* counts, int
 }
 
 // what swr_query_depth may be handed, and every box against the full target
-int check_query_args(swr_context* c, const swr_depth_box* boxes, int64_t n, const uint32_t* passed) {
+int check_query(swr_context* c, const swr_depth_box* boxes, int64_t n, const uint32_t* passed) {
     if (n < 0 || (n > 0 && (!boxes || !passed)))
         return fail(c, SWR_ERR_BAD_ARG, "swr_query_depth: boxes or passed is NULL, or n is negative (n = %lld)", (long long)n);
     if (n > SWR_DEPTH_QUERY_MAX)
         return fail(c, SWR_ERR_UNSUPPORTED, "swr_query_depth: %lld boxes, at most %d per call", (long long)n, SWR_DEPTH_QUERY_MAX);
-    return SWR_OK;
-}
-
-int check_query_boxes(swr_context* c, const swr_depth_box* boxes, int64_t n, const Target& t) {
+    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_query_depth needs swr_target_set first");
+    const Target& t = c->tg;
     for (int64_t k = 0; k < n; k++) {
         const swr_depth_box& b = boxes[k];
         if (b.reserved[0] || b.reserved[1] || b.reserved[2])
@@ -2461,12 +2513,9 @@ int check_query_boxes(swr_context* c, const swr_depth_box* boxes, int64_t n, con
 // swr_query_depth on one band: the part of every box in the band's rows, tested against the band's depth image — the buffer
 // single_read copies for swr_read_depth — into c->query_passed[0 .. n).  A band no box touches, or one without tiles, launches nothing
 // and leaves zeros there.
-int single_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, const uint32_t* passed) {
+int band_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n) {
     if (const int f = sticky(c)) return f;
-    int rc = check_query_args(c, boxes, n, passed);
-    if (rc) return rc;
-    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_query_depth needs swr_target_set first");
-    if ((rc = check_query_boxes(c, boxes, n, c->tg))) return rc;
+    int rc;
     if ((rc = single_sync(c))) return rc;       // (an overflowed last frame is repaired here)
     c->query_passed = nullptr;
     if (n == 0) return SWR_OK;
@@ -2511,10 +2560,10 @@ int single_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, co
                                     // gets no work units, the workgroups of the first apply every matrix of the run
 #endif
 
-// what swr_item_bounds may be handed: swr_draw_list's own checks (ready / ni as there), then what the call adds to them
-int check_bounds_args(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags, const swr_item_bound* out, bool ready, int64_t ni) {
+// what swr_item_bounds may be handed: swr_draw_list's own checks, then what the call adds to them
+int check_bounds(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags, const swr_item_bound* out) {
     int64_t tris = 0;
-    const int rc = check_list_args(c, items, n, flags, ready, ni, &tris);
+    const int rc = check_list_args(c, items, n, flags, &tris);
     if (rc) return rc;
     if (flags & SWR_FLAG_DEPTH_CLIP)
         return fail(c, SWR_ERR_UNSUPPORTED, "swr_item_bounds: SWR_FLAG_DEPTH_CLIP (the rectangle of a clipped fan is not its triangle's)");
@@ -2524,10 +2573,9 @@ int check_bounds_args(swr_context* c, const swr_draw_item* items, int32_t n, uin
 
 // swr_item_bounds on one band (a group: its first): the n records into c->bounds_out[0 .. n), inside the band's page-locked staging.
 // The items are resolved and the stream is cut as single_draw_list does, so the same list drawn afterwards finds its cuts in place.
-int single_item_bounds(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags, const swr_item_bound* out) {
+int band_item_bounds(swr_context* c, const swr_draw_item* items, int32_t n, uint32_t flags) {
     if (const int f = sticky(c)) return f;
-    int rc = check_bounds_args(c, items, n, flags, out, c->has_scene && c->has_target, c->ni);
-    if (rc) return rc;
+    int rc;
     if ((rc = single_sync(c))) return rc;       // (an overflowed last frame is repaired here)
     c->bounds_out = nullptr;
     if (n == 0) return SWR_OK;
@@ -2587,10 +2635,14 @@ int single_item_bounds(swr_context* c, const swr_draw_item* items, int32_t n, ui
 // swr_read_color_delta / swr_read_depth_delta on one band (img: 0 colour, 1 depth): the band's rows of `dst`, which hold what the last
 // delta read of this kind delivered, become what single_read would deliver now; only the bounding box of the tiles that differ from
 // the band's baseline is written.  What was done is left in c->delta_stats.
-int single_read_delta(swr_context* c, int img, void* dst) {
-    if (const int f = sticky(c)) return f;
+int check_delta(swr_context* c, const void* dst) {
     if (!dst) return fail(c, SWR_ERR_BAD_ARG, "swr_read_*_delta: the destination is NULL");
     if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_*_delta needs swr_target_set first");
+    return SWR_OK;
+}
+
+int band_read_delta(swr_context* c, int img, void* dst) {
+    if (const int f = sticky(c)) return f;
     int rc = single_sync(c);        // (an overflowed last frame is repaired here)
     if (rc) return rc;
     swr_delta_stats st{};
@@ -2673,7 +2725,7 @@ int single_read_delta(swr_context* c, int img, void* dst) {
             if (k > 0) {
                 const size_t j = k - 1;
                 if ((rc = poll_event(c, c->stage_ev[img][j & 1], "a staged copy to the host (delta read)", frame))) return rc;
-                const uint8_t* from = (const uint8_t*)c->stage[img][j & 1];
+                const uint8_t* from = c->stage[img][j & 1];
                 for (size_t off = j * CH, left = std::min(CH, rbytes - j * CH); left;) {       // (a chunk may start and end inside a row)
                     const size_t r = off / rrow, col = off - r * rrow, len = std::min(left, rrow - col);
                     memcpy(band_dst + ((size_t)y0 + r) * row + (size_t)x0 * 4 + col, from, len);
@@ -2688,11 +2740,13 @@ int single_read_delta(swr_context* c, int img, void* dst) {
     return SWR_OK;
 }
 
+// Stop the helpers, wait (bounded) for the streams, delete the context: what it owns frees itself (see "ORDER OF FREEING").  A context
+// whose streams do not drain is leaked whole instead — no HIP free or destroy call is made while the GPU may still use its memory.
 void destroy_single(swr_context* c) {
     hipSetDevice(c->device);
     // helper jobs are bounded (every wait in them is) and give up at once on a failed context: the drains return
-    if (c->ts.ras_worker) { c->ts.ras_worker->drain(); c->ts.ras_worker->stop(); delete c->ts.ras_worker; c->ts.ras_worker = nullptr; }
-    if (c->ts.bin_worker) { c->ts.bin_worker->drain(); c->ts.bin_worker->stop(); delete c->ts.bin_worker; c->ts.bin_worker = nullptr; }
+    for (std::unique_ptr<Worker>* w : {&c->ts.ras_worker, &c->ts.bin_worker})
+        if (*w) { (*w)->drain(); w->reset(); }
     // bounded too: a GPU that never finishes must not hang the destructor (what it still owns is then leaked)
     c->wait_budget_ms = std::min<uint32_t>(c->wait_budget_ms, 5000u);
     auto drain = [c](hipStream_t st) {           // (looks at the stream, not at the failed flag: the GPU may be fine)
@@ -2711,60 +2765,13 @@ void destroy_single(swr_context* c) {
     if (!drained) {
         fprintf(stderr, "[swr] context on device %d destroyed in a failed state (%s); device memory it may still be using is not freed\n",
                 c->device, c->failed_msg.c_str());
-        delete c;
-        return;
+        return;         // (the context object goes with it: a few KB of host memory beside everything the device holds)
     }
     if (c->hp_on && c->hp_frames)
         fprintf(stderr, "[swr host profile] device %d, %llu frames, us/frame: prepare %.2f | wait(slot) %.2f | binning launches %.2f | "
                         "event record+wait %.2f | raster-stream launches %.2f | record(ras_done) %.2f\n", c->device,
                 (unsigned long long)c->hp_frames, c->hp_t[0] / c->hp_frames, c->hp_t[1] / c->hp_frames, c->hp_t[2] / c->hp_frames,
                 c->hp_t[3] / c->hp_frames, c->hp_t[4] / c->hp_frames, c->hp_t[5] / c->hp_frames);
-    DevBuf* bufs[] = {&c->redo_cnt, &c->vertices, &c->indices, &c->tri_rgb, &c->tri_xyz, &c->inv, &c->box64, &c->stream_scratch, &c->sort_temp,
-                      &c->attrs, &c->tri_nrm, &c->texture, &c->texture_bytes, &c->cuts_dev, &c->rs_color, &c->rs_depth, &c->count_dev, &c->query_dev,
-                      &c->query_tiles, &c->delta_base[0], &c->delta_base[1], &c->delta_flags, &c->delta_pack, &c->skin, &c->pose_dev, &c->posed,
-                      &c->posed_nrm, &c->morph_dpos, &c->morph_dnrm, &c->morph_list_dev, &c->morphed, &c->morphed_attrs, &c->bounds_dev, &c->bounds_scratch};
-    for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
-    for (DevBuf& b : c->color) if (b.p) hipFree(b.p);
-    for (DevBuf& b : c->depth) if (b.p) hipFree(b.p);
-    for (DevBuf& b : c->ids) if (b.p) hipFree(b.p);
-    for (DevBuf& b : c->ts.fillbuf) if (b.p) hipFree(b.p);
-    for (auto& lf : c->lanefill) for (DevBuf& b : lf) if (b.p) hipFree(b.p);
-    for (hipStream_t ls : c->lane_stream) if (ls) hipStreamDestroy(ls);
-    for (hipEvent_t e : c->pace_ev) if (e) hipEventDestroy(e);
-    for (auto& rd : c->ts.ras_done) if (rd.ev) hipEventDestroy(rd.ev);
-    for (auto& sl : c->slot) {
-        DevBuf* sb[] = {&sl.geo, &sl.geo_full, &sl.ranges, &sl.bins, &sl.bin_matrix, &sl.live, &sl.tilebuf, &sl.biglist,
-                        &sl.items, &sl.lrgb, &sl.lnrm, &sl.linv, &sl.cxyz, &sl.crgb, &sl.cnrm, &sl.cmap, &sl.cbox,
-                        &sl.csums, &sl.pq};
-        for (DevBuf* b : sb) if (b->p) hipFree(b->p);
-        if (sl.items_host) hipHostFree(sl.items_host);
-        if (sl.items_copied) hipEventDestroy(sl.items_copied);
-        if (sl.bin_done) hipEventDestroy(sl.bin_done);
-    }
-    for (int i = 0; i < swr_context::NFB; i++) {
-        if (c->frame_done[i]) hipEventDestroy(c->frame_done[i]);
-        for (int j = 0; j < 2; j++) if (c->copy_done[i][j]) hipEventDestroy(c->copy_done[i][j]);
-        if (c->read_done[i]) hipEventDestroy(c->read_done[i]);
-    }
-    if (c->src_ready) hipEventDestroy(c->src_ready);
-    for (int i = 0; i < 2; i++) {
-        for (int j = 0; j < 2; j++) {
-            if (c->stage[i][j]) hipHostFree(c->stage[i][j]);
-            if (c->stage_ev[i][j]) hipEventDestroy(c->stage_ev[i][j]);
-        }
-        if (c->copy_stream[i]) hipStreamDestroy(c->copy_stream[i]);
-    }
-    if (c->bin_stream_own) hipStreamDestroy(c->bin_stream_own);
-    if (c->h_pairs) hipHostFree(c->h_pairs);
-    if (c->h_misc) hipHostFree(c->h_misc);
-    if (c->h_clip) hipHostFree(c->h_clip);
-    for (HostBuf* b : {&c->count_host, &c->query_host, &c->delta_host, &c->bounds_host}) if (b->p) hipHostFree(b->p);
-    if (c->ev_ok)
-        for (int r = 0; r < swr_context::RING; r++)
-            for (int i = 0; i < 5; i++) hipEventDestroy(c->ev[r][i]);
-    for (auto& e : c->up_ev) if (e) hipEventDestroy(e);
-    if (c->up_chunk_ev) hipEventDestroy(c->up_chunk_ev);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -2772,24 +2779,20 @@ void destroy_single(swr_context* c) {
 // calls swr_draw enqueues the binning itself (sub-contexts of a group: that thread is the group's per-device worker, so
 // a device has ONE thread that polls for completions, not two), 0 = none.
 int create_single(int dev, swr_context** out, int helpers, uint32_t wait_budget_ms) {
-    swr_context* c = new swr_context();
+    std::unique_ptr<swr_context> c(new swr_context());      // (a failure below frees what was created so far; nothing is enqueued yet)
     c->device = dev;
     if (wait_budget_ms) c->wait_budget_ms = wait_budget_ms;
     c->hp_on = getenv("SWR_HOST_PROFILE") && atoi(getenv("SWR_HOST_PROFILE")) == 1;
     hipError_t e;
     if ((e = hipSetDevice(dev)) != hipSuccess || (e = prepare_device()) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&c->copy_stream[0], hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&c->copy_stream[1], hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&c->h_pairs, (2 * swr_context::PAIR_RING + 2) * 4, hipHostMallocMapped)) != hipSuccess ||
+        (e = c->stream.create()) != hipSuccess || (e = c->copy_stream[0].create()) != hipSuccess ||
+        (e = c->copy_stream[1].create()) != hipSuccess ||
+        (e = c->h_pairs.alloc((2 * swr_context::PAIR_RING + 2) * 4, hipHostMallocMapped)) != hipSuccess ||
         (e = hipHostGetDevicePointer((void**)&c->h_pairs_dev, c->h_pairs, 0)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&c->h_misc, CNT_WORDS * 4, hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&c->h_clip, (swr_context::PAIR_RING + 1) * 4, hipHostMallocMapped)) != hipSuccess ||
-        (e = hipHostGetDevicePointer((void**)&c->h_clip_dev, c->h_clip, 0)) != hipSuccess) {
-        int rc = fail(nullptr, SWR_ERR_HIP, "context init on device %d failed: %s", dev, hipGetErrorString(e));
-        destroy_single(c);
-        return rc;
-    }
+        (e = c->h_misc.alloc(CNT_WORDS * 4, hipHostMallocDefault)) != hipSuccess ||
+        (e = c->h_clip.alloc((swr_context::PAIR_RING + 1) * 4, hipHostMallocMapped)) != hipSuccess ||
+        (e = hipHostGetDevicePointer((void**)&c->h_clip_dev, c->h_clip, 0)) != hipSuccess)
+        return fail(nullptr, SWR_ERR_HIP, "context init on device %d failed: %s", dev, hipGetErrorString(e));
     memset(c->h_pairs, 0, (2 * swr_context::PAIR_RING + 2) * 4);
     c->h_pairs[swr_context::PAIR_RING] = 0xFFFFFFFFu;     // fullest bin: unknown
     memset(c->h_misc, 0, CNT_WORDS * 4);
@@ -2801,45 +2804,42 @@ int create_single(int dev, swr_context** out, int helpers, uint32_t wait_budget_
         else {
             // a plain second stream: stream priorities (binning highest or lowest) were measured to make
             // no difference to how the two queues share the CUs on this platform
-            if (hipStreamCreateWithFlags(&c->bin_stream, hipStreamNonBlocking) != hipSuccess) c->bin_stream = c->stream;
-            else c->bin_stream_own = c->bin_stream;
+            c->bin_stream = c->bin_stream_own.create() == hipSuccess ? c->bin_stream_own.h : c->stream.h;
             // SWR_HOST_THREADS=1: enqueue everything from the caller's thread (no helper)
             const char* ht = getenv("SWR_HOST_THREADS");
             if (ht && ht[0] == '1') helpers = 0;
             { const char* be = getenv("SWR_BIND_EVENTS"); c->ts.bind_events = !(be && be[0] == '0'); }
             { const char* ii = getenv("SWR_INLINE_IDLE"); c->ts.inline_idle = !(ii && ii[0] == '0'); }
             const char* ew = getenv("SWR_EVENT_WAITS");     // =1: no raster helper; the caller's thread orders the streams by event waits
-            if (c->bin_stream_own && helpers >= 2) { c->ts.bin_worker = new Worker(); c->ts.bin_worker->start(dev, true); }
-            if (c->bin_stream_own && helpers >= 1 && !(ew && ew[0] == '1')) { c->ts.ras_worker = new Worker(); c->ts.ras_worker->start(dev, true); }
+            if (c->bin_stream_own && helpers >= 2) { c->ts.bin_worker.reset(new Worker()); c->ts.bin_worker->start(dev, true); }
+            if (c->bin_stream_own && helpers >= 1 && !(ew && ew[0] == '1')) { c->ts.ras_worker.reset(new Worker()); c->ts.ras_worker->start(dev, true); }
         }
         for (int k = 0; k < swr_context::NSLOT; k++) {
-            hipEventCreateWithFlags(&c->slot[k].bin_done, hipEventDisableTiming);
-            hipEventCreateWithFlags(&c->ts.ras_done[k].ev, hipEventDisableTiming);
+            c->slot[k].bin_done.create(hipEventDisableTiming);
+            c->ts.ras_done[k].ev.create(hipEventDisableTiming);
         }
         for (int i = 0; i < swr_context::NFB; i++) {
-            hipEventCreateWithFlags(&c->frame_done[i], hipEventDisableTiming);
-            for (int j = 0; j < 2; j++) hipEventCreateWithFlags(&c->copy_done[i][j], hipEventDisableTiming);
-            hipEventCreateWithFlags(&c->read_done[i], hipEventDisableTiming);
+            c->frame_done[i].create(hipEventDisableTiming);
+            for (int j = 0; j < 2; j++) c->copy_done[i][j].create(hipEventDisableTiming);
+            c->read_done[i].create(hipEventDisableTiming);
         }
-        hipEventCreateWithFlags(&c->src_ready, hipEventDisableTiming);
+        c->src_ready.create(hipEventDisableTiming);
         // frame lanes (swr_context::lane_stream): one stream per working set.  SWR_LANES=0: the two-stream pipeline of rounds 1-3
         {
             const char* ln = getenv("SWR_LANES");
-            c->lanes_ok = c->bin_stream_own != nullptr && !(ln && ln[0] == '0');
+            c->lanes_ok = c->bin_stream_own && !(ln && ln[0] == '0');
             for (int l = 0; l < swr_context::NSLOT && c->lanes_ok; l++)
-                if (hipStreamCreateWithFlags(&c->lane_stream[l], hipStreamNonBlocking) != hipSuccess) c->lanes_ok = false;
-            for (hipEvent_t& e : c->pace_ev) hipEventCreateWithFlags(&e, hipEventDisableTiming);
+                if (c->lane_stream[l].create() != hipSuccess) c->lanes_ok = false;
+            for (Event& e : c->pace_ev) e.create(hipEventDisableTiming);
         }
     }
     for (int r = 0; r < swr_context::RING; r++)
-        for (int i = 0; i < 5; i++) hipEventCreate(&c->ev[r][i]);
-    c->ev_ok = true;
-    *out = c;
+        for (int i = 0; i < 5; i++) c->ev[r][i].create();
+    *out = c.release();
     return SWR_OK;
 }
 
 // ---- group fan-out -----------------------------------------------------------------------------------------------
-inline bool is_group(const swr_context* c) { return !c->kids.empty(); }
 
 // run fn(kid) on every sub-context's own thread and wait; the first failure (and its text) becomes the group's
 template <class F>
@@ -2860,7 +2860,9 @@ int group_run(swr_context* g, F fn) {
     return first;
 }
 
-// an entry point that waits: fn on every band of a group, or on the one context
+// An entry point that waits: fn on every band of c — a group's on their own threads — and the wait for all of them.  Every such entry
+// point has one shape: its NULL checks, sticky(c), the call's checks against c (check_X: once, before a band is touched), fan(c, the
+// band's work), then one gather over the bands of c, which writes the caller's arrays only after every band succeeded.
 template <class F>
 int fan(swr_context* c, F fn) { return is_group(c) ? group_run(c, fn) : fn(c); }
 
@@ -2934,12 +2936,12 @@ int swr_context_create(const swr_config* cfg, swr_context** out) {
             delete g;
             return rc;
         }
+        kid->band = (int)k;
         g->kids.push_back(kid);
     }
     for (uint32_t k = 0; k < n; k++) {
-        Worker* w = new Worker();
-        w->start(g->kids[k]->device);
-        g->workers.push_back(w);
+        g->workers.emplace_back(new Worker());
+        g->workers[k]->start(g->kids[k]->device);
     }
     *out = g;
     return SWR_OK;
@@ -2948,7 +2950,8 @@ int swr_context_create(const swr_config* cfg, swr_context** out) {
 void swr_context_destroy(swr_context* c) {
     if (!c) return;
     if (is_group(c)) {
-        for (Worker* w : c->workers) { w->drain(); w->stop(); delete w; }
+        for (auto& w : c->workers) w->drain();
+        c->workers.clear();
         for (swr_context* kid : c->kids) destroy_single(kid);
         delete c;
         return;
@@ -2956,11 +2959,11 @@ void swr_context_destroy(swr_context* c) {
     destroy_single(c);
 }
 
-int swr_context_bands(const swr_context* c) { return c ? (is_group(c) ? (int)c->kids.size() : 1) : 0; }
+int swr_context_bands(const swr_context* c) { return c ? (int)band_count(c) : 0; }
 
 int swr_context_band_info(const swr_context* c, int32_t band, int32_t* device, int64_t* row_begin, int64_t* row_end) {
     if (!c || band < 0 || band >= swr_context_bands(c)) return SWR_ERR_BAD_ARG;
-    const swr_context* k = is_group(c) ? c->kids[band] : c;
+    const swr_context* k = ::band(c, (size_t)band);
     if (device) *device = k->device;
     if (row_begin) *row_begin = k->has_target ? k->tg.row_begin : 0;
     if (row_end) *row_end = k->has_target ? k->tg.row_end : 0;
@@ -3041,20 +3044,20 @@ int swr_texture_upload(swr_context* c, const void* bgra8, int32_t width, int32_t
 
 int swr_target_set(swr_context* c, int64_t width, int64_t height, int64_t row_begin, int64_t row_end) {
     if (!c) return SWR_ERR_BAD_ARG;
-    if (!is_group(c)) return single_target_set(c, width, height, row_begin, row_end);
+    if (const int f = sticky(c)) return f;
     int rc = check_target_args(c, width, height, row_begin, row_end);
     if (rc) return rc;
-    const int n = (int)c->kids.size();
-    for (int k = 0; k < n; k++) {
+    const int n = (int)band_count(c);       // (one band: its rows are the target's)
+    rc = fan(c, [=](swr_context* k) {
         int64_t r0, r1;
-        sub_band(row_begin, row_end, n, k, &r0, &r1);
-        swr_context* kid = c->kids[k];
-        c->workers[k]->post([=] { return single_target_set(kid, width, height, r0, r1); });
-    }
-    rc = group_run(c, [](swr_context*) { return SWR_OK; });
+        sub_band(row_begin, row_end, n, k->band, &r0, &r1);
+        return single_target_set(k, width, height, r0, r1);
+    });
     if (rc) return rc;
-    c->group_tg = Target{(int32_t)width, (int32_t)height, (int32_t)row_begin, (int32_t)row_end, 0, 0};
-    c->group_has_target = true;
+    if (is_group(c)) {      // the full target, for the checks of the calls that follow
+        c->tg = Target{(int32_t)width, (int32_t)height, (int32_t)row_begin, (int32_t)row_end, 0, 0};
+        c->has_target = true;
+    }
     return SWR_OK;
 }
 
@@ -3075,20 +3078,21 @@ int swr_draw(swr_context* c, const float transform[16], uint32_t flags) {
 
 int swr_draw_list(swr_context* c, const swr_draw_item* items, int32_t item_count, uint32_t flags) {
     if (!c) return SWR_ERR_BAD_ARG;
-    if (!is_group(c)) return single_draw_list(c, items, item_count, flags);
-    // the group checks what it can see (every band holds the same scene); the bands draw their own copy of the list
+    if (const int f = sticky(c)) return f;
     int64_t tris = 0;
-    const swr_context* k0 = c->kids[0];
-    int rc = check_list_args(c, items, item_count, flags, k0->has_scene && c->group_has_target, k0->ni, &tris);
+    const int rc = check_list_args(c, items, item_count, flags, &tris);
     if (rc) return rc;
+    if (!is_group(c)) return single_draw_list(c, items, item_count, flags, tris);
+    // asynchronous, like swr_draw: the bands draw their own copy of the list
     auto list = std::make_shared<std::vector<swr_draw_item>>(items, items + item_count);
-    group_post(c, [=](swr_context* k) { return single_draw_list(k, list->data(), item_count, flags); });
+    group_post(c, [=](swr_context* k) { return single_draw_list(k, list->data(), item_count, flags, tris); });
     return SWR_OK;
 }
 
 int swr_target_write(swr_context* c, const void* color_full, const float* depth_full) {
     if (!c) return SWR_ERR_BAD_ARG;
-    if (is_group(c) && !c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_target_write needs swr_target_set first");
+    if (const int f = sticky(c)) return f;
+    if (!c->has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_target_write needs swr_target_set first");
     return fan(c, [=](swr_context* k) { return single_target_write(k, color_full, depth_full); });
 }
 
@@ -3128,26 +3132,16 @@ int swr_read_ids(swr_context* c, uint32_t* dst) {
 int swr_count_ids(swr_context* c, const swr_id_count* query, uint32_t* counts, int64_t n, uint32_t* none) {
     if (!c || !query) return SWR_ERR_BAD_ARG;
     const swr_id_count q = *query;
-    if (!is_group(c)) {
-        const int rc = single_count_ids(c, q, counts, n);
-        if (rc) return rc;
-        if (n) memcpy(counts, c->count_host.p, (size_t)n * 4);
-        if (none) *none = c->count_host.p[n];
-        return SWR_OK;
-    }
-    // a group checks what it can see before any band is touched; every band counts into staging of its own, and the caller's array is
-    // written once, after all of them succeeded
     if (const int f = sticky(c)) return f;
-    int rc = check_count_args(c, q, counts, n);
+    int rc = check_count(c, q, counts, n);
     if (rc) return rc;
-    if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_count_ids needs swr_target_set first");
-    if ((rc = check_count_rect(c, q, c->group_tg))) return rc;
-    if ((rc = group_run(c, [=](swr_context* k) { return single_count_ids(k, q, counts, n); }))) return rc;
+    if ((rc = fan(c, [=](swr_context* k) { return band_count_ids(k, q, n); }))) return rc;
     if (n) memset(counts, 0, (size_t)n * 4);
     uint32_t nn = 0;
-    for (const swr_context* k : c->kids) {
-        for (int64_t i = 0; i < n; i++) counts[i] += k->count_host.p[i];
-        nn += k->count_host.p[n];
+    for (size_t b = 0; b < band_count(c); b++) {
+        const uint32_t* part = band(c, b)->count_host.p;
+        for (int64_t i = 0; i < n; i++) counts[i] += part[i];
+        nn += part[n];
     }
     if (none) *none = nn;
     return SWR_OK;
@@ -3155,43 +3149,26 @@ int swr_count_ids(swr_context* c, const swr_id_count* query, uint32_t* counts, i
 
 int swr_query_depth(swr_context* c, const swr_depth_box* boxes, int64_t n, uint32_t* passed) {
     if (!c) return SWR_ERR_BAD_ARG;
-    if (!is_group(c)) {
-        const int rc = single_query_depth(c, boxes, n, passed);
-        if (rc) return rc;
-        if (n) memcpy(passed, c->query_passed, (size_t)n * 4);
-        return SWR_OK;
-    }
-    // a group checks what it can see before any band is touched; every band counts into staging of its own, and the caller's array is
-    // written once, after all of them succeeded
     if (const int f = sticky(c)) return f;
-    int rc = check_query_args(c, boxes, n, passed);
+    int rc = check_query(c, boxes, n, passed);
     if (rc) return rc;
-    if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_query_depth needs swr_target_set first");
-    if ((rc = check_query_boxes(c, boxes, n, c->group_tg))) return rc;
-    if ((rc = group_run(c, [=](swr_context* k) { return single_query_depth(k, boxes, n, passed); }))) return rc;
+    if ((rc = fan(c, [=](swr_context* k) { return band_query_depth(k, boxes, n); }))) return rc;
     if (n) memset(passed, 0, (size_t)n * 4);
-    for (const swr_context* k : c->kids)
-        for (int64_t i = 0; i < n; i++) passed[i] += k->query_passed[i];
+    for (size_t b = 0; b < band_count(c); b++)
+        for (int64_t i = 0; i < n; i++) passed[i] += band(c, b)->query_passed[i];
     return SWR_OK;
 }
 
 int swr_item_bounds(swr_context* c, const swr_draw_item* items, int32_t item_count, uint32_t flags, swr_item_bound* out) {
     if (!c) return SWR_ERR_BAD_ARG;
-    swr_context* k0 = c;
-    if (is_group(c)) {
-        // a group checks what it can see before a band is touched; the result does not depend on rows and every band holds the whole
-        // scene, so the first band answers for the full target
-        if (const int f = sticky(c)) return f;
-        k0 = c->kids[0];
-        int rc = check_bounds_args(c, items, item_count, flags, out, k0->has_scene && c->group_has_target, k0->ni);
-        if (rc) return rc;
-        c->workers[0]->post([=] { return single_item_bounds(k0, items, item_count, flags, out); });
-        if ((rc = group_run(c, [](swr_context* k) { return single_sync(k); }))) return rc;
-    } else {
-        const int rc = single_item_bounds(c, items, item_count, flags, out);
-        if (rc) return rc;
-    }
-    if (item_count) memcpy(out, k0->bounds_out, (size_t)item_count * sizeof(swr_item_bound));
+    if (const int f = sticky(c)) return f;
+    int rc = check_bounds(c, items, item_count, flags, out);
+    if (rc) return rc;
+    // the result does not depend on rows and every band holds the whole scene: the first band answers for the full target, the
+    // others finish what they have in flight
+    swr_context* first = band(c, 0);
+    if ((rc = fan(c, [=](swr_context* k) { return k == first ? band_item_bounds(k, items, item_count, flags) : single_sync(k); }))) return rc;
+    if (item_count) memcpy(out, first->bounds_out, (size_t)item_count * sizeof(swr_item_bound));
     return SWR_OK;
 }
 
@@ -3207,22 +3184,16 @@ static void delta_add(swr_delta_stats& t, const swr_delta_stats& k, bool first) 
 
 // swr_read_color_delta / swr_read_depth_delta and the gather of swr_render_delta; `out` (never NULL) is written after every band succeeded
 static int read_delta(swr_context* c, int img, void* dst, swr_delta_stats* out) {
-    if (!is_group(c)) {
-        const int rc = single_read_delta(c, img, dst);
-        if (rc) return rc;
-        *out = c->delta_stats;
-        return SWR_OK;
-    }
     if (const int f = sticky(c)) return f;
-    if (!dst) return fail(c, SWR_ERR_BAD_ARG, "swr_read_*_delta: the destination is NULL");
-    if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_*_delta needs swr_target_set first");
-    const int rc = group_run(c, [=](swr_context* k) { return single_read_delta(k, img, dst); });
+    int rc = check_delta(c, dst);
     if (rc) return rc;
+    if ((rc = fan(c, [=](swr_context* k) { return band_read_delta(k, img, dst); }))) return rc;
     swr_delta_stats t{};
     bool first = true;
-    for (const swr_context* k : c->kids) {
-        delta_add(t, k->delta_stats, first);
-        if (k->delta_stats.tiles) first = false;
+    for (size_t b = 0; b < band_count(c); b++) {
+        const swr_delta_stats& part = band(c, b)->delta_stats;
+        delta_add(t, part, first);
+        if (part.tiles) first = false;
     }
     *out = t;
     return SWR_OK;
@@ -3258,15 +3229,13 @@ int swr_delta_reset(swr_context* c, uint32_t images) {
     return fan(c, reset);
 }
 
-// the resolved read of one or both images (NULL: not wanted); a group checks what it can see before any band is touched
+// the resolved read of one or both images (NULL: not wanted); every band writes its own rows of the caller's images: nothing to gather
 static int read_resolved(swr_context* c, const swr_resolve* resolve, void* color_dst, float* depth_dst) {
     const swr_resolve rs = *resolve;
-    if (!is_group(c)) return single_read_resolved(c, rs, color_dst, depth_dst);
-    int rc = check_resolve_args(c, rs);
+    if (const int f = sticky(c)) return f;
+    const int rc = check_resolve(c, rs);
     if (rc) return rc;
-    if (!c->group_has_target) return fail(c, SWR_ERR_NO_SCENE, "swr_read_*_resolved needs swr_target_set first");
-    if ((rc = check_resolve_target(c, rs, c->group_tg))) return rc;
-    return group_run(c, [=](swr_context* k) { return single_read_resolved(k, rs, color_dst, depth_dst); });
+    return fan(c, [=](swr_context* k) { return band_read_resolved(k, rs, color_dst, depth_dst); });
 }
 
 int swr_read_color_resolved(swr_context* c, const swr_resolve* resolve, void* dst) {
@@ -3288,7 +3257,8 @@ void* swr_host_alloc(size_t bytes) {
 }
 
 void swr_host_free(void* p) {
-    if (p) (void)hipHostFree(p);
+    Pinned<void> owner;         // (freed as the owner goes)
+    owner.p = p;
 }
 
 int swr_host_register(void* p, size_t bytes) {
@@ -3348,24 +3318,17 @@ static void merge_timings(swr_timings* acc, const swr_timings& t, bool first) {
 
 int swr_timing_totals(swr_context* c, swr_timings* sum, int64_t* frames) {
     if (!c || !sum || !frames) return SWR_ERR_BAD_ARG;
-    if (is_group(c)) {
-        int rc = swr_sync(c);
-        if (rc) return rc;
-        for (size_t k = 0; k < c->kids.size(); k++) {
-            swr_timings t; int64_t f = 0;
-            if ((rc = swr_timing_totals(c->kids[k], &t, &f))) return rc;
-            merge_timings(sum, t, k == 0);
-            if (k == 0) *frames = f;
-        }
-        return SWR_OK;
-    }
-    int rc = swr_sync(c);
+    const int rc = swr_sync(c);
     if (rc) return rc;
-    *sum = c->last;
-    sum->setup_bin_ms = (float)c->sum_ms[0]; sum->scan_ms = (float)c->sum_ms[1];
-    sum->scatter_ms = (float)c->sum_ms[2]; sum->raster_ms = (float)c->sum_ms[3];
-    sum->total_ms = (float)c->sum_ms[4];
-    *frames = c->sum_frames;
+    for (size_t b = 0; b < band_count(c); b++) {
+        const swr_context* k = band(c, b);
+        swr_timings t = k->last;
+        t.setup_bin_ms = (float)k->sum_ms[0]; t.scan_ms = (float)k->sum_ms[1];
+        t.scatter_ms = (float)k->sum_ms[2]; t.raster_ms = (float)k->sum_ms[3];
+        t.total_ms = (float)k->sum_ms[4];
+        merge_timings(sum, t, b == 0);
+    }
+    *frames = band(c, 0)->sum_frames;
     return SWR_OK;
 }
 
@@ -3381,19 +3344,9 @@ int swr_timing_reset(swr_context* c) {
 
 int swr_get_timings(swr_context* c, swr_timings* out) {
     if (!c || !out) return SWR_ERR_BAD_ARG;
-    if (is_group(c)) {
-        int rc = swr_sync(c);
-        if (rc) return rc;
-        for (size_t k = 0; k < c->kids.size(); k++) {
-            swr_timings t;
-            if ((rc = swr_get_timings(c->kids[k], &t))) return rc;
-            merge_timings(out, t, k == 0);
-        }
-        return SWR_OK;
-    }
-    int rc = swr_sync(c);
+    const int rc = swr_sync(c);
     if (rc) return rc;
-    *out = c->last;
+    for (size_t b = 0; b < band_count(c); b++) merge_timings(out, band(c, b)->last, b == 0);
     return SWR_OK;
 }
 
@@ -3433,23 +3386,17 @@ static int render_pass(swr_context* c, const swr_render_pass* p, const swr_resol
         c->scene_id = 0;
         // no identity = the scene lives for this frame only: uploaded in index order, built behind the copy
         const bool oneshot = p->scene_id == 0;
-        if (is_group(c))
-            rc = group_run(c, [=](swr_context* k) { return single_scene_upload(k, p->vertices, p->vertex_count, p->indices, p->index_count, oneshot); });
-        else
-            rc = single_scene_upload(c, p->vertices, p->vertex_count, p->indices, p->index_count, oneshot);
-        if (rc) return rc;
+        if ((rc = fan(c, [=](swr_context* k) { return single_scene_upload(k, p->vertices, p->vertex_count, p->indices, p->index_count, oneshot); }))) return rc;
         if (p->attributes && (rc = swr_scene_attributes(c, p->attributes, p->vertex_count))) return rc;
         if (p->texture && (rc = swr_texture_upload(c, p->texture, p->tex_width, p->tex_height))) return rc;
         c->scene_id = p->scene_id; c->scene_nv = p->vertex_count; c->scene_ni = p->index_count;
         c->scene_attrs = p->attributes != nullptr;
         c->scene_tex = p->texture; c->scene_tw = p->tex_width; c->scene_th = p->tex_height;
         // the split inside the upload: HIP events of (the slowest band of) the upload itself
-        const swr_context* k0 = c->kids.empty() ? c : c->kids[0];
-        float h2d = k0->up_h2d_ms, build = k0->up_build_ms;
-        for (const swr_context* k : c->kids) { h2d = std::max(h2d, k->up_h2d_ms); build = std::max(build, k->up_build_ms); }
+        float h2d = band(c, 0)->up_h2d_ms;
+        for (size_t b = 1; b < band_count(c); b++) h2d = std::max(h2d, band(c, b)->up_h2d_ms);
         c->rt.h2d_ms = h2d;
         c->rt.stream_build_ms = ms(t0, clk::now()) - h2d;       // index check, sort, gather, attribute / texture passes, allocation
-        (void)build;
     }
     const auto t1 = clk::now();
     // the pass carries its own fragment stage: NULL material = the reference's passthrough
@@ -3458,7 +3405,7 @@ static int render_pass(swr_context* c, const swr_render_pass* p, const swr_resol
     // a load frame: the caller's images are its starting image (inputs now, never cached)
     if ((p->flags & SWR_FLAG_LOAD) &&
         (rc = swr_target_write(c, (p->flags & SWR_FLAG_NO_COLOR) ? nullptr : p->color, p->depth))) return rc;
-    const swr_context* kf = c->kids.empty() ? c : c->kids[0];
+    const swr_context* kf = band(c, 0);
     const uint64_t frames0 = kf->frame_no;
     if ((rc = swr_draw_primitives(c, p->transform, p->flags, p->primitive_type))) return rc;
     if (resolve) {

@@ -326,26 +326,13 @@ struct ItemBoundsArgs {
     swr_item_bound* records;
 };
 inline int64_t item_bounds_units(uint32_t count) { return ((int64_t)count + ITEM_BOUNDS_CHUNK - 1) / ITEM_BOUNDS_CHUNK; }
-#if defined(__HIPCC__) || defined(SWR_ITEM_BOUNDS_STANDIN)
 void launch_item_bounds(const ItemBoundsArgs& a, hipStream_t s);
-#else
-// (host test programs built without SWR_ITEM_BOUNDS_STANDIN link a stand-in launch set that predates this launch and never call
-// swr_item_bounds: nothing is enqueued.  The product is always compiled by hipcc and references the launch plainly.)
-inline void launch_item_bounds(const ItemBoundsArgs&, hipStream_t) {}
-#endif
 
 // swr_skin_dq.hip: dual-quaternion skinning.  launch_skin_vertices_dq is launch_skin_vertices with the blend of
 // include/swr.h "Dual-quaternion skinning": the same arrays in, the same posed arrays out, launch_skin_stream follows it.  `dual_quats`
 // is the pose on the device: joint_count x 8 floats, per joint the real quaternion (x, y, z, w), then the dual quaternion, 16-byte
 // aligned.  Every joint index of `skin` is below joint_count (the host has checked it).
-#if defined(__HIPCC__) || defined(SWR_SKIN_DQ_STANDIN)
 void launch_skin_vertices_dq(const swr_vertex* vertices, const swr_vertex_attr* attrs, const swr_skin_vertex* skin, int64_t nv,
                              const float* dual_quats, int32_t joint_count, swr_vertex* posed, float4* posed_nrm, hipStream_t s);
-#else
-// (host test programs built without SWR_SKIN_DQ_STANDIN link a stand-in launch set that predates this launch and never call
-// swr_pose_set_dq: nothing is enqueued.  The product is always compiled by hipcc and references the launch plainly.)
-inline void launch_skin_vertices_dq(const swr_vertex*, const swr_vertex_attr*, const swr_skin_vertex*, int64_t, const float*, int32_t,
-                                    swr_vertex*, float4*, hipStream_t) {}
-#endif
 
 }  // namespace swr

@@ -1,4 +1,4 @@
-// The host side of the visibility counts (software-renderer_amd/csrc/swr_api.hip: single_count_ids, the group fan-out and sum,
+// The host side of the visibility counts (software-renderer_amd/csrc/swr_api.hip: band_count_ids, the group fan-out and sum,
 // swr_count_ids) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The stand-in
 // of swr::launch_count_ids (stub_launch.cpp) is a plain CPU loop over the header's definition run as a "kernel" of the fake stream.  The stand-in raster leaves the ID image at zero, so the loop ADDS a pattern of
 // its own to what it reads: the ID of band-local pixel (x, y) is ids[y][x] + pattern(x, y).  The band's rows are read (a rectangle

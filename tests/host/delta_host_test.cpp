@@ -1,4 +1,4 @@
-// The host side of the delta reads (software-renderer_amd/csrc/swr_api.hip: single_read_delta, the group fan-out and sum,
+// The host side of the delta reads (software-renderer_amd/csrc/swr_api.hip: band_read_delta, the group fan-out and sum,
 // swr_read_color_delta / swr_read_depth_delta / swr_delta_reset / swr_render_delta) on the fake HIP runtime of tests/host/hip_stub,
 // under the address and undefined-behaviour sanitizers.  The stand-ins of swr::launch_delta and swr::launch_delta_pack
 // (stub_launch.cpp) are plain CPU loops over the header's definition run as "kernels" of the fake stream.  The images are patterns written with swr_target_write, so the loops read the band's own rows, and a baseline, a flag table

@@ -1,4 +1,4 @@
-// The host side of the depth queries (software-renderer_amd/csrc/swr_api.hip: single_query_depth, the group fan-out and sum,
+// The host side of the depth queries (software-renderer_amd/csrc/swr_api.hip: band_query_depth, the group fan-out and sum,
 // swr_query_depth) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The stand-in
 // of swr::launch_depth_query (stub_launch.cpp) is a plain CPU loop over the header's definition run as a "kernel" of the fake stream.  The depth image is a pattern written with swr_target_write, so the
 // loop reads the band's own rows (a box clipped wrongly is an out-of-bounds read the address sanitizer reports, or a wrong count).
@@ -114,6 +114,7 @@ static void scenario(uint32_t devices, int W, int H) {
         std::vector<swr_depth_box> bad = boxes;
         std::vector<uint32_t> keep(bad.size() + 1, 0xA5A5A5A5u);
         const int64_t n = (int64_t)bad.size();
+        const int launches = g_query_launches.load();           // a refused call touches no band: nothing is launched on any of them
         CHECK(swr_query_depth(nullptr, bad.data(), n, keep.data()) == SWR_ERR_BAD_ARG);
         CHECK(swr_query_depth(c, nullptr, n, keep.data()) == SWR_ERR_BAD_ARG);
         CHECK(swr_query_depth(c, bad.data(), n, nullptr) == SWR_ERR_BAD_ARG);
@@ -137,6 +138,7 @@ static void scenario(uint32_t devices, int W, int H) {
         bool untouched = true;
         for (uint32_t v : keep) untouched = untouched && v == 0xA5A5A5A5u;
         CHECK(untouched);
+        CHECK(g_query_launches.load() == launches);
         query(c, b, boxes);
     }
     // the images are the frame's: reading them and drawing on go on as before

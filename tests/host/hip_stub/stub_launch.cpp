@@ -1,7 +1,7 @@
 // Stand-ins for every kernel launch wrapper of swr_internal.h on the fake HIP runtime: the one set every host test program links.
 // The frame launches (swr_kernels.hip / swr_upload.hip) enqueue host lambdas that leave what the host layer looks at afterwards
 // (pair totals, largest fill, a frame tag in the framebuffer) and touch both ends of every table their DeviceFrame names, at the sizes
-// swr_internal.h gives.  The feature launches (resolve, visibility counts, depth queries, delta reads, skin, morph) are plain CPU loops
+// swr_internal.h gives.  The feature launches (resolve, visibility counts, depth queries, delta reads, skin, morph, item bounds, dual-quaternion skin) are plain CPU loops
 // over the header's arithmetic that read and write every element of every array they are handed.  Either way a buffer the host layer
 // sized too small is an out-of-bounds access the address sanitizer reports.  stub_launch.h holds what the programs observe.
 #include <algorithm>
@@ -17,6 +17,7 @@
 std::atomic<uint32_t> g_count_total{0};
 std::atomic<int> g_count_launches{0}, g_query_launches{0}, g_compares{0}, g_directs{0}, g_packs{0};
 std::atomic<int> g_vertex_launches{0}, g_stream_launches{0}, g_morph_launches{0}, g_morph_nrm_launches{0};
+std::atomic<int> g_bounds_launches{0}, g_dq_launches{0}, g_dq_nrm_launches{0};
 std::atomic<int> g_launch_fails{0};
 
 static std::mutex g_records_m;
@@ -296,5 +297,43 @@ void launch_skin_stream(const float4* pos, int pos_stride, const float4* nrm, in
         std::lock_guard<std::mutex> lk(g_records_m);
         g_records.push_back(Record{tri_xyz, tri_nrm, box64, ntri, nrm != nullptr});
     }, nullptr, "k_skin_stream", (size_t)ntri);
+}
+
+// (also checks what the host resolved: the work units and the ranges)
+void launch_item_bounds(const ItemBoundsArgs& a, hipStream_t s) {
+    g_bounds_launches++;
+    fake_enqueue(s, [a] {
+        int64_t units = 0;
+        memset(a.scratch, 0x5A, item_bounds_scratch_bytes(a.n));            // (partial records sized too small are reported)
+        for (int32_t k = 0; k < a.n; k++) {
+            const ListItem& it = a.items[k];
+            if (it.ubase != (uint32_t)units) { std::printf("FAIL item %d: ubase %u, not %lld\n", (int)k, it.ubase, (long long)units); g_launch_fails++; }
+            units += item_bounds_units(it.count);
+            memset(&a.records[k], 0xA5, sizeof(swr_item_bound));             // (every word of every record is the launch's to write)
+            const float4* tri = a.tri_xyz + 3 * (size_t)it.first;
+            a.records[k] = fold((int64_t)it.count, [tri](int64_t t, int j) { return &tri[3 * t + j].x; }, it.m, a.width, a.height, a.metal != 0);
+        }
+        if (units != a.units) { std::printf("FAIL %lld units handed, the items have %lld\n", (long long)a.units, (long long)units); g_launch_fails++; }
+        if (a.n < 1 || a.n > SWR_DRAW_LIST_MAX || !a.vertices || !a.indices) g_launch_fails++;
+    }, nullptr, "k_item_bounds", (size_t)a.units);
+}
+
+// (also checks the table it is handed: its alignment, its size, the joint range of the skin)
+void launch_skin_vertices_dq(const swr_vertex* vertices, const swr_vertex_attr* attrs, const swr_skin_vertex* skin, int64_t nv,
+                             const float* dual_quats, int32_t joint_count, swr_vertex* posed, float4* posed_nrm, hipStream_t s) {
+    g_dq_launches++;
+    if (attrs) g_dq_nrm_launches++;
+    fake_enqueue(s, [=] {
+        if (joint_count < 1 || joint_count > SWR_SKIN_MAX_JOINTS || ((uintptr_t)dual_quats & 15)) { std::printf("FAIL table of %d joints\n", joint_count); g_launch_fails++; return; }
+        float sum = 0.0f;
+        for (int64_t k = 0; k < 8 * (int64_t)joint_count; k++) sum += dual_quats[k];       // (the whole table is the launch's to read)
+        if (sum == 12345.678f) g_launch_fails++;
+        for (int64_t i = 0; i < nv; i++) {
+            for (int k = 0; k < 4; k++) if ((int64_t)skin[i].joint[k] >= joint_count) { std::printf("FAIL joint %u of %d\n", skin[i].joint[k], joint_count); g_launch_fails++; return; }
+            posed[i] = vertices[i];
+            pose_dq(vertices[i].xyz, skin[i], dual_quats, true, posed[i].xyz);
+            if (attrs) { float n[3]; pose_dq(attrs[i].normal, skin[i], dual_quats, false, n); posed_nrm[i] = make_float4(n[0], n[1], n[2], 0.0f); }
+        }
+    }, nullptr, "k_skin_vertices_dq", (size_t)nv);
 }
 }  // namespace swr

@@ -2,7 +2,9 @@
 // ran, what the last skin stream launches wrote, the failures a stand-in found on the fake stream's thread, and the arithmetic the
 // stand-ins share with the programs' models.  Test infrastructure only.
 #pragma once
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -23,6 +25,8 @@ extern std::atomic<int> g_count_launches, g_query_launches;
 extern std::atomic<int> g_compares, g_directs, g_packs;                     // launch_delta, those with a direct destination, launch_delta_pack
 extern std::atomic<int> g_vertex_launches, g_stream_launches;               // launch_skin_vertices, launch_skin_stream
 extern std::atomic<int> g_morph_launches, g_morph_nrm_launches;             // launch_morph_vertices, those with normals
+extern std::atomic<int> g_bounds_launches;                                  // launch_item_bounds
+extern std::atomic<int> g_dq_launches, g_dq_nrm_launches;                   // launch_skin_vertices_dq, those with normals
 // what a stand-in found wrong in what it was handed (it runs on the fake stream's thread): a program adds this to its failures
 extern std::atomic<int> g_launch_fails;
 
@@ -66,4 +70,91 @@ inline void blend(const float* v, const swr_skin_vertex& sk, const float* joints
         }
     }
     memcpy(out, acc, sizeof acc);
+}
+
+// "Dual-quaternion skinning", for one vertex: every operation its own float operation
+inline void cross(const float* a, const float* b, float* r) {
+    const float x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
+    r[0] = x; r[1] = y; r[2] = z;
+}
+inline void blend_dq(const swr_skin_vertex& sk, const float* dq, float* C) {
+    const float* Q[4];
+    for (int k = 0; k < 4; k++) Q[k] = dq + 8 * (size_t)sk.joint[k];
+    float u[4] = {sk.weight[0], 0, 0, 0};
+    for (int k = 1; k < 4; k++) {
+        float s = Q[0][0] * Q[k][0] + Q[0][1] * Q[k][1];
+        s = s + Q[0][2] * Q[k][2];
+        s = s + Q[0][3] * Q[k][3];
+        u[k] = s < 0.0f ? -sk.weight[k] : sk.weight[k];
+    }
+    float B[8];
+    for (int c = 0; c < 8; c++) {
+        float b = u[0] * Q[0][c];
+        for (int k = 1; k < 4; k++) { const float p = u[k] * Q[k][c]; b = b + p; }
+        B[c] = b;
+    }
+    float n = B[0] * B[0] + B[1] * B[1];
+    n = n + B[2] * B[2];
+    n = n + B[3] * B[3];
+    const float l = sqrtf(n), i = 1.0f / l;
+    for (int c = 0; c < 8; c++) C[c] = B[c] * i;
+}
+inline void rotate(const float* C, const float* x, float* out) {
+    float a[3], b[3], c[3];
+    cross(C, x, a);
+    for (int j = 0; j < 3; j++) { const float p = C[3] * x[j]; b[j] = a[j] + p; }
+    cross(C, b, c);
+    for (int j = 0; j < 3; j++) { const float p = 2.0f * c[j]; out[j] = x[j] + p; }
+}
+inline void pose_dq(const float* v, const swr_skin_vertex& sk, const float* dq, bool translate, float* out) {
+    float C[8], r[3], e[3];
+    blend_dq(sk, dq, C);
+    rotate(C, v, r);
+    if (translate) {
+        cross(C, C + 4, e);
+        for (int j = 0; j < 3; j++) {
+            const float wd = C[3] * C[4 + j], dq_ = C[7] * C[j];
+            float t = wd - dq_;
+            t = t + e[j];
+            t = 2.0f * t;
+            r[j] = r[j] + t;
+        }
+    }
+    memcpy(out, r, sizeof r);
+}
+
+// include/swr.h "Item bounds" over `count` triangles whose corner j of triangle t is corner(t, j) (three floats)
+template <class Corner>
+inline swr_item_bound fold(int64_t count, Corner corner, const float* m, int W, int H, bool metal) {
+    swr_item_bound b{};
+    b.zmin = INFINITY; b.zmax = -INFINITY;
+    int64_t minx = INT64_MAX, miny = INT64_MAX, maxx = INT64_MIN, maxy = INT64_MIN;
+    for (int64_t t = 0; t < count; t++) {
+        float sx[3], sy[3], sz[3];
+        bool ok = true, w_ok = true;
+        for (int j = 0; j < 3; j++) {
+            const float* p = corner(t, j);
+            float r[4];
+            for (int i = 0; i < 4; i++) { r[i] = m[i] * p[0]; r[i] = r[i] + m[4 + i] * p[1]; r[i] = r[i] + m[8 + i] * p[2]; r[i] = r[i] + m[12 + i] * 1.0f; }
+            const float nx = r[0] / r[3], ny = r[1] / r[3];
+            sx[j] = (nx * 0.5f + 0.5f) * (float)W; sy[j] = (ny * -0.5f + 0.5f) * (float)H; sz[j] = r[2] / r[3];
+            if (metal) { sx[j] = roundf(sx[j]); sy[j] = roundf(sy[j]); }
+            ok = ok && std::fabs(sx[j]) < 1073741824.0f && std::fabs(sy[j]) < 1073741824.0f && (!metal || (sx[j] >= 0.0f && sy[j] >= 0.0f));
+            w_ok = w_ok && r[3] > 0.0f;
+        }
+        if (!ok) { b.skipped++; continue; }
+        b.drawable++;
+        if (!w_ok) b.behind++;
+        for (int j = 0; j < 3; j++) {
+            minx = std::min<int64_t>(minx, (int)sx[j]); maxx = std::max<int64_t>(maxx, (int)sx[j]);
+            miny = std::min<int64_t>(miny, (int)sy[j]); maxy = std::max<int64_t>(maxy, (int)sy[j]);
+            b.zmin = sz[j] < b.zmin ? sz[j] : b.zmin; b.zmax = sz[j] > b.zmax ? sz[j] : b.zmax;
+        }
+    }
+    if (b.drawable) {
+        b.x0 = (int32_t)std::clamp<int64_t>(minx, 0, W); b.x1 = (int32_t)std::clamp<int64_t>(maxx + 1, 0, W);
+        b.y0 = (int32_t)std::clamp<int64_t>(miny, 0, H); b.y1 = (int32_t)std::clamp<int64_t>(maxy + 1, 0, H);
+    }
+    b.zmin = b.zmin + 0.0f; b.zmax = b.zmax + 0.0f;
+    return b;
 }

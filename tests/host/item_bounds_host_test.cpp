@@ -1,11 +1,10 @@
-// The host side of the item bounds (software-renderer_amd/csrc/swr_api.hip: single_item_bounds, the cut, the group path,
-// swr_item_bounds) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  Built with
-// -DSWR_ITEM_BOUNDS_STANDIN: the stand-in of swr::launch_item_bounds is this file's own (hip_stub/stub_launch.cpp predates the launch), a
-// plain CPU loop over the stream slots of the items it is handed, run as a "kernel" of the fake stream; it also checks the work units
-// and the ranges.  The fake upload builds no stream, so the scene is skinned and posed: the stand-in skin launch then writes the
+// The host side of the item bounds (software-renderer_amd/csrc/swr_api.hip: band_item_bounds, the cut, the group path,
+// swr_item_bounds) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The stand-in
+// of swr::launch_item_bounds (hip_stub/stub_launch.cpp) is a plain CPU loop over the stream slots of the items it is handed, run as a
+// "kernel" of the fake stream; it also checks the work units and the ranges.  The fake upload builds no stream, so the scene is skinned and posed: the stand-in skin launch then writes the
 // stream, slot s = primitive s, and the loop reads real corners (a range resolved wrongly is a wrong record, one past the stream an
 // out-of-bounds read the address sanitizer reports).
-//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -DSWR_ITEM_BOUNDS_STANDIN -Itests/host/hip_stub -x c++ \
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ \
 //       software-renderer_amd/csrc/swr_api.hip tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp \
 //       tests/host/item_bounds_host_test.cpp -lpthread
 #include <algorithm>
@@ -21,64 +20,7 @@
 #include "host_test.h"
 #include "../../software-renderer_amd/csrc/swr_internal.h"
 
-static std::atomic<int> g_bounds_launches{0};
 static const float INF = std::numeric_limits<float>::infinity();
-
-// include/swr.h "Item bounds" over `count` triangles whose corner j of triangle t is corner(t, j) (three floats)
-template <class Corner>
-static swr_item_bound fold(int64_t count, Corner corner, const float* m, int W, int H, bool metal) {
-    swr_item_bound b{};
-    b.zmin = INF; b.zmax = -INF;
-    int64_t minx = INT64_MAX, miny = INT64_MAX, maxx = INT64_MIN, maxy = INT64_MIN;
-    for (int64_t t = 0; t < count; t++) {
-        float sx[3], sy[3], sz[3];
-        bool ok = true, w_ok = true;
-        for (int j = 0; j < 3; j++) {
-            const float* p = corner(t, j);
-            float r[4];
-            for (int i = 0; i < 4; i++) { r[i] = m[i] * p[0]; r[i] = r[i] + m[4 + i] * p[1]; r[i] = r[i] + m[8 + i] * p[2]; r[i] = r[i] + m[12 + i] * 1.0f; }
-            const float nx = r[0] / r[3], ny = r[1] / r[3];
-            sx[j] = (nx * 0.5f + 0.5f) * (float)W; sy[j] = (ny * -0.5f + 0.5f) * (float)H; sz[j] = r[2] / r[3];
-            if (metal) { sx[j] = roundf(sx[j]); sy[j] = roundf(sy[j]); }
-            ok = ok && std::fabs(sx[j]) < 1073741824.0f && std::fabs(sy[j]) < 1073741824.0f && (!metal || (sx[j] >= 0.0f && sy[j] >= 0.0f));
-            w_ok = w_ok && r[3] > 0.0f;
-        }
-        if (!ok) { b.skipped++; continue; }
-        b.drawable++;
-        if (!w_ok) b.behind++;
-        for (int j = 0; j < 3; j++) {
-            minx = std::min<int64_t>(minx, (int)sx[j]); maxx = std::max<int64_t>(maxx, (int)sx[j]);
-            miny = std::min<int64_t>(miny, (int)sy[j]); maxy = std::max<int64_t>(maxy, (int)sy[j]);
-            b.zmin = sz[j] < b.zmin ? sz[j] : b.zmin; b.zmax = sz[j] > b.zmax ? sz[j] : b.zmax;
-        }
-    }
-    if (b.drawable) {
-        b.x0 = (int32_t)std::clamp<int64_t>(minx, 0, W); b.x1 = (int32_t)std::clamp<int64_t>(maxx + 1, 0, W);
-        b.y0 = (int32_t)std::clamp<int64_t>(miny, 0, H); b.y1 = (int32_t)std::clamp<int64_t>(maxy + 1, 0, H);
-    }
-    b.zmin = b.zmin + 0.0f; b.zmax = b.zmax + 0.0f;
-    return b;
-}
-
-namespace swr {
-void launch_item_bounds(const ItemBoundsArgs& a, hipStream_t s) {
-    g_bounds_launches++;
-    fake_enqueue(s, [a] {
-        int64_t units = 0;
-        memset(a.scratch, 0x5A, item_bounds_scratch_bytes(a.n));            // (partial records sized too small are reported)
-        for (int32_t k = 0; k < a.n; k++) {
-            const ListItem& it = a.items[k];
-            if (it.ubase != (uint32_t)units) { std::printf("FAIL item %d: ubase %u, not %lld\n", (int)k, it.ubase, (long long)units); g_launch_fails++; }
-            units += item_bounds_units(it.count);
-            memset(&a.records[k], 0xA5, sizeof(swr_item_bound));             // (every word of every record is the launch's to write)
-            const float4* tri = a.tri_xyz + 3 * (size_t)it.first;
-            a.records[k] = fold((int64_t)it.count, [tri](int64_t t, int j) { return &tri[3 * t + j].x; }, it.m, a.width, a.height, a.metal != 0);
-        }
-        if (units != a.units) { std::printf("FAIL %lld units handed, the items have %lld\n", (long long)a.units, (long long)units); g_launch_fails++; }
-        if (a.n < 1 || a.n > SWR_DRAW_LIST_MAX || !a.vertices || !a.indices) g_launch_fails++;
-    }, nullptr, "k_item_bounds", (size_t)a.units);
-}
-}  // namespace swr
 
 // ---- the scene: skinned and posed, so that the fake stream holds the posed corners in index order -----------------------------------
 static const int NV = 900, NTRI = 5000;     // more than two work units in one item

@@ -1,4 +1,4 @@
-// The host side of the supersampled resolve (software-renderer_amd/csrc/swr_api.hip: single_read_resolved, the generalised
+// The host side of the supersampled resolve (software-renderer_amd/csrc/swr_api.hip: band_read_resolved, the generalised
 // copy_band, the group fan-out, swr_render_resolved) on the fake HIP runtime of tests/host/hip_stub, under the address and
 // undefined-behaviour sanitizers.  The stand-in of swr::launch_resolve (stub_launch.cpp) is a plain CPU loop over the header's
 // formulas run as a "kernel" of the fake stream.  What is checked is the host layer's

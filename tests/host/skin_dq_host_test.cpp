@@ -1,12 +1,12 @@
 // The host side of the dual-quaternion skinning (software-renderer_amd/csrc/swr_api.hip: single_pose_set as swr_pose_set_dq, the kind
 // of the pose the context remembers, enqueue_pose and its callers in restream, single_scene_attributes, single_scene_morph,
 // single_morph_set and single_scene_skin, the group fan-out) on the fake HIP runtime of tests/host/hip_stub, under the address and
-// undefined-behaviour sanitizers.  Built with -DSWR_SKIN_DQ_STANDIN: the stand-in of swr::launch_skin_vertices_dq is this file's own
-// (hip_stub/stub_launch.cpp predates the launch), a plain CPU loop over the header's arithmetic run as a "kernel" of the fake stream.  It
+// undefined-behaviour sanitizers.  The stand-in of swr::launch_skin_vertices_dq (hip_stub/stub_launch.cpp) is a plain CPU loop over the
+// header's arithmetic (pose_dq of hip_stub/stub_launch.h, which the model below shares) run as a "kernel" of the fake stream.  It
 // reads and writes every element of every array it is handed, at the sizes swr_internal.h states: a table sized for the other kind
 // of pose (8 floats a joint against 16), or the wrong array, is an out-of-bounds access the address sanitizer reports or a stream that
 // differs from the model's.  The other launches are the stand-ins of hip_stub, used as they are.
-//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -DSWR_SKIN_DQ_STANDIN -Itests/host/hip_stub -x c++ \
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ \
 //       software-renderer_amd/csrc/swr_api.hip tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp \
 //       tests/host/skin_dq_host_test.cpp -lpthread
 #include <atomic>
@@ -16,79 +16,6 @@
 
 #include "host_test.h"
 #include "../../software-renderer_amd/csrc/swr_internal.h"
-
-static std::atomic<int> g_dq_launches{0}, g_dq_nrm_launches{0};
-
-// ---- include/swr.h "Dual-quaternion skinning", for one vertex: every operation its own float operation ------------------------------
-static void cross(const float* a, const float* b, float* r) {
-    const float x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-    r[0] = x; r[1] = y; r[2] = z;
-}
-static void blend_dq(const swr_skin_vertex& sk, const float* dq, float* C) {
-    const float* Q[4];
-    for (int k = 0; k < 4; k++) Q[k] = dq + 8 * (size_t)sk.joint[k];
-    float u[4] = {sk.weight[0], 0, 0, 0};
-    for (int k = 1; k < 4; k++) {
-        float s = Q[0][0] * Q[k][0] + Q[0][1] * Q[k][1];
-        s = s + Q[0][2] * Q[k][2];
-        s = s + Q[0][3] * Q[k][3];
-        u[k] = s < 0.0f ? -sk.weight[k] : sk.weight[k];
-    }
-    float B[8];
-    for (int c = 0; c < 8; c++) {
-        float b = u[0] * Q[0][c];
-        for (int k = 1; k < 4; k++) { const float p = u[k] * Q[k][c]; b = b + p; }
-        B[c] = b;
-    }
-    float n = B[0] * B[0] + B[1] * B[1];
-    n = n + B[2] * B[2];
-    n = n + B[3] * B[3];
-    const float l = sqrtf(n), i = 1.0f / l;
-    for (int c = 0; c < 8; c++) C[c] = B[c] * i;
-}
-static void rotate(const float* C, const float* x, float* out) {
-    float a[3], b[3], c[3];
-    cross(C, x, a);
-    for (int j = 0; j < 3; j++) { const float p = C[3] * x[j]; b[j] = a[j] + p; }
-    cross(C, b, c);
-    for (int j = 0; j < 3; j++) { const float p = 2.0f * c[j]; out[j] = x[j] + p; }
-}
-static void pose_dq(const float* v, const swr_skin_vertex& sk, const float* dq, bool translate, float* out) {
-    float C[8], r[3], e[3];
-    blend_dq(sk, dq, C);
-    rotate(C, v, r);
-    if (translate) {
-        cross(C, C + 4, e);
-        for (int j = 0; j < 3; j++) {
-            const float wd = C[3] * C[4 + j], dq_ = C[7] * C[j];
-            float t = wd - dq_;
-            t = t + e[j];
-            t = 2.0f * t;
-            r[j] = r[j] + t;
-        }
-    }
-    memcpy(out, r, sizeof r);
-}
-
-namespace swr {
-void launch_skin_vertices_dq(const swr_vertex* vertices, const swr_vertex_attr* attrs, const swr_skin_vertex* skin, int64_t nv,
-                             const float* dual_quats, int32_t joint_count, swr_vertex* posed, float4* posed_nrm, hipStream_t s) {
-    g_dq_launches++;
-    if (attrs) g_dq_nrm_launches++;
-    fake_enqueue(s, [=] {
-        if (joint_count < 1 || joint_count > SWR_SKIN_MAX_JOINTS || ((uintptr_t)dual_quats & 15)) { std::printf("FAIL table of %d joints\n", joint_count); g_launch_fails++; return; }
-        float sum = 0.0f;
-        for (int64_t k = 0; k < 8 * (int64_t)joint_count; k++) sum += dual_quats[k];       // (the whole table is the launch's to read)
-        if (sum == 12345.678f) g_launch_fails++;
-        for (int64_t i = 0; i < nv; i++) {
-            for (int k = 0; k < 4; k++) if ((int64_t)skin[i].joint[k] >= joint_count) { std::printf("FAIL joint %u of %d\n", skin[i].joint[k], joint_count); g_launch_fails++; return; }
-            posed[i] = vertices[i];
-            pose_dq(vertices[i].xyz, skin[i], dual_quats, true, posed[i].xyz);
-            if (attrs) { float n[3]; pose_dq(attrs[i].normal, skin[i], dual_quats, false, n); posed_nrm[i] = make_float4(n[0], n[1], n[2], 0.0f); }
-        }
-    }, nullptr, "k_skin_vertices_dq", (size_t)nv);
-}
-}  // namespace swr
 
 // ---- poses -----------------------------------------------------------------------------------------------------------------------
 struct Pose { const float* data; bool dq; };
