@@ -116,6 +116,22 @@ def column_major(M):
     return np.ascontiguousarray(np.asarray(M, dtype=np.float64).reshape(-1, 4, 4).transpose(0, 2, 1).reshape(-1, 16), dtype=np.float32)
 
 
+def matrices_of(dq):
+    """The rigid motions of (J, 8) dual quaternions as swr_pose_set takes them (float64, rounded once; q and -q give the same matrix)."""
+    out = []
+    for q in np.asarray(dq, dtype=np.float64).reshape(-1, 8):
+        l = np.linalg.norm(q[0:4])
+        x, y, z, s = q[0:4] / l
+        r, d, ds = np.array([x, y, z]), q[4:7] / l, q[7] / l
+        M = np.eye(4)
+        M[:3, :3] = [[1 - 2 * (y * y + z * z), 2 * (x * y - z * s), 2 * (x * z + y * s)],
+                     [2 * (x * y + z * s), 1 - 2 * (x * x + z * z), 2 * (y * z - x * s)],
+                     [2 * (x * z - y * s), 2 * (y * z + x * s), 1 - 2 * (x * x + y * y)]]
+        M[:3, 3] = 2.0 * ((s * d - ds * r) + np.cross(r, d))
+        out.append(M)
+    return column_major(out)
+
+
 IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0, 0], dtype=np.float32)
 TWIST, TWIST_T = 2.5, (0.04, -0.03, 0.0)
 

@@ -10,8 +10,11 @@ import re
 import numpy as np
 import pytest
 
+import item_bounds_model as IBM
 import kernel_matrix as K
+import skin_dq_model as DQ
 import skin_model as SM
+from test_skin_dq import EDGES, random_rig, strip
 
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -110,6 +113,40 @@ def test_posed_frames_match_the_oracle_and_an_uploaded_context(swr, oracle, case
         if flags & IDS:
             hit = got[2] != K.NONE
             assert hit.sum() > 10000 and np.unique(got[2][hit]).size > 300
+
+
+# ---- 2b: the kernel's edges: the last partial workgroup, the size of the table in LDS, both instantiations --------------------------
+@gpu
+@pytest.mark.parametrize("nv,joints", EDGES)
+def test_kernel_edges(swr, nv, joints):
+    """The strips and rigs of tests/test_skin_dq.py, their joints as matrices: without attributes (k_skin_vertices<LDS, false>), then
+    with them under Phong and textured Phong (<LDS, true>), triangle and vertex frames against a context that uploaded the model's
+    vertices and normals.  1 024 joints are 48 KB of dynamic LDS.  (Every grid here is below the cap of 1024 workgroups: the grid
+    stride is crossed by tests/test_grid_caps.py.)"""
+    v, i = strip(nv)
+    dq, j, w = random_rig(nv, joints, 1000 * joints + nv)
+    m = DQ.matrices_of(dq)
+    assert m.shape == (joints, 16) and int(j.max()) == joints - 1
+    posed = SM.pose_vertices(v, j, w, m)
+    assert np.isfinite(posed).all() and not np.array_equal(posed[:, 0:3], v[:, 0:3]) and np.array_equal(posed[:, 3:], v[:, 3:])
+    with resident(swr, v, i, (j, w), m) as ctx, resident(swr, posed, i) as ref:
+        for flags, prim in ((DT | IDS, 0), (0, VERTICES)):
+            got = grab(ctx, flags, prim)
+            same(got, grab(ref, flags, prim), f"{nv} vertices, {joints} joints, primitive {prim}")
+            drawn = (got[1] != got[1][0, 0]).any(axis=-1).sum() if prim else np.isfinite(got[0]).sum()    # (points write no depth)
+            assert nv < 3 or drawn >= (100 if prim else 1000), "something is drawn"
+        # (one vertex draws nothing: the bounds of its one degenerate triangle show where the kernel put it)
+        got, want = ctx.item_bounds([(0, i.size, IDENT)], 0), IBM.item_bounds(posed, i, [(0, i.size, IDENT)], W, H, 0)
+        assert got[0].tobytes() == want[0].tobytes(), f"{got[0]} is not the model's {want[0]}"
+        assert want[0].tobytes() != IBM.item_bounds(v, i, [(0, i.size, IDENT)], W, H, 0)[0].tobytes()
+        for shader in (1, 2):
+            sh = swr.scenes.random_shading(nv, 0x77, shader)
+            for c, attrs in ((ctx, sh.attrs), (ref, SM.pose_attrs(sh.attrs, j, w, m))):
+                if sh.texture is not None:
+                    c.texture_upload(sh.texture)
+                c.material_set(swr.binding.Material.from_shading(sh))
+                c.scene_attributes(attrs)
+            same(grab(ctx, DT), grab(ref, DT), f"{nv} vertices, {joints} joints, shader {shader}")
 
 
 # ---- 3: a rigid joint is the frame's transform ----------------------------------------------------------------------------------------
@@ -402,8 +439,9 @@ def test_the_example_bends_its_torus(swr, oracle):
 # ---- 13: every kernel swr_skin.hip launches has a GPU case above ----------------------------------------------------------------------
 GPU_CASES = {
     # (k_skin_vertices<TABLE_LDS, NRM>: TABLE_LDS is the build's choice, SWR_TUNE_SKIN_LDS)
-    "k_skin_vertices<LDS.value,NRM.value> NRM=false": ("test_posed_frames_match_the_oracle_and_an_uploaded_context", "test_stream_orders"),
-    "k_skin_vertices<LDS.value,NRM.value> NRM=true": ("test_phong_frames_with_posed_normals",),
+    "k_skin_vertices<LDS.value,NRM.value> NRM=false": ("test_posed_frames_match_the_oracle_and_an_uploaded_context", "test_stream_orders",
+                                                       "test_kernel_edges"),
+    "k_skin_vertices<LDS.value,NRM.value> NRM=true": ("test_phong_frames_with_posed_normals", "test_kernel_edges"),
     "k_skin_stream<false>": ("test_posed_frames_match_the_oracle_and_an_uploaded_context", "test_three_bands_cull_with_the_posed_boxes"),
     "k_skin_stream<true>": ("test_phong_frames_with_posed_normals",),
 }

@@ -119,7 +119,8 @@ def test_posed_frames_match_the_oracle_and_an_uploaded_context(swr, oracle, case
             assert hit.sum() > 10000 and np.unique(got[2][hit]).size > 300
 
 
-# ---- 2: the kernel's edges: the grid stride, the last partial workgroup, the size of the table, both instantiations -----------------
+# ---- 2: the kernel's edges: the last partial workgroup, the size of the table, both instantiations (every grid here is below the cap
+# of 1024 workgroups — 1 025 vertices are 5 — so the grid stride is not among them: tests/test_grid_caps.py crosses it) --------------
 def strip(n):
     """n vertices on a zigzag strip across the target, triangles (k, k + 1, k + 2); one vertex: one degenerate triangle."""
     k = np.arange(n, dtype=np.float64)
@@ -151,7 +152,7 @@ EDGES = [(1, 2), (255, 2), (256, 2), (257, 2), (1025, 2), (257, 1), (257, 64), (
 @pytest.mark.parametrize("nv,joints", EDGES)
 def test_kernel_edges(swr, nv, joints):
     """Without attributes (k_skin_vertices_dq<false>), then with them under Phong and textured Phong (<true>): triangle and vertex
-    frames against a context that uploaded the model's vertices and normals."""
+    frames against a context that uploaded the model's vertices and normals.  No case strides: the largest grid has 5 workgroups."""
     v, i = strip(nv)
     dq, j, w = random_rig(nv, joints, 1000 * joints + nv)
     posed = DQ.pose_vertices(v, j, w, dq)
