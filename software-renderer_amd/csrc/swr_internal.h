@@ -39,7 +39,7 @@ static_assert(sizeof(GeomFull) == 32, "GeomFull must be 32 bytes");
 
 enum : uint32_t {
     GEOM_VALID = 1u << 0,
-    GEOM_SMALL = 1u << 1,          // bbox extents < 2^15: int16 deltas and 32-bit span arithmetic are exact
+    GEOM_SMALL = 1u << 1,          // bbox extents < 2^15 (in y: < 2^15 - TILE_H, setup_triangle_r): int16 deltas and 32-bit span arithmetic are exact
     GEOM_ORD_SHIFT = 2,            // 3 x 2 bits: which of a,b,c is S0,S1,S2 of the y-sorted list (:271)
     GEOM_ORIG_SHIFT = 8            // bits 8..31: the primitive's ORIGINAL index (scenes below 2^24 primitives;
                                    // larger scenes are not reordered, so slot == original index)

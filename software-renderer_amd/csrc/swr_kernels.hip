@@ -385,8 +385,10 @@ __device__ __forceinline__ uint2 setup_triangle_r(const SetupArgs& a, int64_t p,
         s2y = max(iy[0], max(iy[1], iy[2]));
         ok = ok && minx != 0 && s0y != 0;
     }
-    // int16 vertex deltas and 32-bit span arithmetic are exact when the bbox extents are < 2^15
-    const bool small = ((int64_t)maxx - (int64_t)minx < 32768) && ((int64_t)s2y - (int64_t)s0y < 32768);
+    // int16 vertex deltas and 32-bit span arithmetic are exact when the bbox extents are < 2^15.  In y the bound is TILE_H lower: the
+    // dense walk of raster_tile keeps C.y - Y0 in 16 bits (tabB), and a tile the triangle touches starts up to TILE_H - 1 rows above
+    // its first row, so C.y - Y0 <= (S2.y - S0.y) + TILE_H - 1 must stay below 2^15.  (In x that walk is bounded by `big`, 16384.)
+    const bool small = ((int64_t)maxx - (int64_t)minx < 32768) && ((int64_t)s2y - (int64_t)s0y < 32768 - TILE_H);
     const uint32_t flags = (orig << GEOM_ORIG_SHIFT) | (ok ? GEOM_VALID : 0u) | (small ? GEOM_SMALL : 0u) |
                            ((uint32_t)o0 << GEOM_ORD_SHIFT) | ((uint32_t)o1 << (GEOM_ORD_SHIFT + 2)) |
                            ((uint32_t)o2 << (GEOM_ORD_SHIFT + 4));
