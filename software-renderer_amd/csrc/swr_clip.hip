@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "swr_internal.h"
+#include "swr_rules.hip.h"
 #include "swr_shaders.hip.h"
 
 namespace swr {
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(CLIP_THREADS) void k_clip_emit(ClipPrep p) {
     const bool over = total > p.bound;
     if (blockIdx.x == 0 && threadIdx.x == 0 && p.over) *p.over = over ? (uint32_t)total : 0u;
     // slots beyond the post-clip count: one NaN corner makes setup skip the slot
-    const float nan = __uint_as_float(0x7FC00000u);
+    const float nan = quiet_nan();
     for (int64_t s = (over ? 0 : total) + v; s < p.bound; s += (int64_t)gridDim.x * blockDim.x) p.xyz[3 * s] = make_float4(nan, nan, nan, 1.0f);
     float c[3][NC];
     bool ok = false, inside = false;
@@ -262,32 +263,16 @@ __global__ __launch_bounds__(256) void k_clip_box(ClipPrep p) {
     int64_t total = p.sums[(p.n + CLIP_THREADS - 1) / CLIP_THREADS];
     if (total > p.bound) total = 0;                  // (an overflowed frame: every slot invalid)
     const int64_t s = g * 64 + (threadIdx.x & 63);
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    bool bad = false;
+    GroupBox b = box_start();
     if (s < total) {
-        for (int k = 0; k < 3; k++) {
-            const float4 x = p.xyz[3 * s + k];
-            const float c[3] = {x.x, x.y, x.z};
-            for (int j = 0; j < 3; j++) {
-                bad = bad || !(fabsf(c[j]) < INFINITY);
-                lo[j] = fminf(lo[j], c[j]);
-                hi[j] = fmaxf(hi[j], c[j]);
-            }
-        }
+        for (int k = 0; k < 3; k++) box_fold(b, p.xyz[3 * s + k]);
     }
-    const bool any_bad = __ballot(bad) != 0ull;
-    for (int j = 0; j < 3; j++)
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[j] = fminf(lo[j], __shfl_xor(lo[j], off));
-            hi[j] = fmaxf(hi[j], __shfl_xor(hi[j], off));
-        }
+    const bool poisoned = box_reduce(b);
     if ((threadIdx.x & 63) == 0) {
-        const float nan = __uint_as_float(0x7FC00000u);
-        float4 l = make_float4(lo[0], lo[1], lo[2], 0.0f), h = make_float4(hi[0], hi[1], hi[2], 0.0f);
-        if (any_bad) l = h = make_float4(nan, nan, nan, 0.0f);
-        else if (g * 64 >= total) l = h = make_float4(4.0f, 0.0f, 0.5f, 0.0f);    // NDC x = 4: 1.5 widths right of the image
-        p.box[2 * g] = l;
-        p.box[2 * g + 1] = h;
+        if (!poisoned && g * 64 >= total) {      // NDC x = 4: 1.5 widths right of the image
+            b.lo[0] = b.hi[0] = 4.0f; b.lo[1] = b.hi[1] = 0.0f; b.lo[2] = b.hi[2] = 0.5f;
+        }
+        box_store(b, p.box + 2 * g);
     }
 }
 

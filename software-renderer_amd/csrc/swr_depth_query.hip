@@ -32,6 +32,7 @@
 #include <cmath>
 
 #include "swr_internal.h"
+#include "swr_rules.hip.h"
 
 namespace swr {
 
@@ -93,12 +94,9 @@ __global__ __launch_bounds__(DQ_THREADS) void k_depth_tiles(const float* depth, 
         mx = in && d[r] > mx ? d[r] : mx;
         nan += in && d[r] != d[r] ? 1u : 0u;
     }
-    for (int o = 32; o; o >>= 1) {
-        const float a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
-        nan += __shfl_xor(nan, o);
-    }
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    nan = wave_add(nan);
     if (lane == 0) {
         DepthTile t;
         t.mn = mn; t.mx = mx; t.nan = nan; t.pad = 0;
@@ -153,7 +151,7 @@ __global__ __launch_bounds__(DQ_THREADS) void k_depth_boxes(DqArgs a) {
             for (int32_t y = iy0; y < iy1; y++, p += a.width) cnt += z < *p ? 1u : 0u;
         }
     }
-    for (int o = 32; o; o >>= 1) cnt += __shfl_xor(cnt, o);
+    cnt = wave_add(cnt);
     if (lane == 0) s_sum[wave] = cnt + acc;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -1,8 +1,8 @@
 // swr_item_bounds.hip — item bounds (include/swr.h "Item bounds").
 //
 // records[k] = the screen rectangle, the depth range and the three triangle counts of draw item k: a reduction over the item's
-// triangles in the arithmetic of the frame's setup (setup_triangle_r in swr_kernels.hip: vertex_shader, / w, the screen map, roundf
-// under the Metal rules, the 2^30 skip rule, truncation).  The host has cut the resident triangle stream at the items' boundaries, as a
+// triangles in the arithmetic of the frame's setup (screen_vertex and screen_vertices_ok of swr_rules.hip.h, as setup_triangle_r in
+// swr_kernels.hip uses them, then truncation).  The host has cut the resident triangle stream at the items' boundaries, as a
 // draw list does, so item k's triangles are the stream slots [first, first + count): 48 contiguous bytes per triangle, no index gather.
 //
 //   k_item_bounds_init    one lane per partial record (ITEM_BOUNDS_SLOTS per item, 64 bytes each): the fold's start — min from INT_MAX
@@ -13,7 +13,7 @@
 //                         of the nine quantities in registers; then a wave64 reduction with shuffles, four waves through LDS, and ONE
 //                         combine per workgroup into one of the item's partial records (its unit number modulo ITEM_BOUNDS_SLOTS):
 //                         integer atomicMin / atomicMax for ix and iy, the same on orderable(sz) — the monotone float -> uint map of
-//                         the visibility keys (orderable_depth in swr_kernels.hip), so the depth's minimum and maximum are exact and
+//                         the visibility keys (orderable_depth, swr_rules.hip.h), so the depth's minimum and maximum are exact and
 //                         order-free — and atomicAdd for the skipped and behind counts.  No float atomic.  (Atomics on one address
 //                         serialise at 8 to 14 ns each: with one record per item they were 40 of the kernel's 50 us on a million
 //                         triangles; 32 records on lines of their own take them off the critical path.)
@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "swr_internal.h"
+#include "swr_rules.hip.h"
 
 namespace swr {
 
@@ -43,7 +44,6 @@ namespace {
 
 constexpr int IB_THREADS = 256;
 constexpr int IB_WAVES = IB_THREADS / 64;
-constexpr float IB_COORD_LIMIT = 1073741824.0f;     // 2^30: the skip rule of setup_triangle_r
 static_assert(ITEM_BOUNDS_CHUNK % IB_THREADS == 0, "a work unit is a whole number of passes");
 static_assert(sizeof(swr_item_bound) == 48, "include/swr.h");
 
@@ -57,29 +57,10 @@ struct alignas(64) IbAccum {
 };
 static_assert(sizeof(IbAccum) == 64, "item_bounds_scratch_bytes");
 
-// (the map of swr_kernels.hip: negative floats reversed, positive ones offset; monotone for every non-NaN float, -0 below +0)
-__device__ __forceinline__ uint32_t ib_orderable(float d) {
-    const uint32_t u = __float_as_uint(d);
-    return u ^ (uint32_t)(((int32_t)u >> 31) | 0x80000000);
-}
-__device__ __forceinline__ float ib_from_orderable(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
-// the last item whose ubase is <= unit (empty items share their base with the next item and are passed over)
-__device__ __forceinline__ int ib_find(const ListItem* __restrict__ items, int n, uint32_t unit) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (items[mid].ubase <= unit) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
-}
-
 __device__ __forceinline__ IbAccum ib_start() {
     IbAccum a;
     a.minx = a.miny = INT32_MAX; a.maxx = a.maxy = INT32_MIN;
-    a.zmin = ib_orderable(INFINITY); a.zmax = ib_orderable(-INFINITY);
+    a.zmin = orderable_depth(INFINITY); a.zmax = orderable_depth(-INFINITY);
     a.drawable = a.skipped = a.behind = 0;
 #pragma unroll
     for (int i = 0; i < 7; i++) a.pad[i] = 0;
@@ -96,7 +77,7 @@ __global__ __launch_bounds__(IB_THREADS) void k_item_bounds(ItemBoundsArgs a) {
     __shared__ IbAccum s_part[IB_WAVES];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int k = __builtin_amdgcn_readfirstlane(ib_find(a.items, a.n, blockIdx.x));
+    const int k = __builtin_amdgcn_readfirstlane(list_find<true>(a.items, a.n, blockIdx.x));
     const uint32_t first = a.items[k].first, count = a.items[k].count;
     const uint32_t t0 = (blockIdx.x - a.items[k].ubase) * (uint32_t)ITEM_BOUNDS_CHUNK;   // < count: the host gave the item ceil(count / CHUNK) units
     const float fw = (float)a.width, fh = (float)a.height;
@@ -105,7 +86,7 @@ __global__ __launch_bounds__(IB_THREADS) void k_item_bounds(ItemBoundsArgs a) {
         while (k_end < a.n && a.items[k_end].first == first && a.items[k_end].count == count) k_end++;
     for (int kk = k; kk < k_end; kk++) {
         const float4* __restrict__ mc = reinterpret_cast<const float4*>(a.items[kk].m);
-        const float4 c0 = mc[0], c1 = mc[1], c2 = mc[2], c3 = mc[3];
+        const float4x4 M = {{mc[0], mc[1], mc[2], mc[3]}};
 
         int32_t minx = INT32_MAX, miny = INT32_MAX, maxx = INT32_MIN, maxy = INT32_MIN;
         float zmin = INFINITY, zmax = -INFINITY;
@@ -125,24 +106,14 @@ __global__ __launch_bounds__(IB_THREADS) void k_item_bounds(ItemBoundsArgs a) {
                 for (int j = 0; j < 3; j++) x[j] = a.tri_xyz[3 * s + j];
             }
             float sx[3], sy[3], sz[3];
-            bool ok = true, w_ok = true;
+            bool w_ok = true;
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-                float rx = c0.x * x[j].x, ry = c0.y * x[j].x, rz = c0.z * x[j].x, rw = c0.w * x[j].x;
-                rx = rx + c1.x * x[j].y; ry = ry + c1.y * x[j].y; rz = rz + c1.z * x[j].y; rw = rw + c1.w * x[j].y;
-                rx = rx + c2.x * x[j].z; ry = ry + c2.y * x[j].z; rz = rz + c2.z * x[j].z; rw = rw + c2.w * x[j].z;
-                rx = rx + c3.x * 1.0f;   ry = ry + c3.y * 1.0f;   rz = rz + c3.z * 1.0f;   rw = rw + c3.w * 1.0f;
-                const float nx = rx / rw, ny = ry / rw, nz = rz / rw;
-                const float u = nx * 0.5f + 0.5f;
-                const float v = ny * -0.5f + 0.5f;
-                sx[j] = u * fw;
-                sy[j] = v * fh;
-                sz[j] = nz;
-                if (MT) { sx[j] = roundf(sx[j]); sy[j] = roundf(sy[j]); }
-                ok = ok && (fabsf(sx[j]) < IB_COORD_LIMIT) && (fabsf(sy[j]) < IB_COORD_LIMIT);
-                if (MT) ok = ok && (sx[j] >= 0.0f) && (sy[j] >= 0.0f);
-                w_ok = w_ok && (rw > 0.0f);
+                const ScreenVertex v = screen_vertex<MT>(make_float3(x[j].x, x[j].y, x[j].z), M, fw, fh);
+                sx[j] = v.sx; sy[j] = v.sy; sz[j] = v.sz;
+                w_ok = w_ok && (v.w > 0.0f);
             }
+            const bool ok = screen_vertices_ok<MT, 3>(sx, sy);
             const bool d = in && ok;
             drawable += d ? 1u : 0u;
             skipped += (in && !ok) ? 1u : 0u;
@@ -156,18 +127,13 @@ __global__ __launch_bounds__(IB_THREADS) void k_item_bounds(ItemBoundsArgs a) {
                 zmax = (d && sz[j] > zmax) ? sz[j] : zmax;
             }
         }
-        for (int o = 32; o; o >>= 1) {
-            minx = std::min(minx, __shfl_xor(minx, o)); maxx = std::max(maxx, __shfl_xor(maxx, o));
-            miny = std::min(miny, __shfl_xor(miny, o)); maxy = std::max(maxy, __shfl_xor(maxy, o));
-            const float zn = __shfl_xor(zmin, o), zx = __shfl_xor(zmax, o);
-            zmin = zn < zmin ? zn : zmin;
-            zmax = zx > zmax ? zx : zmax;
-            drawable += __shfl_xor(drawable, o); skipped += __shfl_xor(skipped, o); behind += __shfl_xor(behind, o);
-        }
+        minx = wave_min(minx); maxx = wave_max(maxx); miny = wave_min(miny); maxy = wave_max(maxy);
+        zmin = wave_min(zmin); zmax = wave_max(zmax);
+        drawable = wave_add(drawable); skipped = wave_add(skipped); behind = wave_add(behind);
         if (lane == 0) {
             IbAccum w = ib_start();
             w.minx = minx; w.miny = miny; w.maxx = maxx; w.maxy = maxy;
-            w.zmin = ib_orderable(zmin); w.zmax = ib_orderable(zmax);
+            w.zmin = orderable_depth(zmin); w.zmax = orderable_depth(zmax);
             w.drawable = drawable; w.skipped = skipped; w.behind = behind;
             s_part[wave] = w;
         }
@@ -214,8 +180,8 @@ __global__ __launch_bounds__(IB_THREADS) void k_item_bounds_finish(const IbAccum
     b.x1 = any ? std::min(std::max(a.maxx + 1, 0), width) : 0;
     b.y0 = any ? std::min(std::max(a.miny, 0), height) : 0;
     b.y1 = any ? std::min(std::max(a.maxy + 1, 0), height) : 0;
-    b.zmin = ib_from_orderable(a.zmin) + 0.0f;
-    b.zmax = ib_from_orderable(a.zmax) + 0.0f;
+    b.zmin = depth_from_orderable(a.zmin) + 0.0f;
+    b.zmax = depth_from_orderable(a.zmax) + 0.0f;
     b.drawable = drawable; b.skipped = a.skipped; b.behind = a.behind;
     b.reserved[0] = b.reserved[1] = b.reserved[2] = 0;
     records[k] = b;

@@ -52,25 +52,12 @@
 #include <algorithm>
 
 #include "swr_internal.h"
+#include "swr_rules.hip.h"
 #include "swr_shaders.hip.h"
 
 namespace swr {
 
-#define COORD_LIMIT 1073741824.0f  // 2^30, same skip rule as the oracle
-
-// ------------------------------------------------------------------------------------------
-// small helpers
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t orderable_depth(float d) {
-    // monotone map float -> uint32 (valid for non-NaN): negative floats reversed, positive offset
-    uint32_t u = __float_as_uint(d);
-    return u ^ (uint32_t)(((int32_t)u >> 31) | 0x80000000);
-}
-__device__ __forceinline__ float depth_from_orderable(uint32_t k) {
-    uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-    return __uint_as_float(u);
-}
-
+// ---- small helpers (the rules shared with the other kernel files: swr_rules.hip.h) ----
 // trunc(n / d) for d > 0, |n| < 2^31, |n/d| < 2^20: float estimate + exact integer correction.
 __device__ __forceinline__ int tdiv_small(int n, int d, float rcp_d) {
     int an = n < 0 ? -n : n;
@@ -308,35 +295,18 @@ __device__ __forceinline__ uint2 setup_triangle_r(const SetupArgs& a, int64_t p,
     uint2 range = make_uint2(RANGE_NONE_X, 0u);
     const uint32_t orig = LIST ? lorig : (a.reordered ? __float_as_uint(xa.w) : 0u);
     const float4x4& M = LIST ? *mk : a.m;
-    // vertex colours are passed through by vertex_shader untouched (Shaders.metal:53) and are only
-    // consumed by the resolve, which fetches them for the winning primitive through idx32 / rgb
-    const float4 ca = make_float4(0, 0, 0, 0), cb = ca, cc = ca;
-
+    // (vertex colours are only consumed by the resolve, which fetches them for the winning primitive through idx32 / rgb)
     const float fw = (float)a.tg.width, fh = (float)a.tg.height;
     float sx[3], sy[3], sz[3];
     {
         const float4 xs[3] = {xa, xb, xc};
-        const float4 cs[3] = {ca, cb, cc};
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            // Vertex.apply(transform:) (:159-163) through the vertex_shader hook
-            VertexOut vo = vertex_shader(make_float3(xs[k].x, xs[k].y, xs[k].z),
-                                         make_float3(cs[k].x, cs[k].y, cs[k].z), M);
-            const float nx = AFF ? vo.pos.x : vo.pos.x / vo.pos.w;
-            const float ny = AFF ? vo.pos.y : vo.pos.y / vo.pos.w;
-            const float nz = AFF ? vo.pos.z : vo.pos.z / vo.pos.w;
-            // convertedToScreen (:165-171)
-            const float u = nx * 0.5f + 0.5f;
-            const float v = ny * -0.5f + 0.5f;
-            sx[k] = u * fw;
-            sy[k] = v * fh;
-            sz[k] = nz;
-            if (MT) {                      // vertex_pass: pixels = round(uv * screen) (Shaders.metal:71)
-                sx[k] = roundf(sx[k]);          // half away from zero, like Metal's round()
-                sy[k] = roundf(sy[k]);
-            }
+            const ScreenVertex s = screen_vertex<MT, AFF>(make_float3(xs[k].x, xs[k].y, xs[k].z), M, fw, fh);
+            sx[k] = s.sx; sy[k] = s.sy; sz[k] = s.sz;
         }
     }
+    // (the skip rule of screen_vertices_ok<MT, 3>, written out: every form of the call moved the instructions of k_bin and k_setup_hist)
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 3; k++)
@@ -773,19 +743,7 @@ __global__ __launch_bounds__(BT) void k_fill_lds(const uint2* __restrict__ range
 // rotate by three, so the array zeroed here was last read by a raster that finished before this kernel could start).
 // A tile that receives more than cap entries overflows: the frame's largest fill goes to the host, which grows cap and
 // redraws (or falls back to the exact-size path above when a tile needs more than FIXED_CAP_MAX entries).
-// ---- draw-list frames ------------------------------------------------------------------------------------------
-// The item of frame slot v (UNITS: of k_bin work unit v): the last item whose vbase (ubase) is <= v.  Empty items share their base
-// with the next item and are passed over; item 0 starts at 0.  (A binary search over <= SWR_DRAW_LIST_MAX items.)
-template <bool UNITS>
-__device__ __forceinline__ int list_find(const ListItem* __restrict__ items, int n, uint32_t v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const uint32_t key = UNITS ? items[mid].ubase : items[mid].vbase;
-        if (key <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
-}
+// ---- draw-list frames (the item of a frame slot or work unit: list_find, swr_rules.hip.h) -------------------------
 __device__ __forceinline__ float4x4 list_matrix(const ListItem* __restrict__ items, int k) {
     const float4* c = reinterpret_cast<const float4*>(items[k].m);
     float4x4 m;
@@ -995,9 +953,7 @@ __global__ __launch_bounds__(BT) void k_bin(BinArgs b) {
     {
         // totals of the frame: workgroup sums -> two device counters; the last workgroup to arrive hands them to the host
         const uint32_t ws = (uint32_t)wave_incl_add((int)psum);
-        uint32_t wm = pmax;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, off));
+        const uint32_t wm = wave_max(pmax);
         if (lane == 63) red[t >> 6] = ws;
         if (lane == 0) red[BT / 64 + (t >> 6)] = wm;
     }
@@ -2037,9 +1993,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                     hi = min(hi, X1);
                 }
                 // chunk shape from the widest span: 16x4, 32x2 or 64x1 pixels per wave step
-                int wmax = hi - lo + 1;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) wmax = max(wmax, __shfl_xor(wmax, off));
+                const int wmax = wave_max(hi - lo + 1);
                 const int lw = wmax <= 16 ? 4 : (wmax <= 32 ? 5 : 6);
                 const int cw = 1 << lw, rows_per = 64 >> lw;
                 const int nrows = min(64, uyb - yc + 1);
@@ -2590,11 +2544,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                 } else {
                     f = fragment_shader(vin);
                 }
-                // Pixel(float3:) -> .floats(b: z, g: y, r: x, a: 1) truncates (:116-128); the Metal path's bgra8Unorm store rounds to nearest even
-                float ub = fminf(fmaxf(f.z, 0.0f), 1.0f) * 255.0f, ug = fminf(fmaxf(f.y, 0.0f), 1.0f) * 255.0f;
-                float ur = fminf(fmaxf(f.x, 0.0f), 1.0f) * 255.0f, ua = fminf(fmaxf(f.w, 0.0f), 1.0f) * 255.0f;
-                if (METAL) { ub = rintf(ub); ug = rintf(ug); ur = rintf(ur); ua = rintf(ua); }
-                c = (uint32_t)ub | ((uint32_t)ug << 8) | ((uint32_t)ur << 16) | ((uint32_t)ua << 24);
+                c = quantize_bgra<METAL>(f);
             };
             // Passes 2 and 3, in ROUNDS of WTAB_RCAP winners: one round for every tile of the BASELINE scenes; a tile of ~1 000 two-pixel
             // triangles has ~600 winners and takes two.  A pixel is shaded and stored by the round its winner's number falls into
@@ -2884,12 +2834,7 @@ __device__ __forceinline__ bool raster_tile(const RasterArgs& a, typename std::c
                         } else {
                             f = fragment_shader(vin);
                         }
-                        // Pixel(float3:) -> .floats(b: z, g: y, r: x, a: 1) truncates (:116-128);
-                        // the Metal path's bgra8Unorm store rounds to nearest even
-                        float ub = fminf(fmaxf(f.z, 0.0f), 1.0f) * 255.0f, ug = fminf(fmaxf(f.y, 0.0f), 1.0f) * 255.0f;
-                        float ur = fminf(fmaxf(f.x, 0.0f), 1.0f) * 255.0f, ua = fminf(fmaxf(f.w, 0.0f), 1.0f) * 255.0f;
-                        if (METAL) { ub = rintf(ub); ug = rintf(ug); ur = rintf(ur); ua = rintf(ua); }
-                        c = (uint32_t)ub | ((uint32_t)ug << 8) | ((uint32_t)ur << 16) | ((uint32_t)ua << 24);
+                        c = quantize_bgra<METAL>(f);
                     }
                 }
                 if constexpr (COLD) {
@@ -3284,13 +3229,10 @@ __global__ __launch_bounds__(RASTER_THREADS) void k_raster_blend(BlendArgs a) {
                 const float fr = a_r * w0 + b_r * w1 + c_r * w2;                                               // :266
                 const float fg = a_g * w0 + b_g * w1 + c_g * w2;
                 const float fb = a_b * w0 + b_b * w1 + c_b * w2;
-                // Pixel(float3:) truncates (:116-128); the Metal path's bgra8Unorm store rounds to nearest even (raster_tile's resolve)
-                float ub = fminf(fmaxf(fb, 0.0f), 1.0f) * 255.0f, ug = fminf(fmaxf(fg, 0.0f), 1.0f) * 255.0f;
-                float ur = fminf(fmaxf(fr, 0.0f), 1.0f) * 255.0f;
-                if (METAL) { ub = rintf(ub); ug = rintf(ug); ur = rintf(ur); }
+                const uint32_t ub = quantize_channel<METAL>(fb), ug = quantize_channel<METAL>(fg), ur = quantize_channel<METAL>(fr);
                 const uint32_t d = col[r];
-                col[r] = blend_channel((uint32_t)ub, d & 0xFFu, A, add) | (blend_channel((uint32_t)ug, (d >> 8) & 0xFFu, A, add) << 8) |
-                         (blend_channel((uint32_t)ur, (d >> 16) & 0xFFu, A, add) << 16) | (blend_channel(255u, d >> 24, A, add) << 24);
+                col[r] = blend_channel(ub, d & 0xFFu, A, add) | (blend_channel(ug, (d >> 8) & 0xFFu, A, add) << 8) |
+                         (blend_channel(ur, (d >> 16) & 0xFFu, A, add) << 16) | (blend_channel(255u, d >> 24, A, add) << 24);
             }
         }
     }
@@ -3329,11 +3271,12 @@ __global__ void k_points(const swr_vertex* __restrict__ vtx, const int64_t* __re
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ni) return;
     const float4 p = reinterpret_cast<const float4*>(vtx)[2 * idx[i]];
+    // (screen_vertex's map, written out here and in k_lines: the helper's statement order is setup's, and moves these two kernels' instructions)
     const VertexOut vo = vertex_shader(make_float3(p.x, p.y, p.z), make_float3(0, 0, 0), m);   // :160
     const float nx = vo.pos.x / vo.pos.w, ny = vo.pos.y / vo.pos.w;                             // :161
     const float sx = (nx * 0.5f + 0.5f) * (float)tg.width;                                      // :166-168
     const float sy = (ny * -0.5f + 0.5f) * (float)tg.height;
-    if (!(fabsf(sx) < COORD_LIMIT) || !(fabsf(sy) < COORD_LIMIT)) return;   // Swift Int(NaN) would trap
+    if (!screen_vertices_ok<false, 1>(&sx, &sy)) return;                     // Swift Int(NaN) would trap
     const int px = (int)sx, py = (int)sy;                                    // :298-299 truncation
     if (px < 0 || px >= tg.width || py < tg.row_begin || py >= tg.row_end) return;   // setter drops OOB (:30-36)
     atomicMax(&order[(size_t)(py - tg.row_begin) * (size_t)tg.width + (size_t)px], (uint32_t)(i + 1));
@@ -3357,7 +3300,7 @@ __global__ void k_lines(const swr_vertex* __restrict__ vtx, const int64_t* __res
         const float nx = vo.pos.x / vo.pos.w, ny = vo.pos.y / vo.pos.w;                             // :161
         const float sx = (nx * 0.5f + 0.5f) * (float)tg.width;                                      // :166-168
         const float sy = (ny * -0.5f + 0.5f) * (float)tg.height;
-        if (!(fabsf(sx) < COORD_LIMIT) || !(fabsf(sy) < COORD_LIMIT)) return;   // Swift Int(NaN) would trap
+        if (!screen_vertices_ok<false, 1>(&sx, &sy)) return;                     // Swift Int(NaN) would trap
         ex[k] = (int)sx; ey[k] = (int)sy;                                        // :298-299 truncation
     }
     const int dx = ex[1] - ex[0], dy = ey[1] - ey[0];                            // :406-407 (|coordinates| < 2^30: no overflow)
@@ -3388,12 +3331,7 @@ __global__ void k_points_resolve(const swr_vertex* __restrict__ vtx, const int64
             VertexOut vin;
             vin.pos = make_float4(0, 0, 0, 1);
             vin.color = make_float3(v.x, v.y, v.z);
-            const float4 f = fragment_shader(vin);                            // Pixel(float3:) :126-128
-            const uint32_t qb = (uint32_t)(fminf(fmaxf(f.z, 0.0f), 1.0f) * 255.0f);
-            const uint32_t qg = (uint32_t)(fminf(fmaxf(f.y, 0.0f), 1.0f) * 255.0f);
-            const uint32_t qr = (uint32_t)(fminf(fmaxf(f.x, 0.0f), 1.0f) * 255.0f);
-            const uint32_t qa = (uint32_t)(fminf(fmaxf(f.w, 0.0f), 1.0f) * 255.0f);
-            c = qb | (qg << 8) | (qr << 16) | (qa << 24);
+            c = quantize_bgra<false>(fragment_shader(vin));                   // Pixel(float3:) :126-128
         }
         color[i] = c;
         depth_bits[i] = LOAD ? src_depth[i] : 0x7F800000u;                    // +inf (:206)

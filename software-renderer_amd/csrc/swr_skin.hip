@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "swr_internal.h"
+#include "swr_rules.hip.h"
 
 #ifndef SWR_TUNE_SKIN_LDS
 #define SWR_TUNE_SKIN_LDS 1        // the pose table in LDS (1) or left to L2 (0): DESIGN.md §23 has the measurement
@@ -124,8 +125,7 @@ __global__ __launch_bounds__(SKIN_THREADS) void k_skin_stream(StreamArgs a) {
     const int64_t s = (int64_t)blockIdx.x * SKIN_THREADS + threadIdx.x;
     const int64_t g = s >> 6;
     if (g >= (a.ntri + 63) / 64) return;        // (wave-uniform)
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    bool bad = false;
+    GroupBox b = box_start();
     if (s < a.ntri) {
         const int64_t o = a.reordered ? (int64_t)__float_as_uint(a.tri_xyz[3 * s].w) : s;
 #pragma unroll
@@ -141,27 +141,11 @@ __global__ __launch_bounds__(SKIN_THREADS) void k_skin_stream(StreamArgs a) {
                 float* nout = reinterpret_cast<float*>(a.tri_nrm + 3 * s + k);
                 nout[0] = n.x; nout[1] = n.y; nout[2] = n.z;
             }
-            const float c[3] = {x.x, x.y, x.z};
-#pragma unroll
-            for (int j = 0; j < 3; j++) {               // k_box64, operation for operation
-                bad = bad || !(fabsf(c[j]) < INFINITY);
-                lo[j] = fminf(lo[j], c[j]);
-                hi[j] = fmaxf(hi[j], c[j]);
-            }
+            box_fold(b, x);
         }
     }
-    const bool any_bad = __ballot(bad) != 0ull;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[j] = fminf(lo[j], __shfl_xor(lo[j], off));
-            hi[j] = fmaxf(hi[j], __shfl_xor(hi[j], off));
-        }
-    if ((threadIdx.x & 63) == 0) {
-        const float nan = __uint_as_float(0x7FC00000u);
-        a.box64[2 * g] = any_bad ? make_float4(nan, nan, nan, 0) : make_float4(lo[0], lo[1], lo[2], 0);
-        a.box64[2 * g + 1] = any_bad ? make_float4(nan, nan, nan, 0) : make_float4(hi[0], hi[1], hi[2], 0);
-    }
+    box_reduce(b);
+    if ((threadIdx.x & 63) == 0) box_store(b, a.box64 + 2 * g);
 }
 
 }  // namespace

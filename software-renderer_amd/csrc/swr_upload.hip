@@ -24,20 +24,13 @@
 #include <stdint.h>
 
 #include "swr_internal.h"
+#include "swr_rules.hip.h"
 
 namespace swr {
 
 namespace {
 
-__device__ __forceinline__ uint32_t ordered_bits(float f) {           // monotone float -> uint (non-NaN)
-    const uint32_t u = __float_as_uint(f);
-    return u ^ (uint32_t)(((int32_t)u >> 31) | 0x80000000);
-}
-__device__ __forceinline__ float from_ordered_bits(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
-// bounds[0..2] = min xyz, bounds[3..5] = max xyz over the finite vertices (ordered-uint encoding)
+// bounds[0..2] = min xyz, bounds[3..5] = max xyz over the finite vertices (as orderable_depth keys)
 __global__ void k_bounds_init(uint32_t* bounds) {
     if (threadIdx.x < 3) bounds[threadIdx.x] = 0xFFFFFFFFu;
     else if (threadIdx.x < 6) bounds[threadIdx.x] = 0u;
@@ -55,14 +48,12 @@ __global__ void k_scene_bounds(const swr_vertex* __restrict__ vtx, int64_t nv, u
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-        }
+        lo[k] = wave_fmin(lo[k]);
+        hi[k] = wave_fmax(hi[k]);
         if ((threadIdx.x & 63) == 0) {
             if (lo[k] <= hi[k]) {
-                atomicMin(&bounds[k], ordered_bits(lo[k]));
-                atomicMax(&bounds[3 + k], ordered_bits(hi[k]));
+                atomicMin(&bounds[k], orderable_depth(lo[k]));
+                atomicMax(&bounds[3 + k], orderable_depth(hi[k]));
             }
         }
     }
@@ -87,8 +78,8 @@ __global__ void k_morton(const swr_vertex* __restrict__ vtx, int64_t nv, const i
     float lo[3], scale[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        lo[k] = from_ordered_bits(bounds[k]);
-        const float ext = from_ordered_bits(bounds[3 + k]) - lo[k];
+        lo[k] = depth_from_orderable(bounds[k]);
+        const float ext = depth_from_orderable(bounds[3 + k]) - lo[k];
         scale[k] = (ext > 0.0f && ext < INFINITY) ? 1023.0f / ext : 0.0f;
     }
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < ntri; p += stride) {
@@ -150,40 +141,19 @@ __global__ void k_gather_stream(const swr_vertex* __restrict__ v, int64_t nv, co
     }
 }
 
-// one wave per group of 64 slots: object-space box of their 192 vertices.  A non-finite coordinate
-// poisons the box with NaN, which the frame's cull test reads as "cannot be culled".
+// one wave per group of 64 slots: object-space box of their 192 vertices (GroupBox, swr_rules.hip.h)
 __global__ void k_box64(const float4* __restrict__ tri_xyz, int64_t g0, int64_t ntri, float4* __restrict__ box64) {
     const int64_t g = g0 + (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
     const int64_t groups = (ntri + 63) / 64;
     if (g >= groups) return;
     const int64_t s = g * 64 + (threadIdx.x & 63);
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    bool bad = false;
+    GroupBox b = box_start();
     if (s < ntri) {
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float4 x = tri_xyz[3 * s + k];
-            const float c[3] = {x.x, x.y, x.z};
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                bad = bad || !(fabsf(c[j]) < INFINITY);
-                lo[j] = fminf(lo[j], c[j]);
-                hi[j] = fmaxf(hi[j], c[j]);
-            }
-        }
+        for (int k = 0; k < 3; k++) box_fold(b, tri_xyz[3 * s + k]);
     }
-    const bool any_bad = __ballot(bad) != 0ull;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[j] = fminf(lo[j], __shfl_xor(lo[j], off));
-            hi[j] = fmaxf(hi[j], __shfl_xor(hi[j], off));
-        }
-    if ((threadIdx.x & 63) == 0) {
-        const float nan = __uint_as_float(0x7FC00000u);
-        box64[2 * g] = any_bad ? make_float4(nan, nan, nan, 0) : make_float4(lo[0], lo[1], lo[2], 0);
-        box64[2 * g + 1] = any_bad ? make_float4(nan, nan, nan, 0) : make_float4(hi[0], hi[1], hi[2], 0);
-    }
+    box_reduce(b);
+    if ((threadIdx.x & 63) == 0) box_store(b, box64 + 2 * g);
 }
 
 // swr_scene_attributes: the extra varyings, de-indexed into the same sorted slots.
