@@ -7,7 +7,7 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion [--bounds]] [--delta] [--skin [--dq]] [--morph]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion [--bounds]] [--delta] [--skin [--dq]] [--morph [--sparse]]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
@@ -32,6 +32,9 @@ motions, so the twisting tube keeps its volume where the blended matrices of swr
 --morph gives the mesh two procedural morph targets (blend shapes) — a swell along the direction from the mesh's centre and a twist
 about z — uploaded once (swr_scene_morph), and every frame sets two new weights (swr_morph_set): the vertices are morphed on the
 device, nothing but the weights crosses per frame.  With --skin the torus is morphed first and then posed, as glTF orders the two.
+--morph --sparse uploads the same two targets as sparse ones (swr_scene_morph_sparse): each lists only the vertices it moves, and only
+those are stored and rewritten on the device.  With --skin the weights and the pose are then set by one call (swr_morph_pose_set), which
+rewrites the scene once per frame instead of twice.
 --cull {none,back,front} [--front-ccw] turns on face culling (Metal's setCullMode / setFrontFacingWinding): triangles that face
 away (back) or towards the viewer (front) are not drawn; front is clockwise as displayed unless --front-ccw.
 
@@ -543,10 +546,11 @@ def morph_weights(time: float) -> np.ndarray:
 
 
 def run_morph(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, skin: bool = False,
-              device_count: int = 1, obj: str | None = None, dq: bool = False):
+              device_count: int = 1, obj: str | None = None, dq: bool = False, sparse: bool = False):
     """The resident loop with a mesh that changes its shape: two morph targets uploaded once (swr_scene_morph), new weights every
     frame (swr_morph_set), the app's transform.  skin: the torus of run_skin, morphed and then posed (swr_pose_set, or with dq
-    swr_pose_set_dq and twist_pose) every frame.
+    swr_pose_set_dq and twist_pose) every frame.  sparse: the targets are uploaded as sparse ones, restricted to the vertices they
+    move (swr_scene_morph_sparse), and with skin the weights and the pose are set by one call (swr_morph_pose_set).
     Returns the mesh and the (colour, depth) frames."""
     if skin:
         xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
@@ -557,17 +561,24 @@ def run_morph(frames: int, size: int, out: str | None = None, depth_test: bool =
     results = []
     with swr_amd.Context(0, device_count=device_count) as ctx:
         ctx.scene_upload(vertices, indices)
-        ctx.scene_morph(morph_targets(vertices))
+        if sparse:
+            ctx.scene_morph_sparse(swr_amd.binding.sparse_targets(morph_targets(vertices)))
+        else:
+            ctx.scene_morph(morph_targets(vertices))
         if skin:
             ctx.scene_skin(*bend_skin(vertices))
         ctx.target_set(size, size)
         time = time0
         for k in range(frames):
-            ctx.morph_set(morph_weights(time))
-            if skin and dq:
-                ctx.pose_set_dq(swr_amd.binding.dual_quats(twist_pose(time)))
-            elif skin:
-                ctx.pose_set(bend_pose(time))
+            pose = None if not skin else swr_amd.binding.dual_quats(twist_pose(time)) if dq else bend_pose(time)
+            if sparse and skin:
+                ctx.morph_pose_set(morph_weights(time), pose, dq=dq)     # one rewrite of the scene for both
+            else:
+                ctx.morph_set(morph_weights(time))
+                if skin and dq:
+                    ctx.pose_set_dq(pose)
+                elif skin:
+                    ctx.pose_set(pose)
             ctx.draw(S.app_transform(time), flags)
             results.append((ctx.read_color(), ctx.read_depth()))
             if out:
@@ -606,6 +617,9 @@ if __name__ == "__main__":
                          "its volume where blended matrices would pinch it")
     ap.add_argument("--morph", action="store_true",
                     help="two procedural morph targets on the mesh (swr_scene_morph), new weights every frame (swr_morph_set); composes with --skin")
+    ap.add_argument("--sparse", action="store_true",
+                    help="with --morph: the targets list only the vertices they move (swr_scene_morph_sparse); with --skin as well, weights "
+                         "and pose are set by one call (swr_morph_pose_set)")
     ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
     ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
     ap.add_argument("--clip", action="store_true", help="depth clipping: triangles clipped against the near and far planes")
@@ -617,6 +631,8 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.dq and not a.skin:
         ap.error("--dq is a mode of --skin")
+    if a.sparse and not a.morph:
+        ap.error("--sparse is a mode of --morph")
     if a.ssaa != 1 and a.stream:
         ap.error("--ssaa is not part of the --stream loop (there is no asynchronous resolved present)")
     if a.glass is not None:
@@ -631,12 +647,14 @@ if __name__ == "__main__":
     if a.bounds and a.clip:
         ap.error("--bounds does not combine with --clip (swr_item_bounds does not take SWR_FLAG_DEPTH_CLIP)")
     deforming_bounds = a.occlusion and a.bounds and (a.skin or a.morph)
+    if a.sparse and deforming_bounds:
+        ap.error("--sparse is part of the plain --morph loop, not of --occlusion --bounds")
     if deforming_bounds and (a.obj or a.ply or a.stream or a.delta or a.glass is not None):
         ap.error("--occlusion --bounds with --skin / --morph draws copies of the torus: not with --obj, --ply, --stream, --delta or --glass")
     if a.morph and not deforming_bounds:
         if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or (a.skin and (a.obj or a.ply)):
             ap.error("--morph is its own loop: only --frames, --size, --out, --depth-test, --gpus, --skin and (without --skin) --obj / --ply apply")
-        _, idx, res = run_morph(a.frames, a.size, a.out, a.depth_test, skin=a.skin, device_count=a.gpus, obj=a.ply or a.obj, dq=a.dq)
+        _, idx, res = run_morph(a.frames, a.size, a.out, a.depth_test, skin=a.skin, device_count=a.gpus, obj=a.ply or a.obj, dq=a.dq, sparse=a.sparse)
         print(f"{a.frames} morphed{' and posed' if a.skin else ''} frames, {idx.size // 3} triangles, "
               f"coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)

@@ -555,6 +555,58 @@ typedef struct swr_item_bound {
     uint32_t reserved[3];     /* 0 on return */
 } swr_item_bound;             /* 48 bytes */
 
+/* ---- Sparse morph targets (swr_scene_morph_sparse) — DESIGN.md §28 -----------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_scene_morph_sparse symbol is the feature test.
+ * Nothing existing changes.  This section covers the "sparse targets" that the "Not covered" line of "Morph targets" names: a target
+ * lists only the vertices it moves, as a glTF sparse accessor does, and only those are stored on the device and rewritten by
+ * swr_morph_set.
+ *   One morph state.  The targets in effect are those of the last swr_scene_morph or swr_scene_morph_sparse.  Either call with
+ *     NULL removes whichever kind is resident.  swr_morph_set serves both kinds: one weight per target, the same errors.
+ *   Arithmetic (normative): IEEE binary32, one rounding per operation, no FMA.  For vertex i start with p = b, the position as
+ *     uploaded.  Walk t in ascending order.  For every t with w[t] != 0.0f whose index list contains i at position j,
+ *     p = p + w[t] * d_t[j], componentwise: the product is rounded, then the sum.
+ *     A vertex a target does not list is not touched by that target.  This is not the dense target with a zero delta: an unlisted
+ *     -0 coordinate stays -0 where an applied zero delta makes it +0, and a NaN or infinite weight poisons only the listed
+ *     vertices.  A zero-weight target's deltas never enter the arithmetic; the device may still read them.
+ *     Normals take the same loop with normal_deltas, under the conditions of "Morph targets" (the scene has attributes; deltas
+ *     given before swr_scene_attributes take effect when it arrives).  Either every target with count > 0 gives normal_deltas or
+ *     none does.  Colour, uv and the padding lanes never change.
+ *   What a sparse morph is.  Every frame, read and query after the call is bit for bit that of a context that uploaded the
+ *     morphed-then-posed vertices.
+ *   Lifetime, Ordering and "Order with the skin" of "Morph targets" apply unchanged: new targets set every weight to 0 and keep
+ *     skin and pose; an upload discards targets and weights; the call is blocking and first completes and checks everything drawn
+ *     before; the arrays are copied and free on return; a multi-device context morphs every band.
+ *   Errors, all checked before anything changes.  SWR_ERR_NO_SCENE: no scene.  SWR_ERR_BAD_ARG: a NULL ctx; a vertex_count that
+ *     does not match the scene; a NULL targets array; target_count < 1; a non-zero reserved; count < 0 or count > vertex_count;
+ *     NULL indices or position_deltas with count > 0; an index >= vertex_count, or indices not strictly ascending (the message
+ *     names the target and the position); normal deltas on some non-empty targets only.  SWR_ERR_UNSUPPORTED: target_count >
+ *     SWR_MORPH_MAX_TARGETS.  SWR_ERR_NOMEM: a device allocation fails.  A failed context returns its sticky error.  After an
+ *     error the scene, the targets of either kind and the weights are unchanged.
+ *   Not covered: morphing colours or uv, an un-waited morph, and the C++ and Swift mirrors. */
+typedef struct swr_morph_sparse_target {
+    const uint32_t* indices;          /* count vertex indices, strictly ascending, each < vertex_count */
+    const float*    position_deltas;  /* count x 3 floats: entry j belongs to vertex indices[j] */
+    const float*    normal_deltas;    /* count x 3 floats, or NULL */
+    int64_t         count;            /* 0 .. vertex_count; 0 = an empty target, the pointers may be NULL */
+} swr_morph_sparse_target;            /* 32 bytes */
+typedef struct swr_morph_sparse {
+    const swr_morph_sparse_target* targets;
+    int64_t vertex_count;             /* must equal the resident scene's */
+    int32_t target_count;             /* 1 .. SWR_MORPH_MAX_TARGETS */
+    int32_t reserved;                 /* 0 */
+} swr_morph_sparse;                   /* 24 bytes */
+
+/* ---- Weights and joints in one call (swr_morph_pose_set) — DESIGN.md §28 -----------------------------------------------------------
+ * No ABI bump and no flag bit: the presence of the swr_morph_pose_set symbol is the feature test.  This section covers the "one
+ * call that sets weights and joints together" that the "Not covered" line of "Morph targets" names.
+ *   The call is exactly swr_morph_set(weights, weight_count) followed by swr_pose_set (pose_kind SWR_POSE_MATRICES) or
+ *     swr_pose_set_dq (SWR_POSE_DUAL_QUATS) with joints, joint_count, with two differences.  Every argument of both halves is
+ *     validated before anything changes: after an error neither the weights nor the pose have changed.  And the scene is rewritten
+ *     once: the skin and stream passes run once, and the call waits once.
+ *   It needs targets (of either kind) and a skin.  NULL weights with 0 and NULL joints with 0 mean what they mean in the two calls.
+ *   Errors: those of the two calls, under their conditions, and SWR_ERR_BAD_ARG for an unknown pose_kind. */
+enum { SWR_POSE_MATRICES = 0, SWR_POSE_DUAL_QUATS = 1 };
+
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
  * continues from the image already there.
@@ -773,6 +825,10 @@ int swr_pose_set_dq(swr_context* ctx, const float* dual_quats, int32_t joint_cou
 /* Morph targets (see "Morph targets" above): the targets of the resident scene, and the weights it is morphed by. */
 int swr_scene_morph(swr_context* ctx, const swr_morph_targets* targets);                 /* NULL: remove the targets */
 int swr_morph_set(swr_context* ctx, const float* weights, int32_t weight_count);         /* NULL, 0: every weight 0 */
+/* sparse morph targets ("Sparse morph targets" above); weights and joints in one call ("Weights and joints in one call") */
+int swr_scene_morph_sparse(swr_context* ctx, const swr_morph_sparse* targets);           /* NULL: remove the targets */
+int swr_morph_pose_set(swr_context* ctx, const float* weights, int32_t weight_count,
+                       const float* joints, int32_t joint_count, int32_t pose_kind);
 int swr_material_set(swr_context* ctx, const swr_material* material);
 int swr_texture_upload(swr_context* ctx, const void* bgra8, int32_t width, int32_t height);
 /* The blend state of SWR_FLAG_BLEND frames (see "Alpha blending" above); NULL restores the default, SWR_BLEND_OVER with opacity 255.

@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
     "swr_query_depth", "swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta",
     "swr_scene_skin", "swr_pose_set", "swr_scene_morph", "swr_morph_set", "swr_item_bounds",
-    "swr_pose_set_dq",
+    "swr_pose_set_dq", "swr_scene_morph_sparse", "swr_morph_pose_set",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -203,6 +203,44 @@ class MorphTargets(ctypes.Structure):
 
 
 MORPH_MAX_TARGETS = 256      # SWR_MORPH_MAX_TARGETS: targets per scene
+
+
+class MorphSparseTarget(ctypes.Structure):
+    """swr_morph_sparse_target (include/swr.h "Sparse morph targets"): the vertices one target moves, ascending, and their deltas."""
+    _fields_ = [("indices", ctypes.c_void_p), ("position_deltas", ctypes.c_void_p), ("normal_deltas", ctypes.c_void_p),
+                ("count", ctypes.c_int64)]
+
+
+class MorphSparse(ctypes.Structure):
+    """swr_morph_sparse: target_count sparse targets of a scene of vertex_count vertices."""
+    _fields_ = [("targets", ctypes.POINTER(MorphSparseTarget)), ("vertex_count", ctypes.c_int64), ("target_count", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+POSE_MATRICES, POSE_DUAL_QUATS = 0, 1      # SWR_POSE_*: the pose_kind of swr_morph_pose_set
+
+
+def sparse_targets(dense_deltas, dense_normal_deltas=None) -> list:
+    """Dense targets of shape (T, nv, 3) as the list Context.scene_morph_sparse takes: per target the indices of the vertices whose
+    delta (or normal delta) is not all zero, ascending, and their rows.  A vertex that is dropped is one the sparse target does not
+    touch: on it a -0 coordinate stays -0 and a non-finite weight has no effect, where the dense target with its zero row gives +0
+    and NaN; everywhere else the two morph alike, bit for bit."""
+    dp = np.ascontiguousarray(dense_deltas, dtype=np.float32)
+    if dp.ndim != 3 or dp.shape[2] != 3:
+        raise ValueError(f"dense_deltas of shape {dp.shape}, not (T, nv, 3)")
+    dn = None
+    if dense_normal_deltas is not None:
+        dn = np.ascontiguousarray(dense_normal_deltas, dtype=np.float32)
+        if dn.shape != dp.shape:
+            raise ValueError(f"dense_normal_deltas of shape {dn.shape}, not {dp.shape}")
+    out = []
+    for t in range(dp.shape[0]):
+        moved = np.any(dp[t] != 0, axis=1)
+        if dn is not None:
+            moved |= np.any(dn[t] != 0, axis=1)
+        idx = np.flatnonzero(moved).astype(np.uint32)
+        out.append((idx, dp[t][idx]) if dn is None else (idx, dp[t][idx], dn[t][idx]))
+    return out
 
 
 class Config(ctypes.Structure):
@@ -393,6 +431,14 @@ def load_library():
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
             raise
+    try:
+        L.swr_scene_morph_sparse.argtypes = [vp, ctypes.POINTER(MorphSparse)]
+        L.swr_morph_pose_set.argtypes = [vp, vp, i32, vp, i32, i32]
+        for name in ("swr_scene_morph_sparse", "swr_morph_pose_set"):
+            getattr(L, name).restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
+            raise
     L.swr_target_write.argtypes = [vp, vp, vp]
     L.swr_target_write.restype = ctypes.c_int
     L.swr_present_wait.argtypes = [vp]
@@ -489,6 +535,7 @@ class Context:
         self.width = self.height = 0
         self.row_begin = self.row_end = 0
         self._scene_prims = 0           # index_count / 3 of the resident scene
+        self._scene_vertices = 0        # its vertex count
         self._last_list = None          # (primitives, items) of the last frame when it was a draw list (count_ids' default n)
 
     def close(self):
@@ -521,6 +568,7 @@ class Context:
         i = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
         self._check(self._L.swr_scene_upload(self._h, v.ctypes.data, v.shape[0], i.ctypes.data, i.size))
         self._scene_prims = i.size // 3
+        self._scene_vertices = v.shape[0]
 
     def scene_attributes(self, attrs: np.ndarray):
         a = np.ascontiguousarray(attrs, dtype=np.float32).reshape(-1, 8)
@@ -586,6 +634,38 @@ class Context:
             return
         w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
         self._check(self._L.swr_morph_set(self._h, w.ctypes.data, w.shape[0]))
+
+    def scene_morph_sparse(self, targets: "list | None", vertex_count: "int | None" = None):
+        """swr_scene_morph_sparse: sparse morph targets of the resident scene — a list with, per target, (indices, position_deltas)
+        or (indices, position_deltas, normal_deltas): the vertices the target moves, strictly ascending, and count x 3 deltas; an
+        empty index array is an empty target.  None removes the targets, of either kind.  vertex_count: the scene's (default: that
+        of the last scene_upload).  The arrays are copied; every weight is 0 afterwards; morph_set serves these targets too."""
+        if targets is None:
+            self._check(self._L.swr_scene_morph_sparse(self._h, None))
+            return
+        keep, recs = [], (MorphSparseTarget * max(1, len(targets)))()
+        for k, t in enumerate(targets):
+            idx = np.ascontiguousarray(t[0], dtype=np.uint32).reshape(-1)
+            dp = np.ascontiguousarray(t[1], dtype=np.float32).reshape(-1, 3)
+            dn = np.ascontiguousarray(t[2], dtype=np.float32).reshape(-1, 3) if len(t) > 2 and t[2] is not None else None
+            if dp.shape[0] != idx.size or (dn is not None and dn.shape[0] != idx.size):
+                raise ValueError(f"target {k}: {idx.size} indices, {dp.shape[0]} position deltas"
+                                 + (f", {dn.shape[0]} normal deltas" if dn is not None else ""))
+            keep.append((idx, dp, dn))
+            recs[k] = MorphSparseTarget(idx.ctypes.data if idx.size else None, dp.ctypes.data if idx.size else None,
+                                        dn.ctypes.data if dn is not None and idx.size else None, idx.size)
+        nv = self._scene_vertices if vertex_count is None else int(vertex_count)
+        s = MorphSparse(recs, nv, len(targets), 0)
+        self._check(self._L.swr_scene_morph_sparse(self._h, ctypes.byref(s)))
+
+    def morph_pose_set(self, weights: "np.ndarray | None", joints: "np.ndarray | None", dq: bool = False):
+        """swr_morph_pose_set: morph_set(weights), then pose_set(joints) — dq: pose_set_dq(joints) — as one call: every argument of
+        both is checked before anything changes, and the scene is rewritten once.  None means what it means in the two calls."""
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        j = None if joints is None else np.ascontiguousarray(joints, dtype=np.float32).reshape(-1, 8 if dq else 16)
+        self._check(self._L.swr_morph_pose_set(self._h, w.ctypes.data if w is not None else None, w.shape[0] if w is not None else 0,
+                                               j.ctypes.data if j is not None else None, j.shape[0] if j is not None else 0,
+                                               POSE_DUAL_QUATS if dq else POSE_MATRICES))
 
     def material_set(self, material: "Material | None"):
         self._check(self._L.swr_material_set(self._h, ctypes.byref(material) if material is not None else None))
@@ -951,6 +1031,7 @@ class Context:
             S = int(resolve.factor)      # the target is the supersampled one: read_ids delivers S * width x S * height words
         self.width, self.height, self.row_begin, self.row_end = S * width, S * height, 0, S * height     # (swr_render sets the target: read_ids)
         self._scene_prims, self._last_list = i.size // 3, None
+        self._scene_vertices = v.shape[0]
         return color, depth
 
 

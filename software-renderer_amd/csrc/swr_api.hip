@@ -175,7 +175,8 @@ struct Worker {
 static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && sizeof(swr_vertex_attr) == 32 &&
               sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16 &&
               sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32 && sizeof(swr_depth_box) == 32 && sizeof(swr_delta_stats) == 48 &&
-              sizeof(swr_skin_vertex) == 32 && sizeof(swr_morph_targets) == 32 && sizeof(swr_item_bound) == 48,
+              sizeof(swr_skin_vertex) == 32 && sizeof(swr_morph_targets) == 32 && sizeof(swr_item_bound) == 48 &&
+              sizeof(swr_morph_sparse_target) == 32 && sizeof(swr_morph_sparse) == 24,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -254,6 +255,13 @@ struct swr_context {
     bool morph_active = false;          // some weight is not zero
     std::vector<float> morph_w;         // morph_targets weights
     std::vector<MorphEntry> morph_list;
+    // sparse morph targets (swr_scene_morph_sparse): the other kind of resident targets.  The rows over the touched
+    // vertices as swr_internal.h lays them out (entries of positions in morph_dpos, of normals in morph_dnrm) and the weight table on
+    // the device.  While they are resident `morphed` (and, with normal deltas and attributes, `morphed_attrs`) hold the base arrays
+    // wherever no target reaches: the pre-fill of single_scene_morph_sparse and single_scene_attributes
+    DevBuf morph_touched, morph_row, morph_w_dev;
+    bool morph_sparse = false;          // the resident targets are sparse ones
+    int64_t morph_touched_count = 0;    // rows (0: every target is empty, nothing is ever launched)
 
     // target band (RenderPass.colorBuffer / .depthBuffer), double-buffered in HBM: swr_present copies the frame just
     // drawn to the host while the next swr_draw renders into the other buffer
@@ -1507,16 +1515,33 @@ int copy_band(swr_context* c, int fb, int img, const void* src_band, size_t row,
 // ---- single-device implementations of the entry points ----------------------------------------------------------
 int check_frames(swr_context* c);
 int enqueue_present(swr_context* c, void* color_full, float* depth_full);
+int prefill_sparse(swr_context* c, bool positions, bool attrs);
 
-// Skinned meshes and morph targets (DESIGN.md §23, §24).  Enqueue on c->stream (every stream idle) what puts the triangle stream —
-// positions, the normals when with_nrm, the group boxes — into the context's shape: the morph when a weight is not zero, then the pose
+// Skinned meshes and morph targets (DESIGN.md §23, §24, §28).  Enqueue on c->stream (every stream idle) what puts the triangle stream —
+// positions, the normals when with_nrm, the group boxes — into the context's shape: the morph (of sparse or of dense targets, whichever
+// kind is resident) when a weight is not zero, then the pose
 // reading the morphed arrays, then the stream from whichever array is last.  With neither, back to what the upload built, bit for bit.
 int enqueue_pose(swr_context* c, bool with_nrm) {
     const int64_t ntri = c->ni / 3;
     int rc;
     const swr_vertex* v = (const swr_vertex*)c->vertices.p;
     const swr_vertex_attr* at = with_nrm ? (const swr_vertex_attr*)c->attrs.p : nullptr;
-    if (c->morph_active) {
+    if (c->morph_active && c->morph_sparse) {
+        // sparse targets: the touched vertices are rewritten from the base; everywhere else the morphed arrays hold the pre-fill
+        const bool mnrm = with_nrm && c->morph_has_nrm;
+        if (c->morph_touched_count > 0) {
+            HIP_TRY(c, hipMemcpyAsync(c->morph_w_dev.p, c->morph_w.data(), c->morph_w.size() * 4, hipMemcpyHostToDevice, c->stream));
+            MorphSparseArgs a{};
+            a.vertices = v; a.attrs = mnrm ? at : nullptr;
+            a.touched = (const uint32_t*)c->morph_touched.p; a.row = (const int64_t*)c->morph_row.p;
+            a.dpos = (const MorphSparseEntry*)c->morph_dpos.p; a.dnrm = mnrm ? (const MorphSparseEntry*)c->morph_dnrm.p : nullptr;
+            a.weights = (const float*)c->morph_w_dev.p; a.touched_count = c->morph_touched_count; a.targets = c->morph_targets;
+            a.morphed = (swr_vertex*)c->morphed.p; a.morphed_attrs = mnrm ? (swr_vertex_attr*)c->morphed_attrs.p : nullptr;
+            launch_morph_sparse(a, c->stream);
+        }
+        v = (const swr_vertex*)c->morphed.p;
+        if (mnrm) at = (const swr_vertex_attr*)c->morphed_attrs.p;
+    } else if (c->morph_active) {
         const bool mnrm = with_nrm && c->morph_has_nrm;         // (else the normals stay as uploaded)
         c->morph_list.clear();
         for (int32_t t = 0; t < c->morph_targets; t++)
@@ -1556,10 +1581,14 @@ int enqueue_pose(swr_context* c, bool with_nrm) {
     return SWR_OK;
 }
 
-// swr_scene_morph(NULL), a new scene: no targets, no weights; the delta planes go back to the device
+// swr_scene_morph(NULL), a new scene: no targets of either kind, no weights; the delta planes and the rows go back to the device
 void drop_morph(swr_context* c) {
     (void)c->morph_dpos.reset();
     (void)c->morph_dnrm.reset();
+    (void)c->morph_touched.reset();
+    (void)c->morph_row.reset();
+    c->morph_sparse = false;
+    c->morph_touched_count = 0;
     c->morph_targets = 0;
     c->morph_has_nrm = false;
     c->morph_active = false;
@@ -1710,6 +1739,7 @@ int single_scene_attributes(swr_context* c, const swr_vertex_attr* attributes, i
     launch_gather_attrs((const swr_vertex_attr*)c->attrs.p, vertex_count, (const int64_t*)c->indices.p, c->ni / 3,
                         (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
     HIP_TRY(c, hipGetLastError());
+    if ((rc = prefill_sparse(c, false, true))) return rc;       // (sparse normal deltas given earlier take effect on these attributes)
     // (the gather wrote the uploaded normals: morph and pose them)
     if ((c->pose_active || c->morph_active) && (rc = enqueue_pose(c, true))) return rc;
     if ((rc = wait_stream(c, c->stream, "attribute upload"))) return or_sticky(c, rc);
@@ -1752,9 +1782,8 @@ int single_scene_skin(swr_context* c, const swr_skin_vertex* skin, int64_t verte
 // swr_pose_set, swr_pose_set_dq (dq): the resident scene in the pose `joints` (NULL with joint_count 0: the bind pose), in effect when
 // the call returns.  One pose state: the pose in effect is that of the last call of either kind, joint_count x 16 floats of matrices
 // or, dq, joint_count x 8 floats of dual quaternions.
-int single_pose_set(swr_context* c, const float* joints, int32_t joint_count, bool dq) {
-    const char* fn = dq ? "swr_pose_set_dq" : "swr_pose_set";
-    if (const int f = sticky(c)) return f;
+// (check_pose / take_pose: the checks and the host state of the call, shared with swr_morph_pose_set, whose name `fn` is then)
+int check_pose(swr_context* c, const char* fn, const float* joints, int32_t joint_count, bool dq) {
     if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "%s needs swr_scene_upload first", fn);
     if (!c->has_skin) return fail(c, SWR_ERR_BAD_ARG, "%s needs swr_scene_skin first", fn);
     if (joint_count < 0) return fail(c, SWR_ERR_BAD_ARG, "%s: joint_count %d", fn, joint_count);
@@ -1762,17 +1791,27 @@ int single_pose_set(swr_context* c, const float* joints, int32_t joint_count, bo
         return fail(c, SWR_ERR_UNSUPPORTED, "%s: %d joints (at most %d)", fn, joint_count, SWR_SKIN_MAX_JOINTS);
     if (!joints && joint_count > 0)
         return fail(c, SWR_ERR_BAD_ARG, "%s: %d joints without %s", fn, joint_count, dq ? "dual quaternions" : "matrices");
-    const bool bind = !joints;
-    if (!bind && (int64_t)joint_count <= c->skin_max_joint)
+    if (joints && (int64_t)joint_count <= c->skin_max_joint)
         return fail(c, SWR_ERR_BAD_ARG, "%s: %d joints, but the skin uses joint index %lld", fn, joint_count,
                     (long long)c->skin_max_joint);
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the pose it was drawn in)
-    if (bind && !c->pose_active) return SWR_OK;
+    return SWR_OK;
+}
+// the pose becomes the context's; whether the stream has to be rewritten for it
+bool take_pose(swr_context* c, const float* joints, int32_t joint_count, bool dq) {
+    const bool bind = !joints;
+    if (bind && !c->pose_active) return false;
     c->pose_active = !bind;
     c->pose_dq = !bind && dq;
     if (bind) c->pose.clear(); else c->pose.assign(joints, joints + (size_t)joint_count * (dq ? 8 : 16));
+    return true;
+}
+int single_pose_set(swr_context* c, const float* joints, int32_t joint_count, bool dq) {
+    if (const int f = sticky(c)) return f;
+    int rc;
+    if ((rc = check_pose(c, dq ? "swr_pose_set_dq" : "swr_pose_set", joints, joint_count, dq))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the pose it was drawn in)
+    if (!take_pose(c, joints, joint_count, dq)) return SWR_OK;
     if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
     if ((rc = wait_stream(c, c->stream, "pose"))) return or_sticky(c, rc);
     return SWR_OK;
@@ -1802,6 +1841,24 @@ int upload_deltas(swr_context* c, void* dst, const float* src, size_t count /* t
             }
         else memcpy(st, src + 3 * at, n * 12);
         HIP_TRY(c, hipMemcpyAsync((uint8_t*)dst + at * F * 4, st, n * F * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipEventRecord(c->stage_ev[0][k & 1], c->stream));
+    }
+    return SWR_OK;
+}
+
+// A table of the sparse targets (entries, touched vertices, rows: built on the host, so never page-locked) into `dst` on c->stream,
+// through the same staging chunks under the same rule: `chunks` counts the chunks staged since the stream was last idle, the tables
+// of one call share it, and a chunk is written again only once the copy that last read it has ended.
+int upload_staged(swr_context* c, void* dst, const void* src, size_t bytes, size_t& chunks) {
+    if (!bytes) return SWR_OK;
+    int rc = ensure_stage(c, 0);
+    if (rc) return rc;
+    const size_t per = swr_context::STAGE_BYTES;
+    for (size_t at = 0; at < bytes; at += per) {
+        const size_t n = std::min(per, bytes - at), k = chunks++;
+        if (k >= 2 && (rc = poll_event(c, c->stage_ev[0][k & 1], "a staged copy of sparse morph targets", c->frame_no))) return rc;
+        memcpy(c->stage[0][k & 1].p, (const uint8_t*)src + at, n);
+        HIP_TRY(c, hipMemcpyAsync((uint8_t*)dst + at, c->stage[0][k & 1].p, n, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipEventRecord(c->stage_ev[0][k & 1], c->stream));
     }
     return SWR_OK;
@@ -1856,24 +1913,187 @@ int single_scene_morph(swr_context* c, const swr_morph_targets* t) {
     return SWR_OK;
 }
 
-// swr_morph_set: the resident scene under `weights` (NULL with weight_count 0: every weight 0), in effect when the call returns.
-int single_morph_set(swr_context* c, const float* weights, int32_t weight_count) {
+// hipMemcpyDeviceToDevice (the fake runtime the host test programs compile this file against names only the two host directions)
+constexpr hipMemcpyKind COPY_ON_DEVICE = (hipMemcpyKind)3;
+#ifdef __HIPCC__
+static_assert(COPY_ON_DEVICE == hipMemcpyDeviceToDevice, "the copy kind of prefill_sparse");
+#endif
+
+// Sparse targets: the morphed arrays start as copies of the base arrays, made on the device, so that k_morph_sparse
+// has the touched vertices to write and nothing else.  positions: when the targets are installed; attrs: then too, and again when
+// swr_scene_attributes replaces the base attributes (only where normal deltas were given).  On c->stream.
+int prefill_sparse(swr_context* c, bool positions, bool attrs) {
+    if (!c->morph_sparse || c->nv == 0) return SWR_OK;
+    int rc;
+    if (positions) {
+        if ((rc = ensure(c, c->morphed, (size_t)c->nv * sizeof(swr_vertex)))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->morphed.p, c->vertices.p, (size_t)c->nv * sizeof(swr_vertex), COPY_ON_DEVICE, c->stream));
+    }
+    if (attrs && c->morph_has_nrm) {
+        if ((rc = ensure(c, c->morphed_attrs, (size_t)c->nv * sizeof(swr_vertex_attr)))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->morphed_attrs.p, c->attrs.p, (size_t)c->nv * sizeof(swr_vertex_attr), COPY_ON_DEVICE, c->stream));
+    }
+    return SWR_OK;
+}
+
+// a device buffer of its own for new targets: the resident ones stay until the new are filled (a failure frees what it got)
+int alloc_targets(swr_context* c, DevBuf& b, size_t bytes) {
+    bytes = std::max<size_t>(16, bytes);
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        return fail(c, SWR_ERR_NOMEM, "swr_scene_morph_sparse: hipMalloc(%zu) for the targets failed: %s", bytes, hipGetErrorString(e));
+    }
+    b.bytes = bytes;
+    return SWR_OK;
+}
+
+// swr_scene_morph_sparse: sparse morph targets of the resident scene (targets == NULL: none, of either kind).  Every weight is 0
+// afterwards; skin and pose stay.  The rows are built here, on the host, by a counting sort over the vertices: O(vertices + entries).
+int single_scene_morph_sparse(swr_context* c, const swr_morph_sparse* t) {
+    if (!t) return single_scene_morph(c, nullptr);
+    const char* fn = "swr_scene_morph_sparse";
     if (const int f = sticky(c)) return f;
-    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "swr_morph_set needs swr_scene_upload first");
-    if (!c->morph_targets) return fail(c, SWR_ERR_BAD_ARG, "swr_morph_set needs swr_scene_morph first");
-    if (weights ? weight_count != c->morph_targets : weight_count != 0)
-        return fail(c, SWR_ERR_BAD_ARG, "swr_morph_set: %d weights%s for %d targets", weight_count, weights ? "" : " without an array",
-                    c->morph_targets);
+    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "%s needs swr_scene_upload first", fn);
+    if (t->vertex_count != c->nv)
+        return fail(c, SWR_ERR_BAD_ARG, "%s: targets of %lld vertices for %lld vertices", fn, (long long)t->vertex_count, (long long)c->nv);
+    if (t->target_count < 1) return fail(c, SWR_ERR_BAD_ARG, "%s: target_count %d", fn, t->target_count);
+    if (t->reserved != 0) return fail(c, SWR_ERR_BAD_ARG, "%s: reserved must be 0", fn);
+    if (t->target_count > SWR_MORPH_MAX_TARGETS)
+        return fail(c, SWR_ERR_UNSUPPORTED, "%s: %d targets (at most %d)", fn, t->target_count, SWR_MORPH_MAX_TARGETS);
+    if (!t->targets) return fail(c, SWR_ERR_BAD_ARG, "%s: targets is NULL", fn);
+    const int32_t T = t->target_count;
+    const int64_t nv = c->nv;
+    int64_t entries = 0;
+    int with_nrm = -1;                          // of the non-empty targets: -1 none seen yet, else whether they give normal deltas
+    for (int32_t k = 0; k < T; k++) {
+        const swr_morph_sparse_target& g = t->targets[k];
+        if (g.count < 0 || g.count > nv) return fail(c, SWR_ERR_BAD_ARG, "%s: target %d lists %lld of %lld vertices", fn, k, (long long)g.count, (long long)nv);
+        if (g.count == 0) continue;
+        if (!g.indices || !g.position_deltas) return fail(c, SWR_ERR_BAD_ARG, "%s: target %d: %s is NULL", fn, k, g.indices ? "position_deltas" : "indices");
+        for (int64_t j = 0; j < g.count; j++) {
+            if (g.indices[j] >= (uint64_t)nv)
+                return fail(c, SWR_ERR_BAD_ARG, "%s: target %d, position %lld: index %u of %lld vertices", fn, k, (long long)j, g.indices[j], (long long)nv);
+            if (j && g.indices[j] <= g.indices[j - 1])
+                return fail(c, SWR_ERR_BAD_ARG, "%s: target %d, position %lld: index %u after %u is not ascending", fn, k, (long long)j,
+                            g.indices[j], g.indices[j - 1]);
+        }
+        const int has = g.normal_deltas ? 1 : 0;
+        if (with_nrm >= 0 && with_nrm != has) return fail(c, SWR_ERR_BAD_ARG, "%s: target %d: normal deltas on some targets only", fn, k);
+        with_nrm = has;
+        entries += g.count;
+    }
+    const bool nrm = with_nrm == 1;
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
     if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the shape it was drawn in)
+    // the rows: how many targets list each vertex -> the touched vertices, ascending, and their offsets -> the entries, target by
+    // target in ascending order, each appended to its vertex's row: every row comes out sorted by target
+    std::vector<uint32_t> slot((size_t)nv, 0);  // per vertex: its count, then its row
+    for (int32_t k = 0; k < T; k++)
+        for (int64_t j = 0; j < t->targets[k].count; j++) slot[t->targets[k].indices[j]]++;
+    std::vector<uint32_t> touched;
+    std::vector<int64_t> row(1, 0);
+    for (int64_t i = 0; i < nv; i++)
+        if (slot[(size_t)i]) {
+            row.push_back(row.back() + slot[(size_t)i]);
+            slot[(size_t)i] = (uint32_t)touched.size();
+            touched.push_back((uint32_t)i);
+        }
+    std::vector<int64_t> cursor(row.begin(), row.end() - 1);
+    std::vector<MorphSparseEntry> ep((size_t)entries), en(nrm ? (size_t)entries : 0);
+    for (int32_t k = 0; k < T; k++) {
+        const swr_morph_sparse_target& g = t->targets[k];
+        for (int64_t j = 0; j < g.count; j++) {
+            const size_t at = (size_t)cursor[slot[g.indices[j]]]++;
+            ep[at] = MorphSparseEntry{(uint32_t)k, g.position_deltas[3 * j], g.position_deltas[3 * j + 1], g.position_deltas[3 * j + 2]};
+            if (nrm) en[at] = MorphSparseEntry{(uint32_t)k, g.normal_deltas[3 * j], g.normal_deltas[3 * j + 1], g.normal_deltas[3 * j + 2]};
+        }
+    }
+    DevBuf dpos, dnrm, dtouched, drow, dw, dmorphed, dattrs;
+    if ((rc = alloc_targets(c, dpos, ep.size() * sizeof(MorphSparseEntry)))) return rc;
+    if (nrm && (rc = alloc_targets(c, dnrm, en.size() * sizeof(MorphSparseEntry)))) return rc;
+    if ((rc = alloc_targets(c, dtouched, touched.size() * 4))) return rc;
+    if ((rc = alloc_targets(c, drow, row.size() * 8))) return rc;
+    if (!c->morph_w_dev.p && (rc = alloc_targets(c, dw, SWR_MORPH_MAX_TARGETS * 4))) return rc;
+    // (the morphed arrays are kept across targets; where they have to grow, the new ones are allocated before anything changes too)
+    if (c->morphed.bytes < (size_t)nv * sizeof(swr_vertex) && (rc = alloc_targets(c, dmorphed, (size_t)nv * sizeof(swr_vertex)))) return rc;
+    if (nrm && c->morphed_attrs.bytes < (size_t)nv * sizeof(swr_vertex_attr) &&
+        (rc = alloc_targets(c, dattrs, (size_t)nv * sizeof(swr_vertex_attr)))) return rc;
+    size_t chunks = 0;
+    if ((rc = upload_staged(c, dpos.p, ep.data(), ep.size() * sizeof(MorphSparseEntry), chunks))) return rc;
+    if ((rc = upload_staged(c, dnrm.p, en.data(), en.size() * sizeof(MorphSparseEntry), chunks))) return rc;
+    if ((rc = upload_staged(c, dtouched.p, touched.data(), touched.size() * 4, chunks))) return rc;
+    if ((rc = upload_staged(c, drow.p, row.data(), row.size() * 8, chunks))) return rc;
+    if ((rc = wait_stream(c, c->stream, "sparse morph target upload"))) return or_sticky(c, rc);
+    const bool was_active = c->morph_active;
+    drop_morph(c);
+    c->morph_dpos = std::move(dpos); c->morph_dnrm = std::move(dnrm);
+    c->morph_touched = std::move(dtouched); c->morph_row = std::move(drow);
+    if (dw.p) c->morph_w_dev = std::move(dw);
+    if (dmorphed.p) c->morphed = std::move(dmorphed);
+    if (dattrs.p) c->morphed_attrs = std::move(dattrs);
+    c->morph_sparse = true;
+    c->morph_touched_count = (int64_t)touched.size();
+    c->morph_targets = T;
+    c->morph_has_nrm = nrm;
+    c->morph_w.assign((size_t)T, 0.0f);
+    if ((rc = prefill_sparse(c, true, c->has_attrs))) return rc;
+    // (was_active: every weight is 0 now: the unmorphed scene, in the pose it has)
+    if (was_active && (rc = enqueue_pose(c, c->has_attrs))) return rc;
+    if ((rc = wait_stream(c, c->stream, "sparse morph targets"))) return or_sticky(c, rc);
+    return SWR_OK;
+}
+
+// swr_morph_set: the resident scene under `weights` (NULL with weight_count 0: every weight 0), in effect when the call returns.
+// (check_weights / take_weights: the checks and the host state of the call, shared with swr_morph_pose_set, whose name `fn` is then)
+int check_weights(swr_context* c, const char* fn, const float* weights, int32_t weight_count) {
+    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "%s needs swr_scene_upload first", fn);
+    if (!c->morph_targets) return fail(c, SWR_ERR_BAD_ARG, "%s needs swr_scene_morph first", fn);
+    if (weights ? weight_count != c->morph_targets : weight_count != 0)
+        return fail(c, SWR_ERR_BAD_ARG, "%s: %d weights%s for %d targets", fn, weight_count, weights ? "" : " without an array",
+                    c->morph_targets);
+    return SWR_OK;
+}
+// the weights become the context's; whether the stream has to be rewritten for them
+bool take_weights(swr_context* c, const float* weights, int32_t weight_count) {
     bool any = false;
     for (int32_t k = 0; weights && k < weight_count; k++) any = any || weights[k] != 0.0f;
     if (weights) c->morph_w.assign(weights, weights + weight_count); else c->morph_w.assign((size_t)c->morph_targets, 0.0f);
-    if (!any && !c->morph_active) return SWR_OK;
+    if (!any && !c->morph_active) return false;
     c->morph_active = any;
+    return true;
+}
+int single_morph_set(swr_context* c, const float* weights, int32_t weight_count) {
+    if (const int f = sticky(c)) return f;
+    int rc;
+    if ((rc = check_weights(c, "swr_morph_set", weights, weight_count))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the shape it was drawn in)
+    if (!take_weights(c, weights, weight_count)) return SWR_OK;
     if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
     if ((rc = wait_stream(c, c->stream, "morph"))) return or_sticky(c, rc);
+    return SWR_OK;
+}
+
+// swr_morph_pose_set: swr_morph_set, then swr_pose_set (pose_kind SWR_POSE_MATRICES) or swr_pose_set_dq (SWR_POSE_DUAL_QUATS), with
+// every check of both made before either half changes anything, and one rewrite of the scene: one check_frames, one enqueue_pose,
+// one wait.
+int single_morph_pose_set(swr_context* c, const float* weights, int32_t weight_count, const float* joints, int32_t joint_count,
+                          int32_t pose_kind) {
+    const char* fn = "swr_morph_pose_set";
+    if (const int f = sticky(c)) return f;
+    if (pose_kind != SWR_POSE_MATRICES && pose_kind != SWR_POSE_DUAL_QUATS) return fail(c, SWR_ERR_BAD_ARG, "%s: unknown pose_kind %d", fn, pose_kind);
+    const bool dq = pose_kind == SWR_POSE_DUAL_QUATS;
+    int rc;
+    if ((rc = check_weights(c, fn, weights, weight_count))) return rc;
+    if ((rc = check_pose(c, fn, joints, joint_count, dq))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn in the shape and pose it was drawn in)
+    const bool morphed = take_weights(c, weights, weight_count), posed = take_pose(c, joints, joint_count, dq);
+    if (!morphed && !posed) return SWR_OK;
+    if ((rc = enqueue_pose(c, c->has_attrs))) return rc;
+    if ((rc = wait_stream(c, c->stream, "morph and pose"))) return or_sticky(c, rc);
     return SWR_OK;
 }
 
@@ -3012,6 +3232,19 @@ int swr_morph_set(swr_context* c, const float* weights, int32_t weight_count) {
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // (the same)
     return fan(c, [=](swr_context* k) { return single_morph_set(k, weights, weight_count); });
+}
+
+int swr_scene_morph_sparse(swr_context* c, const swr_morph_sparse* targets) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    c->scene_id = 0;      // (the same)
+    return fan(c, [=](swr_context* k) { return single_scene_morph_sparse(k, targets); });
+}
+
+int swr_morph_pose_set(swr_context* c, const float* weights, int32_t weight_count, const float* joints, int32_t joint_count,
+                       int32_t pose_kind) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    c->scene_id = 0;      // (the same)
+    return fan(c, [=](swr_context* k) { return single_morph_pose_set(k, weights, weight_count, joints, joint_count, pose_kind); });
 }
 
 int swr_material_set(swr_context* c, const swr_material* m) {

@@ -335,4 +335,36 @@ void launch_item_bounds(const ItemBoundsArgs& a, hipStream_t s);
 void launch_skin_vertices_dq(const swr_vertex* vertices, const swr_vertex_attr* attrs, const swr_skin_vertex* skin, int64_t nv,
                              const float* dual_quats, int32_t joint_count, swr_vertex* posed, float4* posed_nrm, hipStream_t s);
 
+// swr_morph_sparse.hip: sparse morph targets.  The targets live on the device as vertex-major rows over the TOUCHED
+// vertices, the union of the targets' index lists: touched[r] is the vertex of row r, ascending; row[r] .. row[r + 1] are its entries
+// in dpos (and, in step, dnrm), sorted by target.  weights holds one weight per resident target (`targets` of them, at most
+// SWR_MORPH_MAX_TARGETS).  launch_morph_sparse writes, for every touched vertex i, the xyz and padding lanes of morphed[i] = those of
+// vertices[i] with p = p + weight * delta applied per row entry whose weight is not zero, in row order (include/swr.h "Sparse morph
+// targets"), and, attrs != NULL (then dnrm != NULL), the normal and padding lanes of morphed_attrs[i] from attrs[i] through the same
+// loop over dnrm.  Nothing else is written: the host pre-fills morphed and morphed_attrs with the base arrays, so the colour and uv
+// lanes and every untouched vertex are already there.  touched_count >= 1; every entry's target is below `targets` and every touched
+// vertex below the scene's vertex count (the host built the rows).  All pointers are device memory.
+struct MorphSparseEntry { uint32_t target; float dx, dy, dz; };
+static_assert(sizeof(MorphSparseEntry) == 16, "one 16-byte load per entry");
+struct MorphSparseArgs {
+    const swr_vertex* vertices;
+    const swr_vertex_attr* attrs;
+    const uint32_t* touched;           // [touched_count]
+    const int64_t* row;                // [touched_count + 1]
+    const MorphSparseEntry* dpos;      // [row[touched_count]]
+    const MorphSparseEntry* dnrm;      // the same shape, or NULL
+    const float* weights;              // [targets]
+    int64_t touched_count;
+    int32_t targets;
+    swr_vertex* morphed;
+    swr_vertex_attr* morphed_attrs;
+};
+#if defined(__HIPCC__) || defined(SWR_HOST_TEST_MORPH_SPARSE)
+void launch_morph_sparse(const MorphSparseArgs& a, hipStream_t s);
+#else
+// (host test programs built without SWR_HOST_TEST_MORPH_SPARSE link a launch set that predates this launch and never call
+// swr_scene_morph_sparse: nothing is enqueued.  The product is always compiled by hipcc and references the launch plainly.)
+inline void launch_morph_sparse(const MorphSparseArgs&, hipStream_t) {}
+#endif
+
 }  // namespace swr

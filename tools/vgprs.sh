@@ -1,12 +1,12 @@
 #!/bin/bash
 # Register use of every raster (k_raster_blend and k_blend_order included), binning and setup kernel, of the depth-clip pre-pass and of
-# the supersampled resolve, of the visibility counts, of the depth queries, of the delta reads, of the skinning kernels, of the morph kernel, of the item bounds and of the dual-quaternion skinning kernel, for a set of -D flags:
+# the supersampled resolve, of the visibility counts, of the depth queries, of the delta reads, of the skinning kernels, of the morph kernel, of the item bounds, of the dual-quaternion skinning kernel and of the sparse morph kernel, for a set of -D flags:
 # "SGPRs Spill" is the compiler's count of scalar registers parked in lanes of a VGPR (v_writelane / v_readlane code, no scratch): the
 # raster kernels of the headline and of its colour variant have none.
 # tools/vgprs.sh [-DSWR_...]   (run from anywhere; compiles swr_kernels.hip, swr_clip.hip, swr_resolve.hip, swr_count.hip,
-# swr_depth_query.hip, swr_delta.hip, swr_skin.hip, swr_morph.hip, swr_item_bounds.hip and swr_skin_dq.hip)
+# swr_depth_query.hip, swr_delta.hip, swr_skin.hip, swr_morph.hip, swr_item_bounds.hip, swr_skin_dq.hip and swr_morph_sparse.hip)
 cd "$(dirname "$0")/../software-renderer_amd"
-for src in csrc/swr_kernels.hip csrc/swr_clip.hip csrc/swr_resolve.hip csrc/swr_count.hip csrc/swr_depth_query.hip csrc/swr_delta.hip csrc/swr_skin.hip csrc/swr_morph.hip csrc/swr_item_bounds.hip csrc/swr_skin_dq.hip; do
+for src in csrc/swr_kernels.hip csrc/swr_clip.hip csrc/swr_resolve.hip csrc/swr_count.hip csrc/swr_depth_query.hip csrc/swr_delta.hip csrc/swr_skin.hip csrc/swr_morph.hip csrc/swr_item_bounds.hip csrc/swr_skin_dq.hip csrc/swr_morph_sparse.hip; do
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -fhip-fp32-correctly-rounded-divide-sqrt \
   -fno-fast-math -w "$@" -Rpass-analysis=kernel-resource-usage -c -o /tmp/vgprs_$$.o $src 2>&1 | python3 -c '
 import re, sys
