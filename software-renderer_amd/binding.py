@@ -658,14 +658,15 @@ class Context:
         s = MorphSparse(recs, nv, len(targets), 0)
         self._check(self._L.swr_scene_morph_sparse(self._h, ctypes.byref(s)))
 
-    def morph_pose_set(self, weights: "np.ndarray | None", joints: "np.ndarray | None", dq: bool = False):
+    def morph_pose_set(self, weights: "np.ndarray | None", joints: "np.ndarray | None", dq: bool = False, pose_kind: "int | None" = None):
         """swr_morph_pose_set: morph_set(weights), then pose_set(joints) — dq: pose_set_dq(joints) — as one call: every argument of
-        both is checked before anything changes, and the scene is rewritten once.  None means what it means in the two calls."""
+        both is checked before anything changes, and the scene is rewritten once.  None means what it means in the two calls.
+        pose_kind: the SWR_POSE_* value to pass as it is (default: the one `dq` names)."""
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
         j = None if joints is None else np.ascontiguousarray(joints, dtype=np.float32).reshape(-1, 8 if dq else 16)
         self._check(self._L.swr_morph_pose_set(self._h, w.ctypes.data if w is not None else None, w.shape[0] if w is not None else 0,
                                                j.ctypes.data if j is not None else None, j.shape[0] if j is not None else 0,
-                                               POSE_DUAL_QUATS if dq else POSE_MATRICES))
+                                               (POSE_DUAL_QUATS if dq else POSE_MATRICES) if pose_kind is None else int(pose_kind)))
 
     def material_set(self, material: "Material | None"):
         self._check(self._L.swr_material_set(self._h, ctypes.byref(material) if material is not None else None))

@@ -1,12 +1,13 @@
 """The context as include/swr.h describes it, in NumPy: what one swr_context holds between calls — the scene, its attributes, skin,
-pose (matrices or dual quaternions), morph targets and weights, the material, the target, the last frame's image, whether its IDs
+pose (matrices or dual quaternions), morph targets (dense or sparse: one morph state of two kinds) and weights, the material, the target, the last frame's image, whether its IDs
 are readable, and the delta baselines — and what every observer must answer from that state.  Written from the header's lifetime
 and completion paragraphs, not from swr_api.hip.  A plain helper module of tests/test_state_sequences.py (GPU) and
 tests/test_state_model.py (CPU): not a conftest, not a test file.
 
 Nothing is rasterised here.  The model composes the per-feature models the suite already has:
 
-  shape      tests/morph_model.py (morph first), then tests/skin_model.py or tests/skin_dq_model.py (the pose in effect);
+  shape      tests/morph_model.py or, for sparse targets, tests/morph_sparse_model.py (morph first), then tests/skin_model.py or
+             tests/skin_dq_model.py (the pose in effect);
   frames     tests/frame_model.py `expect` over the shape's vertices and attributes ("every frame, read and query after the call is
              bit for bit that of a context on which swr_scene_upload was given the morphed-then-posed vertices"); a SWR_FLAG_LOAD
              frame starts from the model's own previous image;
@@ -28,6 +29,7 @@ import delta_model as DM
 import frame_model as FM
 import item_bounds_model as IB
 import morph_model as MM
+import morph_sparse_model as MS
 import skin_dq_model as DQ
 import skin_model as SM
 
@@ -38,6 +40,8 @@ DELTA_COLOR, DELTA_DEPTH = 1, 2
 ID_NONE = 0xFFFFFFFF
 TRI, LINE, VERTICES = 0, 1, 2
 TILE_W, TILE_H = 64, 32
+MORPH_MAX_TARGETS = 256                                     # SWR_MORPH_MAX_TARGETS
+DENSE, SPARSE = "dense", "sparse"
 
 
 class Refused(Exception):
@@ -84,7 +88,9 @@ class State:
         self.attrs = None
         self.skin = None                                    # (joint, weight, digest)
         self.pose_kind, self.pose, self.pose_id = None, None, None
-        self.targets = None                                 # (position deltas, normal deltas or None, digest)
+        # one morph state of two kinds ("Sparse morph targets": the targets in effect are those of the last call of either entry)
+        self.targets = None                                 # dense: (position deltas, normal deltas or None, digest);
+        self.kind = None                                    # sparse: ([(indices, position deltas[, normal deltas])], normals?, digest)
         self.weights, self.weights_id = None, None
         self.material = None                                # a scenes.Shading (its attrs are not looked at) or None
         self.size = None
@@ -101,7 +107,7 @@ class State:
         self.v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 8)
         self.i = np.ascontiguousarray(i, dtype=np.int64).reshape(-1)
         self.scene = digest(self.v, self.i)
-        self.attrs = self.skin = self.targets = None
+        self.attrs = self.skin = self.targets = self.kind = None
         self.pose_kind = self.pose = self.pose_id = None
         self.weights = self.weights_id = None
         self.ids_ok = False
@@ -144,19 +150,65 @@ class State:
         self.pose_kind, self.pose, self.pose_id = kind, t, digest(t)
 
     def set_targets(self, dp, dn=None):
-        """New targets — and none — set every weight to 0; skin and pose stay."""
+        """swr_scene_morph.  New targets — and none — set every weight to 0; skin and pose stay.  None removes whichever kind is
+        resident."""
         self._need_scene()
         if dp is None:
-            self.targets = None
+            self.targets = self.kind = None
         else:
             dp = np.ascontiguousarray(dp, dtype=np.float32)
             if dp.ndim != 3 or dp.shape[1] != self.v.shape[0]:
                 raise Refused(BAD_ARG, "target vertex count")
+            if dp.shape[0] > MORPH_MAX_TARGETS:
+                raise Refused(UNSUPPORTED, "more than SWR_MORPH_MAX_TARGETS targets")
             dn = None if dn is None else np.ascontiguousarray(dn, dtype=np.float32)
-            self.targets = (dp, dn, digest(dp, dn))
+            self.targets, self.kind = (dp, dn, digest(dp, dn)), DENSE
         self.weights = self.weights_id = None
 
+    def set_targets_sparse(self, targets, vertex_count=None):
+        """swr_scene_morph_sparse: targets is a list of (indices, position deltas[, normal deltas]) or None (which removes whichever
+        kind is resident); vertex_count: what the caller says the scene has (default: what it has).  Every check is made before
+        anything changes.  New targets set every weight to 0; skin and pose stay."""
+        self._need_scene()
+        if targets is None:
+            self.targets = self.kind = None
+            self.weights = self.weights_id = None
+            return
+        nv = self.v.shape[0]
+        if (nv if vertex_count is None else vertex_count) != nv:
+            raise Refused(BAD_ARG, "a vertex_count that does not match the scene")
+        if len(targets) < 1:
+            raise Refused(BAD_ARG, "target_count < 1")
+        if len(targets) > MORPH_MAX_TARGETS:
+            raise Refused(UNSUPPORTED, "more than SWR_MORPH_MAX_TARGETS targets")
+        kept, normals = [], set()
+        for k, t in enumerate(targets):
+            idx = np.ascontiguousarray(t[0], dtype=np.int64).reshape(-1)
+            dp = np.ascontiguousarray(t[1], dtype=np.float32).reshape(-1, 3)
+            dn = np.ascontiguousarray(t[2], dtype=np.float32).reshape(-1, 3) if len(t) > 2 and t[2] is not None else None
+            if idx.size > nv:
+                raise Refused(BAD_ARG, f"target {k}: count > vertex_count")
+            if idx.size == 0:
+                kept.append((idx.astype(np.uint32), dp))    # (an empty target: its pointers are not looked at)
+                continue
+            if idx.min() < 0 or idx.max() >= nv:
+                raise Refused(BAD_ARG, f"target {k}: an index >= vertex_count")
+            if not (np.diff(idx) > 0).all():
+                raise Refused(BAD_ARG, f"target {k}: indices not strictly ascending")
+            assert dp.shape[0] == idx.size and (dn is None or dn.shape[0] == idx.size), "the binding refuses these itself"
+            normals.add(dn is not None)
+            kept.append((idx.astype(np.uint32), dp) if dn is None else (idx.astype(np.uint32), dp, dn))
+        if len(normals) > 1:
+            raise Refused(BAD_ARG, "normal deltas on some non-empty targets only")
+        self.targets = (kept, normals == {True}, digest(*[x for t in kept for x in t]) + f"/{len(kept)}")
+        self.kind = SPARSE
+        self.weights = self.weights_id = None
+
+    def target_count(self):
+        return 0 if self.targets is None else len(self.targets[0]) if self.kind == SPARSE else self.targets[0].shape[0]
+
     def set_weights(self, w):
+        """swr_morph_set serves both kinds: one weight per target, the same errors."""
         self._need_scene()
         if self.targets is None:
             raise Refused(BAD_ARG, "no targets")
@@ -164,33 +216,60 @@ class State:
             self.weights = self.weights_id = None
             return
         w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
-        if w.shape[0] != self.targets[0].shape[0]:
+        if w.shape[0] != self.target_count():
             raise Refused(BAD_ARG, "weight count")
         if (w != np.float32(0)).any():
             self.weights, self.weights_id = w, digest(w)
         else:
             self.weights = self.weights_id = None           # (+0 and -0: bit for bit what the upload built)
 
+    def morph_pose(self, weights, kind, table):
+        """swr_morph_pose_set: set_weights, then set_pose (kind "mat": SWR_POSE_MATRICES, "dq": SWR_POSE_DUAL_QUATS), with every check
+        of both halves made before either changes anything: a refusal leaves the weights and the pose as they were.  It needs
+        targets (of either kind) and a skin."""
+        self._need_scene()
+        if kind not in ("mat", "dq"):
+            raise Refused(BAD_ARG, "an unknown pose_kind")
+        held = (self.weights, self.weights_id, self.pose_kind, self.pose, self.pose_id)
+        try:
+            self.set_weights(weights)
+            self.set_pose(kind, table)
+        except Refused:
+            self.weights, self.weights_id, self.pose_kind, self.pose, self.pose_id = held
+            raise
+
     def set_material(self, shading):
         self.material = shading if shading is not None and shading.shader else None
 
     # ---- the shape the frames draw ------------------------------------------------------------------------------------------------
     def shape_key(self):
-        morph = (self.targets[2], self.weights_id) if self.weights is not None else None
+        morph = (self.kind, self.targets[2], self.weights_id) if self.weights is not None else None
         pose = (self.skin[2], self.pose_kind, self.pose_id) if self.pose is not None else None
         attrs = None if self.attrs is None else digest(self.attrs)
         return (self.scene, attrs, morph, pose)
+
+    def morphed(self):
+        """(vertices, attributes or None) under the weights, before the pose.  Sparse targets take the loop of "Sparse morph
+        targets" — a vertex a target does not list is not touched by it, which the dense target with zero rows does not say — and
+        move normals only when their non-empty targets carry normal deltas."""
+        v, a = self.v, self.attrs
+        if self.weights is not None and self.kind == SPARSE:
+            lists, normals, _ = self.targets
+            v = MS.morph_vertices(v, lists, self.weights)
+            if a is not None and normals:
+                a = MS.morph_attrs(a, lists, self.weights)
+        elif self.weights is not None:
+            dp, dn, _ = self.targets
+            v = MM.morph_vertices(v, dp, self.weights)
+            if a is not None:
+                a = MM.morph_attrs(a, dn, self.weights)
+        return v, a
 
     def shape(self):
         """(vertices, attributes or None, id) of the resident scene as it is now: morphed, then posed."""
         key = self.shape_key()
         if key not in self.shapes:
-            v, a = self.v, self.attrs
-            if self.weights is not None:
-                dp, dn, _ = self.targets
-                v = MM.morph_vertices(v, dp, self.weights)
-                if a is not None:
-                    a = MM.morph_attrs(a, dn, self.weights)
+            v, a = self.morphed()
             if self.pose is not None:
                 P = SM if self.pose_kind == "mat" else DQ
                 j, w, _ = self.skin

@@ -471,6 +471,37 @@ def test_dense_and_sparse_targets_replace_each_other(swr, oracle, case):
         ctx.scene_morph_sparse(None)
         against(base, grab(ctx, DT), DT, "dense targets removed by swr_scene_morph_sparse(NULL)")
         assert code_of(swr, lambda: ctx.morph_set(MM.WEIGHTS_A))[0] == BAD_ARG
+    # A second pass with the rig without the lift.  Its union is 461 of the 768 vertices, so the 307 others come from the pre-fill
+    # alone: above, the lift lists every vertex, and a pre-fill that is missing or stale changes nothing.  The set in front moves
+    # every vertex each time (weights B lift the whole torus), dense or sparse.
+    T6 = [t for k, t in enumerate(case.T) if k != MS.LIFT]
+    w6a, w6b = np.delete(WA, MS.LIFT), np.delete(WB, MS.LIFT)
+    outside = np.setdiff1d(np.arange(768), MS.touched(T6))
+    dense_b = MM.morph_vertices(case.v, d, MM.WEIGHTS_B)
+    assert outside.size == 307 and (dense_b[outside, 0:3] != case.v[outside, 0:3]).any(axis=1).all()
+    assert (case.vB[outside, 0:3] != case.v[outside, 0:3]).any(axis=1).all()
+    dB = K.expected_frame(oracle, dense_b, case.i, IDENT, W, H, DT)
+    with resident(swr, case.v, case.i) as ctx:
+        ctx.scene_morph(d)
+        ctx.morph_set(MM.WEIGHTS_B)
+        against(dB, grab(ctx, DT), DT, "dense, every vertex moved")
+        ctx.scene_morph_sparse(T6)
+        against(base, grab(ctx, DT), DT, "the partial union over active dense targets: every weight 0")
+        ctx.morph_set(w6b)
+        against(want(oracle, case, w6b, T=T6), grab(ctx, DT), DT, "the partial union: outside it nothing of the dense morph is left")
+        ctx.scene_morph(d)
+        ctx.morph_set(MM.WEIGHTS_B)
+        against(dB, grab(ctx, DT), DT, "dense again")
+        ctx.scene_morph_sparse(T6)
+        ctx.morph_set(w6a)
+        against(want(oracle, case, w6a, T=T6), grab(ctx, DT), DT, "the partial union again, other weights")
+        ctx.scene_morph_sparse(case.T)                  # one sparse set after another, with another union
+        ctx.morph_set(WB)
+        against(want(oracle, case, WB), grab(ctx, DT), DT, "the seven targets: every vertex lifted")
+        ctx.scene_morph_sparse(T6)
+        against(base, grab(ctx, DT), DT, "the partial union over an active sparse set: every weight 0")
+        ctx.morph_set(w6b)
+        against(want(oracle, case, w6b, T=T6), grab(ctx, DT), DT, "the partial union: outside it nothing of the lift is left")
 
 
 # ---- 10: errors -----------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 """On the CPU: what the sequences of tests/test_state_sequences.py cover, that they are not vacuous, and that its player has teeth
 (DESIGN.md §17).  The generator is pure Python; the model runs on the C oracle; the player is run against `StandInContext`, an
 implementation of the binding's Context on top of tests/state_model.py with a table of switchable defects of the kind the sequences
-are about.  Nothing here needs a GPU."""
+are about.  Both families of seeds are covered: 41-43 (dense targets) as they were, and 44-46 (sparse targets of partial unions,
+swr_morph_pose_set, two attribute arrays) with their world, their enlarged pair table, their three scripted parts and ten defects of
+their own.  Nothing here needs a GPU."""
 import hashlib
 import re
 import time
@@ -12,6 +14,9 @@ import pytest
 
 import delta_model as DM
 import frame_model as FM
+import morph_model as MM
+import morph_sparse_model as MS
+import skin_dq_model as DQ
 import state_model as ST
 import test_depth_query as TD
 import test_frame_sequences as FS
@@ -19,6 +24,8 @@ import test_state_sequences as SS
 from frame_model import CLIP, IDS, LOAD, NC
 
 S_OPS, O_OPS = SS.S_OPS, SS.O_OPS
+ALL_SEEDS = SS.STATE_SEEDS + SS.SPARSE_SEEDS
+FAMILIES = {"dense": SS.STATE_SEEDS, "sparse": SS.SPARSE_SEEDS}
 
 
 # ---- a context on the CPU -------------------------------------------------------------------------------------------------------------
@@ -52,6 +59,50 @@ DEFECTS = {
     "overflow_repair_in_new_shape": "an overflowed last frame is redrawn in the shape a following swr_morph_set / swr_pose_set sets",
     "present_copies_late": "swr_present copies what the framebuffer holds at swr_present_wait",
 }
+# defects of the state the second family is about: caught on the scripted parts of seed 44
+SPARSE_DEFECTS = {
+    "prefill_skipped_after_dense": "sparse targets installed over active dense ones: vertices outside the union keep the dense morph",
+    "prefill_skipped_between_sparse_sets": "a sparse set installed over an active one: vertices of the old union outside the new keep their morph",
+    "uv_stale_after_replaced_attrs": "a second swr_scene_attributes under sparse normal deltas: every vertex keeps the first array's colour/uv quad",
+    "normals_morphed_without_normal_deltas": "a set without normal deltas after one with them still reads the morphed normals of the set before",
+    "sparse_played_as_dense": "sparse targets are morphed as dense targets with zero rows: a NaN weight reaches vertices its target does not list",
+    "null_of_other_entry_keeps_targets": "NULL through the entry of the kind that is not resident removes nothing",
+    "weights_survive_new_targets_of_other_kind": "targets of the other kind keep the weights of the targets they replace",
+    "combined_call_takes_weights_before_pose_error": "swr_morph_pose_set takes the weights, then refuses the joints",
+    "combined_call_ignores_pose_kind": "swr_morph_pose_set blends dual quaternions as the matrices of their rigid motions",
+    "combined_call_repairs_overflow_in_new_shape": "an overflowed last frame is redrawn in the shape and pose a following swr_morph_pose_set sets",
+}
+
+
+class SpoiltState(ST.State):
+    """tests/state_model.py with what a defect leaves behind in the morphed arrays.  `residue`: (name, fn) — fn rewrites the
+    (vertices, attributes) between the morph and the pose while a weight is not zero (with every weight zero the stream is built
+    from the base arrays, and nothing stale is read).  `as_dense`: sparse targets are morphed as dense ones with zero rows."""
+    residue = None
+    as_dense = False
+
+    def upload(self, v, i):
+        super().upload(v, i)
+        self.residue = None
+
+    def shape_key(self):
+        key = super().shape_key()
+        if self.weights is None:
+            return key
+        return key + ((self.residue[0],) if self.residue is not None else ()) + (("as dense",) if self.as_dense and self.kind == ST.SPARSE else ())
+
+    def morphed(self):
+        v, a = super().morphed()
+        if self.weights is None:
+            return v, a
+        if self.as_dense and self.kind == ST.SPARSE:
+            lists, normals, _ = self.targets
+            v = MM.morph_vertices(self.v, MS.dense(lists, self.v.shape[0]), self.weights)
+            if self.attrs is not None and normals:
+                a = MM.morph_attrs(self.attrs, MS.dense(lists, self.v.shape[0], which=2), self.weights)
+        if self.residue is not None:
+            v, a = self.residue[1](np.array(v, copy=True), None if a is None else np.array(a, copy=True))
+        return v, a
 
 
 class StandInContext:
@@ -60,7 +111,8 @@ class StandInContext:
     defect = None
 
     def __init__(self, device=0, device_count=0, **kw):
-        self.S = ST.State(self.oracle, SS._CACHE, SS._SHAPES)
+        self.S = SpoiltState(self.oracle, SS._CACHE, SS._SHAPES)
+        self.S.as_dense = self.defect == "sparse_played_as_dense"
         self.nbands = max(1, device_count)
         self.order = 1
         self.cuts = set()
@@ -104,10 +156,19 @@ class StandInContext:
 
     def scene_attributes(self, attrs):
         self._blocking()
-        self._run(self.S.attributes, attrs)
-        if self.defect == "normal_deltas_ignored_by_late_attrs" and self.S.targets is not None:
-            dp = self.S.targets[0]
-            self.S.targets = (dp, None, ST.digest(dp, None))
+        S = self.S
+        old = S.attrs
+        self._run(S.attributes, attrs)
+        if self.defect == "normal_deltas_ignored_by_late_attrs" and S.kind == ST.DENSE:
+            dp = S.targets[0]
+            S.targets = (dp, None, ST.digest(dp, None))
+        elif self.defect == "normal_deltas_ignored_by_late_attrs" and S.kind == ST.SPARSE:
+            S.targets = ([t[:2] for t in S.targets[0]], False, S.targets[2] + " without normals")
+        if self.defect == "uv_stale_after_replaced_attrs" and old is not None and S.kind == ST.SPARSE and S.targets[1]:
+            def stale(v, a):
+                a[:, 4:8] = old[:, 4:8]
+                return v, a
+            S.residue = ("stale uv " + ST.digest(old), stale)
 
     def texture_upload(self, texture):
         self._blocking()
@@ -135,16 +196,63 @@ class StandInContext:
     def pose_set_dq(self, dq):
         self._overflow_defect(lambda: self._pose("dq", dq))
 
+    def _install(self, entry, fn):
+        """New targets — or none — through swr_scene_morph (entry "dense") or swr_scene_morph_sparse ("sparse")."""
+        S, d = self.S, self.defect
+        was, weights = S.kind, S.weights
+        if d == "null_of_other_entry_keeps_targets" and was is not None and was != entry and S.targets is not None and fn is None:
+            return
+        old_v, old_a = S.morphed() if weights is not None else (None, None)
+        had_normals = was == ST.SPARSE and S.targets[1]
+        self._run(*(fn or ((S.set_targets, None) if entry == ST.DENSE else (S.set_targets_sparse, None))))
+        S.residue = None
+        if S.kind == ST.SPARSE and old_v is not None:
+            outside = np.ones(S.v.shape[0], dtype=bool)
+            outside[SS.union_of(S.targets[0])] = False
+            if (d, was) in (("prefill_skipped_after_dense", ST.DENSE), ("prefill_skipped_between_sparse_sets", ST.SPARSE)):
+                def stale(v, a):
+                    v[outside] = old_v[outside]
+                    return v, a
+                S.residue = ("no pre-fill " + ST.digest(old_v), stale)
+            if d == "normals_morphed_without_normal_deltas" and had_normals and not S.targets[1] and old_a is not None:
+                def stale_normals(v, a):
+                    if a is not None:
+                        a[:, 0:3] = old_a[:, 0:3]
+                    return v, a
+                S.residue = ("stale normals " + ST.digest(old_a), stale_normals)
+        if d == "weights_survive_new_targets_of_other_kind" and weights is not None and S.kind not in (None, was):
+            w = np.zeros(S.target_count(), dtype=np.float32)
+            n = min(w.size, weights.size)
+            w[:n] = weights[:n]
+            S.set_weights(w)
+
     def scene_morph(self, dp, dn=None):
-        self._overflow_defect(lambda: self._run(self.S.set_targets, dp, dn))
+        self._overflow_defect(lambda: self._install(ST.DENSE, None if dp is None else (self.S.set_targets, dp, dn)))
+
+    def scene_morph_sparse(self, targets, vertex_count=None):
+        self._overflow_defect(lambda: self._install(ST.SPARSE, None if targets is None else (self.S.set_targets_sparse, targets, vertex_count)))
 
     def morph_set(self, w):
         self._overflow_defect(lambda: self._run(self.S.set_weights, w))
 
-    def _overflow_defect(self, change):
+    def morph_pose_set(self, weights, joints, dq=False, pose_kind=None):
+        S, d = self.S, self.defect
+
+        def change():
+            kind, table = ("dq" if dq else "mat") if pose_kind is None else {0: "mat", 1: "dq"}.get(pose_kind, "neither"), joints
+            if d == "combined_call_ignores_pose_kind" and kind == "dq" and table is not None:
+                kind, table = "mat", DQ.matrices_of(table)
+            if d == "combined_call_takes_weights_before_pose_error":
+                self._run(S.set_weights, weights)
+                self._run(S.set_pose, kind, table)
+            else:
+                self._run(S.morph_pose, weights, kind, table)
+        self._overflow_defect(change, "combined_call_repairs_overflow_in_new_shape")
+
+    def _overflow_defect(self, change, defect="overflow_repair_in_new_shape"):
         """A blocking change of shape: an overflowed last frame is repaired in the shape it was posted in — or, the defect, in the new one."""
         redo = None
-        if self.defect == "overflow_repair_in_new_shape" and self.unwaited and self.last_call is not None:
+        if self.defect == defect and self.unwaited and self.last_call is not None:
             flags, transform, items, kind, start = self.last_call
             v, _, _ = self.S.shape()
             tris = self.S.i.reshape(-1, 3)
@@ -356,7 +464,7 @@ def stand_in(oracle, defect=None):
 # ---- 1. the generator -------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def sequences():
-    return {seed: SS.sequence(seed) for seed in SS.STATE_SEEDS}
+    return {seed: SS.sequence(seed) for seed in ALL_SEEDS}
 
 
 _FRAME_FIELDS = ("n", "scene", "size", "shader", "kind", "flags", "via", "tf", "shape", "scene_id", "write", "overflow", "items")
@@ -372,15 +480,22 @@ def canonical(ops):
 DIGESTS = {41: "838ec2cec4393516e7282ea6e7c433e665994e7893c1037342b0865b07f90412",
            42: "f3c3c516e569a2bb5a8e4eeffd5086dccaa34d7047ca67dbdf74e39ec4152335",
            43: "dfdeabd678e2596996737cb011c8b5309bf2f6ab91285e03f22066cfbc466864"}
+# ... and of seeds 44, 45, 46, the second family, as it made them when that family was added
+DIGESTS.update({44: "a2820265d385933388d2817592c80587ae73bd4438014e5b068969a8ceb554f4", 45: "34527b3e093178e6a66e200adc166aa5926d33e2186ab714cd7527220fac2def", 46: "0c820b15fcd5c65d8eb65f4c90ce71051d136bbc45e5957decb0259e96c7376d"})
 
 
 def test_sequences_are_reproducible_and_pinned(sequences):
-    assert set(DIGESTS) == set(SS.STATE_SEEDS)
+    assert set(DIGESTS) == set(ALL_SEEDS) and not any(SS.sparse_family(s) for s in SS.STATE_SEEDS) and all(map(SS.sparse_family, SS.SPARSE_SEEDS))
     for seed, ops in sequences.items():
         assert canonical(ops) == canonical(SS.sequence(seed)), seed
         assert hashlib.sha256(canonical(ops).encode()).hexdigest() == DIGESTS[seed], seed
-    assert len({SS.hooks_of(seed) for seed in sequences}) == 3
-    assert {dict(SS.hooks_of(seed))[SS.K.DEBUG_STREAM_ORDER] for seed in sequences} == {1, 0, -1}
+    for seeds in FAMILIES.values():
+        assert len({SS.hooks_of(seed) for seed in seeds}) == 3
+        assert [dict(SS.hooks_of(seed))[SS.K.DEBUG_STREAM_ORDER] for seed in seeds] == list(SS.STREAM_ORDERS) == [1, 0, -1]
+    # the first family knows nothing of the second: no sparse set, no combined call, one attribute array
+    for seed in SS.STATE_SEEDS:
+        assert not any(o[0] == "morph_pose" or o[:2] == ("attrs", "other") or (o[0] == "targets" and (isinstance(o[1], str) or len(o) > 2))
+                       for o in sequences[seed]), seed
 
 
 def test_the_operations_and_the_scenes(sequences):
@@ -397,8 +512,44 @@ def test_the_operations_and_the_scenes(sequences):
     # the non-finite target of the torus only ever gets weight +-0
     assert not np.isfinite(W["torus"].targets[0][0][SS.MM.NONFINITE]).any()
     assert all(w[SS.MM.NONFINITE] == 0 for w in W["torus"].weights[0].values()) and np.signbit(W["torus"].weights[0][1][SS.MM.NONFINITE])
+    # the sparse sets and the second attribute array of the second family
+    big_ragged = 0
+    for name, s in W.items():
+        n, s0, s1 = nv[name], s.sparse["s0"], s.sparse["s1"]
+        U0, U1 = SS.union_of(s0), SS.union_of(s1)
+        for U in (U0, U1):
+            assert 1 <= U.size <= n - 1, name
+            big_ragged += U.size > 256 and U.size % 64 != 0
+        assert set(U0) - set(U1) and set(U1) - set(U0) and set(U0) & set(U1), "the unions differ, neither contains the other"
+        assert 0 in U0 and 0 not in U1 and n - 1 in U1 and n - 1 not in U0, "the first and the last vertex: each in one union only"
+        assert all(len(t) == 3 for t in s0 if t[0].size) and all(len(t) == 2 for t in s1), "normal deltas in one set only"
+        assert s0[SS.S0_EMPTY][0].size == 0 and not np.isfinite(s0[SS.S0_NONFINITE][1]).any() and s0[SS.S0_NONFINITE][0].size > 10
+        assert all(w[SS.S0_NONFINITE] == 0 for w in s.weights["s0"].values()) and np.signbit(s.weights["s0"][1][SS.S0_NONFINITE])
+        assert np.isnan(s.weights["s0"][1][SS.S0_EMPTY]), "an empty target at NaN: a zero ROW at NaN would poison every vertex"
+        counts = [len(s0), len(s1), s.targets[0][0].shape[0], s.targets[1][0].shape[0]]
+        assert len(set(counts)) == 4 and counts[:2] == [SS.S0_TARGETS, SS.S1_TARGETS], (name, counts)
+        assert all(len(w) == 2 and all(x.shape == (len(s.sparse[k]),) for x in w.values()) for k, w in s.weights.items() if isinstance(k, str))
+        for t in s0 + s1:                                   # what swr_scene_morph_sparse asks of a list
+            assert t[0].dtype == np.uint32 and (np.diff(t[0].astype(np.int64)) > 0).all() and (t[0].size == 0 or t[0][-1] < n)
+        # every finite delta moves something, and the sets are no dense targets in disguise
+        assert all(np.abs(t[1]).max() > 0.01 for t in s0 + s1 if t[0].size and np.isfinite(t[1]).all())
+        assert all(t[0].size < U.size for ts, U in ((s0, U0), (s1, U1)) for t in ts), "no target lists its set's whole union"
+        assert s.attrs2.shape == s.attrs.shape and (s.attrs2[:, 0:3] != s.attrs[:, 0:3]).any(axis=1).all()
+        assert (s.attrs2[:, 4:6] != s.attrs[:, 4:6]).any(axis=1).all() and np.array_equal(s.attrs2[:, [3, 6, 7]], s.attrs[:, [3, 6, 7]])
+    assert big_ragged >= 1, "two workgroups and a partial last wave"
+    xyz = W["torus"].v[:, 0:3]
+    minus0 = {int(k) for k in np.argwhere((xyz == 0) & np.signbit(xyz))[:, 0]}
+    assert minus0 == {k for k, _ in SS.NEGATIVE_ZERO["torus"]}
+    for key in ("s0", "s1"):
+        assert minus0 - set(SS.union_of(W["torus"].sparse[key])), f"a vertex outside the union of {key} has a -0 coordinate"
     for seed, ops in sequences.items():
         names = {o[0] for o in ops}
+        if seed in SS.SPARSE_SEEDS:
+            assert names >= {"morph_pose"} and {o[1] for o in ops if o[0] == "attrs"} == {True, "other"}, seed
+            assert {o[1] for o in ops if o[0] == "targets"} >= {0, 1, "s0", "s1", None}, seed
+            assert {SS.none_entry(o, 0) for o in ops if o[0] == "targets" and o[1] is None and len(o) > 2} == {"dense", "sparse"}, seed
+            assert {o[1:] for o in ops if o[0] == "morph_pose"} >= {(0, "dq", 0), (1, "mat", 0), (0, "mat", 0)}, seed
+            assert {(o[1] is None, o[3] is None) for o in ops if o[0] == "morph_pose"} >= {(False, False), (True, False), (False, True)}, seed
         assert names >= {"upload", "target", "attrs", "material", "skin", "pose", "targets", "weights", "write", "frame", "render", "render_delta",
                          "present", "wait", "read", "read_ids", "read_resolved", "count", "query", "bounds", "delta", "delta_reset", "feed",
                          "refused"}, seed
@@ -425,6 +576,11 @@ def test_the_operations_and_the_scenes(sequences):
     assert refusals >= {("count_no_ids", -1), ("count_item_no_ids", -1), ("read_ids_no_ids", -1), ("count_wrong_n", -1), ("pose_few_joints", -1),
                         ("pose_no_skin", -1), ("weights_wrong_count", -1), ("weights_no_targets", -1), ("bounds_clip", -5),
                         ("render_delta_load", -5)}
+    for seed in SS.SPARSE_SEEDS:                            # every refusal of the second family in every one of its sequences
+        mine = [o[1:] for o in sequences[seed] if o[0] == "refused"]
+        assert set(mine) >= {("morph_pose_wrong_count", -1), ("morph_pose_few_joints", -1), ("morph_pose_bad_kind", -1), ("morph_pose_no_skin", -1),
+                             ("morph_pose_no_targets", -1), ("sparse_wrong_vertex_count", -1), ("sparse_descending", -1),
+                             ("sparse_some_normals", -1), ("sparse_too_many", -5)}, seed
     rows = [f.row() for ops in sequences.values() for f in SS.checked_frames(ops)]
     for factor, values in FM.FACTORS.items():
         assert {r[factor] for r in rows} == set(values), factor
@@ -437,6 +593,10 @@ def test_the_tables_of_pairs():
     assert not set(SS.ILLEGAL) & set(SS.UNSPECIFIED)
     assert len(S_OPS) == 21 and len(O_OPS) == 11
     assert sum(SS.legal(s, o) for s in S_OPS for o in O_OPS) == 21 * 11 - len(SS.ILLEGAL) - len(SS.UNSPECIFIED) == 198
+    # the second family: six more state changes, none of which makes IDs unreadable or the image unspecified
+    assert SS.S_OPS_SPARSE[:21] == S_OPS and len(SS.S_OPS_SPARSE) == 27 == len(set(SS.S_OPS_SPARSE))
+    assert SS.s_ops(41) == S_OPS and SS.s_ops(44) == SS.s_ops(200) == SS.S_OPS_SPARSE
+    assert sum(SS.legal(s, o) for s in SS.S_OPS_SPARSE for o in O_OPS) == 198 + 6 * 11
 
 
 def played_pairs(sequences):
@@ -458,8 +618,15 @@ def played_pairs(sequences):
 
 
 def test_every_legal_pair_is_played_and_no_other(sequences):
+    """Each family plays every legal pair over its own table across its own three seeds."""
+    for family, seeds in FAMILIES.items():
+        every_legal_pair({seed: sequences[seed] for seed in seeds}, SS.s_ops(seeds[0]), {"dense": 198, "sparse": 264}[family])
+
+
+def every_legal_pair(sequences, s_ops, n):
     so, oo, refused = played_pairs(sequences)
-    want = {(s, o) for s in S_OPS for o in O_OPS if SS.legal(s, o)}
+    want = {(s, o) for s in s_ops for o in O_OPS if SS.legal(s, o)}
+    assert len(want) == n
     assert not want - so, sorted(want - so)
     assert not so & set(SS.ILLEGAL), sorted(so & set(SS.ILLEGAL))
     assert not so & set(SS.UNSPECIFIED), sorted(so & set(SS.UNSPECIFIED))
@@ -539,15 +706,24 @@ def test_the_six_rebuild_callers_and_the_bind_entries(sequences):
         assert binds >= {("bind_mat", "mat"), ("bind_mat", "dq"), ("bind_dq", "mat"), ("bind_dq", "dq")}, seed
 
 
+NEW_PARTS = ["morph kinds", "refusals", "late and replaced attributes"]
+
+
 def test_the_scripted_parts(sequences):
+    for family, seeds in FAMILIES.items():
+        the_scripted_parts({seed: sequences[seed] for seed in seeds}, family == "sparse")
+
+
+def the_scripted_parts(sequences, sparse):
     firsts, hows = set(), set()
     for seed, ops in sequences.items():
         assert [o[1] for o in ops if o[0] == "part"] == ["rebuild tour", "pose kinds", "un-waited", "overflow", "lifetimes", "baselines",
-                                                          "bounds feed", "pairs", "random"]
+                                                          "bounds feed"] + (NEW_PARTS if sparse else []) + ["pairs", "random"]
         # un-waited: presented frames, a change of shape with no wait in front, a frame, the wait
         u = part_of(ops, "un-waited")
-        k = next(j for j, o in enumerate(u) if o[0] in ("weights", "pose") and u[j - 1][0] == "present" and u[j - 2][0] == "frame")
-        hows.add(u[k][0] if u[k][0] == "weights" else u[k][1])
+        k = next(j for j, o in enumerate(u) if o[0] in ("weights", "pose", "morph_pose") and u[j - 1][0] == "present" and u[j - 2][0] == "frame")
+        assert (u[k][0] == "morph_pose") == sparse, seed
+        hows.add(u[k][0] if u[k][0] == "weights" else u[k][1:] if sparse else u[k][1])
         before = [o[1] for o in u[:k] if o[0] == "frame"]
         assert len(before) >= 2 and "wait" not in [o[0] for o in u[k - 2 * len(before):k]]
         assert u[k + 1][0] in ("frame", "material") and SS.normal_shape(before[-1].shape) != SS.normal_shape(
@@ -557,7 +733,11 @@ def test_the_scripted_parts(sequences):
         for j, o in enumerate(ov):
             if o[0] == "frame" and o[1].overflow:
                 firsts.add(ov[j + 1][0])
-                assert ov[j + 1][0] in ("count", "query", "delta", "bounds", "weights") and ov[j + 2][0] == "read", (seed, ov[j + 1:j + 3])
+                assert ov[j + 1][0] in ("count", "query", "delta", "bounds", "morph_pose" if sparse else "weights") and ov[j + 2][0] == "read", \
+                    (seed, ov[j + 1:j + 3])
+                if ov[j + 1][0] == "morph_pose":            # weights AND pose change behind the overflowed frame
+                    f = ov[j][1]
+                    assert ov[j + 1][1] != f.shape[5] and ov[j + 1][1:] == (1, "mat", 0) and f.shape[3] == ("mat", "crowd"), seed
         assert sum(1 for o in ops if o[0] == "frame" and o[1].overflow) == 5
         # lifetimes
         lt = part_of(ops, "lifetimes")
@@ -572,7 +752,65 @@ def test_the_scripted_parts(sequences):
         assert set(bl[a + 1:b]) >= {"frame", "query", "bounds", "count", "present", "wait", "read", "read_resolved"}
         w = bl.index("write")
         assert w > b and bl[w + 1] == "delta" and "delta_reset" in bl and bl.count("render_delta") == 3 and bl.count("target") >= 4
-    assert firsts == {"count", "query", "delta", "bounds", "weights"} and hows == {"weights", "mat", "dq"}
+        if sparse:
+            the_new_parts(seed, ops)
+    if sparse:      # the combined call as the blocking change: both halves, NULL joints, NULL weights
+        assert firsts == {"count", "query", "delta", "bounds", "morph_pose"} and hows == {(0, "dq", 0), (0, "mat", None), (None, "mat", 0)}
+    else:
+        assert firsts == {"count", "query", "delta", "bounds", "weights"} and hows == {"weights", "mat", "dq"}
+
+
+def the_new_parts(seed, ops):
+    """'morph kinds', 'refusals' and 'late and replaced attributes' of the second family, step by step."""
+    def steps(part, attrs=False):
+        """[(the state changes since the last frame, the frame, read back?, the observers behind it)]; attrs: attribute uploads count
+        (elsewhere a material brings them along when it needs them)"""
+        out, changes = [], []
+        for op in part:
+            if op[0] == "frame":
+                out.append([changes, op[1], False, []])
+                changes = []
+            elif op[0] == "read" and out and not changes:
+                out[-1][2] = True
+            elif op[0] in ("count", "query", "bounds", "delta") and out and not changes:
+                out[-1][3].append(op[0])
+            elif op[0] in ("targets", "weights", "morph_pose", "skin", "pose", "upload", "refused") or (attrs and op[0] == "attrs"):
+                changes.append(op)
+        return out
+
+    assert SS.PRIMARY[(seed - 41) % 3] in ("torus", "big") and SS.SCENES[SS.PRIMARY[(seed - 41) % 3]] > SS.FIRST_BIN_GUESS, "it can crowd a tile"
+    mk = steps(part_of(ops, "morph kinds"))
+    assert all(read and f.scene == SS.PRIMARY[(seed - 41) % 3] and f.shape[3] in (("mat", 0), ("dq", 0), None) for _, f, read, _ in mk), seed
+    none = ("refused", "weights_no_targets", -1)
+    assert [c for c, _, _, _ in mk] == [
+        [("targets", 0), ("weights", 0)],                                       # 1
+        [("targets", "s0")],                                                    # 2
+        [("weights", 0)],                                                       # 3
+        [("morph_pose", 0, "dq", 0)], [("morph_pose", None, "dq", 0)], [("morph_pose", 0, "mat", None)], [("morph_pose", 0, "mat", 0)],
+        [("targets", "s1")], [("weights", 0)],                                  # 4
+        [("targets", 1)],                                                       # 5
+        [("targets", "s0"), ("weights", 1)],                                    # 6
+        [("targets", None, "dense"), none],                                     # 7
+        [("targets", 0), ("weights", 0)], [("targets", None, "sparse"), none]], seed
+    # the frame behind a new set is the base; the frame under weights is the set's
+    assert [(f.shape[4], f.shape[5]) for _, f, _, _ in mk] == [(0, 0), ("s0", None), ("s0", 0), ("s0", 0), ("s0", None), ("s0", 0), ("s0", 0), ("s1", None), ("s1", 0), (1, None),
+                                                               ("s0", 1), (None, None), (0, 0), (None, None)], seed
+    assert {o for _, _, _, obs in mk for o in obs} == {"count", "query", "bounds", "delta"} and all(f.flags & IDS for _, f, _, _ in mk), seed
+    rf = steps(part_of(ops, "refusals"))
+    calls = [c[1] for ch, _, _, _ in rf for c in ch if c[0] == "refused"]
+    assert calls == ["morph_pose_no_targets", "morph_pose_wrong_count", "morph_pose_few_joints", "morph_pose_bad_kind", "sparse_wrong_vertex_count",
+                     "sparse_descending", "sparse_some_normals", "sparse_too_many", "morph_pose_no_skin"], seed
+    assert all(read and ch[-1][0] == "refused" for ch, _, read, _ in rf), "a frame, read back, right behind every refusal"
+    # late and replaced attributes: twice, the second time under a pose
+    la = steps(part_of(ops, "late and replaced attributes"), attrs=True)
+    assert len(la) == 8 and all(read and f.shader == 2 and not f.flags & NC for _, f, read, _ in la), seed
+    for k, posed in enumerate((False, True)):
+        a, b, c, d = la[4 * k:4 * k + 4]
+        head = [o[:2] for o in a[0]]
+        assert head[0] == ("upload", SS.PRIMARY[(seed - 41) % 3]) and head.index(("targets", "s0")) < head.index(("attrs", True)) < head.index(("weights", 0))
+        assert (("pose", "mat") in head) == posed and all((f.shape[3] is not None) == posed for _, f, _, _ in (a, b, c, d)), seed
+        assert b[0] == [("attrs", "other")] and b[1].shape[5] == 0 and (a[1].shape[1], b[1].shape[1]) == (True, "other"), seed
+        assert c[0][0] == ("targets", "s1") and (c[1].shape[5] == 0) == posed and d[0] == [("targets", "s0"), ("weights", 0)], seed
 
 
 # ---- 3. not vacuous: from the model, with the C oracle ----------------------------------------------------------------------------------
@@ -594,6 +832,8 @@ def test_the_sequences_are_not_vacuous(oracle, sequences, played):
     depth_of = {}
     for seed, st in played.items():
         assert st["checked"] >= 100 and st["refused"] >= 15, seed
+        if seed in SS.SPARSE_SEEDS:
+            the_new_parts_are_not_vacuous(oracle, seed, sequences[seed], st, by_id, depth_of)
         # consecutive shapes differ in at least 1 % of the pixels of a frame (z-tested, 320 x 192, the scene's affine matrix)
         pairs = {(a, b, scene) for (a, scene), (b, scene_b) in zip(st["shapes"], st["shapes"][1:]) if a != b and scene == scene_b}
         assert len(pairs) >= 15, seed
@@ -625,6 +865,61 @@ def test_the_sequences_are_not_vacuous(oracle, sequences, played):
     assert any(q[3] for st in played.values() for q in st["queries"]), "a query on the cleared image right after swr_target_set"
 
 
+MORPH_KINDS_MIN = 0.01     # of the pixels of a 320 x 192 frame: what consecutive frames of "morph kinds" differ in, at the least
+
+
+def the_new_parts_are_not_vacuous(oracle, seed, ops, st, by_id, depth_of):
+    W = SS.world()
+    scene = SS.PRIMARY[(seed - 41) % 3]
+    D = W[scene]
+    a, b = st["parts"]["morph kinds"], st["parts"]["refusals"]
+    sids = [sid for (sid, sc), k in zip(st["shapes"], st["frame_ops"]) if a < k < b]
+    assert len(sids) == 14 and all(sc == scene for (sid, sc), k in zip(st["shapes"], st["frame_ops"]) if a < k < b)
+
+    def depth(sid):
+        if sid not in depth_of:
+            depth_of[sid] = SS.K.oracle_clear(oracle, by_id[sid], D.i, D.tf["aff"], 320, 192, FM.DT | NC)[1]
+        return depth_of[sid]
+
+    # every consecutive pair of checked frames of "morph kinds" differs (z-tested, 320 x 192, the scene's affine matrix)
+    for x, y in zip(sids, sids[1:]):
+        differ = (depth(x).view(np.uint32) != depth(y).view(np.uint32)).mean()
+        assert differ >= MORPH_KINDS_MIN, (seed, x, y, differ)
+    # every sparse set, without a pose: the frame differs from the base where triangles with a vertex of the union are visible —
+    # before or after the morph — and nowhere else, and some of the scene is visible elsewhere
+    tris = D.i.reshape(-1, 3)
+    base = SS.K.expected_frame(oracle, D.v, D.i, D.tf["aff"], 320, 192, FM.DT | IDS)
+    for key in ("s0", "s1"):
+        U = SS.union_of(D.sparse[key])
+        mine = np.isin(tris, U).any(axis=1)
+        for wid, w in D.weights[key].items():
+            mv = MS.morph_vertices(D.v, D.sparse[key], w)
+            outside = np.setdiff1d(np.arange(D.v.shape[0]), U)
+            assert mv[outside].tobytes() == D.v[outside].tobytes() and (mv[U, 0:3] != D.v[U, 0:3]).any(axis=1).all(), (seed, key, wid)
+            got = SS.K.expected_frame(oracle, mv, D.i, D.tf["aff"], 320, 192, FM.DT | IDS)
+            inside = np.zeros(base.ids.shape, dtype=bool)
+            for ids in (base.ids, got.ids):
+                hit = ids != FM.NONE
+                inside[hit] |= mine[ids[hit]]
+            changed = (got.depth.view(np.uint32) != base.depth.view(np.uint32)) | (got.ids != base.ids)
+            assert changed[inside].sum() >= MORPH_KINDS_MIN * changed.size, (seed, key, wid, int(changed[inside].sum()))
+            assert not changed[~inside].any(), (seed, key, wid, int(changed[~inside].sum()))
+            assert (np.isfinite(base.depth) & ~inside).sum() >= MORPH_KINDS_MIN * changed.size, (seed, key, wid)
+    # the textured frames of "late and replaced attributes" show the second array: its frame differs from the first array's
+    a = st["parts"]["late and replaced attributes"]
+    late = [sid for (sid, sc), k in zip(st["shapes"], st["frame_ops"]) if a < k < st["parts"]["pairs"]]
+    attrs = {sid: x for v, x, sid in SS._SHAPES.values()}
+    assert len(late) == 8 and all(attrs[sid] is not None for sid in late)
+    for k in (0, 4):
+        one, two = attrs[late[k]], attrs[late[k + 1]]
+        assert by_id[late[k]].tobytes() == by_id[late[k + 1]].tobytes() and (one[:, 4:6] != two[:, 4:6]).any(axis=1).all(), seed
+        assert (one[:, 0:3] != two[:, 0:3]).any(axis=1).all(), seed
+        # the set without normal deltas leaves the uploaded normals, the one with them moves every normal of its union
+        U = SS.union_of(D.sparse["s0"])
+        moved = (attrs[late[k + 3]][:, 0:3] != attrs[late[k + 2]][:, 0:3]).any(axis=1)
+        assert moved[U].all(), seed
+
+
 def test_burst_frames_stay_below_the_bin_guess_and_the_overflow_frame_does_not(oracle, sequences):
     """A frame that is not the last of its un-waited run and overflowed its bins would be reported as dropped: every frame but the
     overflow frames stays below the first guess of a tile region in the shape it is drawn in, by the bounding boxes of the deformed
@@ -653,11 +948,18 @@ def tour():
     return SS.sequence(SS.STATE_SEEDS[0], steps=0, pairs=False)      # the scripted parts (stream order 1: the cuts are real)
 
 
-def test_the_scripted_tour_passes_on_the_stand_in(oracle, tour):
-    assert dict(SS.hooks_of(SS.STATE_SEEDS[0]))[SS.K.DEBUG_STREAM_ORDER] == 1
+@pytest.fixture(scope="module")
+def sparse_tour():
+    return SS.sequence(SS.SPARSE_SEEDS[0], steps=0, pairs=False)     # the scripted parts of the second family (stream order 1 too)
+
+
+def test_the_scripted_tour_passes_on_the_stand_in(oracle, tour, sparse_tour):
+    assert dict(SS.hooks_of(SS.STATE_SEEDS[0]))[SS.K.DEBUG_STREAM_ORDER] == 1 == dict(SS.hooks_of(SS.SPARSE_SEEDS[0]))[SS.K.DEBUG_STREAM_ORDER]
     for bands in (1, 3):
         st = SS.play(stand_in(oracle), oracle, tour, bands)
         assert st["checked"] >= 35 and len(st["deltas"]) >= 20 and st["refused"] >= 15
+        st = SS.play(stand_in(oracle), oracle, sparse_tour, bands)
+        assert st["checked"] >= 35 + 14 + 9 + 8 and len(st["deltas"]) >= 20 + 6 and st["refused"] >= 15 + 9 + 2
 
 
 # which part of the tour must catch which defect (profiles/state_sequences/mutations.txt records the operation)
@@ -675,6 +977,19 @@ CAUGHT_IN = {
     "overflow_repair_in_new_shape": "overflow",
     "present_copies_late": "un-waited",
 }
+# ... and which part of the second family's tour (profiles/sparse_sequences/mutations.txt)
+SPARSE_CAUGHT_IN = {
+    "prefill_skipped_after_dense": "morph kinds",
+    "prefill_skipped_between_sparse_sets": "morph kinds",
+    "uv_stale_after_replaced_attrs": "late and replaced attributes",
+    "normals_morphed_without_normal_deltas": "late and replaced attributes",
+    "sparse_played_as_dense": "morph kinds",
+    "null_of_other_entry_keeps_targets": "morph kinds",
+    "weights_survive_new_targets_of_other_kind": "morph kinds",
+    "combined_call_takes_weights_before_pose_error": "refusals",
+    "combined_call_ignores_pose_kind": "morph kinds",
+    "combined_call_repairs_overflow_in_new_shape": "overflow",
+}
 
 
 @pytest.mark.parametrize("defect", sorted(DEFECTS))
@@ -686,3 +1001,34 @@ def test_the_player_catches(oracle, tour, defect):
     part = [o[1] for o in tour[:k] if o[0] == "part"][-1]
     print(f"{defect}: caught at op {k} {tour[k][0]} in '{part}': {str(e.value)[:150]}")
     assert part == CAUGHT_IN[defect], (defect, part, str(e.value)[:300])
+
+
+def caught_at(oracle, ops, defect):
+    with pytest.raises(AssertionError) as e:
+        SS.play(stand_in(oracle, defect), oracle, ops, 1)
+    k = int(re.match(r"op (\d+) ", str(e.value)).group(1))
+    return k, [o[1] for o in ops[:k] if o[0] == "part"][-1], str(e.value)
+
+
+@pytest.mark.parametrize("defect", sorted(SPARSE_DEFECTS))
+def test_the_player_catches_in_the_second_family(oracle, sparse_tour, defect):
+    """The named part catches the defect ON ITS OWN — played alone from the scene's non-trivial shape, so that no earlier part of the
+    tour stands in for it — and the whole tour catches it no later."""
+    assert set(SPARSE_CAUGHT_IN) == set(SPARSE_DEFECTS) and not set(SPARSE_DEFECTS) & set(DEFECTS) and len(SPARSE_DEFECTS) >= 10
+    alone = SS.sequence(SS.SPARSE_SEEDS[0], steps=0, pairs=False, only=(SPARSE_CAUGHT_IN[defect],))
+    assert [o[1] for o in alone if o[0] == "part"] == [SPARSE_CAUGHT_IN[defect]]
+    SS.play(stand_in(oracle), oracle, alone, 1)
+    k, part, text = caught_at(oracle, alone, defect)
+    print(f"{defect}: '{part}' alone: caught at its op {k} {alone[k][0]}, {k - alone.index(('part', part))} operations into the part: {text[:150]}")
+    names = [o[1] for o in sparse_tour if o[0] == "part"]
+    k, first, text = caught_at(oracle, sparse_tour, defect)
+    print(f"{defect}: the whole tour: caught at op {k} {sparse_tour[k][0]} in '{first}': {text[:150]}")
+    assert names.index(first) <= names.index(part), (defect, first, part)
+
+
+@pytest.mark.parametrize("defect", sorted(set(DEFECTS) - {"overflow_repair_in_new_shape"}))
+def test_the_second_family_keeps_the_teeth_of_the_first(oracle, sparse_tour, defect):
+    """The scripted parts the two families share catch in the second what they catch in the first (but for the overflowed frame behind
+    swr_morph_set: the second family has swr_morph_pose_set there, and a defect of its own for it)."""
+    k, part, text = caught_at(oracle, sparse_tour, defect)
+    assert part == CAUGHT_IN[defect], (defect, text[:300])

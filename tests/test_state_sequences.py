@@ -1,9 +1,17 @@
-"""Sequences that mix poses, morph targets, queries and delta reads on ONE context (include/swr.h).
+"""Sequences that mix poses, morph targets of both kinds, queries and delta reads on ONE context (include/swr.h).
 
 tests/test_frame_sequences.py plays frames, draw lists, renders, presents, reads, uploads and target changes in orders; it calls none
 of swr_count_ids, swr_query_depth, swr_read_*_delta, swr_render_delta, swr_delta_reset, swr_scene_skin, swr_pose_set, swr_pose_set_dq,
-swr_scene_morph, swr_morph_set and swr_item_bounds.  Each of those came with a suite of its own: one scene, one target, a fresh context
-per case.  This file plays them in orders, between frames of every kind, on one context.
+swr_scene_morph, swr_scene_morph_sparse, swr_morph_set, swr_morph_pose_set and swr_item_bounds.  Each of those came with a suite of its
+own: one scene, one target, a fresh context per case.  This file plays them in orders, between frames of every kind, on one context.
+
+Two families of seeds.  STATE_SEEDS (41, 42, 43) know dense targets, swr_morph_set and swr_pose_set*, and one attribute array; their
+operation lists are pinned as they were before the second family existed.  SPARSE_SEEDS (44, 45, 46) play the same parts with the
+sparse set "s0" resident instead of dense set 0 and swr_morph_pose_set as the blocking change behind the burst and the overflowed
+frame, and three parts more: "morph kinds" (dense and sparse sets replace each other under active weights; both sparse unions are
+partial, so what a set does not list must come from the base, whatever the set before left behind), "refusals" (every refusal of
+swr_morph_pose_set and swr_scene_morph_sparse, a frame behind each) and "late and replaced attributes" (sparse normal deltas before
+swr_scene_attributes, then a second attribute array, textured).  Their pair table has six state changes more (S_OPS_SPARSE).
 
 (a) `sequence(seed, steps)` is a pure-Python, seeded generator of legal C-ABI calls.  Scripted parts make the coverage certain — a
     tour of the six callers of the stream rebuild, the pose kinds and both bind entries, a burst posted under one shape and a blocking
@@ -13,10 +21,11 @@ per case.  This file plays them in orders, between frames of every kind, on one 
     `steps` random operations.  Calls the header refuses are played as ("refused", call, code).
 (b) `play` makes the calls and compares every image, count, query result, bounds record, delta stat and destination image with
     tests/state_model.py, bit for bit.  A SWR_FLAG_LOAD frame starts from the model's own previous image, never from a read-back.
-(c) tests/test_state_model.py asserts, without a GPU, what the sequences of STATE_SEEDS cover, that they are not vacuous, and — on
+(c) tests/test_state_model.py asserts, without a GPU, what the sequences of STATE_SEEDS and SPARSE_SEEDS cover, that they are not vacuous, and — on
     a stand-in context with switchable defects — that `play` has teeth.
 
-SWR_SEQUENCE_SEEDS=N adds N more sequences (seeds 200..) per scheduler and band count: a soak."""
+SWR_SEQUENCE_SEEDS=N adds N more sequences (seeds 200..) per scheduler and band count: a soak.  They belong to the second family,
+whose operations include the first's."""
 import dataclasses
 import functools
 import os
@@ -29,6 +38,7 @@ import pytest
 import frame_model as FM
 import kernel_matrix as K
 import morph_model as MM
+import morph_sparse_model as MS
 import resolve_model as RM
 import skin_dq_model as DQ
 import skin_model as SM
@@ -40,8 +50,10 @@ from frame_model import CB, CCW, CF, CLIP, DT, IDS, LOAD, METAL, NC, PERSP, REAL
 
 pytestmark = pytest.mark.gpu
 
-STATE_SEEDS = (41, 42, 43)
+STATE_SEEDS = (41, 42, 43)                          # the first family: dense targets, swr_morph_set and swr_pose_set* (pinned as they were)
+SPARSE_SEEDS = (44, 45, 46)                         # the second family: both kinds of targets, swr_morph_pose_set, two attribute arrays
 STEPS = 24
+SPARSE_STEPS = STEPS                                # (measured: the slowest case of the second family takes as long as the slowest of the first)
 SIZES = FS.SIZES                                    # 320 x 192, 256 x 160, 192 x 96: 6, 5 and 3 tile rows
 SCENES = {"torus": 1536, "small": 300, "big": 1300}  # triangles; 768, 900 and 3 900 vertices (900 and 3 900 are no multiples of 64)
 JOINTS = {"torus": 4, "small": 8, "big": 8}
@@ -58,6 +70,9 @@ COLOR, DEPTH = ST.DELTA_COLOR, ST.DELTA_DEPTH
 S_OPS = ("upload_same", "upload_other", "attrs", "skin_new", "skin_none", "pose_mat", "pose_dq", "bind", "targets_new", "targets_none",
          "weights", "weights_zero", "target_same", "target_other", "target_write", "delta_reset", "render", "frame_ids", "frame_noids",
          "frame_list", "frame_points")
+# the second family adds: sparse targets; targets of one kind over resident targets of the other; NULL through the entry of the kind
+# that is not resident; swr_morph_pose_set with both halves, and with a NULL half; an attribute array that replaces another
+S_OPS_SPARSE = S_OPS + ("targets_sparse", "targets_swap_kind", "targets_none_other_entry", "morph_pose", "morph_pose_null_halves", "attrs_other")
 O_OPS = ("read", "present", "count_prim", "count_item", "query", "bounds", "delta_color", "delta_depth", "resolved", "read_ids",
          "load_frame")
 NEEDS_IDS = ("count_prim", "count_item", "read_ids")
@@ -82,6 +97,21 @@ UNSPECIFIED.update({("target_write", o): "swr_present copies 'the frame of the L
 
 def legal(s, o):
     return (s, o) not in ILLEGAL and (s, o) not in UNSPECIFIED
+
+
+def sparse_family(seed):
+    """Seeds 41-43 are the first family; every other seed (44-46, and the soak seeds 200..) belongs to the second."""
+    return seed not in STATE_SEEDS
+
+
+def s_ops(seed):
+    return S_OPS_SPARSE if sparse_family(seed) else S_OPS
+
+
+def none_entry(op, n):
+    """The entry a ("targets", None[, entry]) operation goes through — "dense": swr_scene_morph(NULL), "sparse":
+    swr_scene_morph_sparse(NULL); without a named entry the n-th such operation of a sequence alternates, swr_scene_morph first."""
+    return op[2] if len(op) > 2 else ("dense", "sparse")[n % 2]
 
 
 def hooks_of(seed):
@@ -117,20 +147,27 @@ class Frame:
 
 
 BLOCKING = ("wait", "read", "read_resolved", "read_ids", "sync", "upload", "target", "write", "render", "render_delta", "attrs", "skin", "pose",
-            "targets", "weights", "count", "query", "bounds", "delta", "feed", "refused")
+            "targets", "weights", "morph_pose", "count", "query", "bounds", "delta", "feed", "refused")
 NEUTRAL = ("hooks", "wait", "sync", "material", "part", "refused")     # (neither a state change nor an observer of the tables)
 
 
-def sequence(seed, steps=STEPS, pairs=True):
+def sequence(seed, steps=None, pairs=True, only=None):
     """The operations of one sequence:
-    ("hooks", pairs) ("part", name) ("upload", scene) ("target", size) ("attrs", True) ("material", shader) ("skin", id | None)
-    ("pose", "mat" | "dq" | "bind_mat" | "bind_dq", id) ("targets", id | None) ("weights", id | "zero" | None) ("write", seed)
+    ("hooks", pairs) ("part", name) ("upload", scene) ("target", size) ("attrs", True | "other") ("material", shader) ("skin", id | None)
+    ("pose", "mat" | "dq" | "bind_mat" | "bind_dq", id) ("targets", id | "s0" | "s1" | None[, entry]) ("weights", id | "zero" | None)
+    ("morph_pose", weights id | "zero" | None, "mat" | "dq", pose id | None) ("write", seed)
     ("frame", Frame) ("render", Frame) ("render_delta", Frame, buffer) ("present", image) ("wait",) ("sync",) ("read",) ("read_ids",)
     ("read_resolved", S, depth filter, which) ("count", group, rect name) ("query", boxes, seed) ("bounds", list name, flags)
-    ("delta", kind bits, buffer) ("delta_reset", bits) ("feed",) ("refused", call, code)."""
+    ("delta", kind bits, buffer) ("delta_reset", bits) ("feed",) ("refused", call, code).
+    only: the names of the scripted parts to generate (each starts from the scene's non-trivial shape on its own), for the teeth of
+    tests/test_state_model.py."""
     rng = random.Random(seed)
     ops = [("hooks", hooks_of(seed))]
     primary = PRIMARY[(seed - STATE_SEEDS[0]) % 3]
+    sparse = sparse_family(seed)
+    if steps is None:
+        steps = SPARSE_STEPS if sparse else STEPS
+    T0, T1 = ("s0", "s1") if sparse else (0, 1)             # the targets base() keeps resident, and the tour's second set
     st = dict(scene=None, attrs=False, skin=None, pose=None, targets=None, weights=None, size=None, shader=0, last=None, ids=False,
               countable=False, image=False, color=False, pending=0, count=0, budget=MODEL_BUDGET, paid=set(), boxes=0, dbuf=0, part="")
 
@@ -164,10 +201,10 @@ def sequence(seed, steps=STEPS, pairs=True):
         emit("target", size)
         st.update(size=size, last=None, ids=False, countable=False, image=False, color=False)
 
-    def attrs():
+    def attrs(which=True):
         wait()
-        emit("attrs", True)
-        st["attrs"] = True
+        emit("attrs", which)
+        st["attrs"] = which
 
     def material(shader):
         if shader and not st["attrs"]:
@@ -187,9 +224,9 @@ def sequence(seed, steps=STEPS, pairs=True):
         emit("pose", kind, k)
         st["pose"] = None if kind.startswith("bind") else (kind, k)
 
-    def targets(k):
+    def targets(k, entry=None):
         wait()
-        emit("targets", k)
+        emit("targets", k) if entry is None else emit("targets", k, entry)
         st.update(targets=k, weights=None)
 
     def weights(k):
@@ -197,6 +234,13 @@ def sequence(seed, steps=STEPS, pairs=True):
         assert st["targets"] is not None
         emit("weights", k)
         st["weights"] = None if k in ("zero", None) else k
+
+    def morph_pose(w, kind, k):
+        wait()
+        assert st["targets"] is not None and st["skin"] is not None
+        emit("morph_pose", w, kind, k)
+        st["weights"] = None if w in ("zero", None) else w
+        st["pose"] = None if k is None else (kind, k)
 
     def write():
         wait()
@@ -207,16 +251,17 @@ def sequence(seed, steps=STEPS, pairs=True):
         emit("delta_reset", bits)
 
     def base(scene=None, w=0):
-        """The scene in its non-trivial shape: skin 0, matrix pose 0, targets 0 under weights `w` — only what differs is called.  Every
-        part starts from here, which keeps the distinct shapes of a sequence few (tests/test_state_model.py counts them)."""
+        """The scene in its non-trivial shape: skin 0, matrix pose 0, targets 0 (the second family: the sparse set "s0") under weights
+        `w` — only what differs is called.  Every part starts from here, which keeps the distinct shapes of a sequence few
+        (tests/test_state_model.py counts them)."""
         if scene is not None and scene != st["scene"]:
             upload(scene)
         if st["skin"] != 0:
             skin(0)
         if st["pose"] != ("mat", 0):
             pose("mat", 0)
-        if st["targets"] != 0:
-            targets(0)
+        if st["targets"] != T0:
+            targets(T0)
         if st["weights"] != w:
             weights(w)
 
@@ -386,6 +431,23 @@ def sequence(seed, steps=STEPS, pairs=True):
             weights(1 if st["weights"] == 0 else 0)
         elif s == "weights_zero":
             weights(rng.choice(("zero", None)))
+        elif s == "targets_sparse":
+            targets("s0")                                   # (the same lists again: new targets all the same)
+        elif s == "targets_swap_kind":
+            targets(0)                                      # dense targets over the resident sparse ones
+        elif s == "targets_none_other_entry":
+            targets(None, "dense" if isinstance(st["targets"], str) else "sparse")
+        elif s == "morph_pose":
+            if rng.random() < 0.5:
+                morph_pose(1 if st["weights"] == 0 else 0, "mat", 0)
+            else:
+                morph_pose(0, "dq", 0)
+        elif s == "morph_pose_null_halves":
+            morph_pose(*rng.choice(((None, "mat", 0), (0, "mat", None), ("zero", "dq", None), (None, "dq", None))))
+        elif s == "attrs_other":
+            if not st["attrs"]:
+                attrs()
+            attrs("other" if st["attrs"] is True else True)
         elif s == "target_same":
             target(st["size"])
         elif s == "target_other":
@@ -421,15 +483,15 @@ def sequence(seed, steps=STEPS, pairs=True):
         part("rebuild tour")
         upload(primary)
         target(0)
-        skin(0); pose("mat", 0); targets(0); weights(0)
+        skin(0); pose("mat", 0); targets(T0); weights(0)
         checked(ids=True, force=dict(load=0, shader=0, list=0, clip=0))
         attrs()                                             # 1: attributes arriving after the normal deltas
         checked(force=dict(load=0, shader=1, list=0, no_color=0, clip=0))
-        skin(1)                                             # 2: a new skin: the bind pose, the weights kept
+        skin(0 if sparse else 1)                            # 2: a new skin: the bind pose, the weights kept
         checked(force=dict(load=0, shader=2, list=0, clip=0))
         pose("dq", 0)                                       # 3: a pose of the other kind
         checked(force=dict(load=0, shader=1, list=0, clip=0))
-        targets(1)                                          # 4: new targets under a pose: every weight 0, the pose kept
+        targets(T1)                                         # 4: new targets under a pose: every weight 0, the pose kept
         checked(force=dict(load=0, list=0, clip=0))
         weights(0)                                          # 5: new weights
         checked(force=dict(load=0, shader=rng.choice((1, 2)), list=0, clip=0))
@@ -455,10 +517,12 @@ def sequence(seed, steps=STEPS, pairs=True):
 
     def unwaited():
         """A burst posted under shape A, then swr_morph_set or swr_pose_set* to shape B with no wait in front: the presented images
-        are A's, the next frame is B's."""
+        are A's, the next frame is B's.  The second family: swr_morph_pose_set, with both halves, NULL joints or NULL weights."""
         part("un-waited")
         base(primary)
         how = ("weights", "pose_mat", "pose_dq")[(seed + 1) % 3]
+        if sparse:
+            how = ((0, "dq", 0), (0, "mat", None), (None, "mat", 0))[(seed + 1) % 3]
         if how == "pose_mat":
             pose("dq", 0)
         frame("points", present_it=True)                    # (.vertices and .line frames read the shape too)
@@ -466,7 +530,9 @@ def sequence(seed, steps=STEPS, pairs=True):
         for k in range(rng.randint(2, 4)):
             frame(force=dict(clip=0), present_it=True)
         pending, st["pending"] = st["pending"], 0            # (no wait in front of the change of shape: it completes the burst itself)
-        if how == "weights":
+        if sparse:
+            morph_pose(*how)
+        elif how == "weights":
             weights(1 if st["weights"] == 0 else 0)
         elif how == "pose_mat":
             pose("mat", 0)
@@ -483,7 +549,7 @@ def sequence(seed, steps=STEPS, pairs=True):
         part("overflow")
         mode = dict(hooks_of(seed)).get(K.DEBUG_BIN_MODE, 0)
         emit("hooks", ((K.DEBUG_BIN_MODE, 0),))             # the fixed-stride bins: the only ones a crowded tile overflows
-        for k, first in enumerate(("count", "query", "delta", "bounds", "weights")):
+        for k, first in enumerate(("count", "query", "delta", "bounds", "morph_pose" if sparse else "weights")):
             base(primary)
             target(1)
             target(0)
@@ -500,6 +566,8 @@ def sequence(seed, steps=STEPS, pairs=True):
                 delta(COLOR | DEPTH)
             elif first == "bounds":
                 bounds("split", 0)
+            elif first == "morph_pose":
+                morph_pose(1, "mat", 0)                     # weights and pose change: the read below is of the shape AND pose it was posted in
             else:
                 weights(1 if st["weights"] == 0 else 0)     # the answer and the read below are those of the shape it was posted in
             read()
@@ -594,12 +662,106 @@ def sequence(seed, steps=STEPS, pairs=True):
         refused("count_wrong_n")
         read()
 
+    def step_frame(observer=None, **force):
+        """A checked frame with IDs behind a step of a scripted part of the second family, and one observer of it."""
+        checked(ids=True, force=dict(dict(load=0, clip=0, list=0), **force))
+        if observer == "count":
+            count(ST.COUNT_PER_PRIMITIVE, "all")
+        elif observer == "query":
+            query(40)
+        elif observer == "bounds":
+            bounds("thirds", 0)
+        elif observer == "delta":
+            delta(COLOR | DEPTH)
+
+    def morph_kinds():
+        """Dense and sparse targets replace each other under a pose, every set with active weights when the next arrives: what the
+        new set does not list must come out as the base, whatever the set before left in the morphed arrays.  Both sparse unions
+        are partial and neither contains the other.  A frame is drawn and read after every step."""
+        part("morph kinds")
+        base(primary)
+        target(0)
+        reset(COLOR | DEPTH)                                # (the part's first delta read is a full one)
+        targets(0); weights(0)                              # 1: dense set 0, active: every vertex of the morphed array is written
+        step_frame("bounds")
+        targets("s0")                                       # 2: sparse over active dense targets: every weight 0, the frame is the base
+        step_frame("count")
+        weights(0)                                          # 3: outside the union of "s0" nothing of the dense morph is left
+        step_frame("query")
+        morph_pose(0, "dq", 0)                              #    (the combined call: the other pose kind, NULL weights, NULL joints, and back)
+        step_frame()
+        morph_pose(None, "dq", 0)
+        step_frame()
+        morph_pose(0, "mat", None)
+        step_frame()
+        morph_pose(0, "mat", 0)
+        step_frame()
+        targets("s1")                                       # 4: another sparse set, another union, over the active "s0"
+        step_frame("delta")
+        weights(0)
+        step_frame("bounds")
+        targets(1)                                          # 5: dense set 1 over the active "s1"
+        step_frame("count")
+        targets("s0"); weights(1)                           # 6: back to "s0" (its empty target at NaN, its non-finite one at -0)
+        step_frame("query")
+        targets(None, "dense")                              # 7: swr_scene_morph(NULL) removes sparse targets ...
+        refused("weights_no_targets")
+        step_frame("delta")
+        targets(0); weights(0)
+        step_frame("bounds")
+        targets(None, "sparse")                             #    ... and swr_scene_morph_sparse(NULL) dense ones
+        refused("weights_no_targets")
+        step_frame("delta")
+
+    def refusals():
+        """Every refusal of swr_morph_pose_set and swr_scene_morph_sparse the generator can reach, each followed by a frame: neither
+        the weights nor the pose nor the targets have changed.  (The refused calls carry weights, joints and targets that would
+        change the frame if they were taken.)"""
+        part("refusals")
+        base(primary)
+        targets(None)
+        refused("morph_pose_no_targets")
+        step_frame()
+        targets("s0"); weights(0)
+        for call in ("morph_pose_wrong_count", "morph_pose_few_joints", "morph_pose_bad_kind", "sparse_wrong_vertex_count", "sparse_descending",
+                     "sparse_some_normals"):
+            refused(call)
+            step_frame()
+        refused("sparse_too_many", UNSUPPORTED)
+        skin(None)
+        refused("morph_pose_no_skin")
+        step_frame()
+
+    def late_attrs():
+        """Sparse normal deltas before any attributes, the attributes, a second attribute array under active weights, then a set without
+        normal deltas and the one with them again: without a pose, then under one.  The colour/uv quad of the morphed attributes
+        comes from the base for touched and untouched vertices alike: the frames are textured."""
+        part("late and replaced attributes")
+        tex = dict(load=0, clip=0, list=0, shader=2, no_color=0)
+        for posed in (False, True):
+            upload(primary)                                 # (no attributes, no skin, no targets)
+            if posed:
+                skin(0); pose("mat", 0)
+            targets("s0")                                   # 1: normal deltas before any attributes
+            attrs()                                         # 2: they take effect when the attributes arrive
+            weights(0)
+            checked(force=tex)
+            attrs("other")                                  # 3: other normals and other uv while the weights are active
+            checked(force=tex)
+            targets("s1")                                   # 4: no normal deltas: the normals are the uploaded ones
+            if posed:
+                weights(0)                                  #    (without a pose: a frame of the base — one deformed shape fewer)
+            checked(force=tex)
+            targets("s0")                                   #    normal deltas again
+            weights(0)
+            checked(force=tex)
+
     def pair_tour():
         """Every legal (state change, first observer) pair and every ordered pair of observers, dealt over the three seeds; every
         illegal pair as a refusal."""
         part("pairs")
-        todo = [(s, o) for s in S_OPS for o in O_OPS]
-        mine = [p for k, p in enumerate(todo) if (k + seed) % 3 == 0] if seed in STATE_SEEDS else rng.sample(todo, len(todo) // 3)
+        todo = [(s, o) for s in s_ops(seed) for o in O_OPS]
+        mine = [p for k, p in enumerate(todo) if (k + seed) % 3 == 0] if seed in STATE_SEEDS + SPARSE_SEEDS else rng.sample(todo, len(todo) // 3)
         rng.shuffle(mine)
         scene = primary
         for s, o in mine:
@@ -628,7 +790,7 @@ def sequence(seed, steps=STEPS, pairs=True):
         target(0)
         frame(ids=True, color=True, force=dict(load=0, list=1, clip=0, rules="ztest"))
         order = [(a, b) for a in O_OPS for b in O_OPS]
-        mine = [p for k, p in enumerate(order) if (k + seed) % 3 == 0] if seed in STATE_SEEDS else rng.sample(order, len(order) // 3)
+        mine = [p for k, p in enumerate(order) if (k + seed) % 3 == 0] if seed in STATE_SEEDS + SPARSE_SEEDS else rng.sample(order, len(order) // 3)
         for a, b in mine:
             for o in (a, b):
                 if o in NEEDS_IDS and not st["ids"]:
@@ -640,6 +802,14 @@ def sequence(seed, steps=STEPS, pairs=True):
             wait()
 
     scripted = [rebuild_tour, pose_kinds, unwaited, overflow, lifetimes, baselines, bounds_feed]
+    if sparse:
+        scripted += [morph_kinds, refusals, late_attrs]
+    names = {"rebuild tour": rebuild_tour, "pose kinds": pose_kinds, "un-waited": unwaited, "overflow": overflow, "lifetimes": lifetimes,
+             "baselines": baselines, "bounds feed": bounds_feed, "morph kinds": morph_kinds, "refusals": refusals,
+             "late and replaced attributes": late_attrs}
+    if only is not None:
+        scripted = [names[n] for n in only]
+        target(0)
     for p in scripted:
         p()
     if pairs:
@@ -672,7 +842,8 @@ def sequence(seed, steps=STEPS, pairs=True):
                 frame(ids=True, color=True, force=dict(clip=0))
             observe(o)
         elif op == "change":
-            s = rng.choice(("pose_mat", "pose_dq", "bind", "weights", "weights_zero", "skin_new", "targets_new", "delta_reset"))
+            s = rng.choice(("pose_mat", "pose_dq", "bind", "weights", "weights_zero", "skin_new", "targets_new", "delta_reset")
+                           + (S_OPS_SPARSE[len(S_OPS):] * 2 if sparse else ()))
             change(s)
         elif op == "target":
             target(rng.randrange(len(SIZES)))
@@ -695,6 +866,7 @@ def sequence(seed, steps=STEPS, pairs=True):
 def classes(ops):
     """[(index, S_OPS names, O_OPS names)] of every operation that changes state or observes; a SWR_FLAG_LOAD frame does both."""
     out, nv, size = [], None, None
+    kind, attrs, nones = None, None, 0                      # the kind of the resident targets, the resident attribute array
     verts = {"torus": 768, "small": 900, "big": 3900}
     for k, op in enumerate(ops):
         s, o = set(), set()
@@ -702,16 +874,31 @@ def classes(ops):
         if name == "upload":
             s.add("upload_same" if verts[op[1]] == nv else "upload_other")
             nv = verts[op[1]]
+            kind = attrs = None
         elif name == "attrs":
-            s.add("attrs")
+            s.add("attrs" if attrs in (None, op[1]) else "attrs_other")
+            attrs = op[1]
         elif name == "skin":
             s.add("skin_none" if op[1] is None else "skin_new")
         elif name == "pose":
             s.add({"mat": "pose_mat", "dq": "pose_dq"}.get(op[1], "bind"))
         elif name == "targets":
-            s.add("targets_none" if op[1] is None else "targets_new")
+            if op[1] is None:
+                s.add("targets_none")
+                if kind is not None and none_entry(op, nones) != kind:
+                    s.add("targets_none_other_entry")
+                nones += 1
+                kind = None
+            else:
+                new = "sparse" if isinstance(op[1], str) else "dense"
+                s.add("targets_sparse" if new == "sparse" else "targets_new")
+                if kind is not None and kind != new:
+                    s.add("targets_swap_kind")
+                kind = new
         elif name == "weights":
             s.add("weights_zero" if op[1] in ("zero", None) else "weights")
+        elif name == "morph_pose":
+            s.add("morph_pose_null_halves" if op[1] is None or op[3] is None else "morph_pose")
         elif name == "target":
             s.add("target_same" if op[1] == size else "target_other")
             size = op[1]
@@ -724,6 +911,7 @@ def classes(ops):
             if name != "frame":
                 s.add("render")                             # (its own gather is part of the call: no observer of what came before)
                 nv = verts[f.scene]
+                kind, attrs = None, (True if f.shader else None)
             elif f.kind != "tri":
                 s.add("frame_points")
             else:
@@ -800,6 +988,8 @@ class Scene:
     targets: dict           # id -> (position deltas, normal deltas)
     weights: dict           # target id -> {id: weights}
     tf: dict                # "aff", "aff2", "per", "per2"
+    attrs2: np.ndarray = None   # a second attribute array: other normals, other uv
+    sparse: dict = None     # "s0" | "s1" -> [(indices, position deltas[, normal deltas])]; their weights are in `weights`
 
 
 CROWD = (160.0, 112.0)      # the middle of tile (2, 3) of the 320 x 192 target, in the second of three bands
@@ -815,6 +1005,63 @@ def _crowd(m, scale, z):
     return SM.joint_matrix(0.0, scale, float(t[0]), float(t[1]), z)
 
 
+S0_TARGETS, S1_TARGETS = 4, 6                       # (neither is a number of dense targets of any scene)
+S0_EMPTY, S0_NONFINITE = 2, 3                       # the empty target of "s0", and the one that only ever gets weight +-0
+
+
+def union_of(targets):
+    return MS.touched(targets)
+
+
+def sparse_sets(v, seed, amp):
+    """The sparse target sets of a scene and their weights.  "s0": four targets with normal deltas over the vertices [0, 25/64 nv) —
+    two that together list every vertex of the range (the first vertex of the scene among them), an empty one, and one of
+    non-finite deltas on every fifth.  "s1": six targets without normal deltas over [25/96 nv, nv), the last vertex of the scene
+    among them.  Neither union contains the other, each leaves some of the scene out, and 768, 900 and 3 900 vertices give unions
+    of 300 and 568, 351 and 666, 1 523 and 2 885: more than 256, no multiple of 64."""
+    nv = v.shape[0]
+    rng = np.random.default_rng(seed)
+    U0, U1 = np.arange(0, nv * 25 // 64), np.arange(nv * 25 // 96, nv)
+
+    def deltas(n, shift):
+        return ((np.asarray(shift) + rng.uniform(-0.2, 0.2, (n, 3))) * amp).astype(np.float32)
+
+    def target(idx, shift, normals):
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        t = (idx, deltas(idx.size, shift))
+        return t + (rng.uniform(-0.5, 0.5, (idx.size, 3)).astype(np.float32),) if normals else t
+
+    a = rng.uniform(size=U0.size) < 0.7
+    a[0] = True
+    b = ~a | (rng.uniform(size=U0.size) < 0.4)
+    fifth = np.ascontiguousarray(U0[::5], dtype=np.uint32)
+    bad = np.tile(np.array([np.nan, np.inf, -np.inf], dtype=np.float32), (fifth.size, 1))
+    s0 = [target(U0[a], (0.0, 1.0, 0.0), True), target(U0[b], (0.8, 0.0, 0.3), True),
+          (np.zeros(0, dtype=np.uint32), np.zeros((0, 3), dtype=np.float32)), (fifth, bad, np.full((fifth.size, 3), np.nan, dtype=np.float32))]
+    s1, seen = [], np.zeros(U1.size, dtype=bool)
+    for k in range(S1_TARGETS - 1):
+        m = rng.uniform(size=U1.size) < 0.4
+        m[-1] = False
+        seen |= m
+        s1.append(target(U1[m], rng.uniform(-1.0, 1.0, 3), False))
+    s1.append(target(U1[~seen], (-0.6, -0.7, 0.0), False))
+    weights = {"s0": {0: np.array([0.8, -0.6, 2.0, 0.0], dtype=np.float32), 1: np.array([-0.5, 0.9, np.nan, -0.0], dtype=np.float32)},
+               "s1": {0: rng.uniform(0.4, 1.0, S1_TARGETS).astype(np.float32), 1: (-rng.uniform(0.4, 1.0, S1_TARGETS)).astype(np.float32)}}
+    return {"s0": s0, "s1": s1}, weights
+
+
+def other_attrs(attrs, seed):
+    """A second attribute array: other normals and other uv, the padding lanes as they are."""
+    rng = np.random.default_rng(seed)
+    a = np.array(attrs, dtype=np.float32, copy=True)
+    a[:, 0:3] += rng.uniform(-0.4, 0.4, (a.shape[0], 3)).astype(np.float32)
+    a[:, 4:6] = a[:, 4:6] * np.float32(1.7) + np.float32(0.13)
+    return a
+
+
+NEGATIVE_ZERO = {"torus": ((80, 2), (320, 2))}      # (vertex, coordinate): z = +0 as built; 80 is outside the union of "s1", 320 of "s0"
+
+
 @functools.lru_cache(maxsize=None)
 def world():
     """name -> Scene."""
@@ -824,6 +1071,10 @@ def world():
     out = {}
     # the torus of tests/skin_model.py and tests/morph_model.py, in its own space (x, y in +-0.75, z in +-0.2)
     v, i = MM.torus(S)
+    v = np.array(v, copy=True)
+    for k, c in NEGATIVE_ZERO["torus"]:
+        assert v[k, c] == 0 and not np.signbit(v[k, c])
+        v[k, c] = np.float32(-0.0)                           # (an unlisted -0 stays -0; an applied zero delta would make it +0)
     aff = FS.affine(0.0, 0.95, 0.95, 0.5, 0.0, 0.0, 0.5)
     per = FS.affine(0.0, 0.9, 0.9, 0.5, 0.0, 0.0, 0.5)
     per[11] = np.float32(0.35)                               # w = 1 + 0.35 z
@@ -869,6 +1120,10 @@ def world():
             wt[tid] = {0: rng.uniform(0.4, 1.0, nt).astype(np.float32), 1: (-rng.uniform(0.4, 1.0, nt)).astype(np.float32)}
         out[name] = Scene(v, i, sh[1].attrs, {1: sh[1], 2: sh[2]}, skins, mats, dqs, tg, wt,
                           {n: fs_mats[n] for n in ("aff", "aff2", "per", "per2")})
+    for k, (name, s) in enumerate(out.items()):
+        s.attrs2 = other_attrs(s.attrs, 0xA77 + k)
+        s.sparse, w = sparse_sets(s.v, 0x5BA65E + k, 0.15 if name == "torus" else 0.4)
+        s.weights.update(w)
     for name, s in out.items():
         assert s.i.size // 3 == SCENES[name] and s.mats[0].shape[0] == JOINTS[name] and s.targets[0][0].shape[0] == TARGETS[name][0]
         assert np.array_equal(s.shading[1].attrs, s.shading[2].attrs)
@@ -886,7 +1141,9 @@ def shape_vertices(scene, skin, pose, targets, weights):
     """The vertices of normal_shape(sig), from the names alone: morph first, then the pose."""
     s = world()[scene]
     v = s.v
-    if weights is not None:
+    if weights is not None and isinstance(targets, str):
+        v = MS.morph_vertices(v, s.sparse[targets], s.weights[targets][weights])
+    elif weights is not None:
         v = MM.morph_vertices(v, s.targets[targets][0], s.weights[targets][weights])
     if pose is not None:
         P, table = (SM, s.mats[pose[1]]) if pose[0] == "mat" else (DQ, s.dqs[pose[1]])
@@ -1046,7 +1303,26 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
         assert got == code, f"{what}: {call} returned {got}, not {code} ({state()})"
         stats["refused"] = stats.get("refused", 0) + 1
 
-    cur = dict(weights=None)
+    def weights_of(wid):
+        if wid is None:
+            return None
+        if wid == "zero":
+            w = np.zeros(M.target_count(), dtype=np.float32)
+            w[::2] = np.float32(-0.0)
+            return w
+        return D.weights[cur["targets"]][wid]
+
+    def morph_pose_refused(call, code, w, table, dq, what):
+        check_refused(call, code, lambda: ctx.morph_pose_set(w, table, dq=dq), what)
+        with pytest.raises(ST.Refused):
+            M.morph_pose(w, "dq" if dq else "mat", table)
+
+    def sparse_refused(call, code, targets, what, vertex_count=None):
+        check_refused(call, code, lambda: ctx.scene_morph_sparse(targets, vertex_count), what)
+        with pytest.raises(ST.Refused):
+            M.set_targets_sparse(targets, vertex_count)
+
+    cur = dict(weights=None, nones=0)
     scene = size = None
     try:
         with swr.Context(0, device_count=bands) as ctx:
@@ -1071,8 +1347,9 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
                     ctx.target_set(*SIZES[size])
                     M.target_set(*SIZES[size])
                 elif name == "attrs":
-                    ctx.scene_attributes(D.attrs)
-                    M.attributes(D.attrs)
+                    a = D.attrs if op[1] is True else D.attrs2
+                    ctx.scene_attributes(a)
+                    M.attributes(a)
                 elif name == "material":
                     sh = D.shading[op[1]] if op[1] else None
                     if sh is not None and sh.texture is not None and cur.get("texture") is not sh.texture:
@@ -1095,20 +1372,29 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
                     else:
                         ctx.pose_set_dq(None); M.set_pose("dq", None)
                 elif name == "targets":
-                    tg = D.targets[op[1]] if op[1] is not None else (None, None)
-                    ctx.scene_morph(*tg)
-                    M.set_targets(*tg)
+                    if op[1] is None:                       # NULL through either entry removes whichever kind is resident
+                        if none_entry(op, cur["nones"]) == "dense":
+                            ctx.scene_morph(None); M.set_targets(None)
+                        else:
+                            ctx.scene_morph_sparse(None); M.set_targets_sparse(None)
+                        cur["nones"] += 1
+                    elif isinstance(op[1], str):
+                        ctx.scene_morph_sparse(D.sparse[op[1]])
+                        M.set_targets_sparse(D.sparse[op[1]])
+                    else:
+                        ctx.scene_morph(*D.targets[op[1]])
+                        M.set_targets(*D.targets[op[1]])
                     cur.update(targets=op[1], weights=None)
                 elif name == "weights":
-                    if op[1] is None:
-                        w = None
-                    elif op[1] == "zero":
-                        w = np.zeros(M.targets[0].shape[0], dtype=np.float32)
-                        w[::2] = np.float32(-0.0)
-                    else:
-                        w = D.weights[cur["targets"]][op[1]]
+                    w = weights_of(op[1])
                     ctx.morph_set(w)
                     M.set_weights(w)
+                    cur["weights"] = op[1]
+                elif name == "morph_pose":
+                    w, kind = weights_of(op[1]), op[2]
+                    table = None if op[3] is None else (D.mats if kind == "mat" else D.dqs)[op[3]]
+                    ctx.morph_pose_set(w, table, dq=kind == "dq")
+                    M.morph_pose(w, kind, table)
                     cur["weights"] = op[1]
                 elif name == "write":
                     c, d = TP.start_images(op[1], *SIZES[size])
@@ -1129,6 +1415,7 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
                         ctx.draw(D.tf[f.tf], f.flags, prim)
                         timed(M.frame, f.flags, D.tf[f.tf], None, prim)
                     stats.setdefault("shapes", []).append((M.shape()[2], scene))
+                    stats.setdefault("frame_ops", []).append(k)
                 elif name in ("render", "render_delta"):
                     f = op[1]
                     w, h = SIZES[f.size]
@@ -1295,6 +1582,50 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
                         check_refused(call, code, lambda: ctx.morph_set(wrong), what)
                         with pytest.raises(ST.Refused):
                             M.set_weights(wrong)
+                    elif call == "morph_pose_no_targets":
+                        morph_pose_refused(call, code, None, D.mats[1], False, what)
+                        morph_pose_refused(call, code, D.weights["s0"][1], D.dqs[1], True, what)
+                    elif call == "morph_pose_no_skin":          # (weights that would be taken)
+                        other = D.weights[cur["targets"]][1 if cur["weights"] == 0 else 0]
+                        morph_pose_refused(call, code, other, D.mats[1], False, what)
+                        morph_pose_refused(call, code, other, D.dqs[1], True, what)
+                    elif call == "morph_pose_wrong_count":      # (a pose that would be taken; one weight too many, one too few)
+                        morph_pose_refused(call, code, np.ones(M.target_count() + 1, dtype=np.float32), D.dqs[1], True, what)
+                        morph_pose_refused(call, code, np.ones(M.target_count() - 1, dtype=np.float32), D.mats[1], False, what)
+                    elif call == "morph_pose_few_joints":       # (weights that would be taken)
+                        other = D.weights[cur["targets"]][1 if cur["weights"] == 0 else 0]
+                        morph_pose_refused(call, code, other, D.mats[1][:JOINTS[scene] - 1], False, what)
+                        morph_pose_refused(call, code, other, D.dqs[1][:JOINTS[scene] - 1], True, what)
+                    elif call == "morph_pose_bad_kind":
+                        other = D.weights[cur["targets"]][1 if cur["weights"] == 0 else 0]
+                        for bad in (2, -1):
+                            check_refused(call, code, lambda: ctx.morph_pose_set(other, D.mats[1], pose_kind=bad), what)
+                        with pytest.raises(ST.Refused):
+                            M.morph_pose(other, "neither", D.mats[1])
+                    elif call == "sparse_wrong_vertex_count":
+                        sparse_refused(call, code, D.sparse["s1"], what, D.v.shape[0] - 1)
+                    elif call == "sparse_descending":
+                        t = list(D.sparse["s1"])
+                        idx = t[1][0].copy()
+                        idx[[3, 4]] = idx[[4, 3]]
+                        t[1] = (idx,) + t[1][1:]
+                        sparse_refused(call, code, t, what)
+                        idx = t[1][0].copy()
+                        idx[3] = idx[4]                      # (not STRICTLY ascending)
+                        t[1] = (idx,) + t[1][1:]
+                        sparse_refused(call, code, t, what)
+                        t[1] = D.sparse["s1"][1]
+                        idx = t[2][0].copy()
+                        idx[-1] = D.v.shape[0]              # (out of range)
+                        t[2] = (idx,) + t[2][1:]
+                        sparse_refused(call, code, t, what)
+                    elif call == "sparse_some_normals":
+                        t = list(D.sparse["s0"])
+                        t[1] = t[1][:2]                     # (the empty target gives none either way: it does not count)
+                        sparse_refused(call, code, t, what)
+                    elif call == "sparse_too_many":
+                        none = (np.zeros(0, dtype=np.uint32), np.zeros((0, 3), dtype=np.float32))
+                        sparse_refused(call, code, [D.sparse["s1"][0]] + [none] * ST.MORPH_MAX_TARGETS, what)
                     elif call == "bounds_clip":
                         check_refused(call, code, lambda: ctx.item_bounds(items_of(scene, "aff"), CLIP), what)
                         with pytest.raises(ST.Refused):
@@ -1320,13 +1651,13 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
     return stats
 
 
-# SWR_SEQUENCE_SEEDS=N adds N more sequences (seeds 200..) per scheduler and band count
+# SWR_SEQUENCE_SEEDS=N adds N more sequences (seeds 200..; all of the second family) per scheduler and band count
 _EXTRA = [200 + k for k in range(int(os.environ.get("SWR_SEQUENCE_SEEDS", "0")))]
 
 
 @pytest.mark.parametrize("env", [{}, {"SWR_LANES": "0"}], ids=["lanes", "SWR_LANES=0"])
 @pytest.mark.parametrize("bands", [1, 3])
-@pytest.mark.parametrize("seed", list(STATE_SEEDS) + _EXTRA)
+@pytest.mark.parametrize("seed", list(STATE_SEEDS + SPARSE_SEEDS) + _EXTRA)
 def test_state_sequences(swr, oracle, monkeypatch, seed, bands, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
