@@ -8,6 +8,7 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
                                    [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion [--bounds]] [--delta] [--skin [--dq]] [--morph [--sparse]]
+                                   [--auto-normals {smooth,flat}]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
@@ -35,6 +36,9 @@ device, nothing but the weights crosses per frame.  With --skin the torus is mor
 --morph --sparse uploads the same two targets as sparse ones (swr_scene_morph_sparse): each lists only the vertices it moves, and only
 those are stored and rewritten on the device.  With --skin the weights and the pose are then set by one call (swr_morph_pose_set), which
 rewrites the scene once per frame instead of twice.
+--auto-normals smooth|flat (with --skin and / or --morph) lights the deforming mesh with a Phong material although it brings no
+normals and its targets no normal deltas: the device computes them from the deformed positions after every pose and morph call
+(swr_scene_normals), per vertex (smooth) or per triangle (flat).
 --cull {none,back,front} [--front-ccw] turns on face culling (Metal's setCullMode / setFrontFacingWinding): triangles that face
 away (back) or towards the viewer (front) are not drawn; front is clockwise as displayed unless --front-ccw.
 
@@ -496,11 +500,28 @@ def twist_pose(time: float) -> np.ndarray:
     return np.stack([joint(a, -b, 0.05 * math.sin(3.0 * time)), joint(-a, b, -0.05 * math.sin(3.0 * time))])
 
 
+def auto_normals_shading(vertices: np.ndarray):
+    """The shading of --auto-normals: a mesh that brings no normals (all zero, like its uv) under a Phong material.  The normals the
+    frames read are computed on the device from the deformed positions (swr_scene_normals)."""
+    light, half = S.light_rig()
+    return S.Shading(np.zeros((vertices.shape[0], 8), dtype=np.float32), S.SHADER_PHONG, 4, light, half, 0.2, 0.7, 0.5, None)
+
+
+def use_auto_normals(ctx, vertices: np.ndarray, mode: str | None):
+    """mode "smooth" or "flat": attributes without normals, a Phong material, and normals computed per vertex or per triangle."""
+    if mode:
+        sh = auto_normals_shading(vertices)
+        ctx.scene_attributes(sh.attrs)
+        ctx.material_set(swr_amd.binding.Material.from_shading(sh))
+        ctx.scene_normals(mode)
+
+
 def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, device_count: int = 1,
-             dq: bool = False):
+             dq: bool = False, auto_normals: str | None = None):
     """The resident loop with a deforming mesh: a torus skinned to two joints, a new pose every frame (swr_pose_set), the app's
-    transform.  dq: the pose is twist_pose, which also twists the torus, set as dual quaternions (swr_pose_set_dq).  Returns the mesh
-    and the (colour, depth) frames."""
+    transform.  dq: the pose is twist_pose, which also twists the torus, set as dual quaternions (swr_pose_set_dq).  auto_normals
+    ("smooth" / "flat"): lit by a Phong material with normals recomputed on the device after every pose (swr_scene_normals).
+    Returns the mesh and the (colour, depth) frames."""
     xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
     vertices = S.pack_vertices(xyz, rgb)
     flags = S.FLAG_DEPTH_TEST if depth_test else 0
@@ -508,6 +529,7 @@ def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = 
     with swr_amd.Context(0, device_count=device_count) as ctx:
         ctx.scene_upload(vertices, indices)
         ctx.scene_skin(*bend_skin(vertices))
+        use_auto_normals(ctx, vertices, auto_normals)
         ctx.target_set(size, size)
         time = time0
         for k in range(frames):
@@ -546,12 +568,13 @@ def morph_weights(time: float) -> np.ndarray:
 
 
 def run_morph(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, skin: bool = False,
-              device_count: int = 1, obj: str | None = None, dq: bool = False, sparse: bool = False):
+              device_count: int = 1, obj: str | None = None, dq: bool = False, sparse: bool = False, auto_normals: str | None = None):
     """The resident loop with a mesh that changes its shape: two morph targets uploaded once (swr_scene_morph), new weights every
     frame (swr_morph_set), the app's transform.  skin: the torus of run_skin, morphed and then posed (swr_pose_set, or with dq
     swr_pose_set_dq and twist_pose) every frame.  sparse: the targets are uploaded as sparse ones, restricted to the vertices they
     move (swr_scene_morph_sparse), and with skin the weights and the pose are set by one call (swr_morph_pose_set).
-    Returns the mesh and the (colour, depth) frames."""
+    auto_normals ("smooth" / "flat"): lit by a Phong material with normals recomputed on the device after every change of shape
+    (swr_scene_normals): the targets carry no normal deltas.  Returns the mesh and the (colour, depth) frames."""
     if skin:
         xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
         vertices = S.pack_vertices(xyz, rgb)
@@ -567,6 +590,7 @@ def run_morph(frames: int, size: int, out: str | None = None, depth_test: bool =
             ctx.scene_morph(morph_targets(vertices))
         if skin:
             ctx.scene_skin(*bend_skin(vertices))
+        use_auto_normals(ctx, vertices, auto_normals)
         ctx.target_set(size, size)
         time = time0
         for k in range(frames):
@@ -620,6 +644,9 @@ if __name__ == "__main__":
     ap.add_argument("--sparse", action="store_true",
                     help="with --morph: the targets list only the vertices they move (swr_scene_morph_sparse); with --skin as well, weights "
                          "and pose are set by one call (swr_morph_pose_set)")
+    ap.add_argument("--auto-normals", choices=["smooth", "flat"], default=None,
+                    help="with --skin and / or --morph: a Phong material whose normals are computed on the device from the deformed "
+                         "positions, per vertex or per triangle (swr_scene_normals)")
     ap.add_argument("--cull", choices=["none", "back", "front"], default="none", help="face culling: which facing is not drawn")
     ap.add_argument("--front-ccw", action="store_true", help="front = counter-clockwise as displayed (default: clockwise)")
     ap.add_argument("--clip", action="store_true", help="depth clipping: triangles clipped against the near and far planes")
@@ -647,6 +674,8 @@ if __name__ == "__main__":
     if a.bounds and a.clip:
         ap.error("--bounds does not combine with --clip (swr_item_bounds does not take SWR_FLAG_DEPTH_CLIP)")
     deforming_bounds = a.occlusion and a.bounds and (a.skin or a.morph)
+    if a.auto_normals and (deforming_bounds or not (a.skin or a.morph)):
+        ap.error("--auto-normals is a mode of the --skin and --morph loops")
     if a.sparse and deforming_bounds:
         ap.error("--sparse is part of the plain --morph loop, not of --occlusion --bounds")
     if deforming_bounds and (a.obj or a.ply or a.stream or a.delta or a.glass is not None):
@@ -654,14 +683,15 @@ if __name__ == "__main__":
     if a.morph and not deforming_bounds:
         if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or (a.skin and (a.obj or a.ply)):
             ap.error("--morph is its own loop: only --frames, --size, --out, --depth-test, --gpus, --skin and (without --skin) --obj / --ply apply")
-        _, idx, res = run_morph(a.frames, a.size, a.out, a.depth_test, skin=a.skin, device_count=a.gpus, obj=a.ply or a.obj, dq=a.dq, sparse=a.sparse)
+        _, idx, res = run_morph(a.frames, a.size, a.out, a.depth_test, skin=a.skin, device_count=a.gpus, obj=a.ply or a.obj, dq=a.dq, sparse=a.sparse,
+                              auto_normals=a.auto_normals)
         print(f"{a.frames} morphed{' and posed' if a.skin else ''} frames, {idx.size // 3} triangles, "
               f"coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
     if a.skin and not deforming_bounds:
         if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or a.obj or a.ply:
             ap.error("--skin is its own loop over its own mesh: only --frames, --size, --out, --depth-test and --gpus apply")
-        _, idx, res = run_skin(a.frames, a.size, a.out, a.depth_test, device_count=a.gpus, dq=a.dq)
+        _, idx, res = run_skin(a.frames, a.size, a.out, a.depth_test, device_count=a.gpus, dq=a.dq, auto_normals=a.auto_normals)
         print(f"{a.frames} posed frames, {idx.size // 3} triangles, coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
     if a.delta:

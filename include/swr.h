@@ -410,7 +410,7 @@ enum { SWR_DELTA_COLOR = 1, SWR_DELTA_DEPTH = 2 };
  *     SWR_ERR_UNSUPPORTED: joint_count > SWR_SKIN_MAX_JOINTS.  A failed context returns its sticky error.  After an error the
  *     scene and the pose are unchanged.
  *   Not covered: a pose that does not wait (ordered by events), a partial vertex update from the host, and the C++ and Swift
- *     mirrors.  (Dual-quaternion skinning is the next section.) */
+ *     mirrors.  (Dual-quaternion skinning is the next section.  Normals that are right under scale or shear: "Computed normals".) */
 typedef struct swr_skin_vertex {
     uint32_t joint[4];   /* indices into the pose; all four are always read */
     float    weight[4];  /* used as given: not normalised, not sorted, not skipped when 0 */
@@ -493,7 +493,8 @@ typedef struct swr_skin_vertex {
  *     SWR_ERR_NOMEM: the delta buffer cannot be allocated.  A failed context returns its sticky error.  After an error the scene,
  *     the targets and the weights are unchanged.
  *   Not covered: sparse targets, morphing colours or uv, one call that sets weights and joints together (today swr_morph_set
- *     followed by swr_pose_set runs the skin and stream passes twice), an un-waited morph, and the C++ and Swift mirrors. */
+ *     followed by swr_pose_set runs the skin and stream passes twice), an un-waited morph, and the C++ and Swift mirrors.
+ *     (Normals for targets without normal_deltas: "Computed normals".) */
 #define SWR_MORPH_MAX_TARGETS 256
 typedef struct swr_morph_targets {
     const float* position_deltas; /* target_count x vertex_count x 3 floats, target-major, tightly packed (glTF VEC3 accessors back to back) */
@@ -606,6 +607,61 @@ typedef struct swr_morph_sparse {
  *   It needs targets (of either kind) and a skin.  NULL weights with 0 and NULL joints with 0 mean what they mean in the two calls.
  *   Errors: those of the two calls, under their conditions, and SWR_ERR_BAD_ARG for an unknown pose_kind. */
 enum { SWR_POSE_MATRICES = 0, SWR_POSE_DUAL_QUATS = 1 };
+
+/* ---- Computed normals (swr_scene_normals) — DESIGN.md §29 ---------------------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_scene_normals symbol is the feature test.  Nothing
+ * existing changes.  The normals of the resident scene can be computed on the device from the positions that are drawn, instead of
+ * being uploaded: a morph target without normal deltas, the matrix skin's blend "without inverse transpose" under scale or shear, and
+ * a mesh that has no normals at all then light the surface as it is drawn.  normals == NULL means SWR_NORMALS_UPLOADED.
+ *   Positions and triangles.  a, b and c are the positions the frame draws for triangle p: the morphed-then-posed xyz of
+ *     indices[3p], indices[3p + 1] and indices[3p + 2].  p runs over 0 .. index_count / 3 - 1; trailing indices are ignored.  The
+ *     normals are in object space, like light_dir: the frame's transform is not involved.
+ *   Face vector (normative): IEEE binary32, one rounding per operation, no FMA.  e1 = b - a and e2 = c - a, componentwise.
+ *     f_p = cross(e1, e2), with cross exactly as "Dual-quaternion skinning" defines it: two products and one subtraction per
+ *     component.  Under SWR_NORMALS_FLIP, f_p = cross(e2, e1).
+ *   SWR_NORMALS_FLAT.  All three corners of triangle p take the normal f_p.  It is not normalised: the fragment stage normalises per
+ *     pixel.  This is what glTF prescribes for a mesh without normals.
+ *   SWR_NORMALS_SMOOTH.  For vertex i start with n = (+0, +0, +0).  Walk p in ascending order, and inside p the corners k = 0, 1, 2.
+ *     For every corner with indices[3p + k] == i, n = n + f_p, componentwise: a triangle that names i twice adds twice.  Then
+ *     normalise:  l = sqrtf((n.x*n.x + n.y*n.y) + n.z*n.z), with sqrtf and the divide correctly rounded.  If l > 0.0f,
+ *     n = n * (1.0f / l): one divide, three multiplies.  Otherwise n stays as it is: a vertex of no triangle stays (0, 0, 0), which
+ *     the Phong stage treats as the zero vector, and a NaN l leaves n as the sum made it.  Every corner that references i takes n.
+ *     The walk order is normative: it is what makes the sum bit-defined.  There are no other special cases: a non-finite position
+ *     poisons the faces that use it and the vertices of those faces, and nothing else.
+ *   What is replaced.  Only the normals the frames read.  Colour, uv, the padding lanes, positions, group boxes and the uploaded
+ *     attribute array are never written.  While a computed mode is in effect, morph normal_deltas and the normal half of either
+ *     skinning mode have no effect on any frame (the implementation may skip them).
+ *   What the mode is.  Under SMOOTH every frame, read and query after the call is bit for bit that of a context on which
+ *     swr_scene_upload got the morphed-then-posed vertices and swr_scene_attributes got the same uv with the n_i above.  Under FLAT
+ *     it is that of the de-indexed scene: vertex 3p + k is corner k of triangle p, the indices are 0 .. 3 * ntri - 1, and each
+ *     corner carries f_p.  Primitive IDs, painter's order and tie order are unchanged.  .vertices and .line frames and the
+ *     passthrough shader never read normals and do not change.
+ *   Lifetime.  The mode follows the swr_scene_upload it belongs to; it may be set before or after swr_scene_attributes,
+ *     swr_scene_skin and swr_scene_morph[_sparse].  It takes effect only while the scene has attributes: set earlier, it is kept and
+ *     takes effect when swr_scene_attributes arrives, as morph normal deltas do.  It persists across swr_pose_set, swr_pose_set_dq,
+ *     swr_morph_set, swr_morph_pose_set, swr_scene_skin, swr_scene_morph and swr_scene_morph_sparse, and the normals are recomputed
+ *     whenever one of them rewrites the scene.  SWR_NORMALS_UPLOADED (or NULL) restores the uploaded normals, morphed and posed as
+ *     before: bit for bit what a context that never set a mode holds.  A new swr_scene_upload (the one a swr_render performs
+ *     included) discards the mode.
+ *   Ordering.  The Ordering paragraph of "Skinned meshes" applies: everything drawn before is completed and checked first, the call
+ *     is blocking, a frame posted before the call never sees the new normals, and a multi-device context recomputes on every band.
+ *   Errors, all checked before anything changes.  SWR_ERR_NO_SCENE: no scene.  SWR_ERR_BAD_ARG: a NULL ctx; an unknown mode; unknown
+ *     flag bits; a non-zero reserved word.  SWR_ERR_UNSUPPORTED: SWR_NORMALS_SMOOTH on a scene with 2^32 or more indices.
+ *     SWR_ERR_NOMEM: a device allocation fails.  A failed context returns its sticky error.  After an error the mode and the scene
+ *     are unchanged.
+ *   Cost.  SWR_NORMALS_SMOOTH builds a vertex-to-triangle adjacency once per scene, on the host, in the call (4 bytes per vertex and
+ *     per index stay resident, beside 16 per triangle and per vertex); every later rewrite of the scene pays two more kernels.
+ *     One lane sums one vertex's faces in order, so a vertex shared by thousands of triangles is slow.  SWR_NORMALS_FLAT needs
+ *     neither and pays one kernel.
+ *   Not covered: angle-weighted normals, crease angles and smoothing groups, tangents, swr_render passes (which have no field for
+ *     the mode), an un-waited call, and the C++ and Swift mirrors. */
+enum { SWR_NORMALS_UPLOADED = 0, SWR_NORMALS_SMOOTH = 1, SWR_NORMALS_FLAT = 2 };
+enum { SWR_NORMALS_FLIP = 1u << 0 };
+typedef struct swr_normals {
+    int32_t  mode;        /* SWR_NORMALS_* */
+    uint32_t flags;       /* SWR_NORMALS_FLIP or 0 */
+    int32_t  reserved[2]; /* 0 */
+} swr_normals;            /* 16 bytes */
 
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
@@ -829,6 +885,8 @@ int swr_morph_set(swr_context* ctx, const float* weights, int32_t weight_count);
 int swr_scene_morph_sparse(swr_context* ctx, const swr_morph_sparse* targets);           /* NULL: remove the targets */
 int swr_morph_pose_set(swr_context* ctx, const float* weights, int32_t weight_count,
                        const float* joints, int32_t joint_count, int32_t pose_kind);
+/* computed normals ("Computed normals" above): where the resident scene's normals come from */
+int swr_scene_normals(swr_context* ctx, const swr_normals* normals);                     /* NULL: SWR_NORMALS_UPLOADED */
 int swr_material_set(swr_context* ctx, const swr_material* material);
 int swr_texture_upload(swr_context* ctx, const void* bgra8, int32_t width, int32_t height);
 /* The blend state of SWR_FLAG_BLEND frames (see "Alpha blending" above); NULL restores the default, SWR_BLEND_OVER with opacity 255.

@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
     "swr_query_depth", "swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta",
     "swr_scene_skin", "swr_pose_set", "swr_scene_morph", "swr_morph_set", "swr_item_bounds",
-    "swr_pose_set_dq", "swr_scene_morph_sparse", "swr_morph_pose_set",
+    "swr_pose_set_dq", "swr_scene_morph_sparse", "swr_morph_pose_set", "swr_scene_normals",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -218,6 +218,16 @@ class MorphSparse(ctypes.Structure):
 
 
 POSE_MATRICES, POSE_DUAL_QUATS = 0, 1      # SWR_POSE_*: the pose_kind of swr_morph_pose_set
+
+
+class Normals(ctypes.Structure):
+    """swr_normals (include/swr.h "Computed normals"): where the resident scene's normals come from."""
+    _fields_ = [("mode", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 2)]
+
+
+NORMALS_UPLOADED, NORMALS_SMOOTH, NORMALS_FLAT = 0, 1, 2    # SWR_NORMALS_*: swr_normals.mode
+NORMALS_FLIP = 1                                             # SWR_NORMALS_FLIP: swr_normals.flags
+NORMALS_MODES = {"uploaded": NORMALS_UPLOADED, "smooth": NORMALS_SMOOTH, "flat": NORMALS_FLAT}
 
 
 def sparse_targets(dense_deltas, dense_normal_deltas=None) -> list:
@@ -438,6 +448,12 @@ def load_library():
             getattr(L, name).restype = ctypes.c_int
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack them)
+            raise
+    try:
+        L.swr_scene_normals.argtypes = [vp, ctypes.POINTER(Normals)]
+        L.swr_scene_normals.restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
             raise
     L.swr_target_write.argtypes = [vp, vp, vp]
     L.swr_target_write.restype = ctypes.c_int
@@ -667,6 +683,16 @@ class Context:
         self._check(self._L.swr_morph_pose_set(self._h, w.ctypes.data if w is not None else None, w.shape[0] if w is not None else 0,
                                                j.ctypes.data if j is not None else None, j.shape[0] if j is not None else 0,
                                                (POSE_DUAL_QUATS if dq else POSE_MATRICES) if pose_kind is None else int(pose_kind)))
+
+    def scene_normals(self, mode: "int | str | None", flip: bool = False):
+        """swr_scene_normals: the resident scene's normals as uploaded (NORMALS_UPLOADED, "uploaded"; None passes NULL), or computed on
+        the device from the positions that are drawn — per vertex (NORMALS_SMOOTH, "smooth") or per triangle (NORMALS_FLAT, "flat");
+        flip: the face vectors the other way round (SWR_NORMALS_FLIP)."""
+        if mode is None:
+            self._check(self._L.swr_scene_normals(self._h, None))
+            return
+        n = Normals(NORMALS_MODES[mode] if isinstance(mode, str) else int(mode), NORMALS_FLIP if flip else 0, (ctypes.c_int32 * 2)(0, 0))
+        self._check(self._L.swr_scene_normals(self._h, ctypes.byref(n)))
 
     def material_set(self, material: "Material | None"):
         self._check(self._L.swr_material_set(self._h, ctypes.byref(material) if material is not None else None))

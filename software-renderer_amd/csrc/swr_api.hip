@@ -176,7 +176,7 @@ static_assert(sizeof(swr_render_pass) == 192 && sizeof(swr_material) == 56 && si
               sizeof(swr_vertex) == 32 && sizeof(swr_config) == 16 && sizeof(swr_render_times) == 28 && sizeof(swr_blend) == 16 &&
               sizeof(swr_resolve) == 16 && sizeof(swr_id_count) == 32 && sizeof(swr_depth_box) == 32 && sizeof(swr_delta_stats) == 48 &&
               sizeof(swr_skin_vertex) == 32 && sizeof(swr_morph_targets) == 32 && sizeof(swr_item_bound) == 48 &&
-              sizeof(swr_morph_sparse_target) == 32 && sizeof(swr_morph_sparse) == 24,
+              sizeof(swr_morph_sparse_target) == 32 && sizeof(swr_morph_sparse) == 24 && sizeof(swr_normals) == 16,
               "include/swr.h layouts (mirrored by the ctypes / Swift bindings)");
 
 struct swr_context {
@@ -262,6 +262,13 @@ struct swr_context {
     DevBuf morph_touched, morph_row, morph_w_dev;
     bool morph_sparse = false;          // the resident targets are sparse ones
     int64_t morph_touched_count = 0;    // rows (0: every target is empty, nothing is ever launched)
+    // computed normals (swr_scene_normals): the mode and flags of the scene (in effect while it has attributes); the
+    // adjacency swr_scene_normals(SMOOTH) builds once per scene, as swr_internal.h lays it out; the face vectors and the vertex
+    // normals the two SMOOTH kernels write
+    int32_t normals_mode = SWR_NORMALS_UPLOADED;
+    uint32_t normals_flags = 0;
+    bool adj_built = false;             // adj_off / adj_tri hold the adjacency of the resident scene
+    DevBuf adj_off, adj_tri, face, auto_nrm;
 
     // target band (RenderPass.colorBuffer / .depthBuffer), double-buffered in HBM: swr_present copies the frame just
     // drawn to the host while the next swr_draw renders into the other buffer
@@ -1524,11 +1531,16 @@ int prefill_sparse(swr_context* c, bool positions, bool attrs);
 int enqueue_pose(swr_context* c, bool with_nrm) {
     const int64_t ntri = c->ni / 3;
     int rc;
+    // computed normals take effect while the scene has attributes: the vertex passes then leave the normals out
+    // (their NRM = false variants), and the normals come from the positions that are last, between the vertex passes and the stream
+    const int32_t computed = with_nrm ? c->normals_mode : SWR_NORMALS_UPLOADED;
+    const bool flip = (c->normals_flags & SWR_NORMALS_FLIP) != 0;
+    const bool vnrm = with_nrm && computed == SWR_NORMALS_UPLOADED;     // the vertex passes carry the uploaded normals along
     const swr_vertex* v = (const swr_vertex*)c->vertices.p;
-    const swr_vertex_attr* at = with_nrm ? (const swr_vertex_attr*)c->attrs.p : nullptr;
+    const swr_vertex_attr* at = vnrm ? (const swr_vertex_attr*)c->attrs.p : nullptr;
     if (c->morph_active && c->morph_sparse) {
         // sparse targets: the touched vertices are rewritten from the base; everywhere else the morphed arrays hold the pre-fill
-        const bool mnrm = with_nrm && c->morph_has_nrm;
+        const bool mnrm = vnrm && c->morph_has_nrm;
         if (c->morph_touched_count > 0) {
             HIP_TRY(c, hipMemcpyAsync(c->morph_w_dev.p, c->morph_w.data(), c->morph_w.size() * 4, hipMemcpyHostToDevice, c->stream));
             MorphSparseArgs a{};
@@ -1542,7 +1554,7 @@ int enqueue_pose(swr_context* c, bool with_nrm) {
         v = (const swr_vertex*)c->morphed.p;
         if (mnrm) at = (const swr_vertex_attr*)c->morphed_attrs.p;
     } else if (c->morph_active) {
-        const bool mnrm = with_nrm && c->morph_has_nrm;         // (else the normals stay as uploaded)
+        const bool mnrm = vnrm && c->morph_has_nrm;             // (else the normals stay as uploaded)
         c->morph_list.clear();
         for (int32_t t = 0; t < c->morph_targets; t++)
             if (c->morph_w[t] != 0.0f) c->morph_list.push_back(MorphEntry{(uint32_t)t, c->morph_w[t]});
@@ -1559,7 +1571,7 @@ int enqueue_pose(swr_context* c, bool with_nrm) {
     }
     if (c->pose_active) {
         if ((rc = ensure(c, c->posed, (size_t)c->nv * sizeof(swr_vertex)))) return rc;
-        if (with_nrm && (rc = ensure(c, c->posed_nrm, (size_t)c->nv * 16))) return rc;
+        if (vnrm && (rc = ensure(c, c->posed_nrm, (size_t)c->nv * 16))) return rc;
         if ((rc = ensure(c, c->pose_dev, c->pose.size() * 4))) return rc;
         if (!c->pose.empty())
             HIP_TRY(c, hipMemcpyAsync(c->pose_dev.p, c->pose.data(), c->pose.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -1569,6 +1581,24 @@ int enqueue_pose(swr_context* c, bool with_nrm) {
         else
             launch_skin_vertices(v, at, (const swr_skin_vertex*)c->skin.p, c->nv, (const float*)c->pose_dev.p,
                                  (int32_t)(c->pose.size() / 16), (swr_vertex*)c->posed.p, (float4*)c->posed_nrm.p, c->stream);
+        v = (const swr_vertex*)c->posed.p;
+    }
+    if (computed != SWR_NORMALS_UPLOADED) {
+        // `v` is the vertex array the frame draws: the scene's, the morphed or the posed one
+        if (computed == SWR_NORMALS_SMOOTH) {
+            if ((rc = ensure(c, c->face, (size_t)ntri * 16))) return rc;
+            if ((rc = ensure(c, c->auto_nrm, (size_t)c->nv * 16))) return rc;
+            launch_face_normals((const float4*)v, 2, c->nv, (const int64_t*)c->indices.p, ntri, flip, (float4*)c->face.p, c->stream);
+            launch_vertex_normals((const uint32_t*)c->adj_off.p, (const uint32_t*)c->adj_tri.p, (const float4*)c->face.p, c->nv,
+                                  (float4*)c->auto_nrm.p, c->stream);
+            launch_skin_stream((const float4*)v, 2, (const float4*)c->auto_nrm.p, 1, c->nv, (const int64_t*)c->indices.p, ntri,
+                               c->reordered ? 1 : 0, (float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->box64.p, c->stream);
+        } else {
+            launch_skin_stream((const float4*)v, 2, nullptr, 1, c->nv, (const int64_t*)c->indices.p, ntri, c->reordered ? 1 : 0,
+                               (float4*)c->tri_xyz.p, nullptr, (float4*)c->box64.p, c->stream);
+            launch_flat_normals((const float4*)c->tri_xyz.p, ntri, flip, (float4*)c->tri_nrm.p, c->stream);
+        }
+    } else if (c->pose_active) {
         launch_skin_stream((const float4*)c->posed.p, 2, with_nrm ? (const float4*)c->posed_nrm.p : nullptr, 1, c->nv,
                            (const int64_t*)c->indices.p, ntri, c->reordered ? 1 : 0, (float4*)c->tri_xyz.p,
                            with_nrm ? (float4*)c->tri_nrm.p : nullptr, (float4*)c->box64.p, c->stream);
@@ -1615,6 +1645,7 @@ int single_scene_upload(swr_context* c, const swr_vertex* vertices, int64_t vert
     c->has_skin = false; c->skin_max_joint = -1;     // (a new scene has neither skin nor pose)
     c->pose_active = false; c->pose_dq = false; c->pose.clear();
     drop_morph(c);                                   // (nor morph targets)
+    c->normals_mode = SWR_NORMALS_UPLOADED; c->normals_flags = 0; c->adj_built = false;   // (nor a normals mode: the adjacency is the old indices')
     c->draw_pending = false;
     c->last_draw.is_list = false;
     c->ids_valid = false;            // the IDs number the primitives of the scene that is going: swr_count_ids has no n for them any more
@@ -1740,8 +1771,8 @@ int single_scene_attributes(swr_context* c, const swr_vertex_attr* attributes, i
                         (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
     HIP_TRY(c, hipGetLastError());
     if ((rc = prefill_sparse(c, false, true))) return rc;       // (sparse normal deltas given earlier take effect on these attributes)
-    // (the gather wrote the uploaded normals: morph and pose them)
-    if ((c->pose_active || c->morph_active) && (rc = enqueue_pose(c, true))) return rc;
+    // (the gather wrote the uploaded normals: morph and pose them, or, under a computed mode given earlier, replace them)
+    if ((c->pose_active || c->morph_active || c->normals_mode != SWR_NORMALS_UPLOADED) && (rc = enqueue_pose(c, true))) return rc;
     if ((rc = wait_stream(c, c->stream, "attribute upload"))) return or_sticky(c, rc);
     c->has_attrs = true;
     return SWR_OK;
@@ -2097,6 +2128,73 @@ int single_morph_pose_set(swr_context* c, const float* weights, int32_t weight_c
     return SWR_OK;
 }
 
+// swr_scene_normals: where the resident scene's normals come from (n == NULL: as uploaded), in effect when the call returns — once
+// the scene has attributes.  SWR_NORMALS_SMOOTH needs the adjacency: built here, once per scene, on the host, by a counting sort of
+// the corners by vertex that keeps corner order — O(vertices + corners) — from the index array as the device holds it.  Everything
+// that can fail is done before the mode changes: the new buffers are the context's only then.
+int single_scene_normals(swr_context* c, const swr_normals* n) {
+    const char* fn = "swr_scene_normals";
+    if (const int f = sticky(c)) return f;
+    if (!c->has_scene) return fail(c, SWR_ERR_NO_SCENE, "%s needs swr_scene_upload first", fn);
+    const int32_t mode = n ? n->mode : SWR_NORMALS_UPLOADED;
+    const uint32_t flags = n ? n->flags : 0;
+    if (mode != SWR_NORMALS_UPLOADED && mode != SWR_NORMALS_SMOOTH && mode != SWR_NORMALS_FLAT)
+        return fail(c, SWR_ERR_BAD_ARG, "%s: unknown mode %d", fn, mode);
+    if (flags & ~(uint32_t)SWR_NORMALS_FLIP) return fail(c, SWR_ERR_BAD_ARG, "%s: unknown flags 0x%x", fn, flags);
+    if (n && (n->reserved[0] != 0 || n->reserved[1] != 0)) return fail(c, SWR_ERR_BAD_ARG, "%s: reserved must be 0", fn);
+    if (mode == SWR_NORMALS_SMOOTH && c->ni >= ((int64_t)1 << 32))
+        return fail(c, SWR_ERR_UNSUPPORTED, "%s: smooth normals of %lld indices (fewer than 2^32)", fn, (long long)c->ni);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = check_frames(c))) return rc;      // (every stream idle; an overflowed last frame redrawn with the normals it was drawn with)
+    if (mode == c->normals_mode && flags == c->normals_flags) return SWR_OK;
+    auto alloc = [&](DevBuf& b, size_t bytes) {         // a buffer of its own: the context's stay until nothing can fail any more
+        bytes = std::max<size_t>(16, bytes);
+        const hipError_t e = hipMalloc(&b.p, bytes);
+        if (e != hipSuccess) {
+            b.p = nullptr;
+            return fail(c, SWR_ERR_NOMEM, "%s: hipMalloc(%zu) failed: %s", fn, bytes, hipGetErrorString(e));
+        }
+        b.bytes = bytes;
+        return (int)SWR_OK;
+    };
+    DevBuf doff, dtri, dface, dnrm;
+    if (mode == SWR_NORMALS_SMOOTH) {
+        const size_t nv = (size_t)c->nv, corners = (size_t)(c->ni / 3) * 3;     // (trailing indices belong to no triangle)
+        if (c->face.bytes < (corners / 3) * 16 && (rc = alloc(dface, (corners / 3) * 16))) return rc;
+        if (c->auto_nrm.bytes < nv * 16 && (rc = alloc(dnrm, nv * 16))) return rc;
+        if (!c->adj_built) {
+            std::vector<int64_t> idx(corners);
+            if (corners) HIP_TRY(c, hipMemcpyAsync(idx.data(), c->indices.p, corners * 8, hipMemcpyDeviceToHost, c->stream));
+            if ((rc = wait_stream(c, c->stream, "index download"))) return or_sticky(c, rc);
+            std::vector<uint32_t> off(nv + 1, 0), tri(corners);
+            for (size_t e = 0; e < corners; e++) {
+                if (idx[e] < 0 || (uint64_t)idx[e] >= (uint64_t)nv)     // (never: the upload validated the indices)
+                    return fail(c, SWR_ERR_INDEX_RANGE, "%s: index %lld of %zu vertices", fn, (long long)idx[e], nv);
+                off[(size_t)idx[e] + 1]++;
+            }
+            for (size_t i = 0; i < nv; i++) off[i + 1] += off[i];
+            std::vector<uint32_t> cursor(off.begin(), off.end() - 1);
+            for (size_t e = 0; e < corners; e++) tri[cursor[(size_t)idx[e]]++] = (uint32_t)(e / 3);
+            if ((rc = alloc(doff, off.size() * 4))) return rc;
+            if ((rc = alloc(dtri, tri.size() * 4))) return rc;
+            size_t chunks = 0;
+            if ((rc = upload_staged(c, doff.p, off.data(), off.size() * 4, chunks))) return rc;
+            if ((rc = upload_staged(c, dtri.p, tri.data(), tri.size() * 4, chunks))) return rc;
+            if ((rc = wait_stream(c, c->stream, "adjacency upload"))) return or_sticky(c, rc);
+        }
+    }
+    if (doff.p) { c->adj_off = std::move(doff); c->adj_tri = std::move(dtri); c->adj_built = true; }
+    if (dface.p) c->face = std::move(dface);
+    if (dnrm.p) c->auto_nrm = std::move(dnrm);
+    c->normals_mode = mode;
+    c->normals_flags = flags;
+    if (!c->has_attrs) return SWR_OK;           // (kept: it takes effect when swr_scene_attributes arrives)
+    if ((rc = enqueue_pose(c, true))) return rc;
+    if ((rc = wait_stream(c, c->stream, "normals"))) return or_sticky(c, rc);
+    return SWR_OK;
+}
+
 int single_material_set(swr_context* c, const swr_material* m) {
     if (!m) { c->material = swr_material{}; return SWR_OK; }
     if (m->shader != SWR_SHADER_PASSTHROUGH && m->shader != SWR_SHADER_PHONG && m->shader != SWR_SHADER_TEXTURED_PHONG)
@@ -2325,8 +2423,9 @@ int restream(swr_context* c, const std::vector<uint32_t>& cuts) {
         launch_gather_attrs((const swr_vertex_attr*)c->attrs.p, c->nv, (const int64_t*)c->indices.p, ntri,
                             (const float4*)c->tri_xyz.p, (float4*)c->tri_nrm.p, (float4*)c->tri_rgb.p, c->stream);
     HIP_TRY(c, hipGetLastError());
-    // (the rebuild gathered the uploaded scene: morph and pose it again)
-    if ((c->pose_active || c->morph_active) && (rc = enqueue_pose(c, c->has_attrs))) return rc;
+    // (the rebuild gathered the uploaded scene: morph and pose it again, and compute its normals again)
+    if ((c->pose_active || c->morph_active || (c->has_attrs && c->normals_mode != SWR_NORMALS_UPLOADED)) &&
+        (rc = enqueue_pose(c, c->has_attrs))) return rc;
     if ((rc = wait_stream(c, c->stream, "stream rebuild (draw list)"))) return or_sticky(c, rc);
     c->cuts = cuts;
     return SWR_OK;
@@ -3245,6 +3344,12 @@ int swr_morph_pose_set(swr_context* c, const float* weights, int32_t weight_coun
     if (!c) return SWR_ERR_BAD_ARG;
     c->scene_id = 0;      // (the same)
     return fan(c, [=](swr_context* k) { return single_morph_pose_set(k, weights, weight_count, joints, joint_count, pose_kind); });
+}
+
+int swr_scene_normals(swr_context* c, const swr_normals* normals) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    c->scene_id = 0;      // (the same)
+    return fan(c, [=](swr_context* k) { return single_scene_normals(k, normals); });
 }
 
 int swr_material_set(swr_context* c, const swr_material* m) {

@@ -367,4 +367,26 @@ void launch_morph_sparse(const MorphSparseArgs& a, hipStream_t s);
 inline void launch_morph_sparse(const MorphSparseArgs&, hipStream_t) {}
 #endif
 
+// swr_normals.hip: computed normals.  launch_face_normals writes face[p] = (f_p, 0) of include/swr.h "Computed
+// normals" for the ntri triangles of `indices`, from the vertex array in effect — the pos, pos_stride pair launch_skin_stream takes;
+// flip: SWR_NORMALS_FLIP.  launch_vertex_normals writes auto_nrm[i] = (n_i, 0) for the nv vertices: the faces of row i of the
+// adjacency added in row order, then normalised.  adj_off[nv + 1] are the row bounds, adj_tri[adj_off[nv]] the triangle of every
+// corner that names the vertex, ascending by corner number 3p + k, duplicates kept (the host built it: swr_scene_normals); every
+// entry is below ntri.  launch_skin_stream, given auto_nrm with stride 1, then writes the stream.  launch_flat_normals writes the xyz
+// lanes of tri_nrm[3s + k], k = 0..2, = f of the xyz lanes of tri_xyz[3s .. 3s + 2] for the ntri slots of the stream (after
+// launch_skin_stream has written its positions); the w lanes stay.  All pointers are device memory.
+#if defined(__HIPCC__) || defined(SWR_HOST_TEST_NORMALS)
+void launch_face_normals(const float4* pos, int pos_stride, int64_t nv, const int64_t* indices, int64_t ntri, bool flip, float4* face,
+                         hipStream_t s);
+void launch_vertex_normals(const uint32_t* adj_off, const uint32_t* adj_tri, const float4* face, int64_t nv, float4* auto_nrm,
+                           hipStream_t s);
+void launch_flat_normals(const float4* tri_xyz, int64_t ntri, bool flip, float4* tri_nrm, hipStream_t s);
+#else
+// (host test programs built without SWR_HOST_TEST_NORMALS link a launch set that predates these launches and never call
+// swr_scene_normals: nothing is enqueued.  The product is always compiled by hipcc and references the launches plainly.)
+inline void launch_face_normals(const float4*, int, int64_t, const int64_t*, int64_t, bool, float4*, hipStream_t) {}
+inline void launch_vertex_normals(const uint32_t*, const uint32_t*, const float4*, int64_t, float4*, hipStream_t) {}
+inline void launch_flat_normals(const float4*, int64_t, bool, float4*, hipStream_t) {}
+#endif
+
 }  // namespace swr

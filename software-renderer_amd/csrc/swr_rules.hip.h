@@ -140,6 +140,18 @@ __device__ __forceinline__ uint32_t quantize_bgra(float4 f) {
     return (uint32_t)ub | ((uint32_t)ug << 8) | ((uint32_t)ur << 16) | ((uint32_t)ua << 24);
 }
 
+// ---- the cross product -----------------------------------------------------------------------------------------------------------
+// include/swr.h "Dual-quaternion skinning": two products and one subtraction per component, each rounded.  The rotation of the
+// dual-quaternion skin and the face vector of the computed normals (swr_normals.hip).
+struct Vec3 { float x, y, z; };
+__device__ __forceinline__ Vec3 cross3(const Vec3 a, const Vec3 b) {
+    Vec3 r;
+    r.x = a.y * b.z - a.z * b.y;
+    r.y = a.z * b.x - a.x * b.z;
+    r.z = a.x * b.y - a.y * b.x;
+    return r;
+}
+
 // ---- draw lists --------------------------------------------------------------------------------------------------
 // The item of frame slot v (UNITS: of work unit v — k_bin<LIST>'s and k_item_bounds'): the last item whose vbase (ubase) is <= v.  Empty
 // items share their base with the next item and are passed over; item 0 starts at 0.  (A binary search over <= SWR_DRAW_LIST_MAX items.)

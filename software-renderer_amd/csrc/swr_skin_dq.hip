@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "swr_internal.h"
+#include "swr_rules.hip.h"
 
 namespace swr {
 
@@ -30,17 +31,6 @@ struct SkinDqArgs {
     int64_t nv;
     int32_t joint_count;
 };
-
-struct Vec3 { float x, y, z; };
-
-// two products, one subtraction per component
-__device__ __forceinline__ Vec3 cross3(const Vec3 a, const Vec3 b) {
-    Vec3 r;
-    r.x = a.y * b.z - a.z * b.y;
-    r.y = a.z * b.x - a.x * b.z;
-    r.z = a.x * b.y - a.y * b.x;
-    return r;
-}
 
 // a = cross(q, x);  b = a + w*x;  c = cross(q, b);  rot(x) = x + 2*c
 __device__ __forceinline__ Vec3 dq_rotate(const Vec3 q, const float w, const Vec3 x) {
