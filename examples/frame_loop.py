@@ -516,11 +516,27 @@ def use_auto_normals(ctx, vertices: np.ndarray, mode: str | None):
         ctx.scene_normals(mode)
 
 
+def pick_ray(ctx, transform, size: int, pick, frame: int):
+    """--pick X,Y on a deforming mesh: the ray through the centre of that pixel, from depth 0 to depth 1 in object space
+    (binding.pixel_ray), cast against the resident triangles as they are now (swr_cast_rays).  Prints the triangle, t and the hit point;
+    returns the hit record."""
+    ray = swr_amd.binding.pixel_ray(transform, size, size, pick[0], pick[1])
+    hit = ctx.cast_rays(ray.reshape(1))[0]
+    if hit["primitive"] == swr_amd.binding.ID_NONE:
+        print(f"frame {frame}: pixel {pick}: no triangle on the ray")
+    else:
+        p = ray["origin"] + hit["t"] * ray["dir"]
+        print(f"frame {frame}: pixel {pick}: triangle {hit['primitive']}, t {hit['t']:.6f}, u {hit['u']:.4f}, v {hit['v']:.4f}, "
+              f"hit point ({p[0]:.5f}, {p[1]:.5f}, {p[2]:.5f})")
+    return hit
+
+
 def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, device_count: int = 1,
-             dq: bool = False, auto_normals: str | None = None):
+             dq: bool = False, auto_normals: str | None = None, pick=None):
     """The resident loop with a deforming mesh: a torus skinned to two joints, a new pose every frame (swr_pose_set), the app's
     transform.  dq: the pose is twist_pose, which also twists the torus, set as dual quaternions (swr_pose_set_dq).  auto_normals
     ("smooth" / "flat"): lit by a Phong material with normals recomputed on the device after every pose (swr_scene_normals).
+    pick (x, y): the triangle and the point of the posed mesh on that pixel's ray, every frame (pick_ray).
     Returns the mesh and the (colour, depth) frames."""
     xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
     vertices = S.pack_vertices(xyz, rgb)
@@ -538,6 +554,8 @@ def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = 
             else:
                 ctx.pose_set(bend_pose(time))
             ctx.draw(S.app_transform(time), flags)
+            if pick:
+                pick_ray(ctx, S.app_transform(time), size, pick, k)
             results.append((ctx.read_color(), ctx.read_depth()))
             if out:
                 os.makedirs(out, exist_ok=True)
@@ -568,13 +586,15 @@ def morph_weights(time: float) -> np.ndarray:
 
 
 def run_morph(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, skin: bool = False,
-              device_count: int = 1, obj: str | None = None, dq: bool = False, sparse: bool = False, auto_normals: str | None = None):
+              device_count: int = 1, obj: str | None = None, dq: bool = False, sparse: bool = False, auto_normals: str | None = None,
+              pick=None):
     """The resident loop with a mesh that changes its shape: two morph targets uploaded once (swr_scene_morph), new weights every
     frame (swr_morph_set), the app's transform.  skin: the torus of run_skin, morphed and then posed (swr_pose_set, or with dq
     swr_pose_set_dq and twist_pose) every frame.  sparse: the targets are uploaded as sparse ones, restricted to the vertices they
     move (swr_scene_morph_sparse), and with skin the weights and the pose are set by one call (swr_morph_pose_set).
     auto_normals ("smooth" / "flat"): lit by a Phong material with normals recomputed on the device after every change of shape
-    (swr_scene_normals): the targets carry no normal deltas.  Returns the mesh and the (colour, depth) frames."""
+    (swr_scene_normals): the targets carry no normal deltas.  pick (x, y): the triangle and the point of the deformed mesh on that
+    pixel's ray, every frame (pick_ray).  Returns the mesh and the (colour, depth) frames."""
     if skin:
         xyz, rgb, indices = S.torus_mesh(96, 32, 0.3, 0.1)
         vertices = S.pack_vertices(xyz, rgb)
@@ -604,6 +624,8 @@ def run_morph(frames: int, size: int, out: str | None = None, depth_test: bool =
                 elif skin:
                     ctx.pose_set(pose)
             ctx.draw(S.app_transform(time), flags)
+            if pick:
+                pick_ray(ctx, S.app_transform(time), size, pick, k)
             results.append((ctx.read_color(), ctx.read_depth()))
             if out:
                 os.makedirs(out, exist_ok=True)
@@ -623,7 +645,9 @@ if __name__ == "__main__":
     ap.add_argument("--stream", action="store_true", help="asynchronous presents into two page-locked image sets")
     ap.add_argument("--gpus", type=int, default=1, help="bands / GPUs of the one context (with --stream)")
     ap.add_argument("--objects", type=int, default=1, help="copies of the mesh, each with its own matrix: one draw list per frame")
-    ap.add_argument("--pick", default=None, help="X,Y: print the copy and the triangle under that pixel every frame (primitive IDs)")
+    ap.add_argument("--pick", default=None,
+                    help="X,Y: print the copy and the triangle under that pixel every frame (primitive IDs); with --skin / --morph: the "
+                         "triangle, t and the hit point of that pixel's ray on the deformed mesh (swr_cast_rays)")
     ap.add_argument("--ids", action="store_true",
                     help="write the ID image and print the last frame's visibility counts: visible triangles, pixels per copy (swr_count_ids)")
     ap.add_argument("--occlusion", action="store_true",
@@ -681,17 +705,18 @@ if __name__ == "__main__":
     if deforming_bounds and (a.obj or a.ply or a.stream or a.delta or a.glass is not None):
         ap.error("--occlusion --bounds with --skin / --morph draws copies of the torus: not with --obj, --ply, --stream, --delta or --glass")
     if a.morph and not deforming_bounds:
-        if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or (a.skin and (a.obj or a.ply)):
-            ap.error("--morph is its own loop: only --frames, --size, --out, --depth-test, --gpus, --skin and (without --skin) --obj / --ply apply")
+        if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.ids or a.occlusion or (a.skin and (a.obj or a.ply)):
+            ap.error("--morph is its own loop: only --frames, --size, --out, --depth-test, --gpus, --pick, --skin and (without --skin) --obj / --ply apply")
         _, idx, res = run_morph(a.frames, a.size, a.out, a.depth_test, skin=a.skin, device_count=a.gpus, obj=a.ply or a.obj, dq=a.dq, sparse=a.sparse,
-                              auto_normals=a.auto_normals)
+                              auto_normals=a.auto_normals, pick=tuple(int(t) for t in a.pick.split(",")) if a.pick else None)
         print(f"{a.frames} morphed{' and posed' if a.skin else ''} frames, {idx.size // 3} triangles, "
               f"coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
     if a.skin and not deforming_bounds:
-        if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.pick or a.ids or a.occlusion or a.obj or a.ply:
-            ap.error("--skin is its own loop over its own mesh: only --frames, --size, --out, --depth-test and --gpus apply")
-        _, idx, res = run_skin(a.frames, a.size, a.out, a.depth_test, device_count=a.gpus, dq=a.dq, auto_normals=a.auto_normals)
+        if a.stream or a.delta or a.ssaa != 1 or a.glass is not None or a.objects > 1 or a.ids or a.occlusion or a.obj or a.ply:
+            ap.error("--skin is its own loop over its own mesh: only --frames, --size, --out, --depth-test, --gpus and --pick apply")
+        _, idx, res = run_skin(a.frames, a.size, a.out, a.depth_test, device_count=a.gpus, dq=a.dq, auto_normals=a.auto_normals,
+                               pick=tuple(int(t) for t in a.pick.split(",")) if a.pick else None)
         print(f"{a.frames} posed frames, {idx.size // 3} triangles, coverage per frame: {[round(float((c[..., 3] == 255).mean()), 4) for c, _ in res]}")
         sys.exit(0)
     if a.delta:

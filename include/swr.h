@@ -663,6 +663,58 @@ typedef struct swr_normals {
     int32_t  reserved[2]; /* 0 */
 } swr_normals;            /* 16 bytes */
 
+/* ---- Ray casts (swr_cast_rays) — DESIGN.md §30 --------------------------------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_cast_rays symbol is the feature test.  Nothing
+ * existing changes.  Once a scene is morphed and posed on the device, the vertices an object is drawn from exist only there.
+ * swr_cast_rays answers "what does this line hit?" against them: hits[k] is the nearest accepted hit of rays[k], for n rays a call.
+ *   Space.  Rays are in the space of the resident vertices: object space, the scene as it is now — morphed, posed, and with whatever
+ *     swr_scene_upload gave.  No transform is applied: a caller with a draw item's transform brings the ray into that space itself.
+ *   Which triangles.  Triangle p has the corners a, b, c = the positions of indices[3p], indices[3p + 1], indices[3p + 2], for
+ *     p < index_count / 3, whatever the primitive type of later draws; trailing indices are ignored.
+ *   Result.  hits[k].primitive is p in the numbering of the index array, as primitive IDs use it; t, u, v come from the arithmetic
+ *     below.  The hit point is origin + t*dir, or equivalently (1-u-v)*a + u*b + v*c.  A miss is primitive = SWR_ID_NONE,
+ *     t = u = v = 0.
+ *   Arithmetic (normative): IEEE binary32, one rounding per operation, no FMA; / is correctly rounded.
+ *     dot(x, y) = (x.x*y.x + x.y*y.y) + x.z*y.z;  cross exactly as "Dual-quaternion skinning" defines it: two products and one
+ *     subtraction per component.  Per ray and triangle:
+ *     1. Skip.  A triangle with a corner coordinate that is not finite is never hit (the frames skip it too).
+ *     2. Box pre-test.  Start [nr, fr] = [tmin, tmax].  For each axis j = x, y, z:  lo = the smallest and hi = the largest of the
+ *        three corners' coordinate j;  r = 1.0f / dir[j].
+ *          If dir[j] == 0.0f or !(fabsf(r) <= FLT_MAX), the axis is parallel: the triangle is rejected unless
+ *            lo <= origin[j] && origin[j] <= hi.
+ *          Otherwise  t0 = (lo - origin[j]) * r;  t1 = (hi - origin[j]) * r;  near = t0 < t1 ? t0 : t1;  far = t0 < t1 ? t1 : t0;
+ *            nr = near > nr ? near : nr;  fr = far < fr ? far : fr.
+ *        After the three axes the triangle is rejected unless nr <= fr.  With finite inputs none of these values is a NaN: on an
+ *        axis that is not parallel r is finite and not zero, so t0 and t1 are products of a finite number or an infinity (a
+ *        difference that overflowed) with a finite non-zero number, never 0 * inf and never inf - inf.  The pre-test is normative:
+ *        it may reject a triangle the next step would graze, and it is what lets an implementation cull whole groups exactly.
+ *     3. Moeller-Trumbore.  e1 = b - a;  e2 = c - a;  pv = cross(dir, e2);  det = dot(e1, pv).  Reject unless fabsf(det) > 0.0f.
+ *        inv = 1.0f / det;  tv = origin - a;  u = dot(tv, pv) * inv.  Reject unless u >= 0.0f && u <= 1.0f.
+ *        qv = cross(tv, e1);  v = dot(dir, qv) * inv.  Reject unless v >= 0.0f && u + v <= 1.0f.
+ *        t = dot(e2, qv) * inv + 0.0f (a zero comes out as +0).  Reject unless t >= tmin && t <= tmax.
+ *        Both facings are hit.  A comparison with a NaN (an overflowed intermediate) rejects.
+ *     4. Winner.  Of the accepted triangles the one with the smallest t wins; on equal t the smallest p.  This does not depend on any
+ *        order of evaluation: the result is bit-defined.
+ *   State.  The call changes nothing: the next frame, read and query are bit for bit what they would have been without it.
+ *   Ordering.  Blocking, as swr_item_bounds: everything posted before is completed and checked first.  A multi-device context answers
+ *     from its first band's copy of the scene (the scene is replicated).
+ *   Errors, all checked before anything runs.  SWR_ERR_NO_SCENE: no scene.  SWR_ERR_BAD_ARG: a NULL ctx; n < 0; NULL rays or hits with
+ *     n > 0; flags != 0; a ray with a float that is not finite; an all-zero direction; tmin > tmax — the message names the ray's index.
+ *     SWR_ERR_UNSUPPORTED: n > SWR_RAYS_MAX.  SWR_ERR_NOMEM: an allocation fails.  A failed context returns its sticky error.
+ *     n == 0 succeeds.  A scene without triangles answers every ray with a miss.
+ *   Not covered: any-hit / occlusion-only rays; the facing of the hit and face culling; rays restricted to an index range or a draw
+ *     item; more than one hit per ray; watertight edges (a ray that grazes an edge or a triangle's box can miss both neighbours, as
+ *     with any Moeller-Trumbore test); an un-waited call; and the C++ and Swift mirrors. */
+typedef struct swr_ray {
+    float origin[3]; float tmin;
+    float dir[3];    float tmax;
+} swr_ray;                /* 32 bytes */
+typedef struct swr_ray_hit {
+    uint32_t primitive;   /* SWR_ID_NONE: a miss */
+    float t, u, v;
+} swr_ray_hit;            /* 16 bytes */
+#define SWR_RAYS_MAX (1 << 16)
+
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
  * continues from the image already there.
@@ -985,6 +1037,8 @@ int swr_query_depth(swr_context* ctx, const swr_depth_box* boxes, int64_t n, uin
 /* Item bounds (see "Item bounds" above): swr_sync + the copy of the items + a reduction of the resident triangle stream on the device +
  * the copy of the item_count records + wait.  items and out have item_count elements. */
 int swr_item_bounds(swr_context* ctx, const swr_draw_item* items, int32_t item_count, uint32_t flags, swr_item_bound* out);
+/* the nearest hit of each of n rays on the resident triangles (see "Ray casts" above; blocking) */
+int swr_cast_rays(swr_context* ctx, const swr_ray* rays, int64_t n, uint32_t flags /* 0 */, swr_ray_hit* hits);
 /* Delta reads (see "Delta reads" above): swr_sync + the compare against the band's baseline on the device + the copy of the tile
  * flags + the copy of the changed rectangle + wait.  dst is the full W x H image, as for swr_read_*; stats may be NULL. */
 int swr_read_color_delta(swr_context* ctx, void*  dst_full_image, swr_delta_stats* stats);

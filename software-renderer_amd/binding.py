@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "swr_blend_set", "swr_read_color_resolved", "swr_read_depth_resolved", "swr_render_resolved", "swr_count_ids",
     "swr_query_depth", "swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta",
     "swr_scene_skin", "swr_pose_set", "swr_scene_morph", "swr_morph_set", "swr_item_bounds",
-    "swr_pose_set_dq", "swr_scene_morph_sparse", "swr_morph_pose_set", "swr_scene_normals",
+    "swr_pose_set_dq", "swr_scene_morph_sparse", "swr_morph_pose_set", "swr_scene_normals", "swr_cast_rays",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -228,6 +228,38 @@ class Normals(ctypes.Structure):
 NORMALS_UPLOADED, NORMALS_SMOOTH, NORMALS_FLAT = 0, 1, 2    # SWR_NORMALS_*: swr_normals.mode
 NORMALS_FLIP = 1                                             # SWR_NORMALS_FLIP: swr_normals.flags
 NORMALS_MODES = {"uploaded": NORMALS_UPLOADED, "smooth": NORMALS_SMOOTH, "flat": NORMALS_FLAT}
+
+RAYS_MAX = 1 << 16           # SWR_RAYS_MAX: rays per swr_cast_rays call
+# swr_ray and swr_ray_hit as numpy records (include/swr.h "Ray casts"): what Context.cast_rays takes and returns
+RAY_DTYPE = np.dtype([("origin", np.float32, (3,)), ("tmin", np.float32), ("dir", np.float32, (3,)), ("tmax", np.float32)])
+RAY_HIT_DTYPE = np.dtype([("primitive", np.uint32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
+
+
+def pixel_ray(transform, W: int, H: int, x, y) -> np.ndarray:
+    """The object-space ray(s) through the centre of pixel (x, y) of a W x H target drawn with `transform` (16 floats, column-major, as
+    for draw): a RAY_DTYPE record, or an array of them when x and y are arrays.  The ray runs from NDC depth 0 (t = 0) to depth 1
+    (t = 1): origin and origin + dir are the un-projected near and far points, tmin = 0, tmax = 1, and `dir` is not normalised.  The
+    matrix is inverted on the host in float64; a singular one raises numpy.linalg.LinAlgError.  A projection without a far plane
+    (depth 1 lies at infinity, like scenes.app_transform's) gives the direction towards it instead: the point of depth d is then
+    origin + d / (1 - d) * dir, and tmax is the largest float."""
+    m = np.asarray(transform, dtype=np.float64).reshape(4, 4).T       # (column-major in memory)
+    inv = np.linalg.inv(m)
+    xs, ys = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
+    nx = (xs + 0.5) / W * 2.0 - 1.0
+    ny = 1.0 - (ys + 0.5) / H * 2.0
+    one = np.ones_like(nx)
+    near = np.stack([nx, ny, 0.0 * one, one], axis=-1) @ inv.T
+    far = np.stack([nx, ny, one, one], axis=-1) @ inv.T
+    origin = near[..., :3] / near[..., 3:]
+    infinite = np.abs(far[..., 3:]) <= 1e-12 * np.abs(near[..., 3:])
+    wf = np.where(infinite, 1.0, far[..., 3:])
+    direction = np.where(infinite, far[..., :3] / near[..., 3:], far[..., :3] / wf - origin)
+    rays = np.zeros(xs.shape, dtype=RAY_DTYPE)
+    rays["origin"] = origin
+    rays["dir"] = direction
+    rays["tmin"] = 0.0
+    rays["tmax"] = np.where(infinite[..., 0], np.finfo(np.float32).max, 1.0)
+    return rays
 
 
 def sparse_targets(dense_deltas, dense_normal_deltas=None) -> list:
@@ -452,6 +484,12 @@ def load_library():
     try:
         L.swr_scene_normals.argtypes = [vp, ctypes.POINTER(Normals)]
         L.swr_scene_normals.restype = ctypes.c_int
+    except AttributeError:
+        if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
+            raise
+    try:
+        L.swr_cast_rays.argtypes = [vp, vp, i64, u32, vp]
+        L.swr_cast_rays.restype = ctypes.c_int
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
             raise
@@ -914,6 +952,18 @@ class Context:
         a = self.draw_items(items)
         out = np.zeros(a.size, dtype=ITEM_BOUND_DTYPE)
         self._check(self._L.swr_item_bounds(self._h, a.ctypes.data if a.size else None, a.size, flags, out.ctypes.data if a.size else None))
+        return out
+
+    def cast_rays(self, rays) -> np.ndarray:
+        """swr_cast_rays: a RAY_HIT_DTYPE array, for every ray its nearest hit on the resident triangles as they are now (morphed and
+        posed), in object space; a miss has primitive == ID_NONE and t = u = v = 0.  `rays`: a RAY_DTYPE array (pixel_ray makes them),
+        or an (n, 8) float array of rows (origin xyz, tmin, dir xyz, tmax)."""
+        a = np.asarray(rays)
+        if a.dtype != RAY_DTYPE:
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8).view(RAY_DTYPE).reshape(-1)
+        a = np.ascontiguousarray(a).reshape(-1)
+        out = np.zeros(a.size, dtype=RAY_HIT_DTYPE)
+        self._check(self._L.swr_cast_rays(self._h, a.ctypes.data if a.size else None, a.size, 0, out.ctypes.data if a.size else None))
         return out
 
     @staticmethod

@@ -20,6 +20,7 @@
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -299,6 +300,11 @@ struct swr_context {
     DevBuf bounds_dev, bounds_scratch;
     HostBuf bounds_host;
     const swr_item_bound* bounds_out = nullptr; // the records of the last call inside bounds_host
+    // ray casts: the n rays, the n key words k_rays combines into and the n hits of a call on the device, and the
+    // band's own page-locked staging (the rays, then the hits), all sized by the largest call so far
+    DevBuf rays_dev, rays_keys, rays_hits;
+    HostBuf rays_host;
+    const swr_ray_hit* rays_out = nullptr;      // the hits of the last call inside rays_host
     // delta reads: per image kind (0 colour, 1 depth) the band's baseline — the image the last delta read delivered —
     // and whether it holds one; the tile flags k_delta_tiles writes, on the device and in the band's own page-locked copy; the rows of
     // a changed rectangle gathered for one linear copy; what the band's last delta read did (a group adds the bands up)
@@ -2943,6 +2949,65 @@ int band_item_bounds(swr_context* c, const swr_draw_item* items, int32_t n, uint
     return SWR_OK;
 }
 
+// what swr_cast_rays may be handed (include/swr.h "Ray casts"): on a band or a group alike, against the scene every band holds
+int check_rays(swr_context* c, const swr_ray* rays, int64_t n, uint32_t flags, const swr_ray_hit* hits) {
+    const char* fn = "swr_cast_rays";
+    if (!band(c, 0)->has_scene) return fail(c, SWR_ERR_NO_SCENE, "%s needs swr_scene_upload first", fn);
+    if (n < 0) return fail(c, SWR_ERR_BAD_ARG, "%s: n %lld", fn, (long long)n);
+    if (flags != 0) return fail(c, SWR_ERR_BAD_ARG, "%s: unknown flags 0x%x", fn, (unsigned)flags);
+    if (n > SWR_RAYS_MAX) return fail(c, SWR_ERR_UNSUPPORTED, "%s: %lld rays (at most %d)", fn, (long long)n, SWR_RAYS_MAX);
+    if (n > 0 && !rays) return fail(c, SWR_ERR_BAD_ARG, "%s: rays is NULL", fn);
+    if (n > 0 && !hits) return fail(c, SWR_ERR_BAD_ARG, "%s: hits is NULL", fn);
+    for (int64_t k = 0; k < n; k++) {
+        const swr_ray& r = rays[k];
+        const float f[8] = {r.origin[0], r.origin[1], r.origin[2], r.tmin, r.dir[0], r.dir[1], r.dir[2], r.tmax};
+        for (int j = 0; j < 8; j++)
+            if (!std::isfinite(f[j])) return fail(c, SWR_ERR_BAD_ARG, "%s: ray %lld: float %d is not finite", fn, (long long)k, j);
+        if (r.dir[0] == 0.0f && r.dir[1] == 0.0f && r.dir[2] == 0.0f)
+            return fail(c, SWR_ERR_BAD_ARG, "%s: ray %lld: the direction is zero", fn, (long long)k);
+        if (r.tmin > r.tmax) return fail(c, SWR_ERR_BAD_ARG, "%s: ray %lld: tmin %g > tmax %g", fn, (long long)k, r.tmin, r.tmax);
+    }
+    return SWR_OK;
+}
+
+// swr_cast_rays on one band (a group: its first): the n hits into c->rays_out[0 .. n), inside the band's page-locked staging.  The
+// stream read is the resident one as it is now — cut by an earlier draw list or not, never a frame's clip stream — and nothing of
+// the context but the call's own buffers is written.
+int band_cast_rays(swr_context* c, const swr_ray* rays, int64_t n) {
+    if (const int f = sticky(c)) return f;
+    int rc;
+    if ((rc = single_sync(c))) return rc;       // (an overflowed last frame is repaired here)
+    c->rays_out = nullptr;
+    if (n == 0) return SWR_OK;
+    const size_t nn = (size_t)n, ray_words = sizeof(swr_ray) / 4, hit_words = sizeof(swr_ray_hit) / 4;
+    if ((rc = ensure_host(c, c->rays_host, nn * (ray_words + hit_words)))) return rc;       // rays | hits
+    swr_ray* in = (swr_ray*)c->rays_host.p;
+    swr_ray_hit* out = (swr_ray_hit*)(c->rays_host.p + nn * ray_words);
+    memcpy(in, rays, nn * sizeof(swr_ray));
+    memset(out, 0, nn * sizeof(swr_ray_hit));
+    if ((rc = ensure(c, c->rays_dev, nn * sizeof(swr_ray)))) return rc;
+    if ((rc = ensure(c, c->rays_keys, nn * 8))) return rc;
+    if ((rc = ensure(c, c->rays_hits, nn * sizeof(swr_ray_hit)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->rays_dev.p, in, nn * sizeof(swr_ray), hipMemcpyHostToDevice, c->stream));
+    RaysArgs a{};
+    a.tri_xyz = (const float4*)c->tri_xyz.p;
+    a.box64 = (const float4*)c->box64.p;
+    a.inv = (const uint32_t*)c->inv.p;
+    a.reordered = c->reordered ? 1 : 0;
+    a.ntri = c->ni / 3;
+    a.groups = (a.ntri + 63) / 64;
+    a.rays = (const swr_ray*)c->rays_dev.p;
+    a.n = n;
+    a.keys = (unsigned long long*)c->rays_keys.p;
+    a.hits = (swr_ray_hit*)c->rays_hits.p;
+    launch_cast_rays(a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, a.hits, nn * sizeof(swr_ray_hit), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = wait_stream(c, c->stream, "raster stream (ray casts)"))) return or_sticky(c, rc);
+    c->rays_out = out;
+    return SWR_OK;
+}
+
 #ifndef SWR_TUNE_DELTA_DIRECT
 #define SWR_TUNE_DELTA_DIRECT 1    // how the changed part reaches a page-locked destination, chosen by measurement:
                                     // 1 = k_delta_tiles stores the changed tiles straight into the caller's image through its
@@ -3507,6 +3572,18 @@ int swr_item_bounds(swr_context* c, const swr_draw_item* items, int32_t item_cou
     swr_context* first = band(c, 0);
     if ((rc = fan(c, [=](swr_context* k) { return k == first ? band_item_bounds(k, items, item_count, flags) : single_sync(k); }))) return rc;
     if (item_count) memcpy(out, first->bounds_out, (size_t)item_count * sizeof(swr_item_bound));
+    return SWR_OK;
+}
+
+int swr_cast_rays(swr_context* c, const swr_ray* rays, int64_t n, uint32_t flags, swr_ray_hit* hits) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    if (const int f = sticky(c)) return f;
+    int rc = check_rays(c, rays, n, flags, hits);
+    if (rc) return rc;
+    // every band holds the whole scene: the first band answers, the others finish what they have in flight
+    swr_context* first = band(c, 0);
+    if ((rc = fan(c, [=](swr_context* k) { return k == first ? band_cast_rays(k, rays, n) : single_sync(k); }))) return rc;
+    if (n) memcpy(hits, first->rays_out, (size_t)n * sizeof(swr_ray_hit));
     return SWR_OK;
 }
 

@@ -389,4 +389,35 @@ inline void launch_vertex_normals(const uint32_t*, const uint32_t*, const float4
 inline void launch_flat_normals(const float4*, int64_t, bool, float4*, hipStream_t) {}
 #endif
 
+// swr_rays.hip: ray casts.  hits[k] = the swr_ray_hit of rays[k] (include/swr.h "Ray casts") over the ntri slots of
+// tri_xyz, with box64 — the box of every 64-slot group, `groups` = ceil(ntri / 64) of them — as the cull.  The primitive of slot s is
+// tri_xyz[3s].w when `reordered`, else s; inv[p] is then the slot of primitive p (not read otherwise).  One workgroup per (ray,
+// chunk of RAYS_GROUPS_PER_WG groups) combines into keys[k], one 64-bit word per ray, which the launch initialises itself and decodes
+// into hits[k] at its end: nothing has to be zeroed.  Every ray has been checked by the host.  ntri == 0: every ray misses.  All
+// pointers are device memory.
+#ifndef SWR_TUNE_RAYS_GROUPS_PER_WG
+#define SWR_TUNE_RAYS_GROUPS_PER_WG 1024    // group boxes per workgroup, a multiple of 256: DESIGN.md §30
+#endif
+constexpr int RAYS_GROUPS_PER_WG = SWR_TUNE_RAYS_GROUPS_PER_WG;
+struct RaysArgs {
+    const float4* tri_xyz;
+    const float4* box64;
+    const uint32_t* inv;
+    int32_t reordered;
+    int64_t ntri;
+    int64_t groups;
+    const swr_ray* rays;
+    int64_t n;
+    unsigned long long* keys;
+    swr_ray_hit* hits;
+};
+inline int64_t rays_chunks(int64_t groups) { return (groups + RAYS_GROUPS_PER_WG - 1) / RAYS_GROUPS_PER_WG; }
+#if defined(__HIPCC__) || defined(SWR_HOST_TEST_RAYS)
+void launch_cast_rays(const RaysArgs& a, hipStream_t s);
+#else
+// (host test programs built without SWR_HOST_TEST_RAYS link a launch set that predates this launch and never call swr_cast_rays:
+// nothing is enqueued.  The product is always compiled by hipcc and references the launch plainly.)
+inline void launch_cast_rays(const RaysArgs&, hipStream_t) {}
+#endif
+
 }  // namespace swr
