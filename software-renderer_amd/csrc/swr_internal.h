@@ -359,13 +359,7 @@ struct MorphSparseArgs {
     swr_vertex* morphed;
     swr_vertex_attr* morphed_attrs;
 };
-#if defined(__HIPCC__) || defined(SWR_HOST_TEST_MORPH_SPARSE)
 void launch_morph_sparse(const MorphSparseArgs& a, hipStream_t s);
-#else
-// (host test programs built without SWR_HOST_TEST_MORPH_SPARSE link a launch set that predates this launch and never call
-// swr_scene_morph_sparse: nothing is enqueued.  The product is always compiled by hipcc and references the launch plainly.)
-inline void launch_morph_sparse(const MorphSparseArgs&, hipStream_t) {}
-#endif
 
 // swr_normals.hip: computed normals.  launch_face_normals writes face[p] = (f_p, 0) of include/swr.h "Computed
 // normals" for the ntri triangles of `indices`, from the vertex array in effect — the pos, pos_stride pair launch_skin_stream takes;
@@ -375,19 +369,11 @@ inline void launch_morph_sparse(const MorphSparseArgs&, hipStream_t) {}
 // entry is below ntri.  launch_skin_stream, given auto_nrm with stride 1, then writes the stream.  launch_flat_normals writes the xyz
 // lanes of tri_nrm[3s + k], k = 0..2, = f of the xyz lanes of tri_xyz[3s .. 3s + 2] for the ntri slots of the stream (after
 // launch_skin_stream has written its positions); the w lanes stay.  All pointers are device memory.
-#if defined(__HIPCC__) || defined(SWR_HOST_TEST_NORMALS)
 void launch_face_normals(const float4* pos, int pos_stride, int64_t nv, const int64_t* indices, int64_t ntri, bool flip, float4* face,
                          hipStream_t s);
 void launch_vertex_normals(const uint32_t* adj_off, const uint32_t* adj_tri, const float4* face, int64_t nv, float4* auto_nrm,
                            hipStream_t s);
 void launch_flat_normals(const float4* tri_xyz, int64_t ntri, bool flip, float4* tri_nrm, hipStream_t s);
-#else
-// (host test programs built without SWR_HOST_TEST_NORMALS link a launch set that predates these launches and never call
-// swr_scene_normals: nothing is enqueued.  The product is always compiled by hipcc and references the launches plainly.)
-inline void launch_face_normals(const float4*, int, int64_t, const int64_t*, int64_t, bool, float4*, hipStream_t) {}
-inline void launch_vertex_normals(const uint32_t*, const uint32_t*, const float4*, int64_t, float4*, hipStream_t) {}
-inline void launch_flat_normals(const float4*, int64_t, bool, float4*, hipStream_t) {}
-#endif
 
 // swr_rays.hip: ray casts.  hits[k] = the swr_ray_hit of rays[k] (include/swr.h "Ray casts") over the ntri slots of
 // tri_xyz, with box64 — the box of every 64-slot group, `groups` = ceil(ntri / 64) of them — as the cull.  The primitive of slot s is
@@ -412,12 +398,6 @@ struct RaysArgs {
     swr_ray_hit* hits;
 };
 inline int64_t rays_chunks(int64_t groups) { return (groups + RAYS_GROUPS_PER_WG - 1) / RAYS_GROUPS_PER_WG; }
-#if defined(__HIPCC__) || defined(SWR_HOST_TEST_RAYS)
 void launch_cast_rays(const RaysArgs& a, hipStream_t s);
-#else
-// (host test programs built without SWR_HOST_TEST_RAYS link a launch set that predates this launch and never call swr_cast_rays:
-// nothing is enqueued.  The product is always compiled by hipcc and references the launch plainly.)
-inline void launch_cast_rays(const RaysArgs&, hipStream_t) {}
-#endif
 
 }  // namespace swr

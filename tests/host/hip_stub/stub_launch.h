@@ -1,16 +1,17 @@
 // What the host test programs see of the stand-in launch set (stub_launch.cpp): the knobs they turn, how often each feature launch
-// ran, what the last skin stream launches wrote, the failures a stand-in found on the fake stream's thread, and the arithmetic the
-// stand-ins share with the programs' models.  Test infrastructure only.
+// ran, what the last skin stream launches wrote, what the normals and ray launches noted about their arguments and their order, the
+// failures a stand-in found on the fake stream's thread, and the arithmetic the stand-ins share with the programs' models.  Test
+// infrastructure only.
 #pragma once
 #include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <mutex>
 #include <vector>
 
-#include "../../../include/swr.h"
-#include <hip/hip_runtime.h>
+#include "../../../software-renderer_amd/csrc/swr_internal.h"
 
 namespace swr {
 extern std::atomic<uint32_t> g_fake_fill;        // largest tile fill the fake k_bin reports (tests raise it to force a regrow)
@@ -27,12 +28,36 @@ extern std::atomic<int> g_vertex_launches, g_stream_launches;               // l
 extern std::atomic<int> g_morph_launches, g_morph_nrm_launches;             // launch_morph_vertices, those with normals
 extern std::atomic<int> g_bounds_launches;                                  // launch_item_bounds
 extern std::atomic<int> g_dq_launches, g_dq_nrm_launches;                   // launch_skin_vertices_dq, those with normals
+extern std::atomic<int> g_sparse_launches, g_sparse_nrm_launches;           // launch_morph_sparse, those with normals
+extern std::atomic<int64_t> g_sparse_rows;                                  // touched vertices of the last launch_morph_sparse
+extern std::atomic<int> g_face_launches, g_vnrm_launches, g_flat_launches;  // launch_face_normals, launch_vertex_normals, launch_flat_normals
+extern std::atomic<int> g_flip_launches;                                    // face and flat launches with flip
+extern std::atomic<int> g_ray_launches;                                     // launch_cast_rays
 // what a stand-in found wrong in what it was handed (it runs on the fake stream's thread): a program adds this to its failures
 extern std::atomic<int> g_launch_fails;
 
 // what a stream launch wrote; take_records: the launches since the last call, the list cleared
 struct Record { const float4* tri_xyz; const float4* tri_nrm; const float4* box; int64_t ntri; bool nrm; };
 std::vector<Record> take_records();
+
+// the stream write, either skin, either morph: launches so far
+struct LaunchCounts { int stream, skin, morph; };
+inline LaunchCounts launch_counts() {
+    return LaunchCounts{g_stream_launches.load(), g_vertex_launches.load() + g_dq_launches.load(), g_morph_launches.load() + g_sparse_launches.load()};
+}
+// what the normals and ray launches note, under g_note_m
+extern std::mutex g_note_m;
+extern LaunchCounts g_face_at, g_flat_at;            // what had been launched when the last face / flat launch was made
+extern int g_vnrm_after_faces;                       // face launches made when the last vertex-normal launch was made
+struct FlatNote { const float4* tri_xyz; const float4* tri_nrm; };
+extern std::vector<FlatNote> g_flat_notes;           // the flat launches since the last look
+extern std::vector<uint32_t> g_adj_off, g_adj_tri;   // the adjacency the last vertex-normal launch was handed
+struct RayNote {
+    swr::RaysArgs a;
+    int streams_before;         // stream launches made when the ray launch was made
+    bool ran;
+};
+std::vector<RayNote> take_ray_notes();               // the ray launches since the last call, the list cleared
 
 // the ID the pattern gives band-local pixel (x, y): 0 .. total - 1, or SWR_ID_NONE
 inline uint32_t count_pattern(uint32_t x, uint32_t y, uint32_t total) {
@@ -121,6 +146,25 @@ inline void pose_dq(const float* v, const swr_skin_vertex& sk, const float* dq, 
         }
     }
     memcpy(out, r, sizeof r);
+}
+
+// "Computed normals": the face normal of a triangle, and the normalisation of a vertex normal
+inline void face_of(const float* a, const float* b, const float* c, bool flip, float* f) {
+    float e1[3], e2[3];
+    for (int j = 0; j < 3; j++) { e1[j] = b[j] - a[j]; e2[j] = c[j] - a[j]; }
+    if (flip) cross(e2, e1, f); else cross(e1, e2, f);
+}
+inline void normalise(float* n) {
+    float q = n[0] * n[0] + n[1] * n[1];
+    q = q + n[2] * n[2];
+    const float l = sqrtf(q);
+    if (l > 0.0f) { const float r = 1.0f / l; for (int j = 0; j < 3; j++) n[j] = n[j] * r; }
+}
+
+// what the ray stand-in answers for ray k: a function of the ray and of the scene's size
+inline uint32_t float_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+inline swr_ray_hit ray_echo(const swr_ray& r, int64_t k, int64_t ntri) {
+    return swr_ray_hit{(uint32_t)k ^ float_bits(r.origin[0]), r.tmin + r.dir[2], r.origin[1], (float)ntri + r.tmax};
 }
 
 // include/swr.h "Item bounds" over `count` triangles whose corner j of triangle t is corner(t, j) (three floats)

@@ -1,68 +1,19 @@
 // The host side of the sparse morph targets and of swr_morph_pose_set (software-renderer_amd/csrc/swr_api.hip:
 // single_scene_morph_sparse — the checks, the rows it builds, their upload through the staging chunks, the pre-fill of the morphed
 // arrays — enqueue_pose with sparse targets, single_morph_pose_set and the checks it shares with single_morph_set and single_pose_set,
-// the group fan-out) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The launch
-// set every host program links predates swr::launch_morph_sparse, so this program is built with -DSWR_HOST_TEST_MORPH_SPARSE
-// (swr_internal.h then declares the launch instead of defining a no-op) and brings the stand-in itself: a CPU loop over the header's
-// arithmetic that checks the rows it is handed and reads and writes every element of every array, at the sizes swr_internal.h states.
-// Like the kernel it writes the position (and normal) quads of the touched vertices only: everything else of the morphed arrays is
-// the host layer's pre-fill, which the skin stream launch then reads.
-//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -DSWR_HOST_TEST_MORPH_SPARSE -Itests/host/hip_stub -x c++ \
-//       software-renderer_amd/csrc/swr_api.hip tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp \
-//       tests/host/morph_sparse_host_test.cpp -lpthread
+// the group fan-out) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The
+// stand-in of swr::launch_morph_sparse is the launch set's (hip_stub/stub_launch.cpp): a CPU loop over the header's arithmetic that
+// checks the rows it is handed and reads and writes every element of every array, at the sizes swr_internal.h states.  Like the
+// kernel it writes the position (and normal) quads of the touched vertices only: everything else of the morphed arrays is the host
+// layer's pre-fill, which the skin stream launch then reads.
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ software-renderer_amd/csrc/swr_api.hip \
+//       tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp tests/host/morph_sparse_host_test.cpp -lpthread
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "host_test.h"
-#include "../../software-renderer_amd/csrc/swr_internal.h"
-
-static std::atomic<int> g_sparse_launches{0}, g_sparse_nrm_launches{0};
-static std::atomic<int64_t> g_sparse_rows{0};           // touched vertices of the last launch
-
-namespace swr {
-void launch_morph_sparse(const MorphSparseArgs& a, hipStream_t s) {
-    g_sparse_launches++;
-    if (a.attrs) g_sparse_nrm_launches++;
-    g_sparse_rows.store(a.touched_count);
-    const MorphSparseArgs b = a;
-    fake_enqueue(s, [b] {
-        auto bad = [](const char* what, long long x) { std::printf("FAIL sparse launch: %s %lld\n", what, x); g_launch_fails++; };
-        if (b.touched_count < 1) return bad("touched_count", b.touched_count);
-        if (b.targets < 1 || b.targets > SWR_MORPH_MAX_TARGETS) return bad("targets", b.targets);
-        if (b.row[0] != 0) return bad("row[0]", b.row[0]);
-        if ((b.attrs != nullptr) != (b.dnrm != nullptr) || (b.attrs != nullptr) != (b.morphed_attrs != nullptr)) return bad("normal arrays", 0);
-        float sum = 0.0f;
-        for (int t = 0; t < b.targets; t++) sum += b.weights[t] == b.weights[t] ? b.weights[t] : 0.0f;     // (the whole table is read)
-        if (sum == 12345.678f) g_launch_fails++;
-        for (int64_t r = 0; r < b.touched_count; r++) {
-            const int64_t i = b.touched[r];
-            if (r && b.touched[r] <= b.touched[r - 1]) return bad("touched not ascending at row", r);
-            if (b.row[r + 1] <= b.row[r]) return bad("an empty or negative row", r);
-            float p[4], n[4] = {0, 0, 0, 0};
-            memcpy(p, b.vertices[i].xyz, 16);
-            if (b.attrs) memcpy(n, b.attrs[i].normal, 16);
-            for (int64_t k = b.row[r]; k < b.row[r + 1]; k++) {
-                const MorphSparseEntry e = b.dpos[k];
-                if (e.target >= (uint32_t)b.targets || (k > b.row[r] && e.target <= b.dpos[k - 1].target)) return bad("row not sorted by target at entry", k);
-                if (b.dnrm && b.dnrm[k].target != e.target) return bad("normal entry of another target at", k);
-                const float w = b.weights[e.target];
-                if (!(w != 0.0f)) continue;
-                const float d[3] = {e.dx, e.dy, e.dz};
-                for (int c = 0; c < 3; c++) { const float m = w * d[c]; p[c] = p[c] + m; }
-                if (b.dnrm) {
-                    const float f[3] = {b.dnrm[k].dx, b.dnrm[k].dy, b.dnrm[k].dz};
-                    for (int c = 0; c < 3; c++) { const float m = w * f[c]; n[c] = n[c] + m; }
-                }
-            }
-            memcpy(b.morphed[i].xyz, p, 16);
-            if (b.attrs) memcpy(b.morphed_attrs[i].normal, n, 16);
-        }
-    }, nullptr, "k_morph_sparse", (size_t)b.touched_count);
-}
-}  // namespace swr
 
 // sparse targets as the caller holds them
 struct Sparse {

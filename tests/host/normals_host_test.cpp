@@ -1,136 +1,18 @@
 // The host side of the computed normals (software-renderer_amd/csrc/swr_api.hip: single_scene_normals — the checks, the adjacency it
 // builds by a counting sort, its upload — and the stage enqueue_pose gained between the vertex passes and the stream write, the group
-// fan-out) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The launch set every
-// host program links predates swr::launch_face_normals, launch_vertex_normals and launch_flat_normals, so this program is built with
-// -DSWR_HOST_TEST_NORMALS (swr_internal.h then declares the launches instead of defining no-ops) and brings the stand-ins itself: CPU
-// loops over the header's arithmetic that read and write every element of every array they are handed, at the sizes swr_internal.h
-// states, and note when they were called relative to the other launches.  It is built with -DSWR_HOST_TEST_MORPH_SPARSE as well and
-// brings that stand-in too, so that a sparse morph under a computed mode runs.
-//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -DSWR_HOST_TEST_NORMALS -DSWR_HOST_TEST_MORPH_SPARSE -Itests/host/hip_stub \
-//       -x c++ software-renderer_amd/csrc/swr_api.hip tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp \
-//       tests/host/normals_host_test.cpp -lpthread
+// fan-out) on the fake HIP runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The stand-ins of
+// swr::launch_face_normals, launch_vertex_normals and launch_flat_normals are the launch set's (hip_stub/stub_launch.cpp): CPU loops
+// over the header's arithmetic that read and write every element of every array they are handed, at the sizes swr_internal.h states,
+// and note when they were called relative to the other launches (hip_stub/stub_launch.h has the notes and the adjacency copy).
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ software-renderer_amd/csrc/swr_api.hip \
+//       tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp tests/host/normals_host_test.cpp -lpthread
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "host_test.h"
-#include "../../software-renderer_amd/csrc/swr_internal.h"
-
-// ---- the stand-ins --------------------------------------------------------------------------------------------------------------------
-struct Counters { int stream, skin, morph; };        // launches so far: the stream write, either skin, either morph
-static std::atomic<int> g_sparse_launches{0}, g_sparse_nrm_launches{0};
-static Counters counters() {
-    return Counters{g_stream_launches.load(), g_vertex_launches.load() + g_dq_launches.load(), g_morph_launches.load() + g_sparse_launches.load()};
-}
-static std::atomic<int> g_face_launches{0}, g_vnrm_launches{0}, g_flat_launches{0}, g_flip_launches{0};
-static std::mutex g_note_m;
-static Counters g_face_at{}, g_flat_at{};            // what had been launched when the last face / flat launch was made
-static int g_vnrm_after_faces = 0;                   // face launches made when the last vertex-normal launch was made
-struct FlatNote { const float4* tri_xyz; const float4* tri_nrm; };
-static std::vector<FlatNote> g_flat_notes;           // the flat launches since the last look
-static std::vector<uint32_t> g_adj_off, g_adj_tri;   // the adjacency the last vertex-normal launch was handed
-
-static void face_of(const float* a, const float* b, const float* c, bool flip, float* f) {
-    float e1[3], e2[3];
-    for (int j = 0; j < 3; j++) { e1[j] = b[j] - a[j]; e2[j] = c[j] - a[j]; }
-    if (flip) cross(e2, e1, f); else cross(e1, e2, f);
-}
-static void normalise(float* n) {
-    float q = n[0] * n[0] + n[1] * n[1];
-    q = q + n[2] * n[2];
-    const float l = sqrtf(q);
-    if (l > 0.0f) { const float r = 1.0f / l; for (int j = 0; j < 3; j++) n[j] = n[j] * r; }
-}
-
-namespace swr {
-void launch_face_normals(const float4* pos, int pos_stride, int64_t nv, const int64_t* indices, int64_t ntri, bool flip, float4* face,
-                         hipStream_t s) {
-    if (ntri <= 0) return;          // (as the launches themselves: a zero grid is a launch error)
-    { std::lock_guard<std::mutex> lk(g_note_m); g_face_at = counters(); }
-    g_face_launches++;
-    if (flip) g_flip_launches++;
-    fake_enqueue(s, [=] {
-        if (pos_stride != 2 || ntri < 1) { std::printf("FAIL face launch: stride %d, %lld triangles\n", pos_stride, (long long)ntri); g_launch_fails++; return; }
-        for (int64_t p = 0; p < ntri; p++) {
-            const float4* x[3];
-            for (int k = 0; k < 3; k++) {
-                const int64_t ix = indices[3 * p + k];
-                if (ix < 0 || ix >= nv) { std::printf("FAIL face launch: index\n"); g_launch_fails++; return; }
-                x[k] = pos + (size_t)pos_stride * ix;
-            }
-            float f[3];
-            face_of(&x[0]->x, &x[1]->x, &x[2]->x, flip, f);
-            face[p] = make_float4(f[0], f[1], f[2], 0.0f);
-        }
-    }, nullptr, "k_face_normals", (size_t)ntri);
-}
-void launch_vertex_normals(const uint32_t* adj_off, const uint32_t* adj_tri, const float4* face, int64_t nv, float4* auto_nrm, hipStream_t s) {
-    if (nv <= 0) return;
-    { std::lock_guard<std::mutex> lk(g_note_m); g_vnrm_after_faces = g_face_launches.load(); }
-    g_vnrm_launches++;
-    fake_enqueue(s, [=] {
-        if (adj_off[0] != 0) { std::printf("FAIL vertex normals: adj_off[0] = %u\n", adj_off[0]); g_launch_fails++; return; }
-        for (int64_t i = 0; i < nv; i++) {
-            if (adj_off[i + 1] < adj_off[i]) { std::printf("FAIL vertex normals: row %lld\n", (long long)i); g_launch_fails++; return; }
-            float n[3] = {0.0f, 0.0f, 0.0f};
-            for (uint32_t e = adj_off[i]; e < adj_off[i + 1]; e++) {
-                const float4 f = face[adj_tri[e]];
-                n[0] = n[0] + f.x; n[1] = n[1] + f.y; n[2] = n[2] + f.z;
-            }
-            normalise(n);
-            auto_nrm[i] = make_float4(n[0], n[1], n[2], 0.0f);
-        }
-        std::lock_guard<std::mutex> lk(g_note_m);
-        g_adj_off.assign(adj_off, adj_off + nv + 1);
-        g_adj_tri.assign(adj_tri, adj_tri + adj_off[nv]);
-    }, nullptr, "k_vertex_normals", (size_t)nv);
-}
-void launch_flat_normals(const float4* tri_xyz, int64_t ntri, bool flip, float4* tri_nrm, hipStream_t s) {
-    if (ntri <= 0) return;
-    { std::lock_guard<std::mutex> lk(g_note_m); g_flat_at = counters(); }
-    g_flat_launches++;
-    if (flip) g_flip_launches++;
-    fake_enqueue(s, [=] {
-        for (int64_t t = 0; t < ntri; t++) {
-            float f[3];
-            face_of(&tri_xyz[3 * t].x, &tri_xyz[3 * t + 1].x, &tri_xyz[3 * t + 2].x, flip, f);
-            for (int k = 0; k < 3; k++) { float4& q = tri_nrm[3 * t + k]; q.x = f[0]; q.y = f[1]; q.z = f[2]; }
-        }
-        std::lock_guard<std::mutex> lk(g_note_m);
-        g_flat_notes.push_back(FlatNote{tri_xyz, tri_nrm});
-    }, nullptr, "k_flat_normals", (size_t)ntri);
-}
-// (tests/host/morph_sparse_host_test.cpp checks the rows; here the loop only has to morph)
-void launch_morph_sparse(const MorphSparseArgs& a, hipStream_t s) {
-    g_sparse_launches++;
-    if (a.attrs) g_sparse_nrm_launches++;
-    const MorphSparseArgs b = a;
-    fake_enqueue(s, [b] {
-        for (int64_t r = 0; r < b.touched_count; r++) {
-            const int64_t i = b.touched[r];
-            float p[4], n[4] = {0, 0, 0, 0};
-            memcpy(p, b.vertices[i].xyz, 16);
-            if (b.attrs) memcpy(n, b.attrs[i].normal, 16);
-            for (int64_t k = b.row[r]; k < b.row[r + 1]; k++) {
-                const MorphSparseEntry e = b.dpos[k];
-                const float w = b.weights[e.target];
-                if (!(w != 0.0f)) continue;
-                const float d[3] = {e.dx, e.dy, e.dz};
-                for (int c = 0; c < 3; c++) { const float m = w * d[c]; p[c] = p[c] + m; }
-                if (b.dnrm) {
-                    const float f[3] = {b.dnrm[k].dx, b.dnrm[k].dy, b.dnrm[k].dz};
-                    for (int c = 0; c < 3; c++) { const float m = w * f[c]; n[c] = n[c] + m; }
-                }
-            }
-            memcpy(b.morphed[i].xyz, p, 16);
-            if (b.attrs) memcpy(b.morphed_attrs[i].normal, n, 16);
-        }
-    }, nullptr, "k_morph_sparse", (size_t)b.touched_count);
-}
-}  // namespace swr
 
 // ---- the model ------------------------------------------------------------------------------------------------------------------------
 enum { UPLOADED = SWR_NORMALS_UPLOADED, SMOOTH = SWR_NORMALS_SMOOTH, FLAT = SWR_NORMALS_FLAT };
@@ -287,7 +169,7 @@ static void sequences() {
             else expect_computed(s, bind, mode, flip, 1, st_.name);
             CHECK(g_face_launches.load() == face0 + (mode == SMOOTH) && g_vnrm_launches.load() == vn0 + (mode == SMOOTH) && g_flat_launches.load() == flat0 + (mode == FLAT));
             // the deforming call
-            const Counters before = counters();
+            const LaunchCounts before = launch_counts();
             const int mn0 = g_morph_nrm_launches.load() + g_sparse_nrm_launches.load(), dqn0 = g_dq_nrm_launches.load();
             const int face1 = g_face_launches.load(), vn1 = g_vnrm_launches.load(), flat1 = g_flat_launches.load();
             const bool dq = st_.pose == 2;
@@ -301,7 +183,7 @@ static void sequences() {
             }
             const Shape shape{st_.morph ? &T : nullptr, st_.morph ? w : nullptr, st_.pose ? (dq ? Q.data() : A.data()) : nullptr, dq};
             const int calls = (st_.morph && st_.pose && st_.pose != 3) ? 2 : (st_.morph || st_.pose) ? 1 : 0;
-            const Counters after = counters();
+            const LaunchCounts after = launch_counts();
             if (!calls) continue;
             CHECK(after.stream == before.stream + calls);
             CHECK(after.morph == before.morph + (st_.morph ? calls : 0) && after.skin == before.skin + (st_.pose ? 1 : 0));

@@ -1,98 +1,15 @@
 // The host side of the ray casts (software-renderer_amd/csrc/swr_api.hip: check_rays, band_cast_rays, swr_cast_rays) on the fake HIP
-// runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The launch set every host program links
-// predates swr::launch_cast_rays, so this program is built with -DSWR_HOST_TEST_RAYS (swr_internal.h then declares the launch instead
-// of defining a no-op) and brings the stand-in itself: a CPU loop that reads every ray, every stream slot, every group box and, when
-// the stream is reordered, every inv entry it is handed, writes every key word and every hit, and notes what it was handed and when.
-// Its hits echo the rays, so that the program sees the upload in front of the launch and the read-back behind it.  It is built with
-// -DSWR_HOST_TEST_NORMALS and -DSWR_HOST_TEST_MORPH_SPARSE as well and brings those stand-ins too.
-//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -DSWR_HOST_TEST_RAYS -DSWR_HOST_TEST_NORMALS -DSWR_HOST_TEST_MORPH_SPARSE \
-//       -Itests/host/hip_stub -x c++ software-renderer_amd/csrc/swr_api.hip tests/host/hip_stub/stub_runtime.cpp \
-//       tests/host/hip_stub/stub_launch.cpp tests/host/rays_host_test.cpp -lpthread
-#include <atomic>
-#include <cfloat>
+// runtime of tests/host/hip_stub, under the address and undefined-behaviour sanitizers.  The stand-in of swr::launch_cast_rays is the
+// launch set's (hip_stub/stub_launch.cpp): a CPU loop that reads every ray, every stream slot, every group box and, when the stream is
+// reordered, every inv entry it is handed, writes every key word and every hit, and notes what it was handed and when.  Its hits echo
+// the rays (hip_stub/stub_launch.h: ray_echo), so that the program sees the upload in front of the launch and the read-back behind it.
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Itests/host/hip_stub -x c++ software-renderer_amd/csrc/swr_api.hip \
+//       tests/host/hip_stub/stub_runtime.cpp tests/host/hip_stub/stub_launch.cpp tests/host/rays_host_test.cpp -lpthread
 #include <cmath>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "host_test.h"
-#include "../../software-renderer_amd/csrc/swr_internal.h"
-
-// ---- the stand-ins --------------------------------------------------------------------------------------------------------------------
-struct RayNote {
-    swr::RaysArgs a;
-    int streams_before;         // stream launches made when the ray launch was made
-    bool ran;
-};
-static std::mutex g_note_m;
-static std::vector<RayNote> g_notes;        // the ray launches since the last look
-static std::atomic<int> g_ray_launches{0};
-static std::atomic<uint32_t> g_sink{0};     // what the reads add up to (so that no read is optimised away)
-
-static uint32_t bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-// what the stand-in answers for ray k: a function of the ray and of the scene's size
-static swr_ray_hit echo(const swr_ray& r, int64_t k, int64_t ntri) {
-    return swr_ray_hit{(uint32_t)k ^ bits(r.origin[0]), r.tmin + r.dir[2], r.origin[1], (float)ntri + r.tmax};
-}
-
-namespace swr {
-void launch_cast_rays(const RaysArgs& a, hipStream_t s) {
-    if (a.n <= 0) return;
-    g_ray_launches++;
-    size_t at;
-    {
-        std::lock_guard<std::mutex> lk(g_note_m);
-        at = g_notes.size();
-        g_notes.push_back(RayNote{a, g_stream_launches.load(), false});
-    }
-    const RaysArgs b = a;
-    fake_enqueue(s, [b, at] {
-        if (b.n > SWR_RAYS_MAX || b.groups != (b.ntri + 63) / 64 || !b.rays || !b.keys || !b.hits) {
-            std::printf("FAIL ray launch: n %lld ntri %lld groups %lld\n", (long long)b.n, (long long)b.ntri, (long long)b.groups); g_launch_fails++; return;
-        }
-        uint32_t sum = 0;
-        for (int64_t e = 0; e < 3 * b.ntri; e++) sum += bits(b.tri_xyz[e].x) + bits(b.tri_xyz[e].w);
-        for (int64_t g = 0; g < 2 * b.groups; g++) sum += bits(b.box64[g].x) + bits(b.box64[g].z);
-        if (b.reordered) for (int64_t p = 0; p < b.ntri; p++) sum += b.inv[p];
-        g_sink += sum;
-        for (int64_t k = 0; k < b.n; k++) {
-            const swr_ray r = b.rays[k];
-            const float f[8] = {r.origin[0], r.origin[1], r.origin[2], r.tmin, r.dir[0], r.dir[1], r.dir[2], r.tmax};
-            for (float x : f) if (!std::isfinite(x)) { std::printf("FAIL ray launch: ray %lld is not finite\n", (long long)k); g_launch_fails++; return; }
-            b.keys[k] = ~0ull;
-            b.hits[k] = echo(r, k, b.ntri);
-        }
-        std::lock_guard<std::mutex> lk(g_note_m);
-        if (at < g_notes.size()) g_notes[at].ran = true;
-    }, nullptr, "k_rays", (size_t)b.n);
-}
-// (tests/host/normals_host_test.cpp and morph_sparse_host_test.cpp check these launches; this program never sets a mode or sparse
-// targets, so the loops only have to touch what they are handed)
-void launch_face_normals(const float4* pos, int pos_stride, int64_t nv, const int64_t* indices, int64_t ntri, bool, float4* face, hipStream_t s) {
-    fake_enqueue(s, [=] { for (int64_t p = 0; p < ntri; p++) { const int64_t i = indices[3 * p]; face[p] = (i >= 0 && i < nv) ? pos[(size_t)pos_stride * i] : float4{}; } },
-                 nullptr, "k_face_normals", (size_t)ntri);
-}
-void launch_vertex_normals(const uint32_t* adj_off, const uint32_t* adj_tri, const float4* face, int64_t nv, float4* auto_nrm, hipStream_t s) {
-    fake_enqueue(s, [=] { for (int64_t i = 0; i < nv; i++) auto_nrm[i] = adj_off[i + 1] > adj_off[i] ? face[adj_tri[adj_off[i]]] : float4{}; },
-                 nullptr, "k_vertex_normals", (size_t)nv);
-}
-void launch_flat_normals(const float4* tri_xyz, int64_t ntri, bool, float4* tri_nrm, hipStream_t s) {
-    fake_enqueue(s, [=] { for (int64_t e = 0; e < 3 * ntri; e++) { tri_nrm[e].x = tri_xyz[e].x; tri_nrm[e].y = tri_xyz[e].y; tri_nrm[e].z = tri_xyz[e].z; } },
-                 nullptr, "k_flat_normals", (size_t)ntri);
-}
-void launch_morph_sparse(const MorphSparseArgs& a, hipStream_t s) {
-    const MorphSparseArgs b = a;
-    fake_enqueue(s, [b] { for (int64_t r = 0; r < b.touched_count; r++) memcpy(b.morphed[b.touched[r]].xyz, b.vertices[b.touched[r]].xyz, 16); },
-                 nullptr, "k_morph_sparse", (size_t)b.touched_count);
-}
-}  // namespace swr
-
-static std::vector<RayNote> take_notes() {
-    std::lock_guard<std::mutex> lk(g_note_m);
-    std::vector<RayNote> out;
-    out.swap(g_notes);
-    return out;
-}
 
 static std::vector<swr_ray> make_rays(size_t n, float salt) {
     std::vector<swr_ray> r(n);
@@ -107,9 +24,9 @@ static const RayNote* g_last = nullptr;
 static RayNote g_last_note;
 static void cast_ok(swr_context* c, const std::vector<swr_ray>& rays, int64_t ntri, const char* what) {
     std::vector<swr_ray_hit> hits(rays.size() + 1, swr_ray_hit{0xA5A5A5A5u, -7.0f, -7.0f, -7.0f});
-    (void)take_notes();
+    (void)take_ray_notes();
     const int rc = swr_cast_rays(c, rays.data(), (int64_t)rays.size(), 0, hits.data());
-    const std::vector<RayNote> notes = take_notes();
+    const std::vector<RayNote> notes = take_ray_notes();
     if (rc != SWR_OK || notes.size() != 1 || !notes[0].ran) {
         std::printf("FAIL %s: rc %d (%s), %zu launches\n", what, rc, swr_last_error(c), notes.size()); fails++; g_last = nullptr; return;
     }
@@ -117,7 +34,7 @@ static void cast_ok(swr_context* c, const std::vector<swr_ray>& rays, int64_t nt
     const swr::RaysArgs& a = notes[0].a;
     bool ok = a.n == (int64_t)rays.size() && a.ntri == ntri && (ntri == 0 || (a.tri_xyz && a.box64));
     for (size_t k = 0; ok && k < rays.size(); k++) {
-        const swr_ray_hit e = echo(rays[k], (int64_t)k, ntri);
+        const swr_ray_hit e = ray_echo(rays[k], (int64_t)k, ntri);
         ok = memcmp(&hits[k], &e, sizeof e) == 0;
     }
     ok = ok && hits[rays.size()].primitive == 0xA5A5A5A5u;      // nothing behind the n-th hit is written
@@ -154,7 +71,7 @@ static void refusals(swr_context* c, bool have_scene) {
         CHECK(std::string(swr_last_error(c)).find("swr_cast_rays: ray 4: the direction is zero") != std::string::npos);
         CHECK(swr_cast_rays(c, r.data(), 4, 0, hits.data()) == SWR_OK);                                             // (the first four are fine)
         for (int k = 0; k < 4; k++) hits[(size_t)k] = swr_ray_hit{0xA5A5A5A5u, -7.0f, -7.0f, -7.0f};
-        (void)take_notes();
+        (void)take_ray_notes();
         r = rays;
         r[0].tmin = 2.0f; r[0].tmax = 1.0f;
         CHECK(swr_cast_rays(c, r.data(), 5, 0, hits.data()) == SWR_ERR_BAD_ARG);
@@ -162,7 +79,7 @@ static void refusals(swr_context* c, bool have_scene) {
         r[0].tmin = 1.0f;                                                                                           // tmin == tmax is legal
         CHECK(swr_cast_rays(c, r.data(), 1, 0, hits.data()) == SWR_OK);
         hits[0] = swr_ray_hit{0xA5A5A5A5u, -7.0f, -7.0f, -7.0f};
-        (void)take_notes();
+        (void)take_ray_notes();
         CHECK(g_ray_launches.load() == launches + 2);
     }
     if (!have_scene) CHECK(g_ray_launches.load() == launches);

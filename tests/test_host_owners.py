@@ -56,7 +56,7 @@ def test_owner_types_cannot_be_copied():
         assert re.search(r"%s\(const %s&\) = delete" % (name, name), body) or re.search(r"%s\(%s&& o\)" % (name, name), body), name
 
 
-@pytest.mark.parametrize("word", ["group_tg", "group_has_target", "STANDIN"])
+@pytest.mark.parametrize("word", ["group_tg", "group_has_target", "STANDIN", "SWR_HOST_TEST_"])
 def test_retired_names_stay_retired(word):
     hits = []
     for folder, _, files in os.walk(PRODUCT):
