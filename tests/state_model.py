@@ -30,6 +30,8 @@ import frame_model as FM
 import item_bounds_model as IB
 import morph_model as MM
 import morph_sparse_model as MS
+import normals_model as NM
+import rays_model as RM
 import skin_dq_model as DQ
 import skin_model as SM
 
@@ -42,6 +44,8 @@ TRI, LINE, VERTICES = 0, 1, 2
 TILE_W, TILE_H = 64, 32
 MORPH_MAX_TARGETS = 256                                     # SWR_MORPH_MAX_TARGETS
 DENSE, SPARSE = "dense", "sparse"
+UPLOADED, SMOOTH, FLAT, FLIP = NM.UPLOADED, NM.SMOOTH, NM.FLAT, NM.FLIP     # SWR_NORMALS_*
+RAYS_MAX = RM.RAYS_MAX                                      # SWR_RAYS_MAX
 
 
 class Refused(Exception):
@@ -79,7 +83,7 @@ class Last:
 
 
 class State:
-    def __init__(self, oracle, cache=None, shapes=None):
+    def __init__(self, oracle, cache=None, shapes=None, casts=None):
         self.oracle = oracle
         self.cache = {} if cache is None else cache         # frame_model's clear frames, by (shape id, ...)
         self.shapes = {} if shapes is None else shapes      # shape key -> (vertices, attrs or None)
@@ -92,6 +96,9 @@ class State:
         self.targets = None                                 # dense: (position deltas, normal deltas or None, digest);
         self.kind = None                                    # sparse: ([(indices, position deltas[, normal deltas])], normals?, digest)
         self.weights, self.weights_id = None, None
+        self.normals = None                                 # "Computed normals": (SMOOTH | FLAT, flip) or None (as uploaded)
+        self.flat = {}                                      # shape id -> the de-indexed scene a lit frame draws under FLAT
+        self.casts = {} if casts is None else casts         # (positions, rays) -> hits (the model's answers are kept: a set is cast often)
         self.material = None                                # a scenes.Shading (its attrs are not looked at) or None
         self.size = None
         self.image = None                                   # (colour or None or masked, depth, IDs or None)
@@ -102,14 +109,15 @@ class State:
 
     # ---- the scene ----------------------------------------------------------------------------------------------------------------
     def upload(self, v, i):
-        """A new scene discards attributes, skin, pose, targets and weights, and makes the IDs unreadable: they number the primitives
-        of the scene that is gone (the colour and depth images and the target stay)."""
+        """A new scene discards attributes, skin, pose, targets, weights and the normals mode, and makes the IDs unreadable: they
+        number the primitives of the scene that is gone (the colour and depth images and the target stay)."""
         self.v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 8)
         self.i = np.ascontiguousarray(i, dtype=np.int64).reshape(-1)
         self.scene = digest(self.v, self.i)
         self.attrs = self.skin = self.targets = self.kind = None
         self.pose_kind = self.pose = self.pose_id = None
         self.weights = self.weights_id = None
+        self.normals = None
         self.ids_ok = False
 
     def _need_scene(self):
@@ -238,6 +246,25 @@ class State:
             self.weights, self.weights_id, self.pose_kind, self.pose, self.pose_id = held
             raise
 
+    def set_normals(self, mode, flags=0, reserved=(0, 0)):
+        """swr_scene_normals (mode None: NULL, which means UPLOADED).  Every check is made before anything changes.  The mode follows
+        the upload it belongs to; it is in effect only while the scene has attributes and is kept when it is set earlier.  It
+        changes no image, no ID and no baseline: the last frame stays as it was drawn."""
+        self._need_scene()
+        if mode is None:
+            mode, flags, reserved = UPLOADED, 0, (0, 0)
+        if mode not in (UPLOADED, SMOOTH, FLAT):
+            raise Refused(BAD_ARG, "an unknown mode")
+        if flags & ~FLIP:
+            raise Refused(BAD_ARG, "unknown flag bits")
+        if any(reserved):
+            raise Refused(BAD_ARG, "a non-zero reserved word")
+        self.normals = None if mode == UPLOADED else (mode, bool(flags & FLIP))
+
+    def mode(self):
+        """The computed mode in effect — (SMOOTH | FLAT, flip) — or None: it needs attributes."""
+        return self.normals if self.attrs is not None else None
+
     def set_material(self, shading):
         self.material = shading if shading is not None and shading.shader else None
 
@@ -246,7 +273,7 @@ class State:
         morph = (self.kind, self.targets[2], self.weights_id) if self.weights is not None else None
         pose = (self.skin[2], self.pose_kind, self.pose_id) if self.pose is not None else None
         attrs = None if self.attrs is None else digest(self.attrs)
-        return (self.scene, attrs, morph, pose)
+        return (self.scene, attrs, morph, pose) + ((self.mode(),) if self.mode() is not None else ())
 
     def morphed(self):
         """(vertices, attributes or None) under the weights, before the pose.  Sparse targets take the loop of "Sparse morph
@@ -266,7 +293,9 @@ class State:
         return v, a
 
     def shape(self):
-        """(vertices, attributes or None, id) of the resident scene as it is now: morphed, then posed."""
+        """(vertices, attributes or None, id) of the resident, indexed scene as it is now: morphed, then posed, then — under
+        SWR_NORMALS_SMOOTH — with the n_i of the posed vertices for normals (normal deltas and the normal half of the pose are left
+        out).  Under SWR_NORMALS_FLAT the attributes are the morphed-and-posed ones: what a lit frame draws is `drawn`."""
         key = self.shape_key()
         if key not in self.shapes:
             v, a = self.morphed()
@@ -276,8 +305,21 @@ class State:
                 v = P.pose_vertices(v, j, w, self.pose)
                 if a is not None:
                     a = P.pose_attrs(a, j, w, self.pose)
+            if self.mode() is not None and self.mode()[0] == SMOOTH:
+                _, a, _ = NM.expected_scene(SMOOTH, v, self.attrs, self.i, self.mode()[1])
             self.shapes[key] = (np.ascontiguousarray(v), None if a is None else np.ascontiguousarray(a), len(self.shapes))
         return self.shapes[key]
+
+    def drawn(self):
+        """(vertices, attributes or None, indices, id) of what a frame that reads normals draws: the indexed scene, or, under
+        SWR_NORMALS_FLAT, the de-indexed one — vertex 3p + k is corner k of triangle p and carries f_p.  Index positions are the
+        same in both, so draw-list ranges, primitive IDs and counts carry over."""
+        v, a, sid = self.shape()
+        if self.mode() is None or self.mode()[0] != FLAT:
+            return v, a, self.i, sid
+        if sid not in self.flat:
+            self.flat[sid] = NM.expected_scene(FLAT, v, self.attrs, self.i, self.mode()[1])
+        return self.flat[sid] + (sid,)
 
     # ---- the target ---------------------------------------------------------------------------------------------------------------
     def target_set(self, w, h):
@@ -313,13 +355,14 @@ class State:
         w, h = self.size
         v, a, sid = self.shape()
         if kind == TRI:
-            shading = None
+            shading, idx = None, self.i
             if self.material is not None and not flags & NC:
                 if a is None:
                     raise Refused(BAD_ARG, "a Phong material without attributes")
+                v, a, idx, sid = self.drawn()               # (depth-only frames and the passthrough shader read no normals)
                 shading = dataclasses.replace(self.material, attrs=a)
             tkey = digest(transform) if items is None else items_key(items)
-            spec = FM.FrameSpec(v, self.i, w, h, flags, transform, items, shading,
+            spec = FM.FrameSpec(v, idx, w, h, flags, transform, items, shading,
                                 key=("state", sid, w, h, tkey, 0 if shading is None else shading.shader))
             start = None
             if flags & LOAD and not self.cleared:
@@ -391,6 +434,25 @@ class State:
             raise Refused(UNSUPPORTED, "SWR_FLAG_DEPTH_CLIP")
         v, _, _ = self.shape()
         return IB.item_bounds(v, self.i, items, self.size[0], self.size[1], flags)
+
+    def cast(self, rays, n=None, flags=0):
+        """swr_cast_rays: rays_model.cast over the triangles of the shape's vertices and the scene's indices.  It needs a scene
+        only — no target, no frame — and changes nothing.  n: what the caller says the array holds (default: what it holds)."""
+        self._need_scene()
+        rays = np.ascontiguousarray(rays, dtype=RM.RAY_DTYPE).reshape(-1)
+        n = rays.size if n is None else n
+        if n < 0 or flags != 0:
+            raise Refused(BAD_ARG, "n < 0 or flags != 0")
+        if n > RAYS_MAX:
+            raise Refused(UNSUPPORTED, "more than SWR_RAYS_MAX rays")
+        for k, r in enumerate(rays[:n]):
+            if RM.check_ray(r) is not None:
+                raise Refused(BAD_ARG, f"ray {k}: {RM.check_ray(r)}")
+        v, _, sid = self.shape()
+        key = (self.scene, digest(v[:, 0:3]), digest(rays[:n].view(np.uint32)))
+        if key not in self.casts:
+            self.casts[key] = RM.cast(RM.triangles(v, self.i), rays[:n])
+        return self.casts[key]
 
     def delta(self, bit, dst, bands):
         """(delta_model.Delta, dst after the call) of a delta read of the image kind `bit`; the baseline becomes the image."""

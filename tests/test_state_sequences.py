@@ -1,17 +1,27 @@
-"""Sequences that mix poses, morph targets of both kinds, queries and delta reads on ONE context (include/swr.h).
+"""Sequences that mix poses, morph targets of both kinds, computed normals, ray casts, queries and delta reads on ONE context
+(include/swr.h).
 
 tests/test_frame_sequences.py plays frames, draw lists, renders, presents, reads, uploads and target changes in orders; it calls none
 of swr_count_ids, swr_query_depth, swr_read_*_delta, swr_render_delta, swr_delta_reset, swr_scene_skin, swr_pose_set, swr_pose_set_dq,
-swr_scene_morph, swr_scene_morph_sparse, swr_morph_set, swr_morph_pose_set and swr_item_bounds.  Each of those came with a suite of its
-own: one scene, one target, a fresh context per case.  This file plays them in orders, between frames of every kind, on one context.
+swr_scene_morph, swr_scene_morph_sparse, swr_morph_set, swr_morph_pose_set, swr_item_bounds, swr_scene_normals and swr_cast_rays.  Each
+of those came with a suite of its own: one scene, one target, a fresh context per case.  This file plays them in orders, between frames of every kind, on one context.
 
-Two families of seeds.  STATE_SEEDS (41, 42, 43) know dense targets, swr_morph_set and swr_pose_set*, and one attribute array; their
+Three families of seeds.  STATE_SEEDS (41, 42, 43) know dense targets, swr_morph_set and swr_pose_set*, and one attribute array; their
 operation lists are pinned as they were before the second family existed.  SPARSE_SEEDS (44, 45, 46) play the same parts with the
 sparse set "s0" resident instead of dense set 0 and swr_morph_pose_set as the blocking change behind the burst and the overflowed
 frame, and three parts more: "morph kinds" (dense and sparse sets replace each other under active weights; both sparse unions are
 partial, so what a set does not list must come from the base, whatever the set before left behind), "refusals" (every refusal of
 swr_morph_pose_set and swr_scene_morph_sparse, a frame behind each) and "late and replaced attributes" (sparse normal deltas before
 swr_scene_attributes, then a second attribute array, textured).  Their pair table has six state changes more (S_OPS_SPARSE).
+NORMALS_SEEDS (47, 48, 49) play all of that, swr_scene_normals — a mode that persists on the scene — and swr_cast_rays — a blocking
+observer of the resident stream — with a fourth scene (the hub of tests/normals_model.py: shared vertices, 312 of them) and seven parts
+more, each from base() under a Phong material: "normals tour" (a mode before swr_scene_attributes, every mode with and without FLIP over
+seven deformations, UPLOADED and NULL, the same mode twice), "rebuild tour under a mode" (the six callers of the stream rebuild under
+SMOOTH and under FLAT with FLIP), "un-waited normals" and "overflow normals" (swr_scene_normals, its early return and swr_cast_rays as
+the blocking call behind a burst and behind an overflowed frame), "mode lifetimes" (uploads and swr_render discard the mode; a second
+attribute array, skins and targets of the other kind keep it), "rays change nothing" (a ray cast between an ID frame and its counts,
+between delta reads, in front of a load frame and between swr_present and swr_present_wait) and "normals and rays refusals".  Their pair
+table has six state changes and one observer more (S_OPS_NORMALS, O_OPS_NORMALS).  Hit records are compared as bytes.
 
 (a) `sequence(seed, steps)` is a pure-Python, seeded generator of legal C-ABI calls.  Scripted parts make the coverage certain — a
     tour of the six callers of the stream rebuild, the pose kinds and both bind entries, a burst posted under one shape and a blocking
@@ -21,11 +31,11 @@ swr_scene_attributes, then a second attribute array, textured).  Their pair tabl
     `steps` random operations.  Calls the header refuses are played as ("refused", call, code).
 (b) `play` makes the calls and compares every image, count, query result, bounds record, delta stat and destination image with
     tests/state_model.py, bit for bit.  A SWR_FLAG_LOAD frame starts from the model's own previous image, never from a read-back.
-(c) tests/test_state_model.py asserts, without a GPU, what the sequences of STATE_SEEDS and SPARSE_SEEDS cover, that they are not vacuous, and — on
+(c) tests/test_state_model.py asserts, without a GPU, what the sequences of the three families cover, that they are not vacuous, and — on
     a stand-in context with switchable defects — that `play` has teeth.
 
 SWR_SEQUENCE_SEEDS=N adds N more sequences (seeds 200..) per scheduler and band count: a soak.  They belong to the second family,
-whose operations include the first's."""
+whose operations include the first's; the third family is seeds 47-49 alone."""
 import dataclasses
 import functools
 import os
@@ -39,6 +49,8 @@ import frame_model as FM
 import kernel_matrix as K
 import morph_model as MM
 import morph_sparse_model as MS
+import normals_model as NM
+import rays_model as RY
 import resolve_model as RM
 import skin_dq_model as DQ
 import skin_model as SM
@@ -52,12 +64,18 @@ pytestmark = pytest.mark.gpu
 
 STATE_SEEDS = (41, 42, 43)                          # the first family: dense targets, swr_morph_set and swr_pose_set* (pinned as they were)
 SPARSE_SEEDS = (44, 45, 46)                         # the second family: both kinds of targets, swr_morph_pose_set, two attribute arrays
+NORMALS_SEEDS = (47, 48, 49)                        # the third family: the second's operations, swr_scene_normals and swr_cast_rays
 STEPS = 24
+NORMALS_STEPS = STEPS                               # (measured: with the whole tail its slowest case stays under the bound)
 SPARSE_STEPS = STEPS                                # (measured: the slowest case of the second family takes as long as the slowest of the first)
 SIZES = FS.SIZES                                    # 320 x 192, 256 x 160, 192 x 96: 6, 5 and 3 tile rows
 SCENES = {"torus": 1536, "small": 300, "big": 1300}  # triangles; 768, 900 and 3 900 vertices (900 and 3 900 are no multiples of 64)
-JOINTS = {"torus": 4, "small": 8, "big": 8}
-TARGETS = {"torus": (5, 2), "small": (3, 2), "big": (3, 2)}     # targets in target set 0 and 1
+# the third family has a scene more: the hub of tests/normals_model.py, 304 triangles on 312 vertices (no multiple of 64), one of them
+# shared by 300 triangles, one by none — k_vertex_normals is one lane per vertex, the torus has 768 and both soups share no vertex
+SCENES3 = dict(SCENES, hub=304)
+VERTICES = {"torus": 768, "small": 900, "big": 3900, "hub": 312}
+JOINTS = {"torus": 4, "small": 8, "big": 8, "hub": 8}
+TARGETS = {"torus": (5, 2), "small": (3, 2), "big": (3, 2), "hub": (3, 2)}     # targets in target set 0 and 1
 STREAM_ORDERS = (1, 0, -1)                          # SWR_DEBUG_STREAM_ORDER of seeds 41, 42, 43
 PRIMARY = ("torus", "big", "torus")                 # the scene the scripted parts run on (it must be able to crowd a tile: > 1 024)
 MODEL_BUDGET = 3200         # triangles a sequence may send through the NumPy perspective model (as in tests/test_frame_sequences.py)
@@ -75,6 +93,11 @@ S_OPS = ("upload_same", "upload_other", "attrs", "skin_new", "skin_none", "pose_
 S_OPS_SPARSE = S_OPS + ("targets_sparse", "targets_swap_kind", "targets_none_other_entry", "morph_pose", "morph_pose_null_halves", "attrs_other")
 O_OPS = ("read", "present", "count_prim", "count_item", "query", "bounds", "delta_color", "delta_depth", "resolved", "read_ids",
          "load_frame")
+# the third family adds: each computed mode, the same mode with the other SWR_NORMALS_FLIP, UPLOADED, NULL and the no-op repeat of the
+# mode and flags in effect; and one observer, swr_cast_rays
+S_OPS_NORMALS = S_OPS_SPARSE + ("normals_smooth", "normals_flat", "normals_flip", "normals_uploaded", "normals_null", "normals_same")
+O_OPS_NORMALS = O_OPS + ("rays",)
+RAY_SETS = ("one", "many")                          # 1 ray, and 65: one lane into a second wave of k_rays_init / k_rays_finish
 NEEDS_IDS = ("count_prim", "count_item", "read_ids")
 
 # (state change, observer) pairs the header forbids, each with the sentence that does; the sequences play them as refusals
@@ -95,6 +118,17 @@ UNSPECIFIED.update({("target_write", o): "swr_present copies 'the frame of the L
                     "image': swr_target_write is no frame" for o in ("present", "resolved")})
 
 
+# the new pairs, decided from the header: none is illegal and none is open.  Each sentence is the one that decides its pairs.
+DECIDED = {(s, "rays"): "Ray casts, Errors: SWR_ERR_NO_SCENE: no scene (no other state is named: swr_cast_rays needs neither a target nor a "
+           "frame, so it is defined right after swr_target_set, swr_target_write and a frame of any kind)" for s in S_OPS_NORMALS}
+DECIDED.update({(s, o): "Computed normals, What the mode is: Primitive IDs, painter's order and tie order are unchanged (and swr_read_ids "
+                "names swr_target_set, swr_target_write and swr_scene_upload as what makes IDs unreadable: swr_scene_normals is not among them)"
+                for s in S_OPS_NORMALS[len(S_OPS_SPARSE):] for o in NEEDS_IDS})
+DECIDED.update({(s, o): "Computed normals, Ordering: a frame posted before the call never sees the new normals (the image, its reads, "
+                "queries and delta reads are those of the frame as it was drawn; only the next frame draws the new normals)"
+                for s in S_OPS_NORMALS[len(S_OPS_SPARSE):] for o in O_OPS if o not in NEEDS_IDS})
+
+
 def legal(s, o):
     return (s, o) not in ILLEGAL and (s, o) not in UNSPECIFIED
 
@@ -104,8 +138,17 @@ def sparse_family(seed):
     return seed not in STATE_SEEDS
 
 
+def normals_family(seed):
+    """Seeds 47-49: the third family.  It plays everything the second plays (sparse_family is true of it)."""
+    return seed in NORMALS_SEEDS
+
+
 def s_ops(seed):
-    return S_OPS_SPARSE if sparse_family(seed) else S_OPS
+    return S_OPS_NORMALS if normals_family(seed) else S_OPS_SPARSE if sparse_family(seed) else S_OPS
+
+
+def o_ops(seed):
+    return O_OPS_NORMALS if normals_family(seed) else O_OPS
 
 
 def none_entry(op, n):
@@ -135,6 +178,7 @@ class Frame:
     overflow: bool = False  # the one frame of a part that crowds a tile beyond the first bin guess
     items: str = "split"    # (list) the draw list, a name of items_of
     part: str = ""
+    normals: tuple = None   # (the third family) the computed mode in effect when the frame is drawn: ("smooth" | "flat", flip) or None
 
     def row(self):
         return FM.row_of(self.flags, self.shader, self.via == "list", self.tf == "per")
@@ -147,7 +191,7 @@ class Frame:
 
 
 BLOCKING = ("wait", "read", "read_resolved", "read_ids", "sync", "upload", "target", "write", "render", "render_delta", "attrs", "skin", "pose",
-            "targets", "weights", "morph_pose", "count", "query", "bounds", "delta", "feed", "refused")
+            "targets", "weights", "morph_pose", "count", "query", "bounds", "delta", "feed", "refused", "normals", "rays")
 NEUTRAL = ("hooks", "wait", "sync", "material", "part", "refused")     # (neither a state change nor an observer of the tables)
 
 
@@ -158,18 +202,22 @@ def sequence(seed, steps=None, pairs=True, only=None):
     ("morph_pose", weights id | "zero" | None, "mat" | "dq", pose id | None) ("write", seed)
     ("frame", Frame) ("render", Frame) ("render_delta", Frame, buffer) ("present", image) ("wait",) ("sync",) ("read",) ("read_ids",)
     ("read_resolved", S, depth filter, which) ("count", group, rect name) ("query", boxes, seed) ("bounds", list name, flags)
-    ("delta", kind bits, buffer) ("delta_reset", bits) ("feed",) ("refused", call, code).
+    ("delta", kind bits, buffer) ("delta_reset", bits) ("feed",) ("refused", call, code); the third family:
+    ("normals", "smooth" | "flat" | "uploaded" | None, flip) ("rays", "one" | "many").
     only: the names of the scripted parts to generate (each starts from the scene's non-trivial shape on its own), for the teeth of
     tests/test_state_model.py."""
     rng = random.Random(seed)
     ops = [("hooks", hooks_of(seed))]
     primary = PRIMARY[(seed - STATE_SEEDS[0]) % 3]
     sparse = sparse_family(seed)
+    third = normals_family(seed)
+    scenes = SCENES3 if third else SCENES
     if steps is None:
-        steps = SPARSE_STEPS if sparse else STEPS
+        steps = NORMALS_STEPS if third else SPARSE_STEPS if sparse else STEPS
     T0, T1 = ("s0", "s1") if sparse else (0, 1)             # the targets base() keeps resident, and the tour's second set
     st = dict(scene=None, attrs=False, skin=None, pose=None, targets=None, weights=None, size=None, shader=0, last=None, ids=False,
-              countable=False, image=False, color=False, pending=0, count=0, budget=MODEL_BUDGET, paid=set(), boxes=0, dbuf=0, part="")
+              countable=False, image=False, color=False, pending=0, count=0, budget=MODEL_BUDGET, paid=set(), boxes=0, dbuf=0, part="",
+              normals=None)
 
     def emit(*op):
         ops.append(tuple(op))
@@ -192,7 +240,7 @@ def sequence(seed, steps=None, pairs=True, only=None):
         wait()
         emit("upload", scene)
         st.update(ids=False, countable=False)               # (the IDs numbered the primitives of the scene that is gone)
-        st.update(scene=scene, attrs=False, skin=None, pose=None, targets=None, weights=None)
+        st.update(scene=scene, attrs=False, skin=None, pose=None, targets=None, weights=None, normals=None)
         if st["shader"]:
             material(0)
 
@@ -242,6 +290,12 @@ def sequence(seed, steps=None, pairs=True, only=None):
         st["weights"] = None if w in ("zero", None) else w
         st["pose"] = None if k is None else (kind, k)
 
+    def normals(mode, flip=False):
+        """swr_scene_normals: blocking; "uploaded" and None (NULL) leave no mode."""
+        wait()
+        emit("normals", mode, bool(flip))
+        st["normals"] = (mode, bool(flip)) if mode in ("smooth", "flat") else None
+
     def write():
         wait()
         emit("write", rng.randrange(1 << 16))
@@ -286,7 +340,7 @@ def sequence(seed, steps=None, pairs=True, only=None):
         tf = "per" if row["transform"] == "perspective" else "aff"
         flags = FM.flags_of(row)
         if kind == "tri" and flags & PERSP and not flags & NC and tf == "per":
-            cost = SCENES[st["scene"]] * (3 if row["clip"] else 1) * (2 if row["list"] else 1)
+            cost = scenes[st["scene"]] * (3 if row["clip"] else 1) * (2 if row["list"] else 1)
             key = (shape(), st["size"], row["list"], row["shader"], flags & (DT | METAL | CB | CF | CCW | CLIP))
             if key in st["paid"]:
                 pass
@@ -302,14 +356,15 @@ def sequence(seed, steps=None, pairs=True, only=None):
             flags = (flags & (CB | CF | CCW | CLIP | PERSP)) | (REAL_LINES if kind == "lines" and rng.random() < 0.7 else 0)
             how = "draw"
         f = Frame(st["count"], st["scene"], st["size"], st["shader"], kind, flags, how, tf, shape(), overflow=overflow, part=st["part"],
-                  items=items)
+                  items=items, normals=st["normals"] if st["attrs"] else None)
         st["count"] += 1
         if how in ("render", "render_delta"):
             # swr_render uploads the scene itself (skin, pose, targets and weights are gone), sets its own target (the same size: a
             # delta baseline is kept) and the pass's own fragment stage
             wait()
-            f.scene_id = rng.choice((0, 70 + list(SCENES).index(f.scene)))
+            f.scene_id = rng.choice((0, 70 + list(scenes).index(f.scene)))
             f.shape = (st["scene"], bool(f.shader), None, None, None, None)
+            f.normals = None                                # (the upload it performs discards the mode)
             if flags & LOAD:
                 f.write = rng.randrange(1 << 16)
             if how == "render":
@@ -317,7 +372,7 @@ def sequence(seed, steps=None, pairs=True, only=None):
             else:
                 emit("render_delta", f, ("pinned", "pageable")[st["dbuf"] % 2])
                 st["dbuf"] += 1
-            st.update(attrs=bool(f.shader), skin=None, pose=None, targets=None, weights=None)
+            st.update(attrs=bool(f.shader), skin=None, pose=None, targets=None, weights=None, normals=None)
         else:
             emit("frame", f)
         loaded_color = bool(flags & LOAD) and st["color"] if st["image"] else True
@@ -371,6 +426,9 @@ def sequence(seed, steps=None, pairs=True, only=None):
     def refused(call, code=BAD_ARG):
         emit("refused", call, code)
 
+    def rays(name=None):
+        emit("rays", name or ("many" if rng.random() < 0.8 else "one"))
+
     def observe(o):
         """The observer `o` of O_OPS, on the state as it is (its legality is the caller's business)."""
         if o == "read":
@@ -397,6 +455,8 @@ def sequence(seed, steps=None, pairs=True, only=None):
             st["pending"] = 0
         elif o == "load_frame":
             frame(force=dict(load=1, no_color=0, clip=0, **({} if st["attrs"] else {"shader": 0})), ids=rng.random() < 0.5)
+        elif o == "rays":
+            rays()
         else:
             raise AssertionError(o)
 
@@ -405,8 +465,27 @@ def sequence(seed, steps=None, pairs=True, only=None):
         if s == "upload_same":
             upload(st["scene"])
         elif s == "upload_other":
-            others = [x for x in SCENES if x != st["scene"]]
+            others = [x for x in scenes if x != st["scene"]]
             upload(min(others, key=lambda x: (sum(1 for o in ops if o == ("upload", x)), rng.random())))
+        elif s.startswith("normals_"):
+            # a mode shows only with attributes; a change "of mode" starts from the other one, the rest from some mode in effect
+            if not st["attrs"]:
+                attrs()
+            cur, flip = st["normals"], rng.random() < 0.5
+            if s in ("normals_smooth", "normals_flat"):
+                if cur is not None and cur[0] == s[8:]:
+                    normals("flat" if s == "normals_smooth" else "smooth", cur[1])
+                normals(s[8:], flip)
+            else:
+                if cur is None:
+                    normals(rng.choice(("smooth", "flat")), flip)
+                cur = st["normals"]
+                if s == "normals_flip":
+                    normals(cur[0], not cur[1])
+                elif s == "normals_same":
+                    normals(*cur)
+                else:
+                    normals("uploaded" if s == "normals_uploaded" else None)
         elif s == "attrs":
             if st["attrs"]:
                 upload(st["scene"])
@@ -760,8 +839,10 @@ def sequence(seed, steps=None, pairs=True, only=None):
         """Every legal (state change, first observer) pair and every ordered pair of observers, dealt over the three seeds; every
         illegal pair as a refusal."""
         part("pairs")
-        todo = [(s, o) for s in s_ops(seed) for o in O_OPS]
-        mine = [p for k, p in enumerate(todo) if (k + seed) % 3 == 0] if seed in STATE_SEEDS + SPARSE_SEEDS else rng.sample(todo, len(todo) // 3)
+        skew = int(third)       # (twelve observers are a multiple of three: without it a seed would meet the same four behind every change)
+        todo = [(s, o) for s in s_ops(seed) for o in o_ops(seed)]
+        mine = [p for k, p in enumerate(todo) if (k + skew * (k // len(o_ops(seed))) + seed) % 3 == 0] if seed in STATE_SEEDS + SPARSE_SEEDS + NORMALS_SEEDS \
+            else rng.sample(todo, len(todo) // 3)
         rng.shuffle(mine)
         scene = primary
         for s, o in mine:
@@ -789,8 +870,9 @@ def sequence(seed, steps=None, pairs=True, only=None):
         base(scene)
         target(0)
         frame(ids=True, color=True, force=dict(load=0, list=1, clip=0, rules="ztest"))
-        order = [(a, b) for a in O_OPS for b in O_OPS]
-        mine = [p for k, p in enumerate(order) if (k + seed) % 3 == 0] if seed in STATE_SEEDS + SPARSE_SEEDS else rng.sample(order, len(order) // 3)
+        order = [(a, b) for a in o_ops(seed) for b in o_ops(seed)]
+        mine = [p for k, p in enumerate(order) if (k + skew * (k // len(o_ops(seed))) + seed) % 3 == 0] if seed in STATE_SEEDS + SPARSE_SEEDS + NORMALS_SEEDS \
+            else rng.sample(order, len(order) // 3)
         for a, b in mine:
             for o in (a, b):
                 if o in NEEDS_IDS and not st["ids"]:
@@ -801,10 +883,245 @@ def sequence(seed, steps=None, pairs=True, only=None):
                     observe(o)
             wait()
 
+    # -- the scripted parts of the third family: each starts from base() under a Phong material ------------------------------------------
+    def lit(which="many", observer=None, **force):
+        """A Phong frame that shows its normals (colour, no load; without the perspective model, whose budget is the pairs'), read
+        back, and a ray cast behind it; observer "bounds": swr_item_bounds in front of it."""
+        if observer == "bounds":                            # (in front: the frame is drawn from the stream it may have cut)
+            bounds(rng.choice(("split", "one", "thirds")), 0)
+        f = checked(force=dict(dict(load=0, clip=0, list=0, persp=0, no_color=0, shader=rng.choice((1, 2))), **force))
+        rays(which)
+        return f
+
+    def normals_tour():
+        """A mode before swr_scene_attributes (no effect on a passthrough frame; in effect when they arrive), then every mode with and
+        without FLIP, and under each: the bind pose, dense weights on a set with normal deltas, sparse weights on "s0" (normal deltas)
+        and "s1" (none), a matrix pose, a dual-quaternion pose and swr_morph_pose_set.  Then UPLOADED and NULL over the same
+        deformations — normal deltas and posed normals are back — and the same mode and flags twice.  On the hub: shared vertices,
+        312 of them."""
+        part("normals tour")
+        upload("hub")
+        target(0)
+        skin(0); pose("mat", 0); targets("s0"); weights(0)
+        normals("smooth", False)                            # before any attributes: kept, and of no effect yet
+        checked(ids=True, force=dict(load=0, shader=0, list=0, clip=0, persp=0))
+        rays("many")
+        attrs()                                             # it takes effect when they arrive
+        lit()
+
+        def deformations():
+            pose("bind_mat", 0)                             # the bind pose (under the weights of "s0")
+            lit()
+            targets(0); weights(0)                          # dense weights, normal deltas
+            lit("one")
+            targets("s0"); weights(1)                       # sparse, normal deltas (the NaN weight on the empty target)
+            lit()
+            targets("s1"); weights(0)                       # sparse, none
+            lit()
+            pose("mat", 0)
+            lit()
+            pose("dq", 0)
+            lit("one")
+            targets("s0")
+            morph_pose(0, "mat", 0)                         # the combined call: back in the shape of base()
+            lit()
+
+        for k, (mode, flip) in enumerate((("smooth", False), ("smooth", True), ("flat", True), ("flat", False))):
+            if k:                                           # (the second and the fourth change FLIP alone)
+                normals(mode, flip)
+                lit()
+            deformations()
+        normals("uploaded")                                 # as a context that never set a mode
+        lit()
+        deformations()
+        normals("flat", True)
+        lit()
+        normals(None)                                       # NULL means UPLOADED
+        lit()
+        pose("dq", 0)
+        lit()
+        for _ in range(2):                                  # the same mode and flags twice: the second changes nothing
+            normals("smooth", True)
+            lit()
+
+    def rebuild_tour_moded():
+        """The six callers of the stream rebuild once under SMOOTH and once under FLAT with FLIP — the mode set before the attributes
+        — each observed by a Phong frame, swr_item_bounds and a ray cast; the draw list's items cut a sorted stream."""
+        part("rebuild tour under a mode")
+        for mode, flip in (("smooth", False), ("flat", True)):
+            upload(primary)
+            target(0)
+            normals(mode, flip)
+            skin(0); pose("mat", 0); targets(T0); weights(0)
+            checked(ids=True, force=dict(load=0, shader=0, list=0, clip=0, persp=0))
+            rays("many")
+            attrs()                                         # 1: attributes arriving under a mode that was set earlier
+            lit(observer="bounds")
+            skin(0)                                         # 2
+            lit(observer="bounds")
+            pose("dq", 0)                                   # 3
+            lit(observer="bounds")
+            targets(T1)                                     # 4
+            lit(observer="bounds")
+            weights(0)                                      # 5
+            lit(observer="bounds")
+            if seed % 2:                                    # 6: a draw list or swr_item_bounds cuts a Morton-sorted stream
+                lit(ids=1, list=1)
+                bounds("thirds", 0)
+            else:
+                bounds("split", 0)
+                lit(ids=1, list=1)
+            lit(observer="bounds")                          # (a plain frame on the cut stream)
+            bounds("thirds", METAL)                         # (other boundaries: the stream is cut again)
+            lit()
+
+    def unwaited_normals():
+        """A burst posted under one mode and swr_scene_normals behind it with no wait in front: every presented image shows the old
+        normals, the next frame the new ones.  Then the same burst with swr_cast_rays behind it."""
+        part("un-waited normals")
+        for behind in ("normals", "rays"):
+            base(primary)
+            material(1)
+            normals("smooth", behind == "rays")
+            for k in range(3):
+                frame(force=dict(clip=0, load=0, shader=1 + k % 2, no_color=0, persp=0, cull=("none", "back", "front")[(seed + k) % 3]), present_it=True)
+            pending, st["pending"] = st["pending"], 0        # (no wait in front: the call completes the burst itself)
+            if behind == "normals":
+                normals("flat", bool(seed % 2))
+            else:
+                rays("many")
+            st["pending"] = pending
+            frame(force=dict(load=0, clip=0, shader=1, no_color=0, persp=0, cull="none"), present_it=True)
+            wait()
+            read()
+            rays("many")
+
+    def overflow_normals():
+        """The overflowed frame under SMOOTH, and the first call that waits: swr_scene_normals with another mode, swr_scene_normals with
+        the same mode and flags (its early return lies behind the repair), swr_cast_rays.  The read shows the normals it was drawn with."""
+        part("overflow normals")
+        mode = dict(hooks_of(seed)).get(K.DEBUG_BIN_MODE, 0)
+        emit("hooks", ((K.DEBUG_BIN_MODE, 0),))
+        for k, first in enumerate(("other", "same", "rays")):
+            base(primary)
+            target(1)
+            target(0)
+            material(1)
+            normals("smooth", k == 1)
+            pose("mat", "crowd")
+            frame(ids=True, overflow=True, force=dict(rules=("ztest", "metal")[k % 2], shader=1, no_color=0))
+            if first == "other":
+                normals("flat", False)
+            elif first == "same":
+                normals("smooth", True)
+            else:
+                rays("one")                                 # (the crowded shape is a sixth of the scene's size: the 65 mostly miss it)
+            read()
+            pose("mat", 0)
+            lit()
+        emit("hooks", ((K.DEBUG_BIN_MODE, mode),))
+
+    def mode_lifetimes():
+        """The mode against every other state change: discarded by an upload of the same and of another size and by swr_render with a
+        new scene identity (the cached second render and the plain draw behind it are un-moded); kept across a second attribute
+        array, swr_scene_skin (NULL and a new one) and targets of the other kind."""
+        part("mode lifetimes")
+        base(primary)
+        material(1)
+        normals("smooth", False)
+        lit()
+        upload(primary)                                     # the same size
+        attrs()
+        lit()
+        normals("smooth", False)                            # two cuts of the sorted stream with no pose and no weights, where the mode
+        lit()                                               # alone makes the rebuild compute again: swr_item_bounds under SMOOTH (both
+        bounds("thirds", 0)                                 # of its kernels, over the adjacency) ...
+        lit()
+        normals("flat", True)
+        lit()
+        lit(ids=1, list=1)                                  # ... and a draw list, of other boundaries, under FLAT with FLIP
+        lit()
+        upload("hub")                                       # another size
+        attrs()
+        lit()
+        base(primary)
+        material(1)
+        normals("flat", False)
+        lit()
+        for _ in range(2):                                  # swr_render with a scene identity, twice: the second is cached
+            f = frame(via="render", color=True, force=dict(load=0, clip=0, shader=1, persp=0))
+            f.scene_id = 190 + seed
+        lit()                                               # (a plain draw behind them)
+        base(primary)
+        normals("smooth", True)
+        lit()
+        attrs("other")                                      # uv and colour of the new array, normals computed
+        lit(shader=2)
+        skin(None)
+        lit()
+        skin(0)                                             # a new skin: the bind pose
+        lit()
+        pose("mat", 0)
+        lit()
+        targets(0); weights(0)                              # dense targets over the sparse ones
+        lit()
+        targets("s1"); weights(0)                           # and sparse ones over them
+        lit()
+
+    def rays_change_nothing():
+        """A ray cast between an ID frame and its count and swr_read_ids, between two delta reads of each kind (a frame of another
+        pose in front of it: the second read reports that frame's tiles, not none), between a frame and its load frame, and between
+        swr_present and swr_present_wait."""
+        part("rays change nothing")
+        base(primary)
+        target(0)
+        material(1)
+        normals("smooth", False)
+        plain = dict(load=0, clip=0, list=0, rules="ztest", shader=1, persp=0, no_color=0, cull="none", transform="affine")
+        frame(ids=True, force=plain)
+        rays("many")
+        count(ST.COUNT_PER_PRIMITIVE, "all")
+        rays("one")
+        emit("read_ids")
+        for bit in (COLOR, DEPTH):
+            delta(bit)
+            pose("dq", 0)
+            frame(ids=True, force=plain)
+            rays("many")
+            delta(bit)                                      # 0 < tiles_changed: the baseline is the first read's
+            pose("mat", 0)
+        frame(force=plain)
+        rays("many")
+        frame(force=dict(plain, load=1, list=1), items="few")
+        read()
+        frame(force=plain)
+        present()
+        rays("many")
+        wait()
+        read()
+
+    def refusals3():
+        """Every refusal of swr_scene_normals and swr_cast_rays the generator can reach, a frame and a ray cast behind each."""
+        part("normals and rays refusals")
+        base(primary)
+        material(1)
+        normals("flat", True)
+        lit()
+        for call, code in (("normals_bad_mode", BAD_ARG), ("normals_bad_flags", BAD_ARG), ("normals_reserved", BAD_ARG),
+                           ("rays_too_many", UNSUPPORTED), ("rays_flags", BAD_ARG), ("rays_nan", BAD_ARG), ("rays_zero_dir", BAD_ARG),
+                           ("rays_tmin_tmax", BAD_ARG)):
+            refused(call, code)
+            lit()
+
     scripted = [rebuild_tour, pose_kinds, unwaited, overflow, lifetimes, baselines, bounds_feed]
     if sparse:
         scripted += [morph_kinds, refusals, late_attrs]
-    names = {"rebuild tour": rebuild_tour, "pose kinds": pose_kinds, "un-waited": unwaited, "overflow": overflow, "lifetimes": lifetimes,
+    if third:
+        scripted += [normals_tour, rebuild_tour_moded, unwaited_normals, overflow_normals, mode_lifetimes, rays_change_nothing, refusals3]
+    names = {"normals tour": normals_tour, "rebuild tour under a mode": rebuild_tour_moded, "un-waited normals": unwaited_normals,
+             "overflow normals": overflow_normals, "mode lifetimes": mode_lifetimes, "rays change nothing": rays_change_nothing,
+             "normals and rays refusals": refusals3}
+    names |= {"rebuild tour": rebuild_tour, "pose kinds": pose_kinds, "un-waited": unwaited, "overflow": overflow, "lifetimes": lifetimes,
              "baselines": baselines, "bounds feed": bounds_feed, "morph kinds": morph_kinds, "refusals": refusals,
              "late and replaced attributes": late_attrs}
     if only is not None:
@@ -836,19 +1153,19 @@ def sequence(seed, steps=None, pairs=True, only=None):
         elif op == "draw":
             frame(rng.choice(("tri",) * 8 + ("points", "lines")), force=dict(clip=0) if st["scene"] == "big" else None)
         elif op == "observe":
-            o = rng.choice(O_OPS)
+            o = rng.choice(o_ops(seed))
             if not st["image"] or (o in NEEDS_IDS and not st["countable"]) or (o == "present" and st["last"] is None) \
                     or (o == "resolved" and st["last"] is None):
                 frame(ids=True, color=True, force=dict(clip=0))
             observe(o)
         elif op == "change":
             s = rng.choice(("pose_mat", "pose_dq", "bind", "weights", "weights_zero", "skin_new", "targets_new", "delta_reset")
-                           + (S_OPS_SPARSE[len(S_OPS):] * 2 if sparse else ()))
+                           + (S_OPS_SPARSE[len(S_OPS):] * 2 if sparse else ()) + (S_OPS_NORMALS[len(S_OPS_SPARSE):] * 2 if third else ()))
             change(s)
         elif op == "target":
             target(rng.randrange(len(SIZES)))
         elif op == "upload":
-            upload(rng.choice(list(SCENES)))
+            upload(rng.choice(list(scenes)))
             frame(force=dict(clip=0))
         elif op == "render":
             frame(via="render", force=dict(clip=0))
@@ -867,14 +1184,15 @@ def classes(ops):
     """[(index, S_OPS names, O_OPS names)] of every operation that changes state or observes; a SWR_FLAG_LOAD frame does both."""
     out, nv, size = [], None, None
     kind, attrs, nones = None, None, 0                      # the kind of the resident targets, the resident attribute array
-    verts = {"torus": 768, "small": 900, "big": 3900}
+    verts = VERTICES
+    mode = None                                             # the normals mode of the scene (in effect or not)
     for k, op in enumerate(ops):
         s, o = set(), set()
         name = op[0]
         if name == "upload":
             s.add("upload_same" if verts[op[1]] == nv else "upload_other")
             nv = verts[op[1]]
-            kind = attrs = None
+            kind = attrs = mode = None
         elif name == "attrs":
             s.add("attrs" if attrs in (None, op[1]) else "attrs_other")
             attrs = op[1]
@@ -911,7 +1229,7 @@ def classes(ops):
             if name != "frame":
                 s.add("render")                             # (its own gather is part of the call: no observer of what came before)
                 nv = verts[f.scene]
-                kind, attrs = None, (True if f.shader else None)
+                kind, attrs, mode = None, (True if f.shader else None), None
             elif f.kind != "tri":
                 s.add("frame_points")
             else:
@@ -940,6 +1258,17 @@ def classes(ops):
             o.add("bounds")                                 # (its first call; the query and the counts behind it are not credited)
         elif name == "unchecked":
             o.add("unchecked")
+        elif name == "normals":
+            new = (op[1], op[2]) if op[1] in ("smooth", "flat") else None
+            if new is None:
+                s.add("normals_null" if op[1] is None else "normals_uploaded")
+            elif new == mode:
+                s.add("normals_same")
+            else:
+                s.add("normals_flip" if mode is not None and mode[0] == new[0] else "normals_" + new[0])
+            mode = new
+        elif name == "rays":
+            o.add("rays")
         if s or o:
             out.append((k, s, o))
     return out
@@ -1059,6 +1388,66 @@ def other_attrs(attrs, seed):
     return a
 
 
+def hub_scene(S, tf):
+    """The hub of tests/normals_model.py in the torus's space and under its matrices, with what the sequences need of a scene: two
+    random skins of eight joints (as the soups'), two poses of each kind, dense target sets of 3 and 2 with normal deltas.  Its one
+    NaN coordinate is made finite: non-finite positions under a mode belong to tests/test_normals.py.  Vertex 0 is shared by 300
+    triangles, vertex 304 by none, and 312 vertices are four waves and 56 lanes."""
+    v, i = NM.hub(S)
+    v = np.array(v, copy=True)
+    v[NM.NAN_VERTEX, 0] = np.float32(-0.95)
+    nv = v.shape[0]
+    attrs = NM.hub_attrs(S)
+    rng = np.random.default_rng(0x4B0B)
+    skins, mats, dqs, tg, wt = {}, {}, {}, {}, {}
+    for sid in (0, 1):
+        jj = rng.integers(0, 8, (nv, 4)).astype(np.uint32)
+        jj[0, 0], jj[1, 1] = 7, 7
+        ww = rng.dirichlet(np.ones(4), nv).astype(np.float32) * rng.uniform(0.93, 1.07, (nv, 1)).astype(np.float32)
+        skins[sid] = (jj, ww.astype(np.float32))
+    for pid in (0, 1):
+        mats[pid] = np.stack([SM.joint_matrix(rng.uniform(-0.3, 0.3), rng.uniform(0.8, 1.05), rng.uniform(-0.15, 0.15), rng.uniform(-0.15, 0.15),
+                                              rng.uniform(-0.1, 0.1)) for _ in range(8)])
+        dqs[pid] = np.stack([DQ.dq_joint((rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3), 1.0), rng.uniform(-0.4, 0.4),
+                                         (rng.uniform(-0.15, 0.15), rng.uniform(-0.15, 0.15), rng.uniform(-0.1, 0.1))) for _ in range(8)])
+    for tid, nt in ((0, 3), (1, 2)):
+        tg[tid] = ((rng.uniform(-0.15, 0.15, (nt, nv, 3)) * (rng.uniform(size=(nt, nv, 1)) < 0.6)).astype(np.float32),
+                   rng.uniform(-0.5, 0.5, (nt, nv, 3)).astype(np.float32))
+        wt[tid] = {0: rng.uniform(0.4, 1.0, nt).astype(np.float32), 1: (-rng.uniform(0.4, 1.0, nt)).astype(np.float32)}
+    shading = {s: dataclasses.replace(S.random_shading(nv, 0x4B, s, shininess_log2=3), attrs=attrs) for s in (1, 2)}
+    return Scene(v, i, attrs, shading, skins, mats, dqs, tg, wt, tf)
+
+
+RAY_SEED = 0x5EED
+# how far the xy face the odd-numbered rays are aimed at is enlarged.  1.1 leaves the torus, the hub and "small" between 33 and 56 hits
+# of 65 in every shape the sequences cast on.  The 1 300-triangle soup swells under its sparse sets (deltas of 0.4) and random skins
+# until it covers that face and more: 57 to 65 hits, too few misses.  At 1.5 it has 32 to 56.
+RAY_SPREAD = {"torus": 1.1, "small": 1.1, "hub": 1.1, "big": 1.5}
+
+
+@functools.lru_cache(maxsize=None)
+def ray_set(scene, name):
+    """The rays of a scene, built from its bind shape: 65 origins in front of the scene's box, on -z, at 3 * half-depth + 1 from its
+    centre, jittered by 0.2 of the half-extents; the even-numbered rays are aimed at the centroid of a random triangle, the
+    odd-numbered ones at a random point of the box's xy face enlarged by RAY_SPREAD; tmin 0, tmax 10.  "one" is the first of them."""
+    s = world()[scene]
+    tri = RY.triangles(s.v, s.i)
+    pts = tri.reshape(-1, 3)
+    lo, hi = pts.min(axis=0), pts.max(axis=0)
+    c, e = (lo + hi) / 2, (hi - lo) / 2
+    rng = np.random.default_rng(RAY_SEED)
+    n = 65
+    rays = np.zeros(n, dtype=RY.RAY_DTYPE)
+    org = c + np.array([0, 0, -1.0]) * (e[2] * 3 + 1) + rng.uniform(-0.2, 0.2, (n, 3)) * e
+    tgt = c + rng.uniform(-1, 1, (n, 3)) * e * np.array([RAY_SPREAD[scene], RAY_SPREAD[scene], 0.0])
+    aimed = np.arange(n) % 2 == 0
+    tgt[aimed] = tri[rng.integers(0, tri.shape[0], n)].mean(axis=1)[aimed]
+    rays["origin"], rays["dir"], rays["tmin"], rays["tmax"] = org, tgt - org, 0, 10
+    assert all(RY.check_ray(r) is None for r in rays)
+    rays.setflags(write=False)
+    return rays if name == "many" else rays[:1]
+
+
 NEGATIVE_ZERO = {"torus": ((80, 2), (320, 2))}      # (vertex, coordinate): z = +0 as built; 80 is outside the union of "s1", 320 of "s0"
 
 
@@ -1120,12 +1509,13 @@ def world():
             wt[tid] = {0: rng.uniform(0.4, 1.0, nt).astype(np.float32), 1: (-rng.uniform(0.4, 1.0, nt)).astype(np.float32)}
         out[name] = Scene(v, i, sh[1].attrs, {1: sh[1], 2: sh[2]}, skins, mats, dqs, tg, wt,
                           {n: fs_mats[n] for n in ("aff", "aff2", "per", "per2")})
+    out["hub"] = hub_scene(S, tf)
     for k, (name, s) in enumerate(out.items()):
         s.attrs2 = other_attrs(s.attrs, 0xA77 + k)
         s.sparse, w = sparse_sets(s.v, 0x5BA65E + k, 0.15 if name == "torus" else 0.4)
         s.weights.update(w)
     for name, s in out.items():
-        assert s.i.size // 3 == SCENES[name] and s.mats[0].shape[0] == JOINTS[name] and s.targets[0][0].shape[0] == TARGETS[name][0]
+        assert s.i.size // 3 == SCENES3[name] and s.v.shape[0] == VERTICES[name] and s.mats[0].shape[0] == JOINTS[name] and s.targets[0][0].shape[0] == TARGETS[name][0]
         assert np.array_equal(s.shading[1].attrs, s.shading[2].attrs)
     return out
 
@@ -1227,7 +1617,8 @@ def spec_of(f, v=None):
 
 
 # ---- the player -----------------------------------------------------------------------------------------------------------------------
-_CACHE, _SHAPES = {}, {}    # frame_model's clear frames and the shapes, shared by every run of the module
+_CACHE, _SHAPES, _CASTS = {}, {}, {}    # frame_model's clear frames, the shapes and the model's ray hits, shared by every run of the module
+NORMALS = {"uploaded": NM.UPLOADED, "smooth": NM.SMOOTH, "flat": NM.FLAT}
 
 
 def play(swr, oracle, ops, bands, stats=None, model=None):
@@ -1236,7 +1627,7 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
     W = world()
     pool, dsts = {}, {}
     stats = {} if stats is None else stats
-    M = model if model is not None else ST.State(oracle, _CACHE, _SHAPES)
+    M = model if model is not None else ST.State(oracle, _CACHE, _SHAPES, _CASTS)
     clock = [0.0]
 
     def timed(fn, *a, **kw):
@@ -1322,6 +1713,40 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
         with pytest.raises(ST.Refused):
             M.set_targets_sparse(targets, vertex_count)
 
+    def raw_normals(mode, flags, reserved):
+        """swr_scene_normals with any mode, flag and reserved words: the code it returns."""
+        if hasattr(ctx, "raw_scene_normals"):                   # (the stand-in of tests/test_state_model.py)
+            return ctx.raw_scene_normals(mode, flags, reserved)
+        import ctypes
+        return swr.load_library().swr_scene_normals(ctx._h, ctypes.byref(B.Normals(mode, flags, (ctypes.c_int32 * 2)(*reserved))))
+
+    def raw_rays(rays, n, flags):
+        """swr_cast_rays with any n and flags: (the code it returns, the hit records as it left them)."""
+        hits = np.full(4 * max(len(rays), 1), 0xA5A5A5A5, dtype=np.uint32)
+        if hasattr(ctx, "raw_cast_rays"):
+            return ctx.raw_cast_rays(rays, n, flags), hits
+        return swr.load_library().swr_cast_rays(ctx._h, rays.ctypes.data, n, flags, hits.ctypes.data), hits
+
+    def check_rays(name, what):
+        rays = ray_set(scene, name)
+        got = ctx.cast_rays(rays)
+        want = timed(M.cast, rays)
+        bad = [j for j in range(rays.size) if got[j].tobytes() != want[j].tobytes()]
+        assert not bad, f"{what}: {len(bad)} of {rays.size} hit records differ, first ray {bad[0]}: {got[bad[0]]} vs {want[bad[0]]} ({state()})"
+        stats.setdefault("rays", []).append((k, name, scene, M.shape()[2], want))
+
+    def normals_refused(call, code, mode, flags, reserved, what):
+        check_refused(call, code, lambda: ctx._check(raw_normals(mode, flags, reserved)), what)
+        with pytest.raises(ST.Refused):
+            M.set_normals(mode, flags, reserved)
+
+    def rays_refused(call, code, rays, what, n=None, flags=0):
+        out = []
+        check_refused(call, code, lambda: (out.append(raw_rays(rays, len(rays) if n is None else n, flags)), ctx._check(out[0][0])), what)
+        assert (out[0][1] == 0xA5A5A5A5).all(), f"{what}: a refused swr_cast_rays wrote"
+        with pytest.raises(ST.Refused):
+            M.cast(rays, n, flags)
+
     cur = dict(weights=None, nones=0)
     scene = size = None
     try:
@@ -1329,6 +1754,7 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
             pending = []
             for k, op in enumerate(ops):
                 name = op[0]
+                stats["op"] = k
                 what = f"op {k} {op[:1] + tuple(x for x in op[1:] if not isinstance(x, Frame))}"
                 D = W[scene] if scene is not None else None
                 if name == "hooks":
@@ -1396,6 +1822,11 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
                     ctx.morph_pose_set(w, table, dq=kind == "dq")
                     M.morph_pose(w, kind, table)
                     cur["weights"] = op[1]
+                elif name == "normals":
+                    ctx.scene_normals(op[1], op[2])
+                    M.set_normals(None if op[1] is None else NORMALS[op[1]], NM.FLIP if op[2] else 0)
+                elif name == "rays":
+                    check_rays(op[1], what)
                 elif name == "write":
                     c, d = TP.start_images(op[1], *SIZES[size])
                     ctx.target_write(c, d)
@@ -1626,6 +2057,40 @@ def play(swr, oracle, ops, bands, stats=None, model=None):
                     elif call == "sparse_too_many":
                         none = (np.zeros(0, dtype=np.uint32), np.zeros((0, 3), dtype=np.float32))
                         sparse_refused(call, code, [D.sparse["s1"][0]] + [none] * ST.MORPH_MAX_TARGETS, what)
+                    elif call.startswith("normals_"):            # (each would change the next frame if it were taken)
+                        other = NM.FLAT if M.normals is None or M.normals[0] == NM.SMOOTH else NM.SMOOTH
+                        if call == "normals_bad_mode":
+                            for bad in (3, -1):
+                                normals_refused(call, code, bad, 0, (0, 0), what)
+                        elif call == "normals_bad_flags":
+                            for bad in (2, NM.FLIP | 1 << 31):
+                                normals_refused(call, code, other, bad, (0, 0), what)
+                        else:
+                            for bad in ((1, 0), (0, -1)):
+                                normals_refused(call, code, other, 0, bad, what)
+                    elif call.startswith("rays_"):
+                        rays = np.array(ray_set(scene, "many"))
+                        if call == "rays_too_many":
+                            rays_refused(call, code, np.resize(rays, ST.RAYS_MAX + 1), what)
+                        elif call == "rays_flags":
+                            for bad in (1, 1 << 31):
+                                rays_refused(call, code, rays, what, flags=bad)
+                        elif call == "rays_nan":
+                            for field, j, bad in (("origin", 1, np.nan), ("dir", 2, np.inf), ("tmin", None, -np.inf), ("tmax", None, np.nan)):
+                                r = rays.copy()
+                                if j is None:
+                                    r[field][64] = bad
+                                else:
+                                    r[field][64, j] = bad
+                                rays_refused(call, code, r, what)
+                        elif call == "rays_zero_dir":
+                            r = rays.copy()
+                            r["dir"][33] = (0.0, -0.0, 0.0)
+                            rays_refused(call, code, r, what)
+                        else:
+                            r = rays.copy()
+                            r["tmin"][0], r["tmax"][0] = 2.0, 1.0
+                            rays_refused(call, code, r, what)
                     elif call == "bounds_clip":
                         check_refused(call, code, lambda: ctx.item_bounds(items_of(scene, "aff"), CLIP), what)
                         with pytest.raises(ST.Refused):
@@ -1657,7 +2122,7 @@ _EXTRA = [200 + k for k in range(int(os.environ.get("SWR_SEQUENCE_SEEDS", "0")))
 
 @pytest.mark.parametrize("env", [{}, {"SWR_LANES": "0"}], ids=["lanes", "SWR_LANES=0"])
 @pytest.mark.parametrize("bands", [1, 3])
-@pytest.mark.parametrize("seed", list(STATE_SEEDS + SPARSE_SEEDS) + _EXTRA)
+@pytest.mark.parametrize("seed", list(STATE_SEEDS + SPARSE_SEEDS + NORMALS_SEEDS) + _EXTRA)
 def test_state_sequences(swr, oracle, monkeypatch, seed, bands, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -1665,7 +2130,7 @@ def test_state_sequences(swr, oracle, monkeypatch, seed, bands, env):
     stats = play(swr, oracle, sequence(seed), bands)
     print(f"seed {seed} bands {bands} {env}: {stats['checked']} images, {len(stats.get('counts', []))} counts, "
           f"{len(stats.get('queries', []))} queries, {len(stats.get('bounds', []))} bounds, {len(stats.get('deltas', []))} delta reads, "
-          f"{stats.get('refused', 0)} refusals checked, {time.perf_counter() - t0:.1f} s ({stats['model_s']:.1f} s in the model)")
+          f"{len(stats.get('rays', []))} ray casts, {stats.get('refused', 0)} refusals checked, {time.perf_counter() - t0:.1f} s ({stats['model_s']:.1f} s in the model)")
 
 
 # ---- the case the pairs found ---------------------------------------------------------------------------------------------------------
