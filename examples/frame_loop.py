@@ -7,13 +7,16 @@ and advances `time += 1/60` (App.swift:155-157).  Here the mesh stays resident o
 (swr_scene_upload once), each frame is one swr_draw, and frames are written as binary PPM.
 
     python examples/frame_loop.py --frames 4 --size 512 --out /tmp/frames [--obj mesh.obj] [--depth-test] [--objects N]
-                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y] [--occlusion [--bounds]] [--delta] [--skin [--dq]] [--morph [--sparse]]
+                                   [--cull back [--front-ccw]] [--ssaa {1,2,4}] [--ids] [--pick X,Y [--lit]] [--occlusion [--bounds]] [--delta] [--skin [--dq]] [--morph [--sparse]]
                                    [--auto-normals {smooth,flat}]
 
 --objects N draws N copies of the mesh, each with its own model matrix (its own spin, its own place on screen), as ONE draw list
 per frame (swr_draw_list: the mesh is uploaded once, every copy is an item over its whole index range).
 --pick X,Y also writes every frame's ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy of the mesh and which of its
 triangles are visible at pixel (X, Y): mouse picking (use it with --objects N).
+--pick X,Y --lit repeats the pick with rays (swr_query_rays): the pixel's ray is brought into every copy's object space and cast against
+that copy's range of triangles only, the nearest copy is reported, and one occlusion ray from the picked point towards the light says
+whether the point is lit or in the copy's own shadow.
 --ids writes the ID image too and after the last frame prints how many triangles of it are visible and how many
 pixels every copy covers, counted on the device (swr_count_ids: only the counts cross to the host, not the ID image).
 --occlusion (with --objects N and --depth-test) tests every copy's screen rectangle and nearest depth against the depth image of the
@@ -303,10 +306,12 @@ def view_flags(clip: bool = False, perspective: bool = False) -> int:
 def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_test: bool = False,
         time0: float = 0.0, objects: int = 1, pick: tuple[int, int] | None = None, cull: str = "none", front_ccw: bool = False,
         clip: bool = False, perspective: bool = False, glass: int | None = None, ssaa: int = 1, ids: bool = False,
-        occlusion: bool = False, bounds: bool = False, skin: bool = False, morph: bool = False, dq: bool = False):
+        occlusion: bool = False, bounds: bool = False, skin: bool = False, morph: bool = False, dq: bool = False, lit: bool = False):
     """Returns the list of (colour, depth) frames; writes PPMs when `out` is given.  objects > 1: that many copies of the
     mesh, one draw list per frame (the third element of every result is then the list of matrices).  pick = (x, y): every
     frame also writes its ID image (SWR_FLAG_PRIMITIVE_IDS) and prints which copy and which triangle are under that pixel.
+    lit (with pick): the pick is repeated with rays through every copy's own range and transform, and one occlusion ray says whether
+    the picked point is lit (pick_lit, swr_query_rays).
     ids: the ID image is written, and after the last frame its visibility counts are printed (swr_count_ids).
     occlusion: from the second frame on, every copy's screen rectangle and nearest depth are tested against the previous frame's depth
     image before the frame is drawn (swr_query_depth), and the number of copies nothing of which would pass is printed.
@@ -378,12 +383,14 @@ def run(frames: int, size: int, out: str | None, obj: str | None = None, depth_t
             if pick:
                 # mouse picking: the ID under the pixel, mapped to (copy, triangle of the mesh) over the list's item bases
                 x, y = pick
-                ids = ctx.read_ids()[::ssaa, ::ssaa]     # (IDs are not resolved: sample (0,0) of the pixel, like the depth)
-                obj_k, tri = swr_amd.binding.list_ids_to_items(ids[y:y + 1, x:x + 1], items)
+                id_image = ctx.read_ids()[::ssaa, ::ssaa]     # (IDs are not resolved: sample (0,0) of the pixel, like the depth)
+                obj_k, tri = swr_amd.binding.list_ids_to_items(id_image[y:y + 1, x:x + 1], items)
                 if obj_k[0, 0] < 0:
                     print(f"frame {k}: pixel ({x}, {y}): nothing")
                 else:
                     print(f"frame {k}: pixel ({x}, {y}): copy {obj_k[0, 0]}, triangle {tri[0, 0]}, depth {depth[y, x]:.6g}")
+                if lit:
+                    pick_lit(ctx, items, size, pick, k)     # the same pick through each copy's own rays, and whether the point is lit
             results.append((color, depth, m))
             if out:
                 os.makedirs(out, exist_ok=True)
@@ -531,6 +538,40 @@ def pick_ray(ctx, transform, size: int, pick, frame: int):
     return hit
 
 
+def pick_lit(ctx, items, size: int, pick, frame: int):
+    """--pick X,Y --lit: the pick through rays instead of the ID image, and one shadow ray.  For every item (first_index, index_count,
+    transform) of the frame the pixel's ray is brought into that item's object space (binding.pixel_ray with the item's transform) and
+    cast against that item's triangles only (swr_query_rays with the item's range of primitives); the item whose hit is nearest in
+    depth wins.  Then one occlusion ray (any-hit) starts at the hit point, goes towards the light of S.light_rig() — the material's
+    light_dir, in object space — with its tmin just off the surface, against the same item's triangles: the point is lit, or the copy
+    shadows itself.  Prints the item, the triangle and the verdict; returns (item, hit record, lit) or None."""
+    b = swr_amd.binding
+    best = None
+    for k, (first, count, transform) in enumerate(items):
+        ray = b.pixel_ray(transform, size, size, pick[0], pick[1])
+        hit = ctx.query_rays(ray.reshape(1), first_primitive=first // 3, primitive_count=count // 3)[0]
+        if hit["primitive"] == b.ID_NONE:
+            continue
+        p = ray["origin"] + hit["t"] * ray["dir"]
+        clip = np.asarray(transform, dtype=np.float64).reshape(4, 4).T @ np.append(p.astype(np.float64), 1.0)
+        depth = clip[2] / clip[3]
+        if best is None or depth < best[0]:
+            best = (depth, k, hit, p)
+    if best is None:
+        print(f"frame {frame}: pixel {pick}: no triangle on the ray of any item")
+        return None
+    depth, k, hit, p = best
+    first, count, _ = items[k]
+    light, _ = S.light_rig()
+    shadow = np.zeros(1, dtype=b.RAY_DTYPE)
+    shadow["origin"], shadow["dir"] = p, light
+    shadow["tmin"], shadow["tmax"] = 1e-4, np.finfo(np.float32).max
+    occluded = ctx.query_rays(shadow, any_hit=True, first_primitive=first // 3, primitive_count=count // 3)[0]["primitive"] == b.RAY_OCCLUDED
+    print(f"frame {frame}: pixel {pick}: item {k}, triangle {hit['primitive'] - first // 3} of it, depth {depth:.6f}: "
+          f"{'shadowed' if occluded else 'lit'}")
+    return k, hit, not occluded
+
+
 def run_skin(frames: int, size: int, out: str | None = None, depth_test: bool = True, time0: float = 0.0, device_count: int = 1,
              dq: bool = False, auto_normals: str | None = None, pick=None):
     """The resident loop with a deforming mesh: a torus skinned to two joints, a new pose every frame (swr_pose_set), the app's
@@ -648,6 +689,10 @@ if __name__ == "__main__":
     ap.add_argument("--pick", default=None,
                     help="X,Y: print the copy and the triangle under that pixel every frame (primitive IDs); with --skin / --morph: the "
                          "triangle, t and the hit point of that pixel's ray on the deformed mesh (swr_cast_rays)")
+    ap.add_argument("--lit", action="store_true",
+                    help="with --pick X,Y: pick through rays as well — with --objects N through each copy's own range of triangles and "
+                         "transform, reporting the nearest copy — and cast one occlusion ray from the picked point towards the light: "
+                         "lit or shadowed (swr_query_rays)")
     ap.add_argument("--ids", action="store_true",
                     help="write the ID image and print the last frame's visibility counts: visible triangles, pixels per copy (swr_count_ids)")
     ap.add_argument("--occlusion", action="store_true",
@@ -682,6 +727,8 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.dq and not a.skin:
         ap.error("--dq is a mode of --skin")
+    if a.lit and (not a.pick or a.stream or a.delta or ((a.skin or a.morph) and not (a.occlusion and a.bounds))):
+        ap.error("--lit needs --pick X,Y and is part of the plain loop (with or without --objects N)")
     if a.sparse and not a.morph:
         ap.error("--sparse is a mode of --morph")
     if a.ssaa != 1 and a.stream:
@@ -734,6 +781,6 @@ if __name__ == "__main__":
     _, idx, res = run(a.frames, a.size, a.out, a.ply or a.obj, a.depth_test, objects=a.objects, pick=pick, cull=a.cull,
                       front_ccw=a.front_ccw, clip=a.clip, perspective=a.perspective, glass=a.glass, ssaa=a.ssaa, ids=a.ids,
                       occlusion=a.occlusion, bounds=a.bounds, skin=deforming_bounds and a.skin, morph=deforming_bounds and a.morph,
-                      dq=a.dq)
+                      dq=a.dq, lit=a.lit)
     cov = [(c[..., 3] == 255).mean() for c, _, _ in res]
     print(f"{a.frames} frames, {max(1, a.objects)} x {idx.size // 3} triangles, coverage per frame: {[round(float(x), 4) for x in cov]}")

@@ -704,7 +704,7 @@ typedef struct swr_normals {
  *     n == 0 succeeds.  A scene without triangles answers every ray with a miss.
  *   Not covered: any-hit / occlusion-only rays; the facing of the hit and face culling; rays restricted to an index range or a draw
  *     item; more than one hit per ray; watertight edges (a ray that grazes an edge or a triangle's box can miss both neighbours, as
- *     with any Moeller-Trumbore test); an un-waited call; and the C++ and Swift mirrors. */
+ *     with any Moeller-Trumbore test); an un-waited call; and the C++ and Swift mirrors.  "Ray queries" below covers the first three. */
 typedef struct swr_ray {
     float origin[3]; float tmin;
     float dir[3];    float tmax;
@@ -714,6 +714,47 @@ typedef struct swr_ray_hit {
     float t, u, v;
 } swr_ray_hit;            /* 16 bytes */
 #define SWR_RAYS_MAX (1 << 16)
+
+/* ---- Ray queries (swr_query_rays) — DESIGN.md §31 -----------------------------------------------------------------------------------
+ * No ABI bump (SWR_ABI_VERSION stays 6) and no flag bit: the presence of the swr_query_rays symbol is the feature test.  Nothing
+ * existing changes: swr_cast_rays still refuses every non-zero flags.  swr_query_rays is swr_cast_rays with three additions, chosen by
+ * a swr_ray_query: occlusion rays (one bit per ray), a facing cull, and a range of primitives.  query == NULL means all defaults:
+ * flags 0, first_primitive 0, primitive_count -1.
+ *   Carried over from "Ray casts".  Its Space and Which triangles paragraphs, the numbering of p, and steps 1 to 3 with their
+ *     arithmetic: IEEE binary32, one rounding per operation, no FMA.  Its State, Ordering and Errors paragraphs hold with
+ *     swr_query_rays in the messages; a refused ray is named by its index.  n == 0 succeeds.  A scene without triangles answers every
+ *     ray with a miss.
+ *   Range.  Only triangles p with first_primitive <= p < first_primitive + primitive_count are candidates.  With primitive_count -1
+ *     the range runs to index_count / 3.  p and hits[k].primitive stay in the numbering of the whole index array, as for primitive
+ *     IDs.  An empty range is legal and answers every ray with a miss.  For draw item k the range is first_index / 3,
+ *     index_count / 3.
+ *   Facing.  det of step 3 decides.  Without SWR_RAYS_FRONT_CW a triangle is front-facing for the ray iff det > 0.0f: the ray arrives
+ *     from the side cross(b - a, c - a) points to (the face vector of "Computed normals" without SWR_NORMALS_FLIP), and seen from the
+ *     ray's origin a, b, c run counter-clockwise in a right-handed space.  With SWR_RAYS_FRONT_CW front-facing is det < 0.0f.
+ *     SWR_RAYS_CULL_BACK rejects the triangles that are not front-facing, SWR_RAYS_CULL_FRONT rejects the front-facing ones.  The
+ *     reject sits directly after "Reject unless fabsf(det) > 0.0f", on the same det bits.  Both bits reject everything, which is
+ *     legal, as for frames.  This is the geometric winding in object space, not the screen winding of "Face culling": that one
+ *     depends on the frame's transform and the y flip, this one on neither.  The hit record has no room for the facing: a caller
+ *     learns it by culling.
+ *   Nearest mode (no SWR_RAYS_ANY_HIT).  Step 4 of "Ray casts" over the triangles that survive range and cull.  With query == NULL,
+ *     or with flags 0, first_primitive 0 and primitive_count -1, hits is bit for bit what swr_cast_rays writes.
+ *   SWR_RAYS_ANY_HIT.  hits[k] is {SWR_RAY_OCCLUDED, 0, 0, 0} iff at least one surviving triangle is accepted by steps 1 to 3;
+ *     otherwise it is the miss record {SWR_ID_NONE, 0, 0, 0}.  Which triangle is never reported: that is what keeps the answer
+ *     independent of any order of evaluation, and therefore bit-defined.  Equivalently, a ray is occluded iff the nearest-mode answer
+ *     of the same query is not a miss; hits[k].primitive != SWR_ID_NONE means "hit" in both modes.  swr_scene_upload refuses a scene
+ *     of more than 2^32 - 2 primitives, so SWR_RAY_OCCLUDED is never a primitive number.
+ *   Errors, added.  SWR_ERR_BAD_ARG: unknown flag bits; a non-zero reserved; first_primitive < 0; primitive_count < -1; a range
+ *     that ends beyond index_count / 3.  All are checked before anything runs; after an error nothing was written.
+ *   Not covered: more than one hit per ray; watertight edges; an un-waited call; and the C++ and Swift mirrors.  A range is filtered
+ *     per triangle: it does not make the call cheaper on a reordered stream. */
+enum { SWR_RAYS_ANY_HIT = 1u << 0, SWR_RAYS_CULL_BACK = 1u << 1, SWR_RAYS_CULL_FRONT = 1u << 2, SWR_RAYS_FRONT_CW = 1u << 3 };
+#define SWR_RAY_OCCLUDED 0xFFFFFFFEu
+typedef struct swr_ray_query {
+    uint32_t flags;            /* SWR_RAYS_* */
+    uint32_t reserved;         /* 0 */
+    int64_t  first_primitive;  /* >= 0 */
+    int64_t  primitive_count;  /* >= 0, or -1: to the end of the scene */
+} swr_ray_query;               /* 24 bytes */
 
 /* ---- Load frames (SWR_FLAG_LOAD, ABI 6) — DESIGN.md §11 ------------------------------------------------------------------
  * A load frame runs Renderer.render(renderPass:) without Renderer.swift:205-206: the same triangle (.vertices, .line) loop
@@ -1039,6 +1080,8 @@ int swr_query_depth(swr_context* ctx, const swr_depth_box* boxes, int64_t n, uin
 int swr_item_bounds(swr_context* ctx, const swr_draw_item* items, int32_t item_count, uint32_t flags, swr_item_bound* out);
 /* the nearest hit of each of n rays on the resident triangles (see "Ray casts" above; blocking) */
 int swr_cast_rays(swr_context* ctx, const swr_ray* rays, int64_t n, uint32_t flags /* 0 */, swr_ray_hit* hits);
+/* swr_cast_rays with occlusion rays, a facing cull and a range of primitives (see "Ray queries" above; blocking) */
+int swr_query_rays(swr_context* ctx, const swr_ray_query* query /* NULL: all defaults */, const swr_ray* rays, int64_t n, swr_ray_hit* hits);
 /* Delta reads (see "Delta reads" above): swr_sync + the compare against the band's baseline on the device + the copy of the tile
  * flags + the copy of the changed rectangle + wait.  dst is the full W x H image, as for swr_read_*; stats may be NULL. */
 int swr_read_color_delta(swr_context* ctx, void*  dst_full_image, swr_delta_stats* stats);

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "swr_query_depth", "swr_read_color_delta", "swr_read_depth_delta", "swr_delta_reset", "swr_render_delta",
     "swr_scene_skin", "swr_pose_set", "swr_scene_morph", "swr_morph_set", "swr_item_bounds",
     "swr_pose_set_dq", "swr_scene_morph_sparse", "swr_morph_pose_set", "swr_scene_normals", "swr_cast_rays",
+    "swr_query_rays",
 ]
 # swr_debug_set keys (test hooks, include/swr.h)
 DEBUG_STREAM_ORDER, DEBUG_CULL, DEBUG_BIN_MODE, DEBUG_ONESHOT_MIN_TRIS, DEBUG_DEPTH_KEYS32, DEBUG_RASTER_SORT = 1, 2, 3, 4, 5, 6
@@ -233,6 +234,11 @@ RAYS_MAX = 1 << 16           # SWR_RAYS_MAX: rays per swr_cast_rays call
 # swr_ray and swr_ray_hit as numpy records (include/swr.h "Ray casts"): what Context.cast_rays takes and returns
 RAY_DTYPE = np.dtype([("origin", np.float32, (3,)), ("tmin", np.float32), ("dir", np.float32, (3,)), ("tmax", np.float32)])
 RAY_HIT_DTYPE = np.dtype([("primitive", np.uint32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
+# swr_ray_query (include/swr.h "Ray queries"): what Context.query_rays hands swr_query_rays
+RAYS_ANY_HIT, RAYS_CULL_BACK, RAYS_CULL_FRONT, RAYS_FRONT_CW = 1, 2, 4, 8      # SWR_RAYS_*: swr_ray_query.flags
+RAY_OCCLUDED = 0xFFFFFFFE    # SWR_RAY_OCCLUDED: hits[k].primitive of an occluded ray under RAYS_ANY_HIT
+RAY_QUERY_DTYPE = np.dtype([("flags", np.uint32), ("reserved", np.uint32), ("first_primitive", np.int64), ("primitive_count", np.int64)])
+RAYS_CULL = {None: 0, "none": 0, "back": RAYS_CULL_BACK, "front": RAYS_CULL_FRONT, "both": RAYS_CULL_BACK | RAYS_CULL_FRONT}
 
 
 def pixel_ray(transform, W: int, H: int, x, y) -> np.ndarray:
@@ -490,6 +496,8 @@ def load_library():
     try:
         L.swr_cast_rays.argtypes = [vp, vp, i64, u32, vp]
         L.swr_cast_rays.restype = ctypes.c_int
+        L.swr_query_rays.argtypes = [vp, vp, vp, i64, vp]
+        L.swr_query_rays.restype = ctypes.c_int
     except AttributeError:
         if not os.environ.get("SWR_LIBRARY"):      # (an older A/B build loaded by tools/ may lack it)
             raise
@@ -964,6 +972,25 @@ class Context:
         a = np.ascontiguousarray(a).reshape(-1)
         out = np.zeros(a.size, dtype=RAY_HIT_DTYPE)
         self._check(self._L.swr_cast_rays(self._h, a.ctypes.data if a.size else None, a.size, 0, out.ctypes.data if a.size else None))
+        return out
+
+    def query_rays(self, rays, any_hit: bool = False, cull: "str | None" = None, front_cw: bool = False, first_primitive: int = 0,
+                   primitive_count: int = -1) -> np.ndarray:
+        """swr_query_rays: cast_rays restricted to the primitives [first_primitive, first_primitive + primitive_count) (-1: to the end
+        of the scene; for a draw item first_index // 3 and index_count // 3) and to one facing (`cull`: None, "back", "front" or
+        "both"; front-facing means counter-clockwise seen from the ray's origin, clockwise with `front_cw`).  With `any_hit` the
+        answer is one bit per ray: primitive == RAY_OCCLUDED when anything is hit, ID_NONE otherwise, and t = u = v = 0.  The
+        defaults are cast_rays itself."""
+        a = np.asarray(rays)
+        if a.dtype != RAY_DTYPE:
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 8).view(RAY_DTYPE).reshape(-1)
+        a = np.ascontiguousarray(a).reshape(-1)
+        q = np.zeros(1, dtype=RAY_QUERY_DTYPE)
+        q["flags"] = (RAYS_ANY_HIT if any_hit else 0) | RAYS_CULL[cull] | (RAYS_FRONT_CW if front_cw else 0)
+        q["first_primitive"], q["primitive_count"] = first_primitive, primitive_count
+        out = np.zeros(a.size, dtype=RAY_HIT_DTYPE)
+        self._check(self._L.swr_query_rays(self._h, q.ctypes.data, a.ctypes.data if a.size else None, a.size,
+                                           out.ctypes.data if a.size else None))
         return out
 
     @staticmethod

@@ -2949,9 +2949,9 @@ int band_item_bounds(swr_context* c, const swr_draw_item* items, int32_t n, uint
     return SWR_OK;
 }
 
-// what swr_cast_rays may be handed (include/swr.h "Ray casts"): on a band or a group alike, against the scene every band holds
-int check_rays(swr_context* c, const swr_ray* rays, int64_t n, uint32_t flags, const swr_ray_hit* hits) {
-    const char* fn = "swr_cast_rays";
+// what swr_cast_rays and swr_query_rays (`fn`, with flags 0) may be handed (include/swr.h "Ray casts"): on a band or a group alike,
+// against the scene every band holds
+int check_rays(swr_context* c, const char* fn, const swr_ray* rays, int64_t n, uint32_t flags, const swr_ray_hit* hits) {
     if (!band(c, 0)->has_scene) return fail(c, SWR_ERR_NO_SCENE, "%s needs swr_scene_upload first", fn);
     if (n < 0) return fail(c, SWR_ERR_BAD_ARG, "%s: n %lld", fn, (long long)n);
     if (flags != 0) return fail(c, SWR_ERR_BAD_ARG, "%s: unknown flags 0x%x", fn, (unsigned)flags);
@@ -2970,10 +2970,35 @@ int check_rays(swr_context* c, const swr_ray* rays, int64_t n, uint32_t flags, c
     return SWR_OK;
 }
 
-// swr_cast_rays on one band (a group: its first): the n hits into c->rays_out[0 .. n), inside the band's page-locked staging.  The
-// stream read is the resident one as it is now — cut by an earlier draw list or not, never a frame's clip stream — and nothing of
-// the context but the call's own buffers is written.
-int band_cast_rays(swr_context* c, const swr_ray* rays, int64_t n) {
+// the query swr_cast_rays is, resolved over ntri primitives: every primitive, both facings, the nearest hit
+inline swr_ray_query default_ray_query(int64_t ntri) { return swr_ray_query{0, 0, 0, ntri}; }
+
+// what swr_query_rays may be handed as its query (include/swr.h "Ray queries"), the scene being there: `q` = the query with its
+// defaults filled in and primitive_count resolved, which is what band_cast_rays takes.  query == NULL: the defaults.
+int check_ray_query(swr_context* c, const swr_ray_query* query, swr_ray_query& q) {
+    const char* fn = "swr_query_rays";
+    const int64_t ntri = band(c, 0)->ni / 3;
+    q = default_ray_query(ntri);
+    if (!query) return SWR_OK;
+    const uint32_t known = SWR_RAYS_ANY_HIT | SWR_RAYS_CULL_BACK | SWR_RAYS_CULL_FRONT | SWR_RAYS_FRONT_CW;
+    if (query->flags & ~known) return fail(c, SWR_ERR_BAD_ARG, "%s: unknown flags 0x%x", fn, (unsigned)query->flags);
+    if (query->reserved != 0) return fail(c, SWR_ERR_BAD_ARG, "%s: reserved is 0x%x, not 0", fn, (unsigned)query->reserved);
+    if (query->first_primitive < 0) return fail(c, SWR_ERR_BAD_ARG, "%s: first_primitive %lld", fn, (long long)query->first_primitive);
+    if (query->primitive_count < -1) return fail(c, SWR_ERR_BAD_ARG, "%s: primitive_count %lld", fn, (long long)query->primitive_count);
+    // (first <= ntri first: the sum below then cannot overflow)
+    if (query->first_primitive > ntri || (query->primitive_count >= 0 && query->primitive_count > ntri - query->first_primitive))
+        return fail(c, SWR_ERR_BAD_ARG, "%s: primitives %lld + %lld end beyond the scene's %lld", fn, (long long)query->first_primitive,
+                    (long long)query->primitive_count, (long long)ntri);
+    q.flags = query->flags;
+    q.first_primitive = query->first_primitive;
+    q.primitive_count = query->primitive_count < 0 ? ntri - query->first_primitive : query->primitive_count;
+    return SWR_OK;
+}
+
+// swr_cast_rays / swr_query_rays on one band (a group: its first): the n hits into c->rays_out[0 .. n), inside the band's page-locked
+// staging.  `q` is a checked query (check_ray_query).  The stream read is the resident one as it is now — cut by an earlier draw list
+// or not, never a frame's clip stream — and nothing of the context but the call's own buffers is written.
+int band_cast_rays(swr_context* c, const swr_ray_query& q, const swr_ray* rays, int64_t n) {
     if (const int f = sticky(c)) return f;
     int rc;
     if ((rc = single_sync(c))) return rc;       // (an overflowed last frame is repaired here)
@@ -3000,6 +3025,9 @@ int band_cast_rays(swr_context* c, const swr_ray* rays, int64_t n) {
     a.n = n;
     a.keys = (unsigned long long*)c->rays_keys.p;
     a.hits = (swr_ray_hit*)c->rays_hits.p;
+    a.flags = q.flags;
+    a.p_begin = q.first_primitive;
+    a.p_end = q.first_primitive + q.primitive_count;
     launch_cast_rays(a, c->stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out, a.hits, nn * sizeof(swr_ray_hit), hipMemcpyDeviceToHost, c->stream));
@@ -3578,11 +3606,26 @@ int swr_item_bounds(swr_context* c, const swr_draw_item* items, int32_t item_cou
 int swr_cast_rays(swr_context* c, const swr_ray* rays, int64_t n, uint32_t flags, swr_ray_hit* hits) {
     if (!c) return SWR_ERR_BAD_ARG;
     if (const int f = sticky(c)) return f;
-    int rc = check_rays(c, rays, n, flags, hits);
+    int rc = check_rays(c, "swr_cast_rays", rays, n, flags, hits);
     if (rc) return rc;
     // every band holds the whole scene: the first band answers, the others finish what they have in flight
     swr_context* first = band(c, 0);
-    if ((rc = fan(c, [=](swr_context* k) { return k == first ? band_cast_rays(k, rays, n) : single_sync(k); }))) return rc;
+    const swr_ray_query q = default_ray_query(first->ni / 3);
+    if ((rc = fan(c, [=](swr_context* k) { return k == first ? band_cast_rays(k, q, rays, n) : single_sync(k); }))) return rc;
+    if (n) memcpy(hits, first->rays_out, (size_t)n * sizeof(swr_ray_hit));
+    return SWR_OK;
+}
+
+int swr_query_rays(swr_context* c, const swr_ray_query* query, const swr_ray* rays, int64_t n, swr_ray_hit* hits) {
+    if (!c) return SWR_ERR_BAD_ARG;
+    if (const int f = sticky(c)) return f;
+    int rc = check_rays(c, "swr_query_rays", rays, n, 0, hits);
+    if (rc) return rc;
+    swr_ray_query q;
+    if ((rc = check_ray_query(c, query, q))) return rc;
+    // as swr_cast_rays: the first band answers, the others finish what they have in flight
+    swr_context* first = band(c, 0);
+    if ((rc = fan(c, [=](swr_context* k) { return k == first ? band_cast_rays(k, q, rays, n) : single_sync(k); }))) return rc;
     if (n) memcpy(hits, first->rays_out, (size_t)n * sizeof(swr_ray_hit));
     return SWR_OK;
 }

@@ -381,6 +381,9 @@ void launch_flat_normals(const float4* tri_xyz, int64_t ntri, bool flip, float4*
 // chunk of RAYS_GROUPS_PER_WG groups) combines into keys[k], one 64-bit word per ray, which the launch initialises itself and decodes
 // into hits[k] at its end: nothing has to be zeroed.  Every ray has been checked by the host.  ntri == 0: every ray misses.  All
 // pointers are device memory.
+// Ray queries (include/swr.h "Ray queries") ride on the same launch: `flags` are the query's SWR_RAYS_* bits and
+// [p_begin, p_end) its range of primitives, 0 <= p_begin <= p_end <= ntri, resolved by the host.  ntri and groups stay those of the
+// whole stream: the range is a predicate per triangle.  flags 0 with the range [0, ntri) is swr_cast_rays itself.
 #ifndef SWR_TUNE_RAYS_GROUPS_PER_WG
 #define SWR_TUNE_RAYS_GROUPS_PER_WG 1024    // group boxes per workgroup, a multiple of 256: DESIGN.md §30
 #endif
@@ -396,6 +399,9 @@ struct RaysArgs {
     int64_t n;
     unsigned long long* keys;
     swr_ray_hit* hits;
+    uint32_t flags;
+    int64_t p_begin;
+    int64_t p_end;
 };
 inline int64_t rays_chunks(int64_t groups) { return (groups + RAYS_GROUPS_PER_WG - 1) / RAYS_GROUPS_PER_WG; }
 void launch_cast_rays(const RaysArgs& a, hipStream_t s);

@@ -16,6 +16,18 @@
 //                   the keys is the smallest t and, on equal t, the smallest p: order-free, hence bit-defined.  No float atomic.
 //   k_rays_finish   one lane per ray: the winner decoded, its slot found (inv when the stream is reordered), u and v computed again
 //                   with the same operations, the 16-byte record written by one vector store.
+//
+// Ray queries (include/swr.h "Ray queries") ride on the same launch, chosen by RaysArgs::flags and [p_begin, p_end):
+//   k_rays<CULL, true>      nearest mode with a range or a facing cull: pass 2 also tests, per lane, the primitive against the range
+//                           and the sign of the det that step 3 computed against the cull bits.  <CULL, false> is swr_cast_rays: it
+//                           reads none of the three fields.
+//   k_rays_any<FILTER>      SWR_RAYS_ANY_HIT: the same grid and pass 1.  On entry one lane reads the ray's key word once (a relaxed
+//                           agent-scope atomic load) and the workgroup leaves, uniformly, if another workgroup has already found the
+//                           ray occluded.  In pass 2 a wave stops at the first trip whose ballot of hits is not zero and raises a
+//                           flag in LDS, which the other waves read once per trip; no barrier inside that loop, one behind it.  One
+//                           lane publishes by an atomicMin of 0 on the key word: the word is all ones or it is not, and that is the
+//                           whole answer — an OR over the triangles, whatever the order, the timing and the placement.
+//   k_rays_finish<true>     the any-hit decode: {SWR_RAY_OCCLUDED, 0, 0, 0} or the miss; nothing is recomputed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -81,9 +93,9 @@ __device__ __forceinline__ bool ray_box(const RayRegs& R, const float lo[3], con
     return ok && nr <= fr;
 }
 
-// steps 1-3 on one triangle: whether it is accepted, and t, u, v
+// steps 1-3 on one triangle: whether it is accepted, and t, u, v and the det of step 3
 __device__ __forceinline__ bool ray_triangle(const RayRegs& R, const float4& xa, const float4& xb, const float4& xc, float& t, float& u,
-                                             float& v) {
+                                             float& v, float& det) {
     const float ca[3] = {xa.x, xa.y, xa.z}, cb[3] = {xb.x, xb.y, xb.z}, cc[3] = {xc.x, xc.y, xc.z};
     bool finite = true;
     float lo[3], hi[3];
@@ -98,7 +110,7 @@ __device__ __forceinline__ bool ray_triangle(const RayRegs& R, const float4& xa,
     const float3 o = make_float3(R.o[0], R.o[1], R.o[2]), d = make_float3(R.d[0], R.d[1], R.d[2]);
     const float3 e1 = ray_sub(b, a), e2 = ray_sub(c, a);
     const float3 pv = ray_cross(d, e2);
-    const float det = ray_dot(e1, pv);
+    det = ray_dot(e1, pv);
     const float inv = 1.0f / det;
     const float3 tv = ray_sub(o, a);
     u = ray_dot(tv, pv) * inv;
@@ -106,6 +118,20 @@ __device__ __forceinline__ bool ray_triangle(const RayRegs& R, const float4& xa,
     v = ray_dot(d, qv) * inv;
     t = ray_dot(e2, qv) * inv + 0.0f;
     return finite && box && fabsf(det) > 0.0f && u >= 0.0f && u <= 1.0f && v >= 0.0f && u + v <= 1.0f && t >= R.tmin && t <= R.tmax;
+}
+
+__device__ __forceinline__ bool ray_triangle(const RayRegs& R, const float4& xa, const float4& xb, const float4& xc, float& t, float& u,
+                                             float& v) {
+    float det;
+    return ray_triangle(R, xa, xb, xc, t, u, v, det);
+}
+
+// "Ray queries": whether primitive p, whose step 3 gave det, survives the query's range and facing cull.  det is not zero and not a
+// NaN wherever the answer is used (step 3 has rejected the triangle otherwise).
+__device__ __forceinline__ bool ray_query_keeps(const RaysArgs& a, uint32_t p, float det) {
+    const bool front = (a.flags & SWR_RAYS_FRONT_CW) ? det < 0.0f : det > 0.0f;
+    const bool culled = front ? (a.flags & SWR_RAYS_CULL_FRONT) != 0 : (a.flags & SWR_RAYS_CULL_BACK) != 0;
+    return (int64_t)p >= a.p_begin && (int64_t)p < a.p_end && !culled;
 }
 
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k) {
@@ -124,7 +150,7 @@ __global__ __launch_bounds__(RAYS_THREADS) void k_rays_init(unsigned long long* 
     if (k < n) keys[k] = RAYS_NO_HIT;
 }
 
-template <bool CULL>
+template <bool CULL, bool FILTER>
 __global__ __launch_bounds__(RAYS_THREADS) void k_rays(RaysArgs a) {
     __shared__ uint32_t s_queue[RAYS_GROUPS_PER_WG];
     __shared__ uint32_t s_count;
@@ -167,9 +193,10 @@ __global__ __launch_bounds__(RAYS_THREADS) void k_rays(RaysArgs a) {
         const bool in = s < a.ntri;
         const size_t sl = (size_t)(in ? s : a.ntri - 1);       // (ntri >= 1: a scene without triangles has no groups and no launch)
         const float4 xa = a.tri_xyz[3 * sl], xb = a.tri_xyz[3 * sl + 1], xc = a.tri_xyz[3 * sl + 2];
-        float t, u, v;
-        const bool hit = ray_triangle(R, xa, xb, xc, t, u, v) && in;
+        float t, u, v, det;
+        bool hit = ray_triangle(R, xa, xb, xc, t, u, v, det) && in;
         const uint32_t p = a.reordered ? __float_as_uint(xa.w) : (uint32_t)sl;
+        if (FILTER) hit = hit && ray_query_keeps(a, p, det);
         const unsigned long long key = ((unsigned long long)orderable_depth(t) << 32) | p;
         best = (hit && key < best) ? key : best;
     }
@@ -183,12 +210,73 @@ __global__ __launch_bounds__(RAYS_THREADS) void k_rays(RaysArgs a) {
     }
 }
 
+// SWR_RAYS_ANY_HIT: is any triangle of the chunk accepted?  The ray's key word drops from all ones to 0 when one is; nothing else of
+// it is ever read, so which workgroup, wave or lane found the triangle cannot show in the result.
+template <bool FILTER>
+__global__ __launch_bounds__(RAYS_THREADS) void k_rays_any(RaysArgs a) {
+    __shared__ uint32_t s_queue[RAYS_GROUPS_PER_WG];
+    __shared__ uint32_t s_count;
+    __shared__ uint32_t s_done;         // the ray is occluded: on entry by another workgroup's word, in pass 2 by a wave of this one
+    const uint32_t ray = ray_of_block();
+    if (ray >= (uint32_t)a.n) return;           // (uniform: the second z-plane of an odd ray count)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (threadIdx.x == 0) {
+        s_count = 0;
+        // one look at what the other workgroups of this ray have published so far: a stale all-ones costs time, never the answer
+        s_done = __hip_atomic_load(&a.keys[ray], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != RAYS_NO_HIT;
+    }
+    __syncthreads();
+    if (s_done) return;                         // (uniform: one LDS word, read by every lane behind the barrier; it is written again
+                                                // only in pass 2, behind the barrier that closes pass 1)
+    const RayRegs R = ray_regs(a.rays[ray]);
+    const int64_t g0 = (int64_t)blockIdx.x * RAYS_GROUPS_PER_WG;
+    const uint32_t in_chunk = (uint32_t)(a.groups - g0 < RAYS_GROUPS_PER_WG ? a.groups - g0 : RAYS_GROUPS_PER_WG);
+    // pass 1 as in k_rays, line for line (a shared function costs k_rays the schedule DESIGN.md §30 measured: §31)
+    for (uint32_t i = 0; i < (uint32_t)RAYS_GROUPS_PER_WG; i += RAYS_THREADS) {
+        if (i >= in_chunk) break;           // (uniform)
+        const uint32_t gi = i + threadIdx.x;
+        const bool in = gi < in_chunk;
+        const size_t g = (size_t)g0 + (in ? gi : in_chunk - 1u);
+        const float4 bl = a.box64[2 * g], bh = a.box64[2 * g + 1];
+        const float lo[3] = {bl.x, bl.y, bl.z}, hi[3] = {bh.x, bh.y, bh.z};
+        const bool pass = in && (!(bl.x == bl.x) || ray_box(R, lo, hi));
+        const unsigned long long m = __ballot(pass);
+        uint32_t base = 0;
+        if (lane == 0 && m) base = atomicAdd(&s_count, (uint32_t)__popcll(m));
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        if (pass) s_queue[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = gi;
+    }
+    __syncthreads();
+    const uint32_t queued = s_count;
+    for (uint32_t q = wave; q < queued; q += RAYS_WAVES) {
+        // (one read per trip; every lane of the wave reads the same word, so the wave leaves as one)
+        if (__hip_atomic_load(&s_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+        const int64_t s = (g0 + s_queue[q]) * 64 + lane;
+        const bool in = s < a.ntri;
+        const size_t sl = (size_t)(in ? s : a.ntri - 1);
+        const float4 xa = a.tri_xyz[3 * sl], xb = a.tri_xyz[3 * sl + 1], xc = a.tri_xyz[3 * sl + 2];
+        float t, u, v, det;
+        bool hit = ray_triangle(R, xa, xb, xc, t, u, v, det) && in;
+        if (FILTER) hit = hit && ray_query_keeps(a, a.reordered ? __float_as_uint(xa.w) : (uint32_t)sl, det);
+        if (__ballot(hit)) {
+            if (lane == 0) __hip_atomic_store(&s_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            break;
+        }
+    }
+    __syncthreads();                            // (every wave arrives: the loop has no other way out)
+    if (threadIdx.x == 0 && s_done) atomicMin(&a.keys[ray], 0ull);
+}
+
+template <bool ANY>
 __global__ __launch_bounds__(RAYS_THREADS) void k_rays_finish(RaysArgs a) {
     const uint32_t k = blockIdx.x * RAYS_THREADS + threadIdx.x;
     if (k >= (uint32_t)a.n) return;
     const unsigned long long key = a.keys[k];
     uint4 out = make_uint4(SWR_ID_NONE, 0u, 0u, 0u);
-    if (key != RAYS_NO_HIT) {
+    if (ANY) {
+        if (key != RAYS_NO_HIT) out.x = SWR_RAY_OCCLUDED;
+    } else if (key != RAYS_NO_HIT) {
         const uint32_t p = (uint32_t)key;       // (< ntri: the w lane of a reordered stream's corner 0, or the slot itself)
         const size_t s = a.reordered ? a.inv[p] : p;
         const RayRegs R = ray_regs(a.rays[k]);
@@ -206,14 +294,26 @@ void launch_cast_rays(const RaysArgs& a, hipStream_t s) {
     if (a.n <= 0 || a.n > SWR_RAYS_MAX) return;
     const dim3 per_ray((uint32_t)(a.n + RAYS_THREADS - 1) / RAYS_THREADS), block(RAYS_THREADS);
     hipLaunchKernelGGL(k_rays_init, per_ray, block, 0, s, a.keys, (uint32_t)a.n);
-    if (a.groups > 0) {
+    const bool any = (a.flags & SWR_RAYS_ANY_HIT) != 0;
+    // a query that is not swr_cast_rays itself: a facing cull, or a range that leaves a primitive out
+    const bool filter = (a.flags & (SWR_RAYS_CULL_BACK | SWR_RAYS_CULL_FRONT)) != 0 || a.p_begin > 0 || a.p_end < a.ntri;
+    if (a.groups > 0 && a.p_begin < a.p_end) {      // (an empty range: every ray misses, as over no groups)
         // one workgroup per (chunk, ray); the rays split over y and z so that SWR_RAYS_MAX of them fit the 65 535 of a grid's y
         const uint32_t planes = ((uint32_t)a.n + 65534u) / 65535u;
         const dim3 grid((uint32_t)rays_chunks(a.groups), ((uint32_t)a.n + planes - 1u) / planes, planes);
-        if (SWR_TUNE_RAYS_CULL) hipLaunchKernelGGL((k_rays<true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_rays<false>), grid, block, 0, s, a);
+        if (any) {
+            if (filter) hipLaunchKernelGGL((k_rays_any<true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_rays_any<false>), grid, block, 0, s, a);
+        } else if (filter) {
+            hipLaunchKernelGGL((k_rays<true, true>), grid, block, 0, s, a);
+        } else if (SWR_TUNE_RAYS_CULL) {
+            hipLaunchKernelGGL((k_rays<true, false>), grid, block, 0, s, a);
+        } else {
+            hipLaunchKernelGGL((k_rays<false, false>), grid, block, 0, s, a);
+        }
     }
-    hipLaunchKernelGGL(k_rays_finish, per_ray, block, 0, s, a);
+    if (any) hipLaunchKernelGGL((k_rays_finish<true>), per_ray, block, 0, s, a);
+    else hipLaunchKernelGGL((k_rays_finish<false>), per_ray, block, 0, s, a);
 }
 
 }  // namespace swr
